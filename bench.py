@@ -12,10 +12,16 @@ and the max-over-ranks time.
     python bench.py --gpus 1 --steps 3 --warmup 1
     python -m torch.distributed.run --nproc-per-node 8 ... bench.py --gpus 8 --steps K --warmup W
 
-Prints ONE JSON line (rank 0).  Besides the contract's keys it carries
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times --steps steps, writes the last
+step's outputs if --dump-outputs DIR is given, and prints the line; `roofline`, `kernels`,
+`secondary` and `cpu_baseline` are then empty.  With --full it also measures
   roofline     : dominant kernel, duration measured live with HIP events on the launch stream
+  secondary    : the f64 and c3 legs, the files-to-files session leg, SAA alone, host buffers (c2, N = 1)
   cpu_baseline : the CPU oracle (oracle/, a port of the reference's algorithm) timed on this
                  host's cores on a bounded sample of the same workload -- a reported baseline only.
+
+    python bench.py --gpus 1 --steps 20 --warmup 5 --full
+    python bench.py --gpus 1 --steps 20 --warmup 5 --dump-outputs bench_outputs
 """
 import argparse
 import ctypes
@@ -33,6 +39,8 @@ import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
 HBM_PEAK_GBS = 8000.0  # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec (6.3 TB/s achievable)
+DUMP_BYTES = {"hr": 56 << 20, "errors": 6 << 20}  # --dump-outputs: at most 62 MiB in all, index files included
+DUMP_SEED = 459
 
 
 def make_inputs(S, synth, B, f, lr_hw, shifts, psf, n_unique, prec, seed_base):
@@ -177,17 +185,17 @@ def measure(S, synth, lib, wl, prec, steps, warmup, seed_base, barrier=None, all
     sync = barrier or torch.cuda.synchronize
     for _ in range(warmup):
         hr, errs = one_step()
-    path = S.last_path()
     sync()
     t0 = time.perf_counter()
     for _ in range(steps):
         hr, errs = one_step()
     sync()
     dt = time.perf_counter() - t0
+    path = S.last_path()
     if allmax is not None:
         dt = allmax(dt)
     out = {"value": world * B * H * W / 1e6 * steps / dt, "ms_per_step": dt / steps * 1e3, "path": path, "B": B, "N": N, "f": f,
-           "lr_hw": [h, w], "n_iter": n_iter, "desc": desc, "lr": lr,
+           "lr_hw": [h, w], "n_iter": n_iter, "desc": desc, "lr": lr, "hr": hr, "errs": errs,
            "sane": bool(torch.isfinite(hr).all().item()) and float(errs[:, -1].mean().item()) < float(errs[:, 0].mean().item())}
     if not profile:
         return out
@@ -231,6 +239,25 @@ def measure(S, synth, lib, wl, prec, steps, warmup, seed_base, barrier=None, all
                            "achieved": round(nbytes / (launch_us * 1e-6) / 1e9, 1) if nbytes else None,
                            "frac": round(nbytes / (launch_us * 1e-6) / 1e9 / HBM_PEAK_GBS, 4) if nbytes else None}
     return out
+
+
+def dump_outputs(d, arrays):
+    """--dump-outputs: write what the timed path returned in its last step as d/<name>.npy (float32 / float64 as computed).  An array
+    larger than its share of DUMP_BYTES is cut to a seeded sample of its rows (the rows of the array seen as [rows, last axis]; the
+    same rows for the same shape on every run), written as d/<name>.npy [k, last axis] with the row indices in d/<name>_rows.npy."""
+    os.makedirs(d, exist_ok=True)
+    for name, a in arrays.items():
+        if a.dtype not in (torch.float32, torch.float64):
+            raise TypeError(f"{name}: {a.dtype}")
+        rows = a.reshape(-1, a.shape[-1])
+        row_bytes = rows.shape[1] * rows.element_size()
+        if rows.numel() * rows.element_size() <= DUMP_BYTES[name]:
+            np.save(os.path.join(d, name + ".npy"), a.cpu().numpy())
+            continue
+        k = DUMP_BYTES[name] // (row_bytes + 8)
+        idx = np.sort(np.random.default_rng(DUMP_SEED).choice(rows.shape[0], k, replace=False))
+        np.save(os.path.join(d, name + ".npy"), rows.index_select(0, torch.from_numpy(idx).to(rows.device)).cpu().numpy())
+        np.save(os.path.join(d, name + "_rows.npy"), idx.astype(np.float64))  # exact: indices < 2^53
 
 
 def kernel_source_sha16():
@@ -306,7 +333,7 @@ def cpu_baseline(synth, f, lr_hw, shifts, psf, n_iter, step):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=3)
+    ap.add_argument("--steps", type=int, default=3, help="timed steps (at least 1)")
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--batch", type=int, default=0, help="items per GPU per step (default: 1024 patches for c2, 1 frame for c3_*)")
     ap.add_argument("--iters", type=int, default=0, help="IBP iterations (default: the reference's 80; 50 for c3_rgb)")
@@ -315,10 +342,18 @@ def main():
                     help="c2 (default, the headline): 1024 x4 patches, N=16 phases; c3_mono / c3_rgb: the reference's own "
                          "full-frame shapes (mono_cal_target N=5 nominal f=2 3072x4096; rgb_cal_target N=4 measured f=2 1536x2048); "
                          "c3_f4: the x4 variant of SURVEY 8d, 768x1024 -> 3072x4096, all 16 phases")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the secondary legs (f64 and the c3 shapes)")
+    ap.add_argument("--full", action="store_true",
+                    help="also the roofline (a profiled pass), the secondary legs, SAA alone, host buffers and the CPU baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-roofline", action="store_true", help="with --full: skip the profiled pass and everything after the headline but the CPU baseline")
+    ap.add_argument("--no-secondary", action="store_true", help="with --full: skip the secondary legs (f64 and the c3 shapes)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the last timed step's outputs (rank 0) to DIR/hr.npy and DIR/errors.npy, at most 64 MB in all "
+                         "(larger arrays as a seeded sample of rows, indices in DIR/<name>_rows.npy)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    roofline_on = args.full and not args.no_roofline
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -362,8 +397,12 @@ def main():
         return float(t.item())
 
     m = measure(S, synth, lib, wl, prec, args.steps, args.warmup, 1000 * (rank + 1), barrier, allmax,
-                profile=(rank == 0 and not args.no_roofline), world=world)
+                profile=(rank == 0 and roofline_on), world=world)
     lr, path, kernels = m["lr"], m["path"], m.get("kernels", {})
+    hr_last, errs_last = m.pop("hr"), m.pop("errs")
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"hr": hr_last, "errors": errs_last})
+    del hr_last, errs_last
 
     # ---- roofline (contract field): the ITERATION-level figure of SURVEY 8d; the per-kernel view sits in dominant_kernel ----
     roofline = None
@@ -383,7 +422,7 @@ def main():
 
     # ---- secondary legs, timed in this same run (rank 0, N = 1): the reference's precision and its own full-frame shapes ----
     legs = None
-    if rank == 0 and world == 1 and not args.no_roofline and not args.no_secondary and args.workload == "c2":
+    if rank == 0 and world == 1 and roofline_on and not args.no_secondary and args.workload == "c2":
         legs = {}
         for tag, wname, lprec, lb in (("f64", "c2", "f64", None), ("c2_measured", "c2_measured", "f32", None), ("c3_mono", "c3_mono", "f32", None), ("c3_mono_f64", "c3_mono", "f64", None),
                                       ("c3_rgb", "c3_rgb", "f32", None),
@@ -410,7 +449,7 @@ def main():
 
     # ---- secondary figures: shift_and_add alone, and the same step from / to HOST buffers ----
     extras = None
-    if rank == 0 and world == 1 and not args.no_roofline:
+    if rank == 0 and world == 1 and roofline_on:
         torch.cuda.synchronize()
         t1 = time.perf_counter()
         for _ in range(3):
@@ -457,7 +496,7 @@ def main():
         extras = legs
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         cpu, hr_cpu, lr_cpu, it_cpu = cpu_baseline(synth, f, lr_hw, shifts, psf, n_iter, step)
         # parity spot check of the same patch on the GPU (the oracle is only the checker here)
         saa_g = S.shift_and_add_batched(torch.from_numpy(lr_cpu)[None], shifts, f, precision=prec)

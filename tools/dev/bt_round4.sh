@@ -6,7 +6,7 @@ rc=$?; tail -15 gpurun_out/bt4_tests.log
 [ $rc -ne 0 ] && exit $rc
 for wl in c3_rgb c3_rgb_measured; do
   for b in 1 8; do
-    timeout -k 10 200 python3 bench.py --workload $wl --batch $b --no-cpu-baseline --no-secondary --steps 4 --warmup 2 2>/dev/null | python3 -c "
+    timeout -k 10 200 python3 bench.py --full --workload $wl --batch $b --no-cpu-baseline --no-secondary --steps 4 --warmup 2 2>/dev/null | python3 -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])
 print('$wl', 'B=$b', d['config']['path'], 'ms/step', d['ms_per_step'], 'iter us', d['roofline']['iteration_kernels_us'], 'frac', d['roofline']['frac'], d['sane'])" || exit 1

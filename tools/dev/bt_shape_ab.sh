@@ -6,7 +6,7 @@ for lib in default "$@"; do
     for wl in "c3_rgb 1" "c3_rgb 8" "c3_rgb_measured 1"; do
         set -- $wl
         for rep in 1 2; do
-        python3 bench.py --workload $1 --batch $2 --no-cpu-baseline --no-secondary --steps 5 --warmup 2 2>/dev/null | python3 -c "
+        python3 bench.py --full --workload $1 --batch $2 --no-cpu-baseline --no-secondary --steps 5 --warmup 2 2>/dev/null | python3 -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])
 print('${lib##*/}', '$1 x$2', d['config']['path'], 'ms/step', d['ms_per_step'], 'iter us', d['roofline']['iteration_kernels_us'], 'frac', d['roofline']['frac'])"
