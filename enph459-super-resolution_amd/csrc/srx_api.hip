@@ -703,6 +703,12 @@ int srx_edge_dist_range(int H, int W, double m, double b, double norm, int rows_
     {                                                                                                                                         \
         metrics::EdgeLine e{m, b, norm, lo, bw, rows_are_x, nbin};                                                                             \
         return metrics::edge_bins<T>(roi, H, W, e, out, ws, wsb, hs(s));                                                                       \
+    }                                                                                                                                         \
+    int srx_ssim_##SFX(const T *ref, const T *test, int B, int H, int W, int border, int radius, const double *taps, int sample_cov,          \
+                       double data_range, double k1, double k2, const double *affine, double *mssim, T *map, void *ws, size_t wsb,           \
+                       srx_stream_t s)                                                                                                        \
+    {                                                                                                                                         \
+        return metrics::ssim<T>(ref, test, B, H, W, border, radius, taps, sample_cov, data_range, k1, k2, affine, mssim, map, ws, wsb, hs(s)); \
     }
 SRX_DEFINE_METRICS(f32, float)
 SRX_DEFINE_METRICS(f64, double)

@@ -10,6 +10,9 @@
 //   spot moments     subpixel_centre (psf_mtf_utils.py:67-71): first moments where the PSF exceeds a tenth of its peak
 //   edge ROI         slanted_edge_esf's image part (analysis.ipynb cell 7): Gaussian sigma 1.5 (scipy 'reflect'), Sobel magnitude; then every
 //                    ROI pixel projected on the fitted edge's normal and binned at 1/4 px (sums and counts per bin)
+//   SSIM             skimage structural_similarity (2-D; the vendor GUI's SSIM score, XPR_Software.py:1220-1256): the five windowed moments
+//                    held on chip in ONE pass over the two images (k_ssim), the mean of S as a float64 fixed-order reduction, the map optional;
+//                    its affine-fit form applies the fitted line inside the kernel.  The ECC score follows from the pair moments.
 // The percentile, the two line fits, the ESF interpolation, np.gradient / Hann / FFT of 72 samples, the 7-parameter Gaussian fit and the
 // 256^2 FFT of compute_mtf stay on the host (sr_mi355x/metrics.py): a few thousand operations each.
 #pragma once
@@ -254,6 +257,117 @@ __global__ void __launch_bounds__(256) k_edge_dist_range(int H, int W, EdgeLine 
     }
 }
 
+// ---- SSIM (skimage structural_similarity, 2-D): ONE pass over the two images ------------------------------------------------------
+// Block = 256 columns of the crop (4 waves side by side) x rows_per output rows.  Each input row (reflected, 'reflect' = d c b a | a b c d)
+// is staged once in LDS (256 + 2R values of x and of y, after the optional affine and a per-block shift), every lane forms the
+// horizontal window sums of x, y, x^2, y^2, x y for its column, and keeps them in a ring of the last 2R + 1 rows in registers (the row
+// loop is unrolled by 2R + 1, so every ring index is a constant).  When a row completes a window, the vertical sums give S for output
+// row (row - R), which is optionally stored in T and, inside [R, h - R) x [R, w - R), added to a float64 per-thread sum.  No plane other
+// than the optional map goes to memory; the extra input traffic is the 2R-row / 2R-column halos.  The shift (the block's first pixel)
+// leaves the moments unchanged and keeps x^2 - mean^2 from cancelling in float32.  Per-block float64 partials, then k_mean_partials.
+constexpr int SSIM_MAX_R = 7;
+constexpr int SSIM_TW = 256;                         // crop columns per block
+constexpr int SSIM_TARGET_BLOCKS = 1024;             // 4096 waves: 16 per CU
+constexpr int SSIM_MAX_BLOCKS = RED_BLOCKS * NMOM;   // per item: the partials fit in moments_ws(B)
+template <typename T> struct SsimArgs {
+    T k[2 * SSIM_MAX_R + 1];  // correlation taps, 2R + 1 used
+    T c1, c2, cov_norm;
+};
+
+template <typename T, int R>
+__global__ void __launch_bounds__(256) k_ssim(const T *__restrict__ ref, const T *__restrict__ test, int H, int W, int border, int rows_per, SsimArgs<T> a,
+                                              const double *__restrict__ affine /*[B][3] or null*/, double *__restrict__ part, T *__restrict__ map)
+{
+    constexpr int D = 2 * R + 1, NL = SSIM_TW + 2 * R;
+    __shared__ T sx[2][NL], sy[2][NL];
+    __shared__ double sh[4];
+    const int b = blockIdx.z, tid = threadIdx.x, h = H - 2 * border, w = W - 2 * border;
+    const int x0 = blockIdx.x * SSIM_TW, y0 = blockIdx.y * rows_per, y1 = min(y0 + rows_per, h), x = x0 + tid;
+    const T *rp = ref + (size_t)b * H * W + (size_t)border * W + border, *tp = test + (size_t)b * H * W + (size_t)border * W + border;
+    T ar = 1, at = 1, bt = 0;
+    if (affine)
+        ar = (T)affine[3 * b], at = (T)affine[3 * b + 1], bt = (T)affine[3 * b + 2];
+    // crop columns x0 - R + tid and (lanes < 2R) x0 - R + 256 + tid, reflected once (R < w); past w + R they feed no output: clamped
+    auto col = [&](int i) { i = i < 0 ? -1 - i : (i >= w ? 2 * w - 1 - i : i); return max(0, min(i, w - 1)); };
+    const int ca = col(x0 - R + tid), cb = col(x0 - R + SSIM_TW + tid);
+    const bool halo = tid < 2 * R;
+    const T cr = ar * rp[(size_t)y0 * W + min(x0, w - 1)], ct = at * tp[(size_t)y0 * W + min(x0, w - 1)] + bt;
+    const int ylast = y1 - 1 + R;  // input rows y0 - R .. y1 - 1 + R, reflected once (R < h); the last group's rows past them are clamped
+    T ra, ta, rb = 0, tb = 0;
+    auto fetch = [&](int yi) {
+        const int o = max(0, yi < 0 ? -1 - yi : (yi >= h ? 2 * h - 1 - yi : yi)) * W;
+        ra = rp[o + ca], ta = tp[o + ca];
+        if (halo)
+            rb = rp[o + cb], tb = tp[o + cb];
+    };
+    fetch(y0 - R);
+    T ring[5][D];  // horizontal sums of x, y, xx, yy, xy; slot j of a group = row (group start + j)
+    double acc = 0.0;
+    int buf = 0;
+    // groups of D input rows with no early exit (a loop that can break is not unrolled, and the ring would go to scratch); the host
+    // sizes rows_per so that only a batch item's last block row runs past ylast
+#pragma nounroll
+    for (int yi = y0 - R; yi <= ylast;) {
+#pragma unroll
+        for (int j = 0; j < D; j++, yi++) {
+            sx[buf][tid] = ar * ra - cr, sy[buf][tid] = at * ta + bt - ct;
+            if (halo)
+                sx[buf][SSIM_TW + tid] = ar * rb - cr, sy[buf][SSIM_TW + tid] = at * tb + bt - ct;
+            fetch(yi + 1);  // the next row's loads are in flight during this row's arithmetic
+            __syncthreads();  // (one barrier per row: the two buffers alternate)
+            T hx = 0, hy = 0, hxx = 0, hyy = 0, hxy = 0;
+#pragma unroll
+            for (int k = 0; k < D; k++) {
+                const T u = sx[buf][tid + k], v = sy[buf][tid + k], kk = a.k[k];
+                // every product formed the same way for x and y: SSIM(a, b) and SSIM(b, a) are bit-identical
+                hx += kk * u, hy += kk * v, hxx += kk * (u * u), hyy += kk * (v * v), hxy += kk * (u * v);
+            }
+            ring[0][j] = hx, ring[1][j] = hy, ring[2][j] = hxx, ring[3][j] = hyy, ring[4][j] = hxy;
+            buf ^= 1;
+            if (yi >= y0 + R && yi <= ylast) {  // rows yi - 2R .. yi (the first is y0 - R) are in the ring: output row yi - R
+                T m[5];
+#pragma unroll
+                for (int q = 0; q < 5; q++) {
+                    T s = 0;
+#pragma unroll
+                    for (int k = 0; k < D; k++)
+                        s += a.k[k] * ring[q][(j + 1 + k) % D];
+                    m[q] = s;
+                }
+                const int yo = yi - R;
+                T s;
+                {
+#pragma clang fp contract(off)  // symmetric in x and y to the bit
+                    const T mx = m[0] + cr, my = m[1] + ct;
+                    const T vx = a.cov_norm * (m[2] - m[0] * m[0]), vy = a.cov_norm * (m[3] - m[1] * m[1]), vxy = a.cov_norm * (m[4] - m[0] * m[1]);
+                    s = ((T)2 * mx * my + a.c1) * ((T)2 * vxy + a.c2) / ((mx * mx + my * my + a.c1) * (vx + vy + a.c2));
+                }
+                if (x < w) {
+                    if (map)
+                        map[(size_t)b * h * w + (size_t)yo * w + x] = s;
+                    if (yo >= R && yo < h - R && x >= R && x < w - R)
+                        acc += (double)s;
+                }
+            }
+        }
+    }
+    double v[1] = {acc};
+    block_sum<1>(v, sh, part + (size_t)b * gridDim.x * gridDim.y + blockIdx.y * gridDim.x + blockIdx.x);
+}
+
+// stage 2 of k_ssim: grid B, block 64: out[b] = (sum of the block partials) / n; lane l adds partials l, l + 64, ... in order, then the
+// fixed shuffle tree (bit-identical run to run)
+__global__ void __launch_bounds__(64) k_mean_partials(const double *__restrict__ part, int nblk, double n, double *__restrict__ out)
+{
+    const int b = blockIdx.x;
+    double s = 0.0;
+    for (int k = threadIdx.x; k < nblk; k += 64)
+        s += part[(size_t)b * nblk + k];
+    s = wave_sum(s);
+    if (threadIdx.x == 0)
+        out[b] = s / n;
+}
+
 // ---- host ---------------------------------------------------------------------------------------------------------------------------
 static inline size_t moments_ws(int B) { return align_up((size_t)B * RED_BLOCKS * NMOM * sizeof(double)); }
 
@@ -272,6 +386,61 @@ static int pair_moments(const T *ref, const T *test, int B, int H, int W, int bo
     hipLaunchKernelGGL(k_pair_moments<T>, dim3(nblk, B), dim3(256), 0, st, ref, test, H, W, border, part);
     SRX_CHECK_LAUNCH();
     hipLaunchKernelGGL(k_sum_partials, dim3(B), dim3(64), 0, st, part, nblk, NMOM, out);
+    SRX_CHECK_LAUNCH();
+    return SRX_OK;
+}
+
+template <typename T, int R>
+static void launch_ssim(dim3 grid, hipStream_t st, const T *ref, const T *test, int H, int W, int border, int rows_per, const SsimArgs<T> &a,
+                        const double *affine, double *part, T *map)
+{
+    hipLaunchKernelGGL((k_ssim<T, R>), grid, dim3(256), 0, st, ref, test, H, W, border, rows_per, a, affine, part, map);
+}
+
+// mean SSIM per item into mssim[B] (device); map [B][H - 2 border][W - 2 border] in T when not null.  taps: 2 radius + 1 host doubles
+template <typename T>
+static int ssim(const T *ref, const T *test, int B, int H, int W, int border, int radius, const double *taps, int sample_cov, double data_range, double k1,
+                double k2, const double *affine, double *mssim, T *map, void *ws, size_t wsb, hipStream_t st)
+{
+    if (!ref || !test || !taps || !mssim || B <= 0 || H <= 0 || W <= 0 || border < 0 || 2 * border >= H || 2 * border >= W || radius < 1 ||
+        !(data_range > 0.0) || !std::isfinite(data_range) || !std::isfinite(k1) || !std::isfinite(k2))
+        return SRX_E_INVALID;
+    if (radius > SSIM_MAX_R)
+        return SRX_E_UNSUPPORTED;
+    const int h = H - 2 * border, w = W - 2 * border, D = 2 * radius + 1;
+    if (D > h || D > w)
+        return SRX_E_INVALID;
+    const int gx = cdiv(w, SSIM_TW);
+    if (B > 65535 || (size_t)H * W * sizeof(T) >= ((size_t)1 << 31) || gx > SSIM_MAX_BLOCKS)
+        return SRX_E_UNSUPPORTED;
+    SsimArgs<T> a;
+    for (int j = 0; j < 2 * SSIM_MAX_R + 1; j++)
+        a.k[j] = j < D ? (T)taps[j] : (T)0;
+    const double np = (double)D * D;
+    a.c1 = (T)((k1 * data_range) * (k1 * data_range)), a.c2 = (T)((k2 * data_range) * (k2 * data_range));
+    a.cov_norm = (T)(sample_cov ? np / (np - 1.0) : 1.0);
+    // about SSIM_TARGET_BLOCKS blocks over the batch, at least 32 output rows each (the 2R-row halo stays a small share)
+    int gy = std::min(cdiv(SSIM_TARGET_BLOCKS, gx * B), std::max(1, h / 32));
+    gy = std::max(1, std::min(gy, SSIM_MAX_BLOCKS / gx));
+    const int rows_per = cdiv(cdiv(h, gy) + 2 * radius, D) * D - 2 * radius;  // rows_per + 2R input rows: whole groups of D
+    gy = cdiv(h, rows_per);
+    const int nblk = gx * gy;
+    Arena ar(ws, wsb);
+    double *part = ar.take<double>((size_t)B * nblk);
+    if (!ar.ok)
+        return SRX_E_WORKSPACE;
+    const dim3 grid(gx, gy, B);
+    switch (radius) {
+    case 1: launch_ssim<T, 1>(grid, st, ref, test, H, W, border, rows_per, a, affine, part, map); break;
+    case 2: launch_ssim<T, 2>(grid, st, ref, test, H, W, border, rows_per, a, affine, part, map); break;
+    case 3: launch_ssim<T, 3>(grid, st, ref, test, H, W, border, rows_per, a, affine, part, map); break;
+    case 4: launch_ssim<T, 4>(grid, st, ref, test, H, W, border, rows_per, a, affine, part, map); break;
+    case 5: launch_ssim<T, 5>(grid, st, ref, test, H, W, border, rows_per, a, affine, part, map); break;
+    case 6: launch_ssim<T, 6>(grid, st, ref, test, H, W, border, rows_per, a, affine, part, map); break;
+    default: launch_ssim<T, 7>(grid, st, ref, test, H, W, border, rows_per, a, affine, part, map); break;
+    }
+    SRX_CHECK_LAUNCH();
+    hipLaunchKernelGGL(k_mean_partials, dim3(B), dim3(64), 0, st, part, nblk, (double)(h - 2 * radius) * (double)(w - 2 * radius), mssim);
     SRX_CHECK_LAUNCH();
     return SRX_OK;
 }

@@ -43,6 +43,7 @@ _TYPED = {
     "srx_ring_sums_{T}": (_I, [_P, _I, _I, _D, _D, _I, _P, _P, _Z, _P]),
     "srx_spot_moments_{T}": (_I, [_P, _I, _I, _P, _P]),
     "srx_edge_bins_{T}": (_I, [_P, _I, _I, _D, _D, _D, _I, _D, _D, _I, _P, _P, _Z, _P]),
+    "srx_ssim_{T}": (_I, [_P, _P, _I, _I, _I, _I, _I, _HD, _I, _D, _D, _D, _P, _P, _P, _P, _Z, _P]),
 }
 _PLAIN = {
     "srx_version": (_I, []),

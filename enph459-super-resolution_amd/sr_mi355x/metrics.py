@@ -7,6 +7,9 @@ reference's analysis functions, same names, arguments and return values.
   psnr_affine                                                     the vendor GUI's PSNR after an affine intensity fit,
                                                                   opt_materials/software/XPR_Software.py:735-745,1215-1256
                                                                   (skimage is absent here: parity unpinned)
+  ssim                                                            skimage.metrics.structural_similarity, 2-D grayscale
+  ssim_affine, ecc                                                the vendor GUI's SSIM after the same affine fit and its
+                                                                  ECC score (XPR_Software.py:1220-1256; parity unpinned)
 
 These are tiny 1-D / small 2-D computations on the host (the reference runs them in a notebook); they take numpy arrays
 (e.g. the float64 arrays `sr_mi355x.ibp` returns) and do not touch the GPU.  Pinned by tests/golden/metrics.npz, produced
@@ -250,6 +253,94 @@ def psnr_affine(ref, test, border=10, data_range=1.0):
     a, b = np.polyfit(t.ravel(), r.ravel(), 1)
     mse = np.mean((r - (a * t + b)) ** 2)
     return np.inf if mse == 0 else 10.0 * np.log10(data_range ** 2 / mse)
+
+
+def _crop(a, border):
+    return np.asarray(a)[border:-border or None, border:-border or None]
+
+
+def ssim_params(shape, dtype, win_size=None, data_range=None, gaussian_weights=False, sigma=1.5):
+    """Validated SSIM window and range for a crop of `shape` (h, w) of `dtype` input: (radius, taps [2 radius + 1] float64,
+    data_range).  The window is uniform 1 / win_size (default 7) or, with gaussian_weights, scipy.ndimage.gaussian_filter's
+    (truncate 3.5): exp(-x^2 / 2 sigma^2) normalised, win_size = 2 int(3.5 sigma + 0.5) + 1 (a different win_size is refused).
+    win_size must be odd, >= 3 and fit the crop; data_range defaults to the integer dtype's range, float input must give it."""
+    if gaussian_weights:
+        r = int(3.5 * float(sigma) + 0.5)
+        if win_size is not None and int(win_size) != 2 * r + 1:
+            raise ValueError(f"gaussian_weights with sigma {sigma} has win_size {2 * r + 1}, not {win_size}")
+        win_size = 2 * r + 1
+    elif win_size is None:
+        win_size = 7
+    win_size = int(win_size)
+    if win_size < 3 or win_size % 2 == 0:
+        raise ValueError(f"win_size must be odd and at least 3, got {win_size}")
+    if win_size > min(shape):
+        raise ValueError(f"win_size {win_size} exceeds the image side {min(shape)}")
+    if data_range is None:
+        dtype = np.dtype(dtype)
+        if not np.issubdtype(dtype, np.integer):
+            raise ValueError("data_range is required for floating-point images")
+        data_range = float(np.iinfo(dtype).max) - float(np.iinfo(dtype).min)
+    r = win_size // 2
+    if gaussian_weights:
+        x = np.arange(-r, r + 1, dtype=np.float64)
+        taps = np.exp(-0.5 / (sigma * sigma) * x ** 2)
+        taps /= taps.sum()
+    else:
+        taps = np.full(win_size, 1.0 / win_size)
+    return r, taps, float(data_range)
+
+
+def ssim(ref, test, *, win_size=None, data_range=None, gaussian_weights=False, sigma=1.5, use_sample_covariance=True, K1=0.01, K2=0.03,
+         full=False, border=0):
+    """Mean structural similarity of two 2-D grayscale images, as skimage.metrics.structural_similarity computes it: window
+    means of x, y, x^2, y^2, x y ('reflect' boundary), S = (2 ux uy + C1)(2 vxy + C2) / ((ux^2 + uy^2 + C1)(vx + vy + C2)),
+    C1 = (K1 R)^2, C2 = (K2 R)^2, (co)variances scaled by NP / (NP - 1) if use_sample_covariance; the mean of S without a
+    (win_size - 1) / 2 rim, in float64.  `border` crops both images first.  full=True returns (mssim, S over the whole crop)."""
+    ref, test = np.asarray(ref), np.asarray(test)
+    if ref.shape != test.shape or ref.ndim != 2:
+        raise ValueError("ssim takes two 2-D images of the same shape")
+    x, y = _crop(ref, border).astype(np.float64), _crop(test, border).astype(np.float64)
+    r, taps, dr = ssim_params(x.shape, ref.dtype, win_size, data_range, gaussian_weights, sigma)
+    np_ = float(taps.size) ** 2
+    cov_norm = np_ / (np_ - 1.0) if use_sample_covariance else 1.0
+
+    def filt(a):
+        return _correlate1d(_correlate1d(a, taps, 0), taps, 1)
+
+    ux, uy, uxx, uyy, uxy = filt(x), filt(y), filt(x * x), filt(y * y), filt(x * y)
+    vx, vy, vxy = cov_norm * (uxx - ux * ux), cov_norm * (uyy - uy * uy), cov_norm * (uxy - ux * uy)
+    c1, c2 = (K1 * dr) ** 2, (K2 * dr) ** 2
+    s = (2 * ux * uy + c1) * (2 * vxy + c2) / ((ux ** 2 + uy ** 2 + c1) * (vx + vy + c2))
+    mssim = float(s[r:s.shape[0] - r, r:s.shape[1] - r].mean(dtype=np.float64))
+    return (mssim, s) if full else mssim
+
+
+def affine_fit(ref, test, border=10):
+    """(r, a, b): the `border`-cropped images scaled to [0, 1] from 8-bit and the least-squares line test -> a test + b."""
+    r = _crop(ref, border).astype(np.float64) / 255.0
+    t = _crop(test, border).astype(np.float64) / 255.0
+    a, b = np.polyfit(t.ravel(), r.ravel(), 1)
+    return r, t, a, b
+
+
+def ssim_affine(ref, test, border=10, data_range=1.0, **kw):
+    """SSIM of `ref` against `test` after the affine intensity fit of psnr_affine (crop, scale by 1/255, test -> a test + b):
+    the vendor GUI's SSIM of its view (XPR_Software.py:1220-1256; its skimage call cannot be run here, so this restatement is
+    parity-unpinned).  Keywords as for ssim."""
+    r, t, a, b = affine_fit(ref, test, border)
+    return ssim(r, a * t + b, data_range=data_range, **kw)
+
+
+def ecc(ref, test, border=0):
+    """cv2.computeECC's value: the zero-mean normalised cross-correlation sum (r - mean r)(t - mean t) /
+    sqrt(sum (r - mean r)^2 sum (t - mean t)^2) over the `border`-cropped images (the vendor GUI's ECC score,
+    XPR_Software.py:1220-1256; parity-unpinned); nan when either crop is constant."""
+    r = _crop(ref, border).astype(np.float64)
+    t = _crop(test, border).astype(np.float64)
+    r, t = r - r.mean(), t - t.mean()
+    den = np.sqrt(np.sum(r * r) * np.sum(t * t))
+    return float(np.sum(r * t) / den) if den > 0 else float("nan")
 
 
 # ---------------------------------------------------------------------------------------------------------------

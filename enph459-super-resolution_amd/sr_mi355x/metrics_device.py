@@ -1,5 +1,5 @@
 """Device forms of the quality metrics on top of libsrx.so's `srx_pair_moments_*`, `srx_local_contrast_*`,
-`srx_ring_sums_*`, `srx_spot_moments_*`, `srx_edge_magnitude_f64`, `srx_edge_dist_range`, `srx_edge_bins_*` (include/srx.h).
+`srx_ring_sums_*`, `srx_spot_moments_*`, `srx_edge_magnitude_f64`, `srx_edge_dist_range`, `srx_edge_bins_*`, `srx_ssim_*` (include/srx.h).
 
 Same names, arguments and return values as `sr_mi355x.metrics` (which mirrors the reference's notebook / calibration functions:
 mono_cal_target/analysis.ipynb cells 4, 7, 10; data_collection/psf_mtf_utils.py:67-178; the vendor GUI's affine-fit PSNR,
@@ -67,6 +67,79 @@ def psnr_affine(ref, test, border=10, data_range=1.0):
     s_tt, s_tr, s_rr = stt - st * st / n, strr - st * sr / n, srr - sr * sr / n
     mse = max((s_rr - (s_tr * s_tr / s_tt if s_tt > 0 else 0.0)) / n, 0.0) / (255.0 * 255.0)
     return np.inf if mse == 0 else 10.0 * np.log10(data_range ** 2 / mse)
+
+
+def _np_dtype(x):
+    """numpy dtype of a tensor / array (what decides SSIM's default data_range)"""
+    return np.dtype(str(x.dtype).replace("torch.", "")) if isinstance(x, torch.Tensor) else np.asarray(x).dtype
+
+
+def _pair(ref, test):
+    """-> (ref, test) as [B, H, W] device tensors of one precision, the precision, whether the input was one image"""
+    r, prec = _dev(ref)
+    t = test.to(device=r.device, dtype=r.dtype).contiguous() if isinstance(test, torch.Tensor) else _dev64(test).to(r.dtype)
+    one = r.dim() == 2
+    if one:
+        r, t = r[None], t[None]
+    if r.shape != t.shape or r.dim() != 3:
+        raise ValueError("ref and test must be [H, W] or [B, H, W] of the same shape")
+    return r, t, prec, one
+
+
+def _ssim(r, t, prec, one, dtype, affine, *, win_size=None, data_range=None, gaussian_weights=False, sigma=1.5, use_sample_covariance=True,
+          K1=0.01, K2=0.03, full=False, border=0):
+    B, H, W = r.shape
+    h, w = H - 2 * border, W - 2 * border
+    if border < 0 or h <= 0 or w <= 0:
+        raise ValueError(f"border {border} leaves nothing of a {H} x {W} image")
+    rad, taps, dr = metrics.ssim_params((h, w), dtype, win_size, data_range, gaussian_weights, sigma)
+    taps = np.ascontiguousarray(taps, dtype=np.float64)
+    mssim = torch.empty(B, dtype=torch.float64, device=r.device)
+    smap = torch.empty((B, h, w), dtype=r.dtype, device=r.device) if full else None
+    aff = None if affine is None else torch.from_numpy(np.ascontiguousarray(affine, dtype=np.float64)).to(r.device)
+    wt, wp, wn = _ws(B, H, W, 1)
+    _lib.check(api._fn("srx_ssim", prec)(api._p(r), api._p(t), B, H, W, int(border), rad, taps.ctypes.data_as(_lib._HD),
+                                         int(bool(use_sample_covariance)), dr, float(K1), float(K2), None if aff is None else api._p(aff),
+                                         api._p(mssim), None if smap is None else api._p(smap), wp, wn, api._stream()), "srx_ssim")
+    m = [float(v) for v in mssim.cpu().numpy()]
+    m = m[0] if one else m
+    if not full:
+        return m
+    return m, (smap[0] if one else smap)
+
+
+def ssim(ref, test, *, win_size=None, data_range=None, gaussian_weights=False, sigma=1.5, use_sample_covariance=True, K1=0.01, K2=0.03,
+         full=False, border=0):
+    """metrics.ssim (skimage structural_similarity, 2-D) of device images [H, W] or [B, H, W] in one pass over the pair (srx_ssim):
+    a float, or a list for a batch; with full=True also the map S over the crop as a device tensor ([h, w] or [B, h, w]).  float32
+    tensors are computed in float32, everything else in float64; data_range defaults to the input dtype's integer range."""
+    r, t, prec, one = _pair(ref, test)
+    return _ssim(r, t, prec, one, _np_dtype(ref), None, win_size=win_size, data_range=data_range, gaussian_weights=gaussian_weights,
+                 sigma=sigma, use_sample_covariance=use_sample_covariance, K1=K1, K2=K2, full=full, border=border)
+
+
+def ssim_affine(ref, test, border=10, data_range=1.0, **kw):
+    """metrics.ssim_affine on device images (per item for a batch): the line test -> a test + b from the pair's moments (as
+    psnr_affine), then SSIM of ref / 255 against (a / 255) test + b / 255 with the affine applied inside the kernel (no fitted
+    copy).  Parity with the vendor GUI is unpinned, as for metrics.ssim_affine."""
+    r, t, prec, one = _pair(ref, test)
+    aff = []
+    for n, st, sr, stt, strr, _, _ in pair_moments(r, t, border=border):
+        s_tt, s_tr = stt - st * st / n, strr - st * sr / n
+        a = s_tr / s_tt if s_tt > 0 else 0.0
+        aff.append((1.0 / 255.0, a / 255.0, (sr - a * st) / n / 255.0))
+    return _ssim(r, t, prec, one, np.float64, np.asarray(aff), data_range=data_range, border=border, **kw)
+
+
+def ecc(ref, test, border=0):
+    """metrics.ecc of device images (a float, or a list for a batch): the zero-mean normalised cross-correlation from the pair's
+    moments (srx_pair_moments); nan when either crop is constant.  Parity with cv2.computeECC is unpinned."""
+    v = []
+    for n, st, sr, stt, strr, srr, _ in pair_moments(ref, test, border=border):
+        s_tt, s_tr, s_rr = stt - st * st / n, strr - st * sr / n, srr - sr * sr / n
+        den = np.sqrt(s_tt * s_rr) if s_tt > 0 and s_rr > 0 else 0.0
+        v.append(float(s_tr / den) if den > 0 else float("nan"))
+    return v[0] if len(v) == 1 else v
 
 
 def local_contrast(profile, window=20):

@@ -238,7 +238,14 @@ int srx_interleave4_u8(const uint8_t *frames, int B, int h, int w, uint8_t *out,
  *   spot_moments : out = {max, sum p, sum p y, sum p x} over the pixels with p > 0.1 max                       (subpixel_centre)
  *   edge_magnitude: Sobel magnitude of the Gaussian(sigma)-smoothed ROI, scipy.ndimage 'reflect' boundaries; float64 [H, W] -> [H, W]
  *   edge_dist_range / edge_bins: every ROI pixel projected on the normal of the line v = m u + b ((u, v) = (row, col) if rows_are_x else
- *                  (col, row)): min / max of the distances in (-8, 10); sums and counts per 1/4-px bin [lo + i bw, lo + (i + 1) bw). */
+ *                  (col, row)): min / max of the distances in (-8, 10); sums and counts per 1/4-px bin [lo + i bw, lo + (i + 1) bw).
+ *   ssim         : skimage structural_similarity (2-D) of the crop [border, size - border) of ref / test [B, H, W], in ONE pass over the two
+ *                  images: window sums of x, y, x^2, y^2, x y by the separable correlation taps[2 radius + 1] (host float64; uniform or
+ *                  Gaussian) with scipy's 'reflect' boundary, C1 = (k1 data_range)^2, C2 = (k2 data_range)^2, cov_norm = NP / (NP - 1) if
+ *                  sample_cov else 1 (NP = (2 radius + 1)^2).  mssim[b] = mean of S over the crop minus a radius-pixel rim (float64 device);
+ *                  map (or NULL) = S over the whole crop, [B, H - 2 border, W - 2 border] in T.  affine (device [B][3] or NULL) = {ar, at, bt}:
+ *                  x = ar ref, y = at test + bt, applied on the fly (the vendor view's fitted SSIM).  radius 1..7 (larger: SRX_E_UNSUPPORTED);
+ *                  2 radius + 1 must not exceed either side of the crop. */
 size_t srx_metrics_workspace_bytes(int B, int H, int W, int nbin);
 int srx_pair_moments_f32(const float *ref, const float *test, int B, int H, int W, int border, double *out, void *ws, size_t ws_bytes,
                          srx_stream_t stream);
@@ -256,6 +263,12 @@ int srx_edge_bins_f32(const float *roi, int H, int W, double m, double b, double
                       double *out, void *ws, size_t ws_bytes, srx_stream_t stream);
 int srx_edge_bins_f64(const double *roi, int H, int W, double m, double b, double norm, int rows_are_x, double lo, double bw, int nbin,
                       double *out, void *ws, size_t ws_bytes, srx_stream_t stream);
+int srx_ssim_f32(const float *ref, const float *test, int B, int H, int W, int border, int radius, const double *taps, int sample_cov,
+                 double data_range, double k1, double k2, const double *affine, double *mssim, float *map, void *ws, size_t ws_bytes,
+                 srx_stream_t stream);
+int srx_ssim_f64(const double *ref, const double *test, int B, int H, int W, int border, int radius, const double *taps, int sample_cov,
+                 double data_range, double k1, double k2, const double *affine, double *mssim, double *map, void *ws, size_t ws_bytes,
+                 srx_stream_t stream);
 
 #ifdef __cplusplus
 }
