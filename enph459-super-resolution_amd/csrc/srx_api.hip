@@ -15,6 +15,7 @@
 #include "srx_atile.hpp"
 #include "srx_stile.hpp"
 #include "srx_metrics.hpp"
+#include "srx_register.hpp"
 
 using namespace srx;
 
@@ -712,6 +713,21 @@ int srx_edge_dist_range(int H, int W, double m, double b, double norm, int rows_
     }
 SRX_DEFINE_METRICS(f32, float)
 SRX_DEFINE_METRICS(f64, double)
+
+size_t srx_register_workspace_bytes(int elem_bytes, int B, int N, int H, int W, int search)
+{
+    return reg::workspace_bytes(elem_bytes, B, N, H, W, search);
+}
+int srx_register_f32(const float *frames, int B, int N, int H, int W, int ref, const double *init_yx, int search, int border, int n_iter, double tol,
+                     double *shifts, double *score, int *status, void *ws, size_t wsb, srx_stream_t s)
+{
+    return reg::register_frames<float>(frames, B, N, H, W, ref, init_yx, search, border, n_iter, tol, shifts, score, status, ws, wsb, hs(s));
+}
+int srx_register_f64(const double *frames, int B, int N, int H, int W, int ref, const double *init_yx, int search, int border, int n_iter,
+                     double tol, double *shifts, double *score, int *status, void *ws, size_t wsb, srx_stream_t s)
+{
+    return reg::register_frames<double>(frames, B, N, H, W, ref, init_yx, search, border, n_iter, tol, shifts, score, status, ws, wsb, hs(s));
+}
 
 #define SRX_DEFINE(SFX, T)                                                                                             \
     int srx_blur_##SFX(const T *img, int B, int H, int W, const double *k, int kh, int kw, T *out, srx_stream_t s)      \

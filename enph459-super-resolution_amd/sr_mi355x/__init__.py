@@ -13,12 +13,14 @@ _API = ("blur", "forward_model", "back_project", "shift_and_add", "ibp", "ndi_zo
         "FLAG_AUTO", "FLAG_COMPOSED", "FLAG_FUSED", "FLAG_PER_FRAME", "FLAG_TILES", "FLAG_DIAG_NO_ZERO_FUSE",
         "FLAG_DIAG_NO_SEPARABLE", "FLAG_DIAG_NO_PREFILTER_TILE", "FLAG_DIAG_V1", "FLAG_DIAG_WIDE_WINDOWS", "FLAG_DIAG_COLUMN_TILES", "FLAG_DIAG_TWO_LAUNCH", "FLAG_DIAG_SAA_ONE_PASS")
 
-__all__ = list(_API)
+__all__ = list(_API) + ["estimate_shifts"]
 
 
 def __getattr__(name):
     if name in _API:
         return getattr(importlib.import_module(".api", __name__), name)
-    if name in ("api", "synth", "_lib", "session", "parallel", "rowband", "metrics"):
+    if name == "estimate_shifts":
+        return importlib.import_module(".register", __name__).estimate_shifts
+    if name in ("api", "synth", "_lib", "session", "parallel", "rowband", "metrics", "register"):
         return importlib.import_module("." + name, __name__)
     raise AttributeError(name)

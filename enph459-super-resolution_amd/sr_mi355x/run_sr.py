@@ -33,6 +33,9 @@ def main(argv=None):
                          "summary of the reference's analysis.ipynb) next to the PNGs")
     ap.add_argument("--row-bands", action="store_true",
                     help="several GPUs on ONE image: split every image's IBP loop into row bands (cal_target kinds; under torchrun)")
+    ap.add_argument("--register", action="store_true",
+                    help="estimate the frames' shifts on the device (table as the start) and reconstruct with them; "
+                         "writes registration.json next to the PNGs")
     args = ap.parse_args(argv)
     rank, world, local_rank = int(os.environ.get("RANK", "0")), int(os.environ.get("WORLD_SIZE", "1")), int(os.environ.get("LOCAL_RANK", "0"))
     dist = None
@@ -58,7 +61,7 @@ def main(argv=None):
     # --metrics: from the device tensors the PNGs were quantised from (session.write_metrics_device), not from the files
     metrics_cb = session.write_metrics_device if (args.metrics and args.kind == "mono_cal_target") else None
     session.process_sessions(sessions, psf, args.output_dir, args.kind, rank=rank, world=world, on_images=metrics_cb,
-                             row_bands=args.row_bands and world > 1)
+                             row_bands=args.row_bands and world > 1, register=args.register)
     if dist is not None:
         dist.barrier()
     if rank == 0:

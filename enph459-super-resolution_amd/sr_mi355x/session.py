@@ -15,6 +15,11 @@ PNG decode/encode stays on the host (PIL), everything between -- uint8 -> float,
 averaging, frame mean, Native-2x zoom, shift_and_add, ibp, clip+truncate to uint8 -- runs in libsrx on the GPU.
 The reference's matplotlib figures (comparison.png, convergence.png) are not produced; the IBP MSE trace is
 written as `convergence.json` instead.
+
+register=True (run_sr --register) measures the shifts from the loaded frames (sr_mi355x.register.estimate_shifts, with the
+table above as init and anchor: one item per rep for the barcode kinds, the rep-averaged red planes for rgb_cal_target) and
+reconstructs with them; frames whose estimate has a nonzero status keep their table shift.  registration.json records the table,
+the estimates, the shifts used, the scores and the status codes.  Without it, nothing differs.
 """
 import json
 import os
@@ -177,6 +182,23 @@ def reconstruct(frames, shifts, psf_kernel, n_iter, factor=UPSAMPLE_FACTOR, step
         return {"native_2x": native, "SAA": saa[0], "SAA_IBP": hr0, "LR_mean": mean_lr}, errs
     hr, errs = api.ibp_batched(lr[None], shifts, psf_kernel, saa.clone(), factor, n_iter, step)
     return {"native_2x": native, "SAA": saa[0], "SAA_IBP": hr[0], "LR_mean": mean_lr}, [float(e) for e in errs[0].cpu()]
+
+
+def register_shifts(frame_sets, shifts):
+    """register=True: estimate_shifts on B frame sets of one shape (a batch of B items) with the table as init and anchor.
+    -> one (shifts used, registration.json content) per frame set; a frame with a nonzero status keeps its table shift."""
+    import torch
+    from . import register
+    table = np.asarray(shifts, dtype=np.float64)
+    lr = torch.stack([torch.stack(list(fr)) for fr in frame_sets])
+    est, score, status = register.estimate_shifts(lr, init=table, full=True)
+    out = []
+    for b in range(len(frame_sets)):
+        used = np.where((status[b] == 0)[:, None], est[b], table)
+        out.append(([tuple(float(v) for v in s) for s in used],
+                    {"nominal": table.tolist(), "estimated": est[b].tolist(), "used": used.tolist(), "score": score[b].tolist(),
+                     "status": status[b].tolist()}))
+    return out
 
 
 def reconstruct_batch(frame_sets, shifts, psf_kernel, n_iter, factor=UPSAMPLE_FACTOR, step=IBP_STEP_SIZE, lazy_errors=False):
@@ -358,12 +380,13 @@ def _save_outputs(out_dir, images, errors, lr_name, extra=None):
 
 
 def process_session(session_dir, psf_kernel, output_base, kind=None, n_iter=None, verbose=True, batch_reps=True, loaded=None, flush=True,
-                    row_bands=False, on_images=None):
+                    row_bands=False, on_images=None, register=False):
     """Counterpart of process_session / process_combo.  Returns the list of output directories written
     (empty if everything was already done).  batch_reps: the reps of a barcode session that are still to do go through the
     library in one B = reps call (reconstruct_batch) instead of one call per rep; `loaded`: frames already decoded by a
     Prefetcher (what load_corner_reps / load_mono_cal_session / load_rgb_cal_combo would return).  row_bands (the two cal_target
-    kinds: one large image per session): all ranks work on this one session (reconstruct(row_bands=True)), rank 0 writes."""
+    kinds: one large image per session): all ranks work on this one session (reconstruct(row_bands=True)), rank 0 writes.
+    register: reconstruct with shifts estimated from the frames (register_shifts) and write registration.json beside the PNGs."""
     kind = kind or detect_kind(session_dir)
     if kind not in IBP_ITERATIONS:
         raise ValueError("kind must be one of " + ", ".join(IBP_ITERATIONS))
@@ -383,6 +406,9 @@ def process_session(session_dir, psf_kernel, output_base, kind=None, n_iter=None
             frames, shifts = loaded or load_rgb_cal_combo(session_dir)
             lr_name = "LR_red_mean.png"
             extra = {"shifts.json": {"shifts_lr_yx": [list(s) for s in shifts], "corner_labels": CORNER_ORDER}}
+        if register:
+            shifts, reg = register_shifts([frames], shifts)[0]
+            extra = dict(extra or {}, **{"registration.json": reg})
         images, errors = reconstruct(frames, shifts, psf_kernel, n_iter, row_bands=row_bands)
         if images["SAA_IBP"] is None:  # row-band mode, not rank 0: the assembled image lives on rank 0
             return written
@@ -405,12 +431,17 @@ def process_session(session_dir, psf_kernel, output_base, kind=None, n_iter=None
         todo.append((out_dir, frames))
     if not todo:
         return written
-    if batch_reps:
+    extras = [None] * len(todo)
+    if register:  # one registration item per rep (one batched call); each rep then reconstructs with its own shifts
+        regs = register_shifts([fr for _, fr in todo], shifts)
+        results = [reconstruct(fr, used, psf_kernel, n_iter) for (_, fr), (used, _) in zip(todo, regs)]
+        extras = [{"registration.json": reg} for _, reg in regs]
+    elif batch_reps:
         results = reconstruct_batch([fr for _, fr in todo], shifts, psf_kernel, n_iter, lazy_errors=True)
     else:
         results = [reconstruct(fr, shifts, psf_kernel, n_iter) for _, fr in todo]
-    for (out_dir, _), (images, errors) in zip(todo, results):
-        _save_outputs(out_dir, images, errors, "LR_red_mean.png" if red else "LR_mean.png")
+    for (out_dir, _), (images, errors), extra in zip(todo, results, extras):
+        _save_outputs(out_dir, images, errors, "LR_red_mean.png" if red else "LR_mean.png", extra)
         say(f"    Output: {out_dir}")
         written.append(out_dir)
     if flush:
@@ -428,7 +459,7 @@ def load_session(session_dir, kind):
 
 
 def process_sessions(sessions, psf_kernel, output_base, kind, n_iter=None, verbose=True, rank=0, world=1, on_written=None, row_bands=False,
-                     on_images=None):
+                     on_images=None, register=False):
     """The reference's outer loop (mono_cal_target/run_sr.py:358-360, mono_barcodes/run_sr.py:301) over the sessions this
     rank owns (session i -> rank i mod world, parallel.map_sharded: independent items, no data-path collective), with the PNG
     decode and upload of session k + 1 overlapped with the device work of session k.  -> output directories written: by every
@@ -457,7 +488,7 @@ def process_sessions(sessions, psf_kernel, output_base, kind, n_iter=None, verbo
         count[0] += 1
         say(f"\n[rank {rank}: {count[0]}/{len(owned)}] {os.path.basename(sessions[i])}")
         out = process_session(sessions[i], psf_kernel, output_base, kind=kind, n_iter=n_iter, verbose=verbose, loaded=loaded,
-                              flush=on_written is not None, row_bands=row_bands, on_images=on_images)
+                              flush=on_written is not None, row_bands=row_bands, on_images=on_images, register=register)
         if on_written:
             for d in out:
                 on_written(d)

@@ -270,6 +270,29 @@ int srx_ssim_f64(const double *ref, const double *test, int B, int H, int W, int
                  double data_range, double k1, double k2, const double *affine, double *mssim, double *map, void *ws, size_t ws_bytes,
                  srx_stream_t stream);
 
+/* ---- sub-pixel frame registration (translation only), on DEVICE frames ----
+ * frames [B, N, H, W] (the srx_saa layout); for every item b and frame k != ref: d = shifts[b][k] with frames[k] ~ ndi.shift(frames[ref], d),
+ * LR pixels, (dy, dx): the sign convention of shifts_yx, so anchor + d (anchor = the reference frame's known shift) goes straight into
+ * srx_saa / srx_ibp.  shifts[b][ref] is exactly (0, 0).  Every sum runs over the reference crop [m, H - m) x [m, W - m),
+ * m = border + search + 2; frame samples outside the frame take the nearest edge value.
+ *   coarse : zero-mean NCC at every integer d = c0_k + (oy, ox), |oy|, |ox| <= search, c0_k = rint(init[k] - init[ref]) (init: host [N][2]
+ *            or NULL = zeros); the argmax is taken on the device, ties to the smallest |dy| + |dx|, then the smaller dy, then dx.
+ *   refine : Gauss-Newton on sum (t(i + d) - r(i))^2 with t the cubic B-spline interpolant of frame k ('nearest' edges, as ndi.shift) and its
+ *            analytic gradient; each step is clamped to +-0.5 px per axis; a frame stops once max |step| < tol or after n_iter steps.
+ *            No host synchronisation: the call only enqueues work on the stream.  Sums are fixed-order float64 (bit-identical run to run,
+ *            a batch item bit-identical to the same item alone).
+ *   score  : [B, N] float64 device or NULL: zero-mean NCC of t(i + d) against the crop at the returned d (0 if either is constant; 1 at ref).
+ *   status : [B, N] int device or NULL: 0 ok; 1 singular normal matrix (flat or one-directional content: the coarse shift is kept, never
+ *            NaN); 2 coarse argmax on the search boundary; 3 not converged after n_iter steps.
+ * SRX_E_INVALID: a null frames / shifts, B or size <= 0, N < 2, ref outside [0, N), search outside [0, 4], border < 0, n_iter < 0, tol < 0
+ * or NaN, |init[k] - init[ref]| > 1e6.  SRX_E_UNSUPPORTED: a crop smaller than 16 x 16, N > SRX_MAX_FRAMES, B (N - 1) > 65535.
+ * Workspace: srx_register_workspace_bytes(sizeof(T), B, N, H, W, search) (0 for arguments no call accepts) covers every border. */
+size_t srx_register_workspace_bytes(int elem_bytes, int B, int N, int H, int W, int search);
+int srx_register_f32(const float *frames, int B, int N, int H, int W, int ref, const double *init_yx, int search, int border, int n_iter, double tol,
+                     double *shifts, double *score, int *status, void *ws, size_t ws_bytes, srx_stream_t stream);
+int srx_register_f64(const double *frames, int B, int N, int H, int W, int ref, const double *init_yx, int search, int border, int n_iter,
+                     double tol, double *shifts, double *score, int *status, void *ws, size_t ws_bytes, srx_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
