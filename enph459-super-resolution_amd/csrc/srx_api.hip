@@ -1,19 +1,15 @@
 // srx_api.hip -- C ABI of libsrx.so (include/srx.h): primitive entry points, the composed
-// (literal, per-frame) SAA / IBP built from the primitive kernels, and dispatch to the fused
-// tile path (srx_fused.hpp) when a call is eligible for it.
+// (literal, per-frame) SAA / IBP built from the primitive kernels, and the route of a call:
+// route_ibp() decides once which of composed / fused / btile / mosaic (and which row of
+// srx_route.hpp's table of mosaic implementations) takes it; the call, a plan and the exact
+// workspace query all read that one record.
 #include <cstdio>
 #include <cstring>
 
 #include "srx_prims.hpp"
 #include "srx_fused.hpp"
-#include "srx_mosaic.hpp"
-#include "srx_patch.hpp"
-#include "srx_ztile.hpp"
-#include "srx_dtile.hpp"
-#include "srx_ctile.hpp"
+#include "srx_route.hpp"  // srx_mosaic.hpp and every implementation built on it
 #include "srx_btile.hpp"
-#include "srx_atile.hpp"
-#include "srx_stile.hpp"
 #include "srx_metrics.hpp"
 #include "srx_register.hpp"
 
@@ -30,9 +26,10 @@ Profiler &profiler()
 }  // namespace srx
 
 static const char *const g_kernel_names[KID_COUNT] = {
-    "k_blur_pad", "k_prefilter_axis0", "k_prefilter_axis1", "k_fwd_residual", "k_back_gather",
-    "k_blurT_update", "k_interp", "k_fir_pad", "k_crop_div", "k_fwd_tile", "k_bwd_tile",
-    "k_mosaic_build", "k_fwd_mosaic", "k_bwd_mosaic", "k_saa_tile", "k_prefilter_small", "k_prefilter_tile", "k_ibp_patch", "k_ibp_ztile", "k_ibp_dtile", "k_ibp_ctile", "k_ibp_bfwd", "k_ibp_bbwd", "k_ibp_afwd", "k_ibp_abwd", "k_patch_build", "k_patch_build_float", "k_atile_near", "k_ibp_sv", "k_ibp_sh", "k_saa_shift"};
+#define X(id, name) name,
+    SRX_KERNEL_LIST(X)
+#undef X
+};
 
 // One image plane (with SciPy's 12-sample pad on every side) and one item's N frames must stay below 2 GiB: the kernels index a plane with
 // 32-bit offsets and describe it to the memory unit as a buffer resource (32-bit byte count).  The batch is not limited (items are
@@ -318,6 +315,33 @@ static bool basic_ibp_args_ok(const void *lr, int B, int N, int h, int w, const 
 
 #define SRX_MAX_BATCH_PER_LAUNCH 32768  // gridDim.z <= 65535; larger batches go through in chunks of this many items
 
+// The route of one srx_ibp call (valid arguments within the library's limits), decided here and nowhere else: the call itself, a plan and the
+// exact workspace query read it.  The batch size plays no part.  Precondition: runs under the entry point's CallFlags guard, like everything
+// below it -- the eligibility predicates and fused::make_kernel7 read the path-forcing flags through call_flags().  Pure host arithmetic.
+enum Path { PATH_COMPOSED, PATH_FUSED, PATH_BTILE, PATH_MOSAIC };
+struct Route {
+    int status;                    // an early answer (SRX_FLAG_FUSED on a call that cannot fuse), else SRX_OK
+    Path path;
+    const mosaic::ImplRow *impl;   // PATH_MOSAIC: the row of srx_route.hpp's table
+    const char *name;              // what srx_last_path() reports
+};
+
+static Route route_ibp(int eb, int N, int h, int w, int H, int W, int f, const double *sh, const double *k, int kh, int kw, unsigned flags)
+{
+    const bool can_fuse = fused::ibp_eligible(N, h, w, sh, kh, kw, H, W, f);
+    if ((flags & SRX_FLAG_FUSED) && !can_fuse)
+        return {SRX_E_UNSUPPORTED, PATH_COMPOSED, nullptr, "none"};
+    if (!can_fuse || (flags & SRX_FLAG_COMPOSED))
+        return {SRX_OK, PATH_COMPOSED, nullptr, "composed"};
+    if (!(flags & SRX_FLAG_PER_FRAME) && mosaic::eligible(N, h, w, sh, kh, kw, H, W, f)) {
+        const mosaic::ImplRow &impl = mosaic::choose_impl(eb, N, H, W, sh, k, kh, kw, f);
+        return {SRX_OK, PATH_MOSAIC, &impl, impl.name};
+    }
+    if (btile::eligible(eb, N, h, w, sh, k, kh, kw, H, W, f))
+        return {SRX_OK, PATH_BTILE, nullptr, "btile"};
+    return {SRX_OK, PATH_FUSED, nullptr, "fused"};
+}
+
 template <typename T>
 static int ibp_dispatch(const T *lr, int B, int N, int h, int w, const double *sh, const double *k, int kh, int kw,
                         const T *hr_init, int H, int W, int f, int n_iter, double step, T *hr, double *errors, void *ws,
@@ -336,23 +360,22 @@ static int ibp_dispatch(const T *lr, int B, int N, int h, int w, const double *s
         }
         return SRX_OK;
     }
-    const bool can_fuse = fused::ibp_eligible(N, h, w, sh, kh, kw, H, W, f);
-    if ((flags & SRX_FLAG_FUSED) && !can_fuse)
-        return SRX_E_UNSUPPORTED;
-    if (can_fuse && !(flags & SRX_FLAG_COMPOSED)) {
-        if (!(flags & SRX_FLAG_PER_FRAME) && mosaic::eligible(N, h, w, sh, kh, kw, H, W, f)) {
-            return mosaic::ibp<T>(lr, B, N, h, w, sh, k, kh, kw, hr_init, H, W, f, n_iter, step, hr, errors, ws, wsb, st, &g_last_path);
-        }
-        if constexpr (sizeof(T) == 4) {
-            if (btile::eligible(4, N, h, w, sh, k, kh, kw, H, W, f)) {
-                g_last_path = "btile";
-                return btile::ibp(lr, B, N, h, w, sh, k, kh, kw, hr_init, H, W, n_iter, step, hr, errors, ws, wsb, st);
-            }
-        }
-        g_last_path = "fused";
+    const Route r = route_ibp((int)sizeof(T), N, h, w, H, W, f, sh, k, kh, kw, flags);
+    if (r.status != SRX_OK)
+        return r.status;
+    g_last_path = r.name;
+    switch (r.path) {
+    case PATH_MOSAIC:
+        return mosaic::ibp<T>(*r.impl, lr, B, N, h, w, sh, k, kh, kw, hr_init, H, W, f, n_iter, step, hr, errors, ws, wsb, st);
+    case PATH_BTILE:
+        if constexpr (sizeof(T) == 4)
+            return btile::ibp(lr, B, N, h, w, sh, k, kh, kw, hr_init, H, W, n_iter, step, hr, errors, ws, wsb, st);
+        return SRX_E_INVALID;  // (route_ibp gives float32 calls alone this path)
+    case PATH_FUSED:
         return fused::ibp<T>(lr, B, N, h, w, sh, k, kh, kw, hr_init, H, W, f, n_iter, step, hr, errors, ws, wsb, st);
+    case PATH_COMPOSED:
+        break;
     }
-    g_last_path = "composed";
     return ibp_composed<T>(lr, B, N, h, w, sh, k, kh, kw, hr_init, H, W, f, n_iter, step, hr, errors, ws, wsb, st);
 }
 
@@ -422,16 +445,14 @@ static int plan_create(const T *lr, int B, int N, int h, int w, const double *sh
     std::memcpy(p->k, k, sizeof(double) * kh * kw);
     Arena ar(ws, wsb);
     int rc = SRX_OK;
-    bool z = false;
-    if constexpr (sizeof(T) == 4) {
-        z = !(flags & (SRX_FLAG_COMPOSED | SRX_FLAG_PER_FRAME)) && fused::ibp_eligible(N, h, w, sh, kh, kw, H, W, f) &&
-            mosaic::eligible(N, h, w, sh, kh, kw, H, W, f) && mosaic::choose_impl(4, N, H, W, sh, k, kh, kw, f) == mosaic::IMPL_ZTILE;
+    const Route r = route_ibp((int)sizeof(T), N, h, w, H, W, f, sh, k, kh, kw, flags);
+    const bool z = r.status == SRX_OK && r.path == PATH_MOSAIC && r.impl->id == mosaic::IMPL_ZTILE;
+    if constexpr (sizeof(T) == 4) {  // (k_ibp_ztile is float32 only: ztile::eligible)
         if (z) {
             mosaic::Common<float> c;
-            rc = mosaic::common_prep<float>(c, mosaic::IMPL_ZTILE, lr, B, N, h, w, sh, k, kh, kw, H, W, f, ar, st, tr_lo, tr_hi);
+            rc = mosaic::common_prep<float>(c, false, lr, B, N, h, w, sh, k, kh, kw, H, W, f, step, ar, st, tr_lo, tr_hi);
             if (rc == SRX_OK)
-                rc = ztile::setup(p->zs, hr_init, B, N, c.py, c.px, c.kc, c.kt, c.Mg, c.Cg, c.Mu, c.ncu, c.nyx, c.NS, c.NB, c.Vtot, ar, H, W, step,
-                                  1.0 / ((double)h * (double)w) / (double)N, tr_lo, tr_hi, st);
+                rc = ztile::setup(p->zs, c, hr_init, tr_lo, tr_hi, ar, st);
             p->z = true, p->path = "ztile";
         }
     }
@@ -640,16 +661,17 @@ size_t srx_ibp_workspace_bytes_for(int eb, int B, int N, int h, int w, int H, in
                                    int kw, unsigned flags)
 {
     const size_t bound = srx_ibp_workspace_bytes(eb, B, N, h, w, H, W, f, flags);
-    if (!sh || !k || N <= 0 || N > SRX_MAX_FRAMES || (flags & (SRX_FLAG_COMPOSED | SRX_FLAG_PER_FRAME)))
+    if (!sh || !k || N <= 0 || N > SRX_MAX_FRAMES)
         return bound;
     if (B > SRX_MAX_BATCH_PER_LAUNCH)
         B = SRX_MAX_BATCH_PER_LAUNCH;
     CallFlags cf(flags);
-    if (!(fused::ibp_eligible(N, h, w, sh, kh, kw, H, W, f) && mosaic::eligible(N, h, w, sh, kh, kw, H, W, f)))
+    const Route r = route_ibp(eb, N, h, w, H, W, f, sh, k, kh, kw, flags);
+    if (r.status != SRX_OK || r.path != PATH_MOSAIC)
         return bound;
     // exactly what the call carves.  The shape-only bound covers it by construction (tests/test_abi.py sweeps shapes for need <= bound);
     // should the two ever disagree, the call's own need is the answer that lets it run
-    return mosaic::ibp_ws_for(eb, B, N, H, W, sh, k, kh, kw, f);
+    return mosaic::ibp_ws_for(*r.impl, eb, B, N, H, W);
 }
 
 int srx_interleave4_u8(const uint8_t *frames, int B, int h, int w, uint8_t *out, srx_stream_t s)

@@ -449,9 +449,11 @@ __global__ void __launch_bounds__(NBY *NBX * 64, 2)
 }
 
 // ---- host ---------------------------------------------------------------------------------------------------------------
+static inline bool shape_admits(int elem_bytes, int H, int W) { return elem_bytes == 4 && H >= 32 && W >= 32; }
+
 static inline bool eligible(int elem_bytes, int N, int H, int W, const double *sh, const double *k, int kh, int kw, int f)
 {
-    if (elem_bytes != 4 || f < 2 || H < 32 || W < 32 || (size_t)(H + 32) * (W + 32) >= (1u << 28) || (call_flags() & SRX_FLAG_TILES))
+    if (!shape_admits(elem_bytes, H, W) || f < 2 || (size_t)(H + 32) * (W + 32) >= (1u << 28) || (call_flags() & SRX_FLAG_TILES))
         return false;
     mosaic::AxisPlan py, px;
     if (!mosaic::plan_axis(N, sh, 0, f, py) || !mosaic::plan_axis(N, sh, 1, f, px))
@@ -461,9 +463,8 @@ static inline bool eligible(int elem_bytes, int N, int H, int W, const double *s
     return kc.separable != 0;
 }
 
-static inline size_t tabs_bytes(int B, int N, int H, int W)
+static inline size_t tabs_bytes(int, int B, int, int H, int W)
 {
-    (void)N;
     const size_t Hp = H + 2 * SRX_NPAD, Wp = W + 2 * SRX_NPAD, Hg = Hp + 3, Wg = Wp + 3;
     const size_t nwin = (size_t)cdiv((int)Hp + 1, Geo<2, 2>::OWNY) * cdiv((int)Wp + 1, Geo<2, 2>::OWNX), nnear = cdiv((int)(20 * (Hg + Wg)), 256);
     const size_t Qn = (Hg + 3) / 4;
@@ -472,12 +473,11 @@ static inline size_t tabs_bytes(int B, int N, int H, int W)
            align_up((size_t)B * (nwin + nnear) * sizeof(double));
 }
 
-static int iterate(const float *hr_init, float *hr, int B, int N, int f, const mosaic::AxisPlan &py, const mosaic::AxisPlan &px,
-                   const fused::Kernel7<float> &kc, const fused::Kernel7<float> &kt, const float *Mg, const float *Cg, const float *Mu,
-                   const int *ncu, const int *nyx, int NS, int NB, const double *Vtot, Arena &ar, int H, int W, int n_iter, double step,
-                   double scale, double *errors, hipStream_t st)
+static int iterate(const mosaic::Common<float> &c, const float *hr_init, float *hr, int n_iter, double *errors, Arena &ar, hipStream_t st)
 {
-    (void)f;
+    const int B = c.B, H = c.H, W = c.W, NB = c.NB;
+    const mosaic::AxisPlan &py = c.py, &px = c.px;
+    const double scale = c.scale;
     constexpr int NBY = 2, NBX = 2;
     const int Hp = H + 2 * SRX_NPAD, Wp = W + 2 * SRX_NPAD, Hg = Hp + 3, Wg = Wp + 3, W4 = (W + 3) / 4;
     AArgs A;
@@ -485,7 +485,7 @@ static int iterate(const float *hr_init, float *hr, int B, int N, int f, const m
     A.nwy = cdiv(Hp + 1, Geo<NBY, NBX>::OWNY), A.nwx = cdiv(Wp + 1, Geo<NBY, NBX>::OWNX);
     A.Dy = py.D, A.Dx = px.D, A.PBy = py.PB, A.PBx = px.PB;
     A.nnear = cdiv(NB, 256);
-    A.sn = (float)step / (float)N;
+    A.sn = (float)c.step / (float)c.N;
     float *S = ar.take<float>((size_t)B * W4 * H * 4);
     const int Qn = (Hg + 3) / 4;
     float *G = ar.take<float>((size_t)B * Qn * Wg * 4);       // four rows interleaved
@@ -499,34 +499,22 @@ static int iterate(const float *hr_init, float *hr, int B, int N, int f, const m
     const double kq = -6.0 * patch::ZD;
     A.kby[7] = A.kbx[7] = A.kty[7] = A.ktx[7] = 0.f;
     for (int i = 0; i < 7; i++) {
-        A.kby[i] = (float)(kq * (double)kc.cy[i]), A.kbx[i] = (float)(kq * (double)kc.cx[i]);
-        A.kty[i] = kt.cy[i], A.ktx[i] = kt.cx[i];
+        A.kby[i] = (float)(kq * (double)c.kc.cy[i]), A.kbx[i] = (float)(kq * (double)c.kc.cx[i]);
+        A.kty[i] = c.kt.cy[i], A.ktx[i] = c.kt.cx[i];
     }
-    double wv[4];
-    fused::host_weights(py.zero ? 0.0 : 1.0 - py.delta, wv);
-    for (int i = 0; i < 4; i++)
-        A.wfy[i] = (float)wv[i];
-    fused::host_weights(px.zero ? 0.0 : 1.0 - px.delta, wv);
-    for (int i = 0; i < 4; i++)
-        A.wfx[i] = (float)wv[i];
-    fused::host_weights(py.delta, wv);
-    for (int i = 0; i < 4; i++)
-        A.wby[i] = (float)(kq * wv[i]);
-    fused::host_weights(px.delta, wv);
-    for (int i = 0; i < 4; i++)
-        A.wbx[i] = (float)(kq * wv[i]);
+    fused::axis_firs<float>(py.delta, px.delta, kq, A.wfy, A.wfx, A.wby, A.wbx);
     const dim3 cgrid(cdiv(W4, 64), cdiv(H, 4), B), cblk(64, 4);
     hipLaunchKernelGGL(k_atile_copy_in, cgrid, cblk, 0, st, hr_init, H, W, W4, S);
     SRX_CHECK_LAUNCH();
-    hipLaunchKernelGGL(k_atile_prep, dim3(cdiv(Wg, 64), Qn, B), dim3(64), 0, st, Mg, Cg, Hg, Wg, Qn, MCq);
+    hipLaunchKernelGGL(k_atile_prep, dim3(cdiv(Wg, 64), Qn, B), dim3(64), 0, st, c.Mg, c.Cg, Hg, Wg, Qn, MCq);
     SRX_CHECK_LAUNCH();
     if (fill_bytes(G, 0, (size_t)B * Qn * Wg * 16, st) != hipSuccess)  // (the rows of the last quad past the plane are read, never written)
         return SRX_E_HIP;
     const dim3 gridf(A.nwx, A.nwy, B), gridb(cdiv(Wp, Geo<NBY, NBX>::OWBX), cdiv(Hp, Geo<NBY, NBX>::OWBY), B), blk(NBY * NBX * 64);
     for (int it = 0; it < n_iter; it++) {
         SRX_LAUNCH(KID_IBP_AFWD, (k_ibp_afwd<NBY, NBX>), gridf, blk, 0, st, S, MCq, G, Yb, A, errors ? epart : nullptr, scale);
-        SRX_LAUNCH(KID_ATILE_NEAR, k_atile_near, dim3(A.nnear, B), dim3(256), 0, st, Mg, Mu, ncu, nyx, NS, NB, Yb, G, A, errors ? epart : nullptr, scale);
-        SRX_LAUNCH(KID_IBP_ABWD, (k_ibp_abwd<NBY, NBX>), gridb, blk, 0, st, G, S, A, epart, Vtot, scale, errors ? errors + it : nullptr, n_iter);
+        SRX_LAUNCH(KID_ATILE_NEAR, k_atile_near, dim3(A.nnear, B), dim3(256), 0, st, c.Mg, c.Mu, c.ncu, c.nyx, c.NS, NB, Yb, G, A, errors ? epart : nullptr, scale);
+        SRX_LAUNCH(KID_IBP_ABWD, (k_ibp_abwd<NBY, NBX>), gridb, blk, 0, st, G, S, A, epart, c.Vtot, scale, errors ? errors + it : nullptr, n_iter);
     }
     hipLaunchKernelGGL(k_atile_copy_out, cgrid, cblk, 0, st, S, H, W, W4, hr);
     SRX_CHECK_LAUNCH();

@@ -66,38 +66,44 @@ struct Arena {
 __host__ __device__ static inline int cdiv(int a, int b) { return (a + b - 1) / b; }
 
 // ---- optional per-kernel timing with HIP events on the launch stream (bench.py's roofline leg) ----
+// one list for the ids and the names srx_profile_kernel_name() reports (bench.py keys its roofline on the strings): order and
+// spelling are ABI, tests/test_abi.py pins them
+#define SRX_KERNEL_LIST(X) \
+    X(KID_BLUR_PAD, "k_blur_pad") \
+    X(KID_PREFILTER_AXIS0, "k_prefilter_axis0") \
+    X(KID_PREFILTER_AXIS1, "k_prefilter_axis1") \
+    X(KID_FWD_RESIDUAL, "k_fwd_residual") \
+    X(KID_BACK_GATHER, "k_back_gather") \
+    X(KID_BLURT_UPDATE, "k_blurT_update") \
+    X(KID_ZOOM_INTERP, "k_interp") \
+    X(KID_FIR_PAD, "k_fir_pad") \
+    X(KID_CROP_DIV, "k_crop_div") \
+    X(KID_FWD_TILE, "k_fwd_tile") \
+    X(KID_BWD_TILE, "k_bwd_tile") \
+    X(KID_MOSAIC_BUILD, "k_mosaic_build") \
+    X(KID_FWD_MOSAIC, "k_fwd_mosaic") \
+    X(KID_BWD_MOSAIC, "k_bwd_mosaic") \
+    X(KID_SAA_TILE, "k_saa_tile") \
+    X(KID_PREFILTER_SMALL, "k_prefilter_small") \
+    X(KID_PREFILTER_TILE, "k_prefilter_tile") \
+    X(KID_IBP_PATCH, "k_ibp_patch") \
+    X(KID_IBP_ZTILE, "k_ibp_ztile") \
+    X(KID_IBP_DTILE, "k_ibp_dtile") \
+    X(KID_IBP_CTILE, "k_ibp_ctile") \
+    X(KID_IBP_BFWD, "k_ibp_bfwd") \
+    X(KID_IBP_BBWD, "k_ibp_bbwd") \
+    X(KID_IBP_AFWD, "k_ibp_afwd") \
+    X(KID_IBP_ABWD, "k_ibp_abwd") \
+    X(KID_PATCH_BUILD, "k_patch_build") \
+    X(KID_PATCH_FLAGS, "k_patch_build_float") \
+    X(KID_ATILE_NEAR, "k_atile_near") \
+    X(KID_IBP_SV, "k_ibp_sv") \
+    X(KID_IBP_SH, "k_ibp_sh") \
+    X(KID_SAA_SHIFT, "k_saa_shift")
 enum KernelId {
-    KID_BLUR_PAD = 0,
-    KID_PREFILTER_AXIS0,
-    KID_PREFILTER_AXIS1,
-    KID_FWD_RESIDUAL,
-    KID_BACK_GATHER,
-    KID_BLURT_UPDATE,
-    KID_ZOOM_INTERP,
-    KID_FIR_PAD,
-    KID_CROP_DIV,
-    KID_FWD_TILE,
-    KID_BWD_TILE,
-    KID_MOSAIC_BUILD,
-    KID_FWD_MOSAIC,
-    KID_BWD_MOSAIC,
-    KID_SAA_TILE,
-    KID_PREFILTER_SMALL,
-    KID_PREFILTER_TILE,
-    KID_IBP_PATCH,
-    KID_IBP_ZTILE,
-    KID_IBP_DTILE,
-    KID_IBP_CTILE,
-    KID_IBP_BFWD,
-    KID_IBP_BBWD,
-    KID_IBP_AFWD,
-    KID_IBP_ABWD,
-    KID_PATCH_BUILD,
-    KID_PATCH_FLAGS,
-    KID_ATILE_NEAR,
-    KID_IBP_SV,
-    KID_IBP_SH,
-    KID_SAA_SHIFT,
+#define X(id, name) id,
+    SRX_KERNEL_LIST(X)
+#undef X
     KID_COUNT
 };
 

@@ -64,19 +64,21 @@ template <int NR> struct Lds {
                          LDS_T = OFF_ZERO + 4;
 };
 
+static inline bool shape_admits(int, int H, int W) { return H >= 128 && W >= 128; }
+
 static inline bool eligible(int elem_bytes, int N, int H, int W, const double *sh, const double *k, int kh, int kw, int f)
 {
     // float64 by default; float32 only on request (SRX_FLAG_DIAG_COLUMN_TILES: the A/B partner of k_ibp_ztile)
     if (elem_bytes == 4 ? !(call_flags() & SRX_FLAG_DIAG_COLUMN_TILES) : elem_bytes != 8)
         return false;
-    if (H < 128 || W < 128 || f < 2 || (call_flags() & SRX_FLAG_TILES))
+    if (!shape_admits(elem_bytes, H, W) || f < 2 || (call_flags() & SRX_FLAG_TILES))
         return false;
     mosaic::AxisPlan py, px;
     if (!mosaic::plan_axis(N, sh, 0, f, py) || !mosaic::plan_axis(N, sh, 1, f, px))
         return false;
     fused::Kernel7<double> kc;
     fused::make_kernel7<double>(k, kh, kw, false, kc);
-    return kc.separable && ztile::axis_ok(py, N, f) && ztile::axis_ok(px, N, f);
+    return kc.separable && ztile::axis_ok(py, f) && ztile::axis_ok(px, f);
 }
 
 // ---- once per call -----------------------------------------------------------------------------------------------------
@@ -533,23 +535,17 @@ static inline size_t tabs_bytes(int eb, int B, int N, int H, int W)
 }
 
 template <typename T>
-static int iterate(const T *hr_init, T *hr, int B, int N, const mosaic::AxisPlan &py, const mosaic::AxisPlan &px, const fused::Kernel7<T> &kc,
-                   const fused::Kernel7<T> &kt, const T *Mg, const T *Cg, const T *Mu, const int *ncu, const int *nyx, int NS, int NB,
-                   const double *Vtot, Arena &ar, int H, int W, int n_iter, double step, double scale, double *errors, hipStream_t st)
+static int iterate(const mosaic::Common<T> &c, const T *hr_init, T *hr, int n_iter, double *errors, Arena &ar, hipStream_t st)
 {
+    const int B = c.B, N = c.N, H = c.H, W = c.W, NS = c.NS;
+    const mosaic::AxisPlan &py = c.py, &px = c.px;
+    const double step = c.step, scale = c.scale, *Vtot = c.Vtot;
     constexpr int VTY = Rows<T>::NR - 2 * HALO;
     ztile::ZArgs za;  // the near-band enumeration and its table builder are srx_ztile.hpp's
     za.H = H, za.W = W, za.tiles_x = cdiv(W, VT), za.tiles_y = cdiv(H, VTY);
     za.HP = za.tiles_y * VTY + 2 * HALO, za.WP = za.tiles_x * VT + 2 * HALO;
     const int HP = za.HP, WP = za.WP;
-    auto ext = [&](const mosaic::AxisPlan &pl, int &ex, int &nb) {
-        int nmin = pl.n[0], nmax = pl.n[0];
-        for (int k = 1; k < N; k++)
-            nmin = std::min(nmin, pl.n[k]), nmax = std::max(nmax, pl.n[k]);
-        ex = nmax, nb = -nmin;
-    };
-    ext(py, za.exy, za.nby);
-    ext(px, za.exx, za.nbx);
+    za.exy = py.nmax, za.nby = -py.nmin, za.exx = px.nmax, za.nbx = -px.nmin;
     za.Ey = py.E, za.Ex = px.E;
     za.WT = W + za.exx, za.LN = za.exx + za.nbx, za.TOPN = (za.exy + za.nby) * za.WT;
     za.ngrp = NS / 4;
@@ -573,12 +569,12 @@ static int iterate(const T *hr_init, T *hr, int B, int N, const mosaic::AxisPlan
         return SRX_E_WORKSPACE;
     KwTab kv;
     for (int i = 0; i < 8; i++) {
-        kv.v[i] = i < 7 ? (double)kc.cy[i] : 0.0, kv.v[8 + i] = i < 7 ? (double)kc.cx[i] : 0.0;
-        kv.v[16 + i] = i < 7 ? (double)kt.cy[i] : 0.0, kv.v[24 + i] = i < 7 ? (double)kt.cx[i] : 0.0;
+        kv.v[i] = i < 7 ? (double)c.kc.cy[i] : 0.0, kv.v[8 + i] = i < 7 ? (double)c.kc.cx[i] : 0.0;
+        kv.v[16 + i] = i < 7 ? (double)c.kt.cy[i] : 0.0, kv.v[24 + i] = i < 7 ? (double)c.kt.cx[i] : 0.0;
     }
     hipLaunchKernelGGL(k_ctile_kw<T>, dim3(1), dim3(64), 0, st, kv, kw);
     SRX_CHECK_LAUNCH();
-    hipLaunchKernelGGL(k_ctile_prep<T>, dim3(cdiv(WP, 256), HP / 2, B + 1), dim3(256), 0, st, Mg, Cg, B, H, W, HP, WP, za.nby, za.nbx, Mp, Cp);
+    hipLaunchKernelGGL(k_ctile_prep<T>, dim3(cdiv(WP, 256), HP / 2, B + 1), dim3(256), 0, st, c.Mg, c.Cg, B, H, W, HP, WP, za.nby, za.nbx, Mp, Cp);
     SRX_CHECK_LAUNCH();
     if (fill_bytes(cmok, 0xff, (size_t)B * sizeof(int), st) != hipSuccess)
         return SRX_E_HIP;
@@ -589,9 +585,9 @@ static int iterate(const T *hr_init, T *hr, int B, int N, const mosaic::AxisPlan
     hipLaunchKernelGGL(k_ctile_copy_in<T>, dim3(cdiv(W, 256), H, B), dim3(256), 0, st, hr_init, H, W, HP, WP, s0);
     SRX_CHECK_LAUNCH();
     if (NT > 0) {
-        hipLaunchKernelGGL(ztile::k_ztile_near_tab, dim3(cdiv(NT, 256)), dim3(256), 0, st, ncu, nyx, NS, py.PB, px.PB, za, NT, nrec, nent);
+        hipLaunchKernelGGL(ztile::k_ztile_near_tab, dim3(cdiv(NT, 256)), dim3(256), 0, st, c.ncu, c.nyx, NS, py.PB, px.PB, za, NT, nrec, nent);
         SRX_CHECK_LAUNCH();
-        hipLaunchKernelGGL(k_ctile_near_m<T>, dim3(cdiv(NT, 256), B), dim3(256), 0, st, Mg, Mu, NB, py.PB, px.PB, za, NT, Mn);
+        hipLaunchKernelGGL(k_ctile_near_m<T>, dim3(cdiv(NT, 256), B), dim3(256), 0, st, c.Mg, c.Mu, c.NB, py.PB, px.PB, za, NT, Mn);
         SRX_CHECK_LAUNCH();
     }
     CTabs<T> tb{Mp, Cp, CM4, cmok, kw, nrec, nent, Mn};

@@ -139,20 +139,13 @@ static inline bool plan(int H, int W, Plan &pl)
     return true;
 }
 
-// the superset of every shape plan() admits whatever the call flags say: what the shape-only workspace bound tests
-static inline bool shape_ok(int H, int W) { return H >= RY && W >= 64 * 3 && H % ALIGN_Y == 0 && W % ALIGN_X == 0; }
-
-static inline void axis_span(const mosaic::AxisPlan &pl, int N, int &ex, int &nb)
-{
-    int nmin = pl.n[0], nmax = pl.n[0];
-    for (int k = 1; k < N; k++)
-        nmin = std::min(nmin, pl.n[k]), nmax = std::max(nmax, pl.n[k]);
-    ex = nmax, nb = -nmin;
-}
+// the superset of every shape plan() admits whatever the call flags say: what the shape-only workspace bound tests (256-row windows of
+// 192 (4 x 3 waves) or 256 columns, origins on row quads / 16-column groups)
+static inline bool shape_admits(int elem_bytes, int H, int W) { return elem_bytes == 4 && H >= RY && W >= 64 * 3 && H % ALIGN_Y == 0 && W % ALIGN_X == 0; }
 
 static inline bool eligible(int elem_bytes, int N, int H, int W, const double *sh, const double *k, int kh, int kw, int f)
 {
-    if (elem_bytes != 4 || f < 2 || (H == patch::PN && W == patch::PN && !(call_flags() & SRX_FLAG_DIAG_WIDE_WINDOWS)) || (call_flags() & SRX_FLAG_TILES))
+    if (!shape_admits(elem_bytes, H, W) || f < 2 || (H == patch::PN && W == patch::PN && !(call_flags() & SRX_FLAG_DIAG_WIDE_WINDOWS)) || (call_flags() & SRX_FLAG_TILES))
         return false;
     mosaic::AxisPlan py, px;
     if (!mosaic::plan_axis(N, sh, 0, f, py) || !mosaic::plan_axis(N, sh, 1, f, px))
@@ -170,14 +163,12 @@ static inline bool eligible(int elem_bytes, int N, int H, int W, const double *s
         if (!ring0)
             return false;
     }
-    if (!(patch::axis_ok(py, N, f) && patch::axis_ok(px, N, f)))
+    if (!(patch::axis_ok(py, f) && patch::axis_ok(px, f)))
         return false;
     Plan pl;
     if (!plan(H, W, pl))
         return false;
-    int exy, nby, exx, nbx;
-    axis_span(py, N, exy, nby);
-    axis_span(px, N, exx, nbx);
+    const int exy = py.nmax, nby = -py.nmin, exx = px.nmax, nbx = -px.nmin;
     return (exy + nby) * (256 + exx) + (RY - nby) * (exx + nbx) <= NN_PAD;  // the corner window's near band fits its lists
 }
 
@@ -793,7 +784,7 @@ __global__ void __launch_bounds__(256 * NSX)
 }
 
 // ---- host ----------------------------------------------------------------------------------------------------------
-static inline size_t tabs_bytes(int B, int N, int H, int W)
+static inline size_t tabs_bytes(int, int B, int N, int H, int W)
 {
     const size_t ngrp = ((size_t)N + 3) / 4, plane = (size_t)H * W, ntabs = 128, ntiles = 1024;
     return 3 * align_up((size_t)B * plane * 4) + align_up((size_t)B * (W / 4) * H * 4) + align_up((size_t)B * 4) + align_up(plane * 4) +
@@ -849,11 +840,12 @@ static int launch_iter(dim3 grid, hipStream_t st, const float *src, float *dst, 
     return SRX_OK;
 }
 
-static int iterate(const float *hr_init, float *hr, int B, int N, int f, const mosaic::AxisPlan &py, const mosaic::AxisPlan &px,
-                   const fused::Kernel7<float> &kc, const fused::Kernel7<float> &kt, const float *Mg, const float *Cg, const float *Mu,
-                   const int *ncu, const int *nyx, int NS, int NB, const double *Vtot, Arena &ar, int H, int W, int n_iter, double step,
-                   double scale, double *errors, hipStream_t st)
+static int iterate(const mosaic::Common<float> &c, const float *hr_init, float *hr, int n_iter, double *errors, Arena &ar, hipStream_t st)
 {
+    const int B = c.B, N = c.N, f = c.f, H = c.H, W = c.W, NS = c.NS;
+    const mosaic::AxisPlan &py = c.py, &px = c.px;
+    const double *Vtot = c.Vtot;
+    const double scale = c.scale;
     Plan pl;
     if (!plan(H, W, pl))
         return SRX_E_UNSUPPORTED;
@@ -873,31 +865,18 @@ static int iterate(const float *hr_init, float *hr, int B, int N, int f, const m
     float *k2 = ar.take<float>(112);
     if (!ar.ok)
         return SRX_E_WORKSPACE;
-    int psf = 0;
-    if (!(kc.separable && kt.separable)) {
+    const int psf = fused::psf_form(c.kc, c.kt);
+    if (psf != 0) {
         if (pl.nsx != 3)
             return SRX_E_UNSUPPORTED;
-        const double kq = -6.0 * patch::ZD;
-        bool ring0 = true;
-        for (int i = 0; i < 7; i++)
-            for (int e : {i, 42 + i, 7 * i, 7 * i + 6})
-                ring0 = ring0 && kc.k[e] == 0.f && kt.k[e] == 0.f;
-        psf = ring0 ? 2 : 3;
-        patch::K2Pair kv;
-        for (int c = 0; c < 7; c++)
-            for (int r = 0; r < 8; r++) {
-                kv.v[8 * c + r] = r < 7 ? (float)(kq * kq * (double)kc.k[7 * r + c]) : 0.f;
-                kv.v[56 + 8 * c + r] = r < 7 ? kt.k[7 * r + c] : 0.f;
-            }
-        hipLaunchKernelGGL(patch::k_patch_k2, dim3(1), dim3(128), 0, st, kv, k2);
-        SRX_CHECK_LAUNCH();
+        SRX_TRY(patch::upload_k2(c.kc, c.kt, k2, st));
     }
     DArgs da;
     da.H = H, da.W = W, da.tiles_x = pl.tx.n, da.tiles_y = pl.ty.n;
     patch::AxisWPair awp;
-    patch::fill_axis(py, N, kc.cy, kt.cy, da.y, awp.y);
-    patch::fill_axis(px, N, kc.cx, kt.cx, da.x, awp.x);
-    da.sn = (float)step / (float)N;
+    patch::fill_axis(py, c.kc.cy, c.kt.cy, da.y, awp.y);
+    patch::fill_axis(px, c.kc.cx, c.kt.cx, da.x, awp.x);
+    da.sn = (float)c.step / (float)N;
     da.ngrp = ngrp;
     unsigned long long d0[4], d1[4];
     da.c01 = patch::c01_masks(py, px, N, f, d0, d1) ? 1 : 0;  // (its masks are a 256-pixel image's: only the verdict is used here)
@@ -912,11 +891,11 @@ static int iterate(const float *hr_init, float *hr, int B, int N, int f, const m
     // ---- operand planes, near-band tables, state
     if (fill_bytes(m8, 0xff, (size_t)B * sizeof(int), st) != hipSuccess)
         return SRX_E_HIP;
-    hipLaunchKernelGGL(k_dtile_prep, dim3(cdiv(W, 32), cdiv(H, 32), B + 1), dim3(32, 8), 0, st, Mg, Cg, B, H, W, da.y.nb, da.x.nb, Mt, Ct, Mt8, m8);
+    hipLaunchKernelGGL(k_dtile_prep, dim3(cdiv(W, 32), cdiv(H, 32), B + 1), dim3(32, 8), 0, st, c.Mg, c.Cg, B, H, W, da.y.nb, da.x.nb, Mt, Ct, Mt8, m8);
     SRX_CHECK_LAUNCH();
-    hipLaunchKernelGGL(k_dtile_near_tab, dim3(NN_PAD / 256, ntabs), dim3(256), 0, st, ncu, nyx, NS, py.PB, px.PB, da, RX, tiles, ntiles, nnt, nrec, nent, ntabs);
+    hipLaunchKernelGGL(k_dtile_near_tab, dim3(NN_PAD / 256, ntabs), dim3(256), 0, st, c.ncu, c.nyx, NS, py.PB, px.PB, da, RX, tiles, ntiles, nnt, nrec, nent, ntabs);
     SRX_CHECK_LAUNCH();
-    hipLaunchKernelGGL(k_dtile_near_m, dim3(NN_PAD / 256, ntabs, B), dim3(256), 0, st, Mg, Mu, NB, py.PB, px.PB, da, RX, tiles, ntiles, Mn, ntabs);
+    hipLaunchKernelGGL(k_dtile_near_m, dim3(NN_PAD / 256, ntabs, B), dim3(256), 0, st, c.Mg, c.Mu, c.NB, py.PB, px.PB, da, RX, tiles, ntiles, Mn, ntabs);
     SRX_CHECK_LAUNCH();
     hipLaunchKernelGGL(k_dtile_copy_in, dim3(cdiv(W, 256), H / 4, B), dim3(256), 0, st, hr_init, H, W, s0);
     SRX_CHECK_LAUNCH();

@@ -105,6 +105,32 @@ template <typename T> static void make_kernel7(const double *k, int kh, int kw, 
     }
 }
 
+// the form of the two blurs a register-resident kernel runs: 0 rank 1 (7 + 7 taps), 2 a 7 x 7 whose outer ring is zero (the reference's
+// measured PSF: a 5 x 5 core), 3 full 7 x 7
+template <typename T> static inline int psf_form(const Kernel7<T> &kc, const Kernel7<T> &kt)
+{
+    if (kc.separable && kt.separable)
+        return 0;
+    bool ring0 = true;
+    for (int i = 0; i < 7; i++)
+        for (int e : {i, 42 + i, 7 * i, 7 * i + 6})
+            ring0 = ring0 && kc.k[e] == (T)0 && kt.k[e] == (T)0;
+    return ring0 ? 2 : 3;
+}
+
+// the four spline FIRs of a call with common fractions dy, dx (srx_mosaic.hpp): forward (after the prefilter) wf*, backward (before
+// it) wb* times `kb`
+template <typename T> static inline void axis_firs(double dy, double dx, double kb, T wfy[4], T wfx[4], T wby[4], T wbx[4])
+{
+    double fy[4], fx[4], by[4], bx[4];
+    host_weights(dy == 0.0 ? 0.0 : 1.0 - dy, fy);
+    host_weights(dx == 0.0 ? 0.0 : 1.0 - dx, fx);
+    host_weights(dy, by);
+    host_weights(dx, bx);
+    for (int i = 0; i < 4; i++)
+        wfy[i] = (T)fy[i], wfx[i] = (T)fx[i], wby[i] = (T)(kb * by[i]), wbx[i] = (T)(kb * bx[i]);
+}
+
 static inline bool shifts_ok(int N, const double *sh, int f)
 {
     for (int i = 0; i < 2 * N; i++)

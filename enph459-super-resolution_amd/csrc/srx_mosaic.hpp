@@ -28,72 +28,6 @@
 
 namespace srx {
 namespace mosaic {
-struct AxisPlan;
-}
-namespace patch {  // srx_patch.hpp: the patch-resident iteration (one workgroup per 256 x 256 HR patch)
-static inline bool eligible(int elem_bytes, int N, int H, int W, const double *sh, const double *k, int kh, int kw, int f, bool rank1_only = false);
-static inline size_t tabs_bytes(int B, int N);
-}  // namespace patch
-namespace ztile {  // srx_ztile.hpp: delta = 0 on CU-resident 256 x 256 tiles of a large frame, one launch per iteration
-static inline bool eligible(int elem_bytes, int N, int H, int W, const double *sh, const double *k, int kh, int kw, int f);
-static inline size_t tabs_bytes(int B, int N, int H, int W);
-static int iterate(const float *hr_init, float *hr, int B, int N, const mosaic::AxisPlan &py, const mosaic::AxisPlan &px,
-                   const fused::Kernel7<float> &kc, const fused::Kernel7<float> &kt, const float *Mg, const float *Cg, const float *Mu,
-                   const int *ncu, const int *nyx, int NS, int NB, const double *Vtot, Arena &ar, int H, int W, int n_iter, double step,
-                   double scale, double *errors, hipStream_t st);
-}  // namespace ztile
-namespace ctile {  // srx_ctile.hpp: delta = 0 on large frames without transposes (rows along the registers, columns along the lanes): f64, f32
-static inline bool eligible(int elem_bytes, int N, int H, int W, const double *sh, const double *k, int kh, int kw, int f);
-static inline size_t tabs_bytes(int eb, int B, int N, int H, int W);
-template <typename T>
-static int iterate(const T *hr_init, T *hr, int B, int N, const mosaic::AxisPlan &py, const mosaic::AxisPlan &px, const fused::Kernel7<T> &kc,
-                   const fused::Kernel7<T> &kt, const T *Mg, const T *Cg, const T *Mu, const int *ncu, const int *nyx, int NS, int NB,
-                   const double *Vtot, Arena &ar, int H, int W, int n_iter, double step, double scale, double *errors, hipStream_t st);
-}  // namespace ctile
-namespace dtile {  // srx_dtile.hpp: a common fraction > 0 on large frames, overlapping register-resident windows, one launch per iteration
-static inline bool shape_ok(int H, int W);  // a window plan exists for the shape under SOME call flags (the workspace bound's predicate)
-static inline bool eligible(int elem_bytes, int N, int H, int W, const double *sh, const double *k, int kh, int kw, int f);
-static inline size_t tabs_bytes(int B, int N, int H, int W);
-static int iterate(const float *hr_init, float *hr, int B, int N, int f, const mosaic::AxisPlan &py, const mosaic::AxisPlan &px,
-                   const fused::Kernel7<float> &kc, const fused::Kernel7<float> &kt, const float *Mg, const float *Cg, const float *Mu,
-                   const int *ncu, const int *nyx, int NS, int NB, const double *Vtot, Arena &ar, int H, int W, int n_iter, double step,
-                   double scale, double *errors, hipStream_t st);
-}  // namespace dtile
-namespace atile {  // srx_atile.hpp: the same frames as two launches per iteration on 2 x 2-wave windows of padded coordinates
-static inline bool eligible(int elem_bytes, int N, int H, int W, const double *sh, const double *k, int kh, int kw, int f);
-static inline size_t tabs_bytes(int B, int N, int H, int W);
-static int iterate(const float *hr_init, float *hr, int B, int N, int f, const mosaic::AxisPlan &py, const mosaic::AxisPlan &px,
-                   const fused::Kernel7<float> &kc, const fused::Kernel7<float> &kt, const float *Mg, const float *Cg, const float *Mu,
-                   const int *ncu, const int *nyx, int NS, int NB, const double *Vtot, Arena &ar, int H, int W, int n_iter, double step,
-                   double scale, double *errors, hipStream_t st);
-}  // namespace atile
-namespace stile {  // srx_stile.hpp: float64 patches with a common fraction > 0 as two launches per iteration on register-resident strips
-static inline bool eligible(int elem_bytes, int N, int H, int W, const double *sh, const double *k, int kh, int kw, int f);
-static inline size_t tabs_bytes(int eb, int B, int N);
-template <typename T>
-static int iterate(const T *hr_init, T *hr, int B, int N, int f, const mosaic::AxisPlan &py, const mosaic::AxisPlan &px, const fused::Kernel7<T> &kc,
-                   const fused::Kernel7<T> &kt, const T *Mg, const T *Cg, const T *Mu, const int *ncu, const int *nyx, int NS, int NB, const double *Vtot,
-                   Arena &ar, int n_iter, double step, double scale, double *errors, hipStream_t st);
-}
-namespace mosaic {
-struct MTap;
-}
-namespace patch {
-// a full phase grid: the patch path builds its operand planes straight from the LR frames (no M / C / Mu planes of the whole batch)
-static inline bool builds_itself(const mosaic::AxisPlan &py, const mosaic::AxisPlan &px, int N, int f);
-struct Source {  // what that build reads
-    const float *lr;
-    int h, w;
-    const mosaic::MTap *tabY, *tabX;  // [N][Hg], [N][Wg]
-    double *Vtot;
-};
-static int iterate(const float *hr_init, float *hr, int B, int N, int f, const mosaic::AxisPlan &py, const mosaic::AxisPlan &px,
-                   const fused::Kernel7<float> &kc, const fused::Kernel7<float> &kt, const float *Mg, const float *Cg, const float *Mu,
-                   const int *ncu, const int *nyx, int NS, int NB, const double *Vtot, Arena &ar, int n_iter, double step, double scale,
-                   double *errors, hipStream_t st, const Source &src);
-}  // namespace patch
-namespace mosaic {
-
 
 #ifndef SRX_FWD_BATCH
 #define SRX_FWD_BATCH 24
@@ -106,6 +40,7 @@ struct AxisPlan {
     double delta;
     int zero, E, D, PB, RS;
     int n[SRX_MAX_FRAMES];
+    int nmin, nmax;  // the extremes of n[0..N)
 };
 
 struct AxisDev {  // kernel-argument part of a plan
@@ -144,16 +79,13 @@ static inline bool plan_axis(int N, const double *sh, int axis, int f, AxisPlan 
     pl.zero = pl.delta == 0.0;
     pl.E = pl.zero ? 11 : 10;
     pl.D = 13 - pl.E;
-    int nmin = pl.n[0];
+    pl.nmin = pl.nmax = pl.n[0];
     for (int k = 1; k < N; k++)
-        nmin = std::min(nmin, pl.n[k]);
-    int nmax = pl.n[0];
-    for (int k = 1; k < N; k++)
-        nmax = std::max(nmax, pl.n[k]);
-    pl.PB = 13 - nmin;
+        pl.nmin = std::min(pl.nmin, pl.n[k]), pl.nmax = std::max(pl.nmax, pl.n[k]);
+    pl.PB = 13 - pl.nmin;
     // For p' <= 13 - n_max every frame has u = p' + n_k - 13 <= 0, i.e. it contributes its LR row 0 and subtracts Y row
     // E - n_k, whether by replication (u < 0) or as its own sample (u = 0): those rows of G are all equal to row RS.
-    pl.RS = std::max(13 - nmax, 0);
+    pl.RS = std::max(13 - pl.nmax, 0);
     return true;
 }
 
@@ -1219,90 +1151,12 @@ __global__ void __launch_bounds__(256)
 // ---------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------
-// Workspace of one call.  At most one of the three implementations runs, and each carves only what it needs behind the tables every
-// one of them uses (M, C, Mu, the tap tables, the near-band lists):
-//   tiles : the blurred plane, G, per-tile MSE partials      patch : srx_patch.hpp's operand planes and tables
-//   ztile : srx_ztile.hpp's padded state / operand planes and tables
-enum Impl { IMPL_TILES = 0, IMPL_PATCH = 1, IMPL_ZTILE = 2, IMPL_DTILE = 3, IMPL_CTILE = 4, IMPL_ATILE = 5, IMPL_STILE = 6 };
-
-static inline Impl choose_impl(int eb, int N, int H, int W, const double *sh, const double *k, int kh, int kw, int f)
-{
-    if (eb == 4 && !(call_flags() & (SRX_FLAG_TILES | SRX_FLAG_DIAG_WIDE_WINDOWS)) && patch::eligible(eb, N, H, W, sh, k, kh, kw, f))
-        return IMPL_PATCH;
-    if (stile::eligible(eb, N, H, W, sh, k, kh, kw, f))
-        return IMPL_STILE;
-    if (ctile::eligible(eb, N, H, W, sh, k, kh, kw, f))
-        return IMPL_CTILE;
-    if (ztile::eligible(eb, N, H, W, sh, k, kh, kw, f))
-        return IMPL_ZTILE;
-    // a common fraction > 0: k_ibp_dtile's one launch per iteration on the frames it takes (75 us on 3072 x 4096 against the 86 of the
-    // two-launch window kernels, whose G plane is a round trip through HBM), those kernels on every other shape (or on request)
-    if (!(call_flags() & SRX_FLAG_DIAG_TWO_LAUNCH) && dtile::eligible(eb, N, H, W, sh, k, kh, kw, f))
-        return IMPL_DTILE;
-    if (atile::eligible(eb, N, H, W, sh, k, kh, kw, f))
-        return IMPL_ATILE;
-    return IMPL_TILES;
-}
-
-static inline size_t ws_common(int eb, int B, int N, int H, int W)
-{
-    const size_t Hg = H + 2 * SRX_NPAD + 3, Wg = W + 2 * SRX_NPAD + 3;
-    const size_t NBmax = 20 * (Hg + Wg);  // near band: PB <= 18 rows + 18 columns of the plane
-    const size_t NS = (N + 3) & ~3;
-    return align_up((size_t)B * Hg * Wg * eb) + align_up(Hg * Wg * eb) + align_up((size_t)B * NBmax * eb) +
-           2 * align_up((size_t)N * (Hg > Wg ? Hg : Wg) * sizeof(MTap)) + align_up((size_t)B * sizeof(double)) +
-           align_up((size_t)B * cdiv((int)Wg, 64) * cdiv((int)Hg, 4) * sizeof(double)) +  // k_mosaic_build's block partials of V
-           align_up(NBmax * sizeof(int)) + align_up(NBmax * NS * sizeof(int));
-}
-
-static inline size_t ws_impl(Impl im, int eb, int B, int N, int H, int W)
-{
-    const size_t Hp = H + 2 * SRX_NPAD, Wp = W + 2 * SRX_NPAD, Hg = Hp + 3, Wg = Wp + 3;
-    if (im == IMPL_PATCH)
-        return patch::tabs_bytes(B, N);
-    if (im == IMPL_ZTILE)
-        return ztile::tabs_bytes(B, N, H, W);
-    if (im == IMPL_DTILE)
-        return dtile::tabs_bytes(B, N, H, W);
-    if (im == IMPL_CTILE)
-        return ctile::tabs_bytes(eb, B, N, H, W);
-    if (im == IMPL_ATILE)
-        return atile::tabs_bytes(B, N, H, W);
-    if (im == IMPL_STILE)
-        return stile::tabs_bytes(eb, B, N);
-    return align_up((size_t)B * Hp * Wp * eb) + align_up((size_t)B * Hg * Wg * eb) +
-           align_up((size_t)B * cdiv((int)Hg, 32) * cdiv((int)Wg, 32) * sizeof(double));
-}
-
-// without the shift table and the PSF the implementation is not known: the largest of those the shape admits
-static inline size_t ibp_ws(int eb, int B, int N, int H, int W)
-{
-    size_t m = ws_impl(IMPL_TILES, eb, B, N, H, W);
-    if (eb == 4 && H == 256 && W == 256)
-        m = std::max(m, ws_impl(IMPL_PATCH, eb, B, N, H, W));
-    if (eb == 8 && H == 256 && W == 256)
-        m = std::max(m, ws_impl(IMPL_STILE, eb, B, N, H, W));
-    if (eb == 4 && H >= 128 && W >= 128)
-        m = std::max(m, ws_impl(IMPL_ZTILE, eb, B, N, H, W));
-    // every shape dtile::plan() admits: 256-row windows of 192 (4 x 3 waves) or 256 columns, origins on row quads / 16-column groups
-    if (eb == 4 && dtile::shape_ok(H, W))
-        m = std::max(m, ws_impl(IMPL_DTILE, eb, B, N, H, W));
-    if (H >= 128 && W >= 128)
-        m = std::max(m, ws_impl(IMPL_CTILE, eb, B, N, H, W));
-    if (eb == 4 && H >= 32 && W >= 32)
-        m = std::max(m, ws_impl(IMPL_ATILE, eb, B, N, H, W));
-    return ws_common(eb, B, N, H, W) + m;
-}
-
-// ... and with them: exactly what the call will carve
-static inline size_t ibp_ws_for(int eb, int B, int N, int H, int W, const double *sh, const double *k, int kh, int kw, int f)
-{
-    return ws_common(eb, B, N, H, W) + ws_impl(choose_impl(eb, N, H, W, sh, k, kh, kw, f), eb, B, N, H, W);
-}
-
-// What every implementation of formulation A shares, built once per call (or once per plan): the index maps, the LR mosaic M, the count
-// map C, the near band's counted sums Mu and lists, the constant part V of the MSE trace.
+// What every implementation of formulation A shares -- the prepared call: its scalars, and what is built once per call (or once per
+// plan): the index maps, the LR mosaic M, the count map C, the near band's counted sums Mu and lists, the constant part V of the MSE trace.
 template <typename T> struct Common {
+    const T *lr;
+    int B, N, h, w, H, W, f;
+    double step, scale;  // scale: 1 / (samples of an item), the MSE trace's normalisation
     AxisPlan py, px;
     Kernel7<T> kc, kt;
     MosaicArgs<T> ma;
@@ -1314,11 +1168,27 @@ template <typename T> struct Common {
     bool sep, zero, own_build;
 };
 
+// what common_prep carves
+static inline size_t ws_common(int eb, int B, int N, int H, int W)
+{
+    const size_t Hg = H + 2 * SRX_NPAD + 3, Wg = W + 2 * SRX_NPAD + 3;
+    const size_t NBmax = 20 * (Hg + Wg);  // near band: PB <= 18 rows + 18 columns of the plane
+    const size_t NS = (N + 3) & ~3;
+    return align_up((size_t)B * Hg * Wg * eb) + align_up(Hg * Wg * eb) + align_up((size_t)B * NBmax * eb) +
+           2 * align_up((size_t)N * (Hg > Wg ? Hg : Wg) * sizeof(MTap)) + align_up((size_t)B * sizeof(double)) +
+           align_up((size_t)B * cdiv((int)Wg, 64) * cdiv((int)Hg, 4) * sizeof(double)) +  // k_mosaic_build's block partials of V
+           align_up(NBmax * sizeof(int)) + align_up(NBmax * NS * sizeof(int));
+}
+
+// own_build: the implementation reads the LR frames itself and wants no M / C / Mu planes (a batch of patches on a full phase grid,
+// srx_patch.hpp's k_patch_build -- the M plane of 1024 patches is 328 MB written here and read back once by k_patch_prep)
 template <typename T>
-static int common_prep(Common<T> &c, Impl impl, const T *lr, int B, int N, int h, int w, const double *sh, const double *k, int kh, int kw, int H, int W,
-                       int f, Arena &ar, hipStream_t st, int tr_lo, int tr_hi)
+static int common_prep(Common<T> &c, bool own_build, const T *lr, int B, int N, int h, int w, const double *sh, const double *k, int kh, int kw, int H,
+                       int W, int f, double step, Arena &ar, hipStream_t st, int tr_lo, int tr_hi)
 {
     const int Hp = H + 2 * SRX_NPAD, Wp = W + 2 * SRX_NPAD, Hg = Hp + 3, Wg = Wp + 3;
+    c.lr = lr, c.B = B, c.N = N, c.h = h, c.w = w, c.H = H, c.W = W, c.f = f, c.step = step;
+    c.scale = 1.0 / ((double)h * (double)w) / (double)N;
     AxisPlan &py = c.py, &px = c.px;
     if (!plan_axis(N, sh, 0, f, py) || !plan_axis(N, sh, 1, f, px))
         return SRX_E_UNSUPPORTED;
@@ -1339,19 +1209,7 @@ static int common_prep(Common<T> &c, Impl impl, const T *lr, int B, int N, int h
         dy.n[q] = q < N ? py.n[q] : 0, dx.n[q] = q < N ? px.n[q] : 0;
     MosaicArgs<T> &ma = c.ma;
     ma.Dy = py.D, ma.Dx = px.D, ma.PBy = py.PB, ma.PBx = px.PB, ma.RSy = py.RS, ma.RSx = px.RS;
-    double wv[4];
-    fused::host_weights(py.zero ? 0.0 : 1.0 - py.delta, wv);
-    for (int i = 0; i < 4; i++)
-        ma.wfy[i] = (T)wv[i];
-    fused::host_weights(px.zero ? 0.0 : 1.0 - px.delta, wv);
-    for (int i = 0; i < 4; i++)
-        ma.wfx[i] = (T)wv[i];
-    fused::host_weights(py.delta, wv);
-    for (int i = 0; i < 4; i++)
-        ma.wby[i] = (T)wv[i];
-    fused::host_weights(px.delta, wv);
-    for (int i = 0; i < 4; i++)
-        ma.wbx[i] = (T)wv[i];
+    fused::axis_firs<T>(py.delta, px.delta, 1.0, ma.wfy, ma.wfx, ma.wby, ma.wbx);
     fused::make_kernel7<T>(k, kh, kw, false, c.kc);
     fused::make_kernel7<T>(k, kh, kw, true, c.kt);
     c.sep = c.kc.separable && c.kt.separable, c.zero = py.zero && px.zero;
@@ -1362,13 +1220,8 @@ static int common_prep(Common<T> &c, Impl impl, const T *lr, int B, int N, int h
     SRX_CHECK_LAUNCH();
     if (fill_bytes(Vtot, 0, (size_t)B * sizeof(double), st) != hipSuccess)
         return SRX_E_HIP;
-    // (a batch of patches on a full phase grid: the patch path reads the LR frames itself, srx_patch.hpp's k_patch_build -- the M plane
-    // of 1024 patches is 328 MB written here and read back once by k_patch_prep)
-    c.own_build = false;
-    if constexpr (sizeof(T) == 4)
-        c.own_build = impl == IMPL_PATCH && patch::builds_itself(py, px, N, f);
-    if (c.own_build) {
-    } else {
+    c.own_build = own_build;
+    if (!own_build) {
         if (B >= 8)
             SRX_LAUNCH(KID_MOSAIC_BUILD, (k_mosaic_build<T, 8, 1>), dim3(cdiv(Wg, 64), cdiv(Hg, 4), cdiv(B, 8)), dim3(64, 4), 0, st, lr, B, N, h,
                        w, tabY, tabX, Hg, Wg, py.PB, px.PB, py.D, px.D, NB, Mg, Cg, Mu, Vpart, tr_lo, tr_hi);
@@ -1384,70 +1237,24 @@ static int common_prep(Common<T> &c, Impl impl, const T *lr, int B, int N, int h
     return SRX_OK;
 }
 
-template <typename T>
-static int ibp(const T *lr, int B, int N, int h, int w, const double *sh, const double *k, int kh, int kw,
-               const T *hr_init, int H, int W, int f, int n_iter, double step, T *hr, double *errors, void *ws,
-               size_t wsb, hipStream_t st, const char **took)
+// ---- the tile kernels of this file: every mosaic call no register-resident implementation (srx_route.hpp's table) takes ----
+// behind the common tables: the blurred plane, G, per-tile MSE partials
+static inline size_t tiles_bytes(int eb, int B, int, int H, int W)
 {
-    const int Hp = H + 2 * SRX_NPAD, Wp = W + 2 * SRX_NPAD, Hg = Hp + 3, Wg = Wp + 3;
-    const Impl impl = choose_impl((int)sizeof(T), N, H, W, sh, k, kh, kw, f);
-    *took = impl == IMPL_PATCH ? "patch" : impl == IMPL_ZTILE ? "ztile" : impl == IMPL_DTILE ? "dtile" : impl == IMPL_CTILE ? "ctile" : impl == IMPL_ATILE ? "atile" : impl == IMPL_STILE ? "stile" : "mosaic";  // what srx_last_path() reports: the branch taken
-    const size_t P = (size_t)B * H * W;
-    if (n_iter == 0 && hr != hr_init && hipMemcpyAsync(hr, hr_init, P * sizeof(T), hipMemcpyDeviceToDevice, st) != hipSuccess)
-        return SRX_E_HIP;
-    if (n_iter == 0)
-        return SRX_OK;
-    Arena ar(ws, wsb);
-    Common<T> c;
-    {
-        const int rc = common_prep<T>(c, impl, lr, B, N, h, w, sh, k, kh, kw, H, W, f, ar, st, 0, H);
-        if (rc != SRX_OK)
-            return rc;
-    }
-    const AxisPlan &py = c.py, &px = c.px;
-    const Kernel7<T> &kc = c.kc, &kt = c.kt;
-    const MosaicArgs<T> &ma = c.ma;
-    T *Mg = c.Mg, *Cg = c.Cg, *Mu = c.Mu;
-    MTap *tabY = c.tabY, *tabX = c.tabX;
-    double *Vtot = c.Vtot;
-    int *ncu = c.ncu, *nyx = c.nyx;
-    const int NB = c.NB, NS = c.NS;
-    const bool sep = c.sep, zero = c.zero;
-    T *pad = nullptr, *G = nullptr;
-    double *epart = nullptr;
-    if (impl == IMPL_TILES) {
-        pad = ar.take<T>((size_t)B * Hp * Wp);
-        G = ar.take<T>((size_t)B * Hg * Wg);
-        epart = ar.take<double>((size_t)B * cdiv(Hg, 32) * cdiv(Wg, 32));  // per-tile MSE partial sums of one iteration
-        if (!ar.ok)
-            return SRX_E_WORKSPACE;
-    }
-    const double scale = 1.0 / ((double)h * (double)w) / (double)N;
-    // integer HR shifts on a large frame, rows along the registers and columns along the lanes (float64; float32 on request)
-    if constexpr (sizeof(T) == 8) {  // float64 patches with a common fraction > 0: two launches per iteration on strips (srx_stile.hpp)
-        if (impl == IMPL_STILE)
-            return stile::iterate<T>(hr_init, hr, B, N, f, py, px, kc, kt, Mg, Cg, Mu, ncu, nyx, NS, NB, Vtot, ar, n_iter, step, scale, errors, st);
-    }
-    if (impl == IMPL_CTILE)
-        return ctile::iterate<T>(hr_init, hr, B, N, py, px, kc, kt, Mg, Cg, Mu, ncu, nyx, NS, NB, Vtot, ar, H, W, n_iter, step, scale, errors, st);
-    if constexpr (sizeof(T) == 4) {
-        // a 256 x 256 patch fits one compute unit: the whole iteration in one launch, no intermediate planes (srx_patch.hpp)
-        if (impl == IMPL_PATCH) {
-            const patch::Source src{lr, h, w, tabY, tabX, Vtot};
-            return patch::iterate(hr_init, hr, B, N, f, py, px, kc, kt, Mg, Cg, Mu, ncu, nyx, NS, NB, Vtot, ar, n_iter, step, scale,
-                                  errors, st, src);
-        }
-        // integer HR shifts on a large frame: the whole iteration in one launch over CU-resident 64 x 256 tiles (srx_ztile.hpp)
-        if (impl == IMPL_DTILE)
-            return dtile::iterate(hr_init, hr, B, N, f, py, px, kc, kt, Mg, Cg, Mu, ncu, nyx, NS, NB, Vtot, ar, H, W, n_iter, step, scale, errors,
-                                  st);
-        if (impl == IMPL_ZTILE)
-            return ztile::iterate(hr_init, hr, B, N, py, px, kc, kt, Mg, Cg, Mu, ncu, nyx, NS, NB, Vtot, ar, H, W, n_iter, step, scale,
-                                  errors, st);
-        if (impl == IMPL_ATILE)
-            return atile::iterate(hr_init, hr, B, N, f, py, px, kc, kt, Mg, Cg, Mu, ncu, nyx, NS, NB, Vtot, ar, H, W, n_iter, step, scale, errors,
-                                  st);
-    }
+    const size_t Hp = H + 2 * SRX_NPAD, Wp = W + 2 * SRX_NPAD, Hg = Hp + 3, Wg = Wp + 3;
+    return align_up((size_t)B * Hp * Wp * eb) + align_up((size_t)B * Hg * Wg * eb) +
+           align_up((size_t)B * cdiv((int)Hg, 32) * cdiv((int)Wg, 32) * sizeof(double));
+}
+
+template <typename T>
+static int iterate(const Common<T> &c, const T *hr_init, T *hr, int n_iter, double *errors, Arena &ar, hipStream_t st)
+{
+    const int B = c.B, H = c.H, W = c.W, Hp = H + 2 * SRX_NPAD, Wp = W + 2 * SRX_NPAD, Hg = c.Hg, Wg = c.Wg;
+    T *pad = ar.take<T>((size_t)B * Hp * Wp);
+    T *G = ar.take<T>((size_t)B * Hg * Wg);
+    double *epart = ar.take<double>((size_t)B * cdiv(Hg, 32) * cdiv(Wg, 32));  // per-tile MSE partial sums of one iteration
+    if (!ar.ok)
+        return SRX_E_WORKSPACE;
     constexpr int TS = TileCfg<T>::T_HR;
     // timing ablations (results are wrong / an occupancy cap): compile-time only, -DSRX_ABLATE=<bits> -DSRX_ABLATE_LDS=<bytes>
 #ifdef SRX_ABLATE
@@ -1461,41 +1268,41 @@ static int ibp(const T *lr, int B, int N, int h, int w, const double *sh, const 
     const size_t dbg_lds = 0;
 #endif
     const dim3 bgrid(cdiv(W, SRX_BT_W), cdiv(H, SRX_BT_H), B), bblk(64, 4);
-    const dim3 fgrid(cdiv(Wg, TS), cdiv(Hg, zero ? FwdRows<T, true>::v : TS), B), wgrid(cdiv(W, TS), cdiv(H, TS), B);
+    const dim3 fgrid(cdiv(Wg, TS), cdiv(Hg, c.zero ? FwdRows<T, true>::v : TS), B), wgrid(cdiv(W, TS), cdiv(H, TS), B);
     // delta = 0: blur and forward map in one kernel over image tiles (no blurred plane); SRX_NO_ZERO_FUSE keeps the two kernels
-    const bool zfuse = zero && !(call_flags() & SRX_FLAG_DIAG_NO_ZERO_FUSE);
+    const bool zfuse = c.zero && !(call_flags() & SRX_FLAG_DIAG_NO_ZERO_FUSE);
     const int nblk = zfuse ? (int)(bgrid.x * bgrid.y) : (int)(fgrid.x * fgrid.y);  // MSE partial sums per item
     for (int it = 0; it < n_iter; it++) {
         const T *cur = it == 0 ? hr_init : hr;
         double *eo = errors ? errors + it : nullptr, *ep = errors ? epart : nullptr;
         if (zfuse) {
-            if (sep)
-                SRX_LAUNCH(KID_FWD_MOSAIC, (k_blurfwd_zero<T, true>), bgrid, bblk, 0, st, cur, H, W, kc, Mg, Cg, Hg, Wg, ma, Mu, ncu, nyx, NS,
-                           NB, G, ep, scale);
+            if (c.sep)
+                SRX_LAUNCH(KID_FWD_MOSAIC, (k_blurfwd_zero<T, true>), bgrid, bblk, 0, st, cur, H, W, c.kc, c.Mg, c.Cg, Hg, Wg, c.ma, c.Mu, c.ncu, c.nyx, c.NS,
+                           c.NB, G, ep, c.scale);
             else
-                SRX_LAUNCH(KID_FWD_MOSAIC, (k_blurfwd_zero<T, false>), bgrid, bblk, 0, st, cur, H, W, kc, Mg, Cg, Hg, Wg, ma, Mu, ncu, nyx, NS,
-                           NB, G, ep, scale);
-        } else if (sep)
-            SRX_LAUNCH(KID_BLUR_PAD, (fused::k_blur_pad<T, true, false>), bgrid, bblk, 0, st, cur, H, W, kc, pad);
+                SRX_LAUNCH(KID_FWD_MOSAIC, (k_blurfwd_zero<T, false>), bgrid, bblk, 0, st, cur, H, W, c.kc, c.Mg, c.Cg, Hg, Wg, c.ma, c.Mu, c.ncu, c.nyx, c.NS,
+                           c.NB, G, ep, c.scale);
+        } else if (c.sep)
+            SRX_LAUNCH(KID_BLUR_PAD, (fused::k_blur_pad<T, true, false>), bgrid, bblk, 0, st, cur, H, W, c.kc, pad);
         else
-            SRX_LAUNCH(KID_BLUR_PAD, (fused::k_blur_pad<T, false, false>), bgrid, bblk, 0, st, cur, H, W, kc, pad);
+            SRX_LAUNCH(KID_BLUR_PAD, (fused::k_blur_pad<T, false, false>), bgrid, bblk, 0, st, cur, H, W, c.kc, pad);
         if (zfuse) {
-        } else if (zero)
-            SRX_LAUNCH(KID_FWD_MOSAIC, (k_fwd_mosaic<T, true>), fgrid, dim3(256), 0, st, pad, Hp, Wp, Mg, Cg, Hg, Wg, ma, Mu, ncu,
-                       nyx, NS, NB, G, ep, scale, dbg);
+        } else if (c.zero)
+            SRX_LAUNCH(KID_FWD_MOSAIC, (k_fwd_mosaic<T, true>), fgrid, dim3(256), 0, st, pad, Hp, Wp, c.Mg, c.Cg, Hg, Wg, c.ma, c.Mu, c.ncu,
+                       c.nyx, c.NS, c.NB, G, ep, c.scale, dbg);
         else
-            SRX_LAUNCH(KID_FWD_MOSAIC, (k_fwd_mosaic<T, false>), fgrid, dim3(256), dbg_lds, st, pad, Hp, Wp, Mg, Cg, Hg, Wg, ma,
-                       Mu, ncu, nyx, NS, NB, G, ep, scale, dbg);
+            SRX_LAUNCH(KID_FWD_MOSAIC, (k_fwd_mosaic<T, false>), fgrid, dim3(256), dbg_lds, st, pad, Hp, Wp, c.Mg, c.Cg, Hg, Wg, c.ma,
+                       c.Mu, c.ncu, c.nyx, c.NS, c.NB, G, ep, c.scale, dbg);
 #define SRX_BWDM(Z_, S_)                                                                                             \
-    SRX_LAUNCH(KID_BWD_MOSAIC, (k_bwd_mosaic<T, Z_, S_>), wgrid, bblk, dbg_lds, st, G, Hg, Wg, ma, H, W, kt, (T)step, (T)N, cur, hr, \
-               epart, nblk, Vtot, scale, eo, n_iter, dbg)
-        if (zero) {
-            if (sep)
+    SRX_LAUNCH(KID_BWD_MOSAIC, (k_bwd_mosaic<T, Z_, S_>), wgrid, bblk, dbg_lds, st, G, Hg, Wg, c.ma, H, W, c.kt, (T)c.step, (T)c.N, cur, hr, \
+               epart, nblk, c.Vtot, c.scale, eo, n_iter, dbg)
+        if (c.zero) {
+            if (c.sep)
                 SRX_BWDM(true, true);
             else
                 SRX_BWDM(true, false);
         } else {
-            if (sep)
+            if (c.sep)
                 SRX_BWDM(false, true);
             else
                 SRX_BWDM(false, false);
@@ -1504,7 +1311,6 @@ static int ibp(const T *lr, int B, int N, int h, int w, const double *sh, const 
     }
     return SRX_OK;
 }
-
 
 static inline bool saa_eligible(int N, int h, int w, const double *sh, int f)
 {

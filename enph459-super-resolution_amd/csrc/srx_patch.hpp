@@ -125,19 +125,20 @@ struct PatchTabs {
 };
 
 // ---- eligibility ----------------------------------------------------------------------------------------------------
-static inline bool axis_ok(const mosaic::AxisPlan &pl, int N, int f)
+static inline bool axis_ok(const mosaic::AxisPlan &pl, int f)
 {
-    int nmin = pl.n[0], nmax = pl.n[0];
-    for (int k = 1; k < N; k++)
-        nmin = std::min(nmin, pl.n[k]), nmax = std::max(nmax, pl.n[k]);
+    const int nmin = pl.nmin, nmax = pl.nmax;
     // a common fraction > 0; at most one sample above the grid; the near band within the strips; the last `ex` grid rows
     // empty (integer shifts span less than f), which also makes G vanish from row n - 1 on when ex = 1
     return !pl.zero && nmax >= 0 && nmax <= 1 && nmin <= 0 && nmax - nmin <= 3 && nmax - nmin <= f - 1 && -nmin < f;
 }
 
-static inline bool eligible(int elem_bytes, int N, int H, int W, const double *sh, const double *k, int kh, int kw, int f, bool rank1_only)
+// may a call of this shape EVER take the path: the shape-only workspace bound asks this, eligible() asks it first
+static inline bool shape_admits(int elem_bytes, int H, int W) { return elem_bytes == 4 && H == PN && W == PN; }
+
+static inline bool eligible(int elem_bytes, int N, int H, int W, const double *sh, const double *k, int kh, int kw, int f, bool rank1_only = false)
 {
-    if (elem_bytes != 4 || H != PN || W != PN || f < 2)
+    if (!shape_admits(elem_bytes, H, W) || f < 2)
         return false;
     mosaic::AxisPlan py, px;
     if (!mosaic::plan_axis(N, sh, 0, f, py) || !mosaic::plan_axis(N, sh, 1, f, px))
@@ -145,18 +146,10 @@ static inline bool eligible(int elem_bytes, int N, int H, int W, const double *s
     fused::Kernel7<float> kc;
     fused::make_kernel7<float>(k, kh, kw, false, kc);
     // (round 4: a PSF that is not rank 1 runs the 7 x 7 form of the two blurs, blur2d_pass1 / blur2d_fix)
-    if (!((kc.separable || !rank1_only) && axis_ok(py, N, f) && axis_ok(px, N, f)))
+    if (!((kc.separable || !rank1_only) && axis_ok(py, f) && axis_ok(px, f)))
         return false;
     // the near band within the kernel's two-pixels-per-thread descriptor lists (iterate() computes the same count)
-    auto span = [&](const mosaic::AxisPlan &pl, int &ex, int &nb) {
-        int nmin = pl.n[0], nmax = pl.n[0];
-        for (int q = 1; q < N; q++)
-            nmin = std::min(nmin, pl.n[q]), nmax = std::max(nmax, pl.n[q]);
-        ex = nmax, nb = -nmin;
-    };
-    int exy, nby, exx, nbx;
-    span(py, exy, nby);
-    span(px, exx, nbx);
+    const int exy = py.nmax, nby = -py.nmin, exx = px.nmax, nbx = -px.nmin;
     return (exy + nby) * (PN + exx) + (PN - nby) * (exx + nbx) <= NN_PAD;
 }
 
@@ -1288,12 +1281,9 @@ __global__ void __launch_bounds__(1024)
 }
 
 // ---- host ----------------------------------------------------------------------------------------------------------
-static inline void fill_axis(const mosaic::AxisPlan &pl, int N, const float *cfwd, const float *cbwd, AxisC &ax, AxisW &aw)
+static inline void fill_axis(const mosaic::AxisPlan &pl, const float *cfwd, const float *cbwd, AxisC &ax, AxisW &aw)
 {
     const double kq = -6.0 * ZD;
-    int nmin = pl.n[0], nmax = pl.n[0];
-    for (int k = 1; k < N; k++)
-        nmin = std::min(nmin, pl.n[k]), nmax = std::max(nmax, pl.n[k]);
     double wv[4];
     fused::host_weights(1.0 - pl.delta, wv);
     for (int i = 0; i < 4; i++)
@@ -1304,7 +1294,7 @@ static inline void fill_axis(const mosaic::AxisPlan &pl, int N, const float *cfw
     aw.kb[7] = aw.kt[7] = 0.f;
     for (int i = 0; i < 7; i++)
         aw.kb[i] = (float)(kq * (double)cfwd[i]), aw.kt[i] = cbwd[i];
-    ax.ex = nmax, ax.nb = -nmin, ax.E = pl.E;
+    ax.ex = pl.nmax, ax.nb = -pl.nmin, ax.E = pl.E;
 }
 
 // Full phase grids (every frame its own (row class, column class), classes distinct modulo f): each far-field HR pixel
@@ -1393,19 +1383,34 @@ static inline bool builds_itself(const mosaic::AxisPlan &py, const mosaic::AxisP
     return axis_map(py, N, f, bm.y, cy, ny) && axis_map(px, N, f, bm.x, cx, nx) && ny * nx == N;
 }
 
-static inline size_t tabs_bytes(int B, int N)
+static inline size_t tabs_bytes(int, int B, int N, int, int)
 {
     const size_t ngrp = ((size_t)N + 3) / 4;
     return align_up(sizeof(BuildMaps)) + align_up((size_t)B * PN * PN * 4) + align_up((size_t)B * (PN / 4) * PN * 4) + align_up((size_t)B * 4) + align_up((size_t)PN * PN * 4) +
            align_up((size_t)NN_PAD * 8) + align_up(ngrp * NN_PAD * 8) + align_up((size_t)B * NN_PAD * 8) + align_up(2 * sizeof(AxisW)) + align_up(112 * 4);
 }
 
-// the iteration loop; the per-call tables (M, C, Mu, near lists, Vtot) are srx_mosaic.hpp's, built by its ibp()
-static int iterate(const float *hr_init, float *hr, int B, int N, int f, const mosaic::AxisPlan &py, const mosaic::AxisPlan &px,
-                   const fused::Kernel7<float> &kc, const fused::Kernel7<float> &kt, const float *Mg, const float *Cg, const float *Mu,
-                   const int *ncu, const int *nyx, int NS, int NB, const double *Vtot, Arena &ar, int n_iter, double step, double scale,
-                   double *errors, hipStream_t st, const Source &src)
+// a PSF that is not rank 1: the 7 x 7 weights in column layout (lane-direction tap, then register-direction tap), the forward ones times
+// kq^2, to k2 (PatchTabs::k2)
+static int upload_k2(const fused::Kernel7<float> &kc, const fused::Kernel7<float> &kt, float *k2, hipStream_t st)
 {
+    const double kq = -6.0 * ZD;
+    K2Pair kv;
+    for (int c = 0; c < 7; c++)
+        for (int r = 0; r < 8; r++) {
+            kv.v[8 * c + r] = r < 7 ? (float)(kq * kq * (double)kc.k[7 * r + c]) : 0.f;
+            kv.v[56 + 8 * c + r] = r < 7 ? kt.k[7 * r + c] : 0.f;
+        }
+    hipLaunchKernelGGL(k_patch_k2, dim3(1), dim3(128), 0, st, kv, k2);
+    SRX_CHECK_LAUNCH();
+    return SRX_OK;
+}
+
+// the iteration loop; the per-call tables (M, C, Mu, near lists, Vtot) are srx_mosaic.hpp's common_prep()'s
+static int iterate(const mosaic::Common<float> &c, const float *hr_init, float *hr, int n_iter, double *errors, Arena &ar, hipStream_t st)
+{
+    const int B = c.B, N = c.N, f = c.f, NS = c.NS;
+    const mosaic::AxisPlan &py = c.py, &px = c.px;
     const int Hg = PN + 27, Wg = PN + 27, ngrp = NS / 4;
     BuildMaps *maps = ar.take<BuildMaps>(1);
     float *Mt = ar.take<float>((size_t)B * PN * PN);
@@ -1420,9 +1425,9 @@ static int iterate(const float *hr_init, float *hr, int B, int N, int f, const m
         return SRX_E_WORKSPACE;
     PatchArgs pa;
     AxisWPair awp;
-    fill_axis(py, N, kc.cy, kt.cy, pa.y, awp.y);
-    fill_axis(px, N, kc.cx, kt.cx, pa.x, awp.x);
-    pa.sn = (float)step / (float)N;
+    fill_axis(py, c.kc.cy, c.kt.cy, pa.y, awp.y);
+    fill_axis(px, c.kc.cx, c.kt.cx, pa.x, awp.x);
+    pa.sn = (float)c.step / (float)N;
     pa.ntop = (pa.y.ex + pa.y.nb) * (PN + pa.x.ex);
     pa.nn = pa.ntop + (PN - pa.y.nb) * (pa.x.ex + pa.x.nb);
     pa.ngrp = ngrp;
@@ -1431,65 +1436,49 @@ static int iterate(const float *hr_init, float *hr, int B, int N, int f, const m
     pa.c01 = c01_masks(py, px, N, f, pa.ry, pa.rx) ? 1 : 0;
     if (fill_bytes(m8, 0xff, (size_t)B * sizeof(int), st) != hipSuccess)
         return SRX_E_HIP;
-    const bool own = builds_itself(py, px, N, f);  // (what mosaic::ibp asked before it decided not to build M / C / Mu)
+    const bool own = c.own_build;  // (common_prep built no M / C / Mu)
     if (own) {
         BuildMaps bm;
         int cy[SRX_MAX_FRAMES], cx[SRX_MAX_FRAMES], ny, nx;
         axis_map(py, N, f, bm.y, cy, ny);
         axis_map(px, N, f, bm.x, cx, nx);
         for (int a = 0; a < 4; a++)
-            for (int c = 0; c < 4; c++)
-                bm.frame[a][c] = 0;
+            for (int b = 0; b < 4; b++)
+                bm.frame[a][b] = 0;
         for (int q = 0; q < N; q++)
             bm.frame[cy[q]][cx[q]] = (signed char)q;
         bm.nby = pa.y.nb, bm.nbx = pa.x.nb;
         hipLaunchKernelGGL(k_patch_maps, dim3(1), dim3(256), 0, st, bm, maps);
         SRX_CHECK_LAUNCH();
-        SRX_LAUNCH(KID_PATCH_BUILD, k_patch_build<0>, dim3(PN / 16, B), dim3(256), 0, st, src.lr, N, src.h, src.w, maps, m8, Mt, Mt8);
-        SRX_LAUNCH(KID_PATCH_FLAGS, k_patch_build<1>, dim3(PN / 16, B), dim3(256), 0, st, src.lr, N, src.h, src.w, maps, m8, Mt, Mt8);
+        SRX_LAUNCH(KID_PATCH_BUILD, k_patch_build<0>, dim3(PN / 16, B), dim3(256), 0, st, c.lr, N, c.h, c.w, maps, m8, Mt, Mt8);
+        SRX_LAUNCH(KID_PATCH_FLAGS, k_patch_build<1>, dim3(PN / 16, B), dim3(256), 0, st, c.lr, N, c.h, c.w, maps, m8, Mt, Mt8);
     } else {
-        hipLaunchKernelGGL(k_patch_prep, dim3(PN / 32, PN / 32, B + 1), dim3(32, 8), 0, st, Mg, Cg, B, Hg, Wg, pa.y.nb, pa.x.nb, Mt, Ct, Mt8, m8);
+        hipLaunchKernelGGL(k_patch_prep, dim3(PN / 32, PN / 32, B + 1), dim3(32, 8), 0, st, c.Mg, c.Cg, B, Hg, Wg, pa.y.nb, pa.x.nb, Mt, Ct, Mt8, m8);
         SRX_CHECK_LAUNCH();
     }
     if (pa.nn > 0) {
-        hipLaunchKernelGGL(k_patch_near_tab, dim3(cdiv(pa.nn, 256)), dim3(256), 0, st, ncu, nyx, NS, py.PB, px.PB, pa.y.ex, pa.x.ex, pa.y.nb,
+        hipLaunchKernelGGL(k_patch_near_tab, dim3(cdiv(pa.nn, 256)), dim3(256), 0, st, c.ncu, c.nyx, NS, py.PB, px.PB, pa.y.ex, pa.x.ex, pa.y.nb,
                            pa.x.nb, pa.y.E, pa.x.E, pa.nn, nrec, nent);
         SRX_CHECK_LAUNCH();
         if (own)
-            hipLaunchKernelGGL(k_patch_near_build, dim3(cdiv(pa.nn, 256), B), dim3(256), 0, st, src.lr, N, src.h, src.w, src.tabY, src.tabX, Hg, Wg,
-                               py.D, px.D, pa.y.ex, pa.x.ex, pa.y.nb, pa.x.nb, pa.nn, Mn, src.Vtot);
+            hipLaunchKernelGGL(k_patch_near_build, dim3(cdiv(pa.nn, 256), B), dim3(256), 0, st, c.lr, N, c.h, c.w, c.tabY, c.tabX, Hg, Wg,
+                               py.D, px.D, pa.y.ex, pa.x.ex, pa.y.nb, pa.x.nb, pa.nn, Mn, c.Vtot);
         else
-            hipLaunchKernelGGL(k_patch_near_m, dim3(cdiv(pa.nn, 256), B), dim3(256), 0, st, Mg, Mu, NB, py.PB, px.PB, pa.y.ex, pa.x.ex, pa.y.nb,
+            hipLaunchKernelGGL(k_patch_near_m, dim3(cdiv(pa.nn, 256), B), dim3(256), 0, st, c.Mg, c.Mu, c.NB, py.PB, px.PB, pa.y.ex, pa.x.ex, pa.y.nb,
                                pa.x.nb, pa.nn, Mn);
         SRX_CHECK_LAUNCH();
     }
     hipLaunchKernelGGL(k_patch_params, dim3(1), dim3(1), 0, st, awp, aw);
     SRX_CHECK_LAUNCH();
-    // a PSF that is not rank 1: the 7 x 7 weights in column layout (lane-direction tap, then register-direction tap), the forward ones
-    // times kq^2; form 2 when the outer ring is zero (the reference's measured PSF: a 5 x 5 core)
-    int psf = 0;
-    if (!(kc.separable && kt.separable)) {
-        const double kq = -6.0 * ZD;
-        bool ring0 = true;
-        for (int i = 0; i < 7; i++)
-            for (int e : {i, 42 + i, 7 * i, 7 * i + 6})
-                ring0 = ring0 && kc.k[e] == 0.f && kt.k[e] == 0.f;
-        psf = ring0 ? 2 : 3;
-        K2Pair kv;
-        for (int c = 0; c < 7; c++)
-            for (int r = 0; r < 8; r++) {
-                kv.v[8 * c + r] = r < 7 ? (float)(kq * kq * (double)kc.k[7 * r + c]) : 0.f;
-                kv.v[56 + 8 * c + r] = r < 7 ? kt.k[7 * r + c] : 0.f;
-            }
-        hipLaunchKernelGGL(k_patch_k2, dim3(1), dim3(128), 0, st, kv, k2);
-        SRX_CHECK_LAUNCH();
-    }
+    const int psf = fused::psf_form(c.kc, c.kt);
+    if (psf != 0)
+        SRX_TRY(upload_k2(c.kc, c.kt, k2, st));
     PatchTabs tb{Mt, Mt8, m8, Ct, aw, nrec, nent, Mn, k2};
     // both mosaic forms over the whole batch: every patch is iterated by exactly one of the two launches (k_patch_prep's m8 flag)
 #define SRX_PATCH_PAIR(C01_, PSF_)                                                                                                              \
     do {                                                                                                                                        \
-        SRX_LAUNCH(KID_IBP_PATCH, (k_ibp_patch<C01_, true, PSF_>), dim3(B), dim3(1024), 0, st, hr_init, hr, tb, pa, Vtot, scale, errors, n_iter);  \
-        SRX_LAUNCH(KID_IBP_PATCH, (k_ibp_patch<C01_, false, PSF_>), dim3(B), dim3(1024), 0, st, hr_init, hr, tb, pa, Vtot, scale, errors, n_iter); \
+        SRX_LAUNCH(KID_IBP_PATCH, (k_ibp_patch<C01_, true, PSF_>), dim3(B), dim3(1024), 0, st, hr_init, hr, tb, pa, c.Vtot, c.scale, errors, n_iter);  \
+        SRX_LAUNCH(KID_IBP_PATCH, (k_ibp_patch<C01_, false, PSF_>), dim3(B), dim3(1024), 0, st, hr_init, hr, tb, pa, c.Vtot, c.scale, errors, n_iter); \
     } while (0)
     if (pa.c01) {
         if (psf == 0)

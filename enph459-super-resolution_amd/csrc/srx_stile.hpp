@@ -268,9 +268,11 @@ __device__ __forceinline__ void bwd_chain(T (&a)[64], bool first, bool last, T *
 }
 
 // ---- eligibility: srx_patch.hpp's, for 8-byte elements -------------------------------------------------------------------------------
+static inline bool shape_admits(int elem_bytes, int H, int W) { return elem_bytes == 8 && H == PN && W == PN; }
+
 static inline bool eligible(int elem_bytes, int N, int H, int W, const double *sh, const double *k, int kh, int kw, int f)
 {
-    if (elem_bytes != 8 || (call_flags() & SRX_FLAG_TILES))
+    if (!shape_admits(elem_bytes, H, W) || (call_flags() & SRX_FLAG_TILES))
         return false;
     return patch::eligible(4, N, H, W, sh, k, kh, kw, f, true);  // rank-1 PSFs only (rank 1 is decided on the float64 weights there too)
 }
@@ -626,12 +628,9 @@ __global__ void __launch_bounds__(256, 2)
 }
 
 // ---- host --------------------------------------------------------------------------------------------------------------------------
-template <typename T> static inline void fill_axis(const mosaic::AxisPlan &pl, int N, const T *cfwd, const T *cbwd, patch::AxisC &ax, AxW<T> &aw)
+template <typename T> static inline void fill_axis(const mosaic::AxisPlan &pl, const T *cfwd, const T *cbwd, patch::AxisC &ax, AxW<T> &aw)
 {
     const double kq = -6.0 * ZD;
-    int nmin = pl.n[0], nmax = pl.n[0];
-    for (int k = 1; k < N; k++)
-        nmin = std::min(nmin, pl.n[k]), nmax = std::max(nmax, pl.n[k]);
     double wv[4];
     fused::host_weights(1.0 - pl.delta, wv);
     for (int i = 0; i < 4; i++)
@@ -641,10 +640,10 @@ template <typename T> static inline void fill_axis(const mosaic::AxisPlan &pl, i
         aw.wb[i] = (T)(kq * wv[i]);
     for (int i = 0; i < 7; i++)
         aw.kb[i] = (T)(kq * (double)cfwd[i]), aw.kt[i] = cbwd[i];
-    ax.ex = nmax, ax.nb = -nmin, ax.E = pl.E;
+    ax.ex = pl.nmax, ax.nb = -pl.nmin, ax.E = pl.E;
 }
 
-static inline size_t tabs_bytes(int eb, int B, int N)
+static inline size_t tabs_bytes(int eb, int B, int N, int, int)
 {
     const size_t ngrp = ((size_t)N + 3) / 4, plane = (size_t)B * PN * PN * eb;
     return 2 * align_up(plane) + align_up((size_t)B * (PN / 4) * PN * 4) + align_up((size_t)B * 4) + align_up((size_t)PN * PN * eb) + align_up((size_t)NN_PAD * 8) +
@@ -652,10 +651,11 @@ static inline size_t tabs_bytes(int eb, int B, int N)
 }
 
 template <typename T>
-static int iterate(const T *hr_init, T *hr, int B, int N, int f, const mosaic::AxisPlan &py, const mosaic::AxisPlan &px, const fused::Kernel7<T> &kc,
-                   const fused::Kernel7<T> &kt, const T *Mg, const T *Cg, const T *Mu, const int *ncu, const int *nyx, int NS, int NB, const double *Vtot,
-                   Arena &ar, int n_iter, double step, double scale, double *errors, hipStream_t st)
+static int iterate(const mosaic::Common<T> &c, const T *hr_init, T *hr, int n_iter, double *errors, Arena &ar, hipStream_t st)
 {
+    const int B = c.B, N = c.N, f = c.f, NS = c.NS;
+    const mosaic::AxisPlan &py = c.py, &px = c.px;
+    const double scale = c.scale;
     const int Hg = PN + 27, Wg = PN + 27, ngrp = NS / 4;
     T *Mt = ar.take<T>((size_t)B * PN * PN), *P = ar.take<T>((size_t)B * PN * PN);
     unsigned *Mt8 = ar.take<unsigned>((size_t)B * (PN / 4) * PN);
@@ -668,8 +668,8 @@ static int iterate(const T *hr_init, T *hr, int B, int N, int f, const mosaic::A
         return SRX_E_WORKSPACE;
     patch::PatchArgs pa;
     AxW<T> awy, awx;
-    fill_axis<T>(py, N, kc.cy, kt.cy, pa.y, awy);
-    fill_axis<T>(px, N, kc.cx, kt.cx, pa.x, awx);
+    fill_axis<T>(py, c.kc.cy, c.kt.cy, pa.y, awy);
+    fill_axis<T>(px, c.kc.cx, c.kt.cx, pa.x, awx);
     pa.sn = 0.f;
     pa.ntop = (pa.y.ex + pa.y.nb) * (PN + pa.x.ex);
     pa.nn = pa.ntop + (PN - pa.y.nb) * (pa.x.ex + pa.x.nb);
@@ -679,17 +679,17 @@ static int iterate(const T *hr_init, T *hr, int B, int N, int f, const mosaic::A
     pa.c01 = patch::c01_masks(py, px, N, f, pa.ry, pa.rx) ? 1 : 0;
     if (fill_bytes(m8, 0xff, (size_t)B * sizeof(int), st) != hipSuccess)
         return SRX_E_HIP;
-    hipLaunchKernelGGL(k_stile_prep<T>, dim3(PN / 32, PN / 32, B + 1), dim3(32, 8), 0, st, Mg, Cg, B, Hg, Wg, pa.y.nb, pa.x.nb, Mt, Ct, Mt8, m8);
+    hipLaunchKernelGGL(k_stile_prep<T>, dim3(PN / 32, PN / 32, B + 1), dim3(32, 8), 0, st, c.Mg, c.Cg, B, Hg, Wg, pa.y.nb, pa.x.nb, Mt, Ct, Mt8, m8);
     SRX_CHECK_LAUNCH();
     if (pa.nn > 0) {
-        hipLaunchKernelGGL(patch::k_patch_near_tab, dim3(cdiv(pa.nn, 256)), dim3(256), 0, st, ncu, nyx, NS, py.PB, px.PB, pa.y.ex, pa.x.ex, pa.y.nb, pa.x.nb,
+        hipLaunchKernelGGL(patch::k_patch_near_tab, dim3(cdiv(pa.nn, 256)), dim3(256), 0, st, c.ncu, c.nyx, NS, py.PB, px.PB, pa.y.ex, pa.x.ex, pa.y.nb, pa.x.nb,
                            pa.y.E, pa.x.E, pa.nn, nrec, nent);
         SRX_CHECK_LAUNCH();
-        hipLaunchKernelGGL(k_stile_near_m<T>, dim3(cdiv(pa.nn, 256), B), dim3(256), 0, st, Mg, Mu, NB, py.PB, px.PB, pa.y.ex, pa.x.ex, pa.y.nb, pa.x.nb, pa.nn,
+        hipLaunchKernelGGL(k_stile_near_m<T>, dim3(cdiv(pa.nn, 256), B), dim3(256), 0, st, c.Mg, c.Mu, c.NB, py.PB, px.PB, pa.y.ex, pa.x.ex, pa.y.nb, pa.x.nb, pa.nn,
                            Mn);
         SRX_CHECK_LAUNCH();
     }
-    const T sn = (T)(step / (double)N);
+    const T sn = (T)(c.step / (double)N);
     const int want = errors ? 1 : 0;
     // The batch in chunks of 128 patches, every launch of a chunk before the next chunk's first: 512 workgroups = one round of the 256
     // compute units at two workgroups each, and the chunk's working set (state, plane, byte mosaic: 1.06 MB per patch) stays in the 256 MB
@@ -700,7 +700,7 @@ static int iterate(const T *hr_init, T *hr, int B, int N, int f, const mosaic::A
         const size_t po = (size_t)c0 * PN * PN;
         const STabs<T> tb{Mt + po, Mt8 + (size_t)c0 * (PN / 4) * PN, m8 + c0, Ct, nrec, nent, Mn + (size_t)c0 * NN_PAD};
         double *ep = epart + 4 * c0, *er = errors ? errors + (size_t)c0 * n_iter : nullptr;
-        const double *vt = Vtot + c0;
+        const double *vt = c.Vtot + c0;
         const dim3 grid(4, nb), blk(256);
         SRX_LAUNCH(KID_IBP_SV, (k_ibp_sv<T>), grid, blk, 0, st, hr_init + po, hr + po, P + po, awy, pa.y.ex, sn, 1, ep, vt, scale, er, n_iter, 0);
         for (int it = 0; it < n_iter; it++) {

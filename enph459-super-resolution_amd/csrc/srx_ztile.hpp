@@ -93,18 +93,18 @@ struct ZTabs {
     const float2 *Mn;        // [B][NT] (M, Mu)
 };
 
-static inline bool axis_ok(const mosaic::AxisPlan &pl, int N, int f)
+static inline bool axis_ok(const mosaic::AxisPlan &pl, int f)
 {
-    int nmin = pl.n[0], nmax = pl.n[0];
-    for (int k = 1; k < N; k++)
-        nmin = std::min(nmin, pl.n[k]), nmax = std::max(nmax, pl.n[k]);
+    const int nmin = pl.nmin, nmax = pl.nmax;
     // integer shifts; near band within the strips; no LR sample beyond the last image row (n_min >= -(f - 1))
     return pl.zero && nmax >= 0 && nmax <= 1 && nmin <= 0 && -nmin <= SW - 1 && -nmin <= f - 1;
 }
 
+static inline bool shape_admits(int elem_bytes, int H, int W) { return elem_bytes == 4 && H >= 128 && W >= 128; }
+
 static inline bool eligible(int elem_bytes, int N, int H, int W, const double *sh, const double *k, int kh, int kw, int f)
 {
-    if (elem_bytes != 4 || H < 128 || W < 128 || f < 2 || (call_flags() & SRX_FLAG_TILES))
+    if (!shape_admits(elem_bytes, H, W) || f < 2 || (call_flags() & SRX_FLAG_TILES))
         return false;
     mosaic::AxisPlan py, px;
     if (!mosaic::plan_axis(N, sh, 0, f, py) || !mosaic::plan_axis(N, sh, 1, f, px))
@@ -113,7 +113,7 @@ static inline bool eligible(int elem_bytes, int N, int H, int W, const double *s
     fused::make_kernel7<float>(k, kh, kw, false, kc);
     // a PSF that is not rank 1 (the reference's --psf measured, mono_cal_target/run_sr.py:114-152) runs both 7 x 7 blurs in row
     // layout, rows = lanes: one block row per tile
-    return (kc.separable || NSY == 1) && axis_ok(py, N, f) && axis_ok(px, N, f);
+    return (kc.separable || NSY == 1) && axis_ok(py, f) && axis_ok(px, f);
 }
 
 // ---- once per call -----------------------------------------------------------------------------------------------------
@@ -675,7 +675,7 @@ __global__ void __launch_bounds__(256 * NSY, SRX_ZTILE_WPE)
 }
 
 // ---- host ----------------------------------------------------------------------------------------------------------
-static inline size_t tabs_bytes(int B, int N, int H, int W)
+static inline size_t tabs_bytes(int, int B, int N, int H, int W)
 {
     const size_t ngrp = ((size_t)N + 3) / 4, NT = (size_t)6 * (W + 4) + (size_t)H * 6;
     const size_t ty = cdiv(H, VTY), tx = cdiv(W, VT), HP = ty * VTY + 2 * HALO, WP = tx * VT + 2 * HALO;
@@ -700,27 +700,19 @@ struct State {
     float *cur() const { return (it & 1) ? s1 : s0; }
 };
 
-static int setup(State &zs, const float *hr_init, int B, int N, const mosaic::AxisPlan &py, const mosaic::AxisPlan &px,
-                 const fused::Kernel7<float> &kc, const fused::Kernel7<float> &kt, const float *Mg, const float *Cg, const float *Mu,
-                 const int *ncu, const int *nyx, int NS, int NB, const double *Vtot, Arena &ar, int H, int W, double step, double scale, int tr_lo,
-                 int tr_hi, hipStream_t st)
+static int setup(State &zs, const mosaic::Common<float> &c, const float *hr_init, int tr_lo, int tr_hi, Arena &ar, hipStream_t st)
 {
+    const int B = c.B, H = c.H, W = c.W, NS = c.NS;
+    const mosaic::AxisPlan &py = c.py, &px = c.px;
     ZArgs &za = zs.za;
     za.H = H, za.W = W, za.tiles_x = cdiv(W, VT), za.tiles_y = cdiv(H, VTY);
     za.HP = za.tiles_y * VTY + 2 * HALO, za.WP = za.tiles_x * VT + 2 * HALO;
     const int HP = za.HP, WP = za.WP;
-    auto ext = [&](const mosaic::AxisPlan &pl, int &ex, int &nb) {
-        int nmin = pl.n[0], nmax = pl.n[0];
-        for (int k = 1; k < N; k++)
-            nmin = std::min(nmin, pl.n[k]), nmax = std::max(nmax, pl.n[k]);
-        ex = nmax, nb = -nmin;
-    };
-    ext(py, za.exy, za.nby);
-    ext(px, za.exx, za.nbx);
+    za.exy = py.nmax, za.nby = -py.nmin, za.exx = px.nmax, za.nbx = -px.nmin;
     za.Ey = py.E, za.Ex = px.E;
     za.WT = W + za.exx, za.LN = za.exx + za.nbx, za.TOPN = (za.exy + za.nby) * za.WT;
     za.ngrp = NS / 4;
-    za.sn = (float)step / (float)N;
+    za.sn = (float)c.step / (float)c.N;
     za.tr_lo = tr_lo, za.tr_hi = tr_hi;
     const int NT = za.TOPN + (H - za.nby) * za.LN, ntiles = za.tiles_x * za.tiles_y;
     const size_t splane = (size_t)(HP + 2) * WP;
@@ -738,26 +730,21 @@ static int setup(State &zs, const float *hr_init, int B, int N, const mosaic::Ax
         return SRX_E_WORKSPACE;
     patch::AxisWPair awp;
     for (int i = 0; i < 8; i++) {
-        awp.y.kb[i] = i < 7 ? kc.cy[i] : 0.f, awp.y.kt[i] = i < 7 ? kt.cy[i] : 0.f, awp.y.wfb[i] = 0.f;
-        awp.x.kb[i] = i < 7 ? kc.cx[i] : 0.f, awp.x.kt[i] = i < 7 ? kt.cx[i] : 0.f, awp.x.wfb[i] = 0.f;
+        awp.y.kb[i] = i < 7 ? c.kc.cy[i] : 0.f, awp.y.kt[i] = i < 7 ? c.kt.cy[i] : 0.f, awp.y.wfb[i] = 0.f;
+        awp.x.kb[i] = i < 7 ? c.kc.cx[i] : 0.f, awp.x.kt[i] = i < 7 ? c.kt.cx[i] : 0.f, awp.x.wfb[i] = 0.f;
     }
     hipLaunchKernelGGL(patch::k_patch_params, dim3(1), dim3(1), 0, st, awp, aw);
     SRX_CHECK_LAUNCH();
-    const bool sep = kc.separable && kt.separable;
-    bool ring0 = true;  // the outer ring of the 7 x 7 weights is zero (the reference's measured PSF is 5 x 5)
-    for (int i = 0; i < 7; i++)
-        for (int e : {i, 42 + i, 7 * i, 7 * i + 6})
-            ring0 = ring0 && kc.k[e] == 0.f && kt.k[e] == 0.f;
-    zs.psf = sep ? 0 : (ring0 ? 2 : 3);
-    if (!sep) {
+    zs.psf = fused::psf_form(c.kc, c.kt);
+    if (!c.sep) {
         K2Tab kv;
         for (int u = 0; u < 7; u++)
             for (int v = 0; v < 8; v++)
-                kv.v[8 * u + v] = v < 7 ? kc.k[7 * u + v] : 0.f, kv.v[56 + 8 * u + v] = v < 7 ? kt.k[7 * u + v] : 0.f;
+                kv.v[8 * u + v] = v < 7 ? c.kc.k[7 * u + v] : 0.f, kv.v[56 + 8 * u + v] = v < 7 ? c.kt.k[7 * u + v] : 0.f;
         hipLaunchKernelGGL(k_ztile_k2, dim3(1), dim3(128), 0, st, kv, k2);
         SRX_CHECK_LAUNCH();
     }
-    hipLaunchKernelGGL(k_ztile_prep, dim3(cdiv(WP, 32), cdiv(HP, 32), B + 1), dim3(32, 8), 0, st, Mg, Cg, B, H, W, HP, WP, za.nby, za.nbx, Mt, Ct);
+    hipLaunchKernelGGL(k_ztile_prep, dim3(cdiv(WP, 32), cdiv(HP, 32), B + 1), dim3(32, 8), 0, st, c.Mg, c.Cg, B, H, W, HP, WP, za.nby, za.nbx, Mt, Ct);
     SRX_CHECK_LAUNCH();
     if (fill_bytes(cmok, 0xff, (size_t)B * sizeof(int), st) != hipSuccess)
         return SRX_E_HIP;
@@ -769,13 +756,13 @@ static int setup(State &zs, const float *hr_init, int B, int N, const mosaic::Ax
     hipLaunchKernelGGL(k_ztile_copy_in, dim3(cdiv(W, 256), H, B), dim3(256), 0, st, hr_init, H, W, HP, WP, s0, 0);
     SRX_CHECK_LAUNCH();
     if (NT > 0) {
-        hipLaunchKernelGGL(k_ztile_near_tab, dim3(cdiv(NT, 256)), dim3(256), 0, st, ncu, nyx, NS, py.PB, px.PB, za, NT, nrec, nent);
+        hipLaunchKernelGGL(k_ztile_near_tab, dim3(cdiv(NT, 256)), dim3(256), 0, st, c.ncu, c.nyx, NS, py.PB, px.PB, za, NT, nrec, nent);
         SRX_CHECK_LAUNCH();
-        hipLaunchKernelGGL(k_ztile_near_m, dim3(cdiv(NT, 256), B), dim3(256), 0, st, Mg, Mu, NB, py.PB, px.PB, za, NT, Mn);
+        hipLaunchKernelGGL(k_ztile_near_m, dim3(cdiv(NT, 256), B), dim3(256), 0, st, c.Mg, c.Mu, c.NB, py.PB, px.PB, za, NT, Mn);
         SRX_CHECK_LAUNCH();
     }
     zs.tb = ZTabs{Mt, Ct, CM, cmok, aw, k2, nrec, nent, Mn};
-    zs.s0 = s0, zs.s1 = s1, zs.ep0 = ep0, zs.ep1 = ep1, zs.Vtot = Vtot, zs.scale = scale, zs.B = B, zs.ntiles = ntiles, zs.it = 0, zs.sep = sep;
+    zs.s0 = s0, zs.s1 = s1, zs.ep0 = ep0, zs.ep1 = ep1, zs.Vtot = c.Vtot, zs.scale = c.scale, zs.B = B, zs.ntiles = ntiles, zs.it = 0, zs.sep = c.sep;
     return SRX_OK;
 }
 
@@ -821,15 +808,12 @@ static int rows_in(const State &zs, int y0, int rows, const float *src, hipStrea
     return SRX_OK;
 }
 
-static int iterate(const float *hr_init, float *hr, int B, int N, const mosaic::AxisPlan &py, const mosaic::AxisPlan &px,
-                   const fused::Kernel7<float> &kc, const fused::Kernel7<float> &kt, const float *Mg, const float *Cg, const float *Mu,
-                   const int *ncu, const int *nyx, int NS, int NB, const double *Vtot, Arena &ar, int H, int W, int n_iter, double step,
-                   double scale, double *errors, hipStream_t st)
+static int iterate(const mosaic::Common<float> &c, const float *hr_init, float *hr, int n_iter, double *errors, Arena &ar, hipStream_t st)
 {
     State zs;
-    SRX_TRY(setup(zs, hr_init, B, N, py, px, kc, kt, Mg, Cg, Mu, ncu, nyx, NS, NB, Vtot, ar, H, W, step, scale, 0, H, st));
+    SRX_TRY(setup(zs, c, hr_init, 0, c.H, ar, st));
     SRX_TRY(run(zs, n_iter, errors, st));
-    return rows_out(zs, 0, H, hr, st);
+    return rows_out(zs, 0, c.H, hr, st);
 }
 
 }  // namespace ztile

@@ -105,3 +105,16 @@ def test_exact_workspace_never_exceeds_the_shape_bound():
                                 assert 0 < need <= bound, (f, N, H, W, eb, B, need, bound)
                                 worst = max(worst, need / bound)
     assert worst <= 1.0
+
+
+def test_profile_kernel_names_are_pinned():
+    """srx_profile_kernel_name(i) is ABI: bench.py keys its roofline on these strings and tools read the ids in this order.  The enum
+    and the names come from one list (SRX_KERNEL_LIST, csrc/srx_common.h); this is that list, spelt out."""
+    names = ["k_blur_pad", "k_prefilter_axis0", "k_prefilter_axis1", "k_fwd_residual", "k_back_gather", "k_blurT_update", "k_interp",
+             "k_fir_pad", "k_crop_div", "k_fwd_tile", "k_bwd_tile", "k_mosaic_build", "k_fwd_mosaic", "k_bwd_mosaic", "k_saa_tile",
+             "k_prefilter_small", "k_prefilter_tile", "k_ibp_patch", "k_ibp_ztile", "k_ibp_dtile", "k_ibp_ctile", "k_ibp_bfwd", "k_ibp_bbwd",
+             "k_ibp_afwd", "k_ibp_abwd", "k_patch_build", "k_patch_build_float", "k_atile_near", "k_ibp_sv", "k_ibp_sh", "k_saa_shift"]
+    lib = _lib.load()
+    assert lib.srx_profile_kernel_count() == 31 == len(names)
+    assert [lib.srx_profile_kernel_name(i).decode() for i in range(31)] == names
+    assert lib.srx_profile_kernel_name(31) == b"" and lib.srx_profile_kernel_name(-1) == b""

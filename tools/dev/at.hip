@@ -6,5 +6,7 @@
 #include "srx_btile.hpp"
 #include "srx_atile.hpp"
 namespace srx { Profiler &profiler() { static Profiler p; return p; } }
-int dummy(srx::Arena &ar, const srx::mosaic::AxisPlan &p, const srx::fused::Kernel7<float> &k, const float *f, float *g, const int *i, const double *d, double *e)
-{ return srx::atile::iterate(f, g, 1, 4, 2, p, p, k, k, f, f, f, i, i, 4, 100, d, ar, 128, 128, 1, 0.5, 1.0, e, 0); }
+int dummy(srx::Arena &ar, const srx::mosaic::Common<float> &c, const float *p, float *q, double *e)
+{
+    return srx::atile::iterate(c, p, q, 2, e, ar, 0);
+}

@@ -6,7 +6,7 @@
 #include "srx_ztile.hpp"
 #include "srx_ctile.hpp"
 namespace srx { Profiler &profiler() { static Profiler p; return p; } }
-int dummy(srx::Arena &ar, const srx::mosaic::AxisPlan &py, const srx::fused::Kernel7<double> &kc, const double *p, double *q, const int *i, const double *d, double *e)
+int dummy(srx::Arena &ar, const srx::mosaic::Common<double> &c, const double *p, double *q, double *e)
 {
-    return srx::ctile::iterate<double>(p, q, 1, 5, py, py, kc, kc, p, p, p, i, i, 8, 100, d, ar, 512, 512, 2, 0.5, 1.0, e, 0);
+    return srx::ctile::iterate<double>(c, p, q, 2, e, ar, 0);
 }

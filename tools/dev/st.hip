@@ -5,7 +5,7 @@
 #include "srx_patch.hpp"
 #include "srx_stile.hpp"
 namespace srx { Profiler &profiler() { static Profiler p; return p; } }
-int dummy(srx::Arena &ar, const srx::mosaic::AxisPlan &py, const srx::fused::Kernel7<double> &kc, const double *p, double *q, const int *i, const double *d, double *e)
+int dummy(srx::Arena &ar, const srx::mosaic::Common<double> &c, const double *p, double *q, double *e)
 {
-    return srx::stile::iterate<double>(p, q, 1, 16, 4, py, py, kc, kc, p, p, p, i, i, 16, 100, d, ar, 2, 0.5, 1.0, e, 0);
+    return srx::stile::iterate<double>(c, p, q, 2, e, ar, 0);
 }
