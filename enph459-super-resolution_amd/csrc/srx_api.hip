@@ -90,6 +90,7 @@ static int shift_cubic(const T *in, int B, int H, int W, double sy, double sx, T
     if (!plane_fits(sizeof(T), 1, H, W, H, W))
         return SRX_E_UNSUPPORTED;
     Arena ar(ws, wsb);
+    ar.require(shift_ws((int)sizeof(T), B, H, W));
     T *pad = ar.take<T>((size_t)B * (H + 2 * SRX_NPAD) * (W + 2 * SRX_NPAD));
     T *scr = ar.take<T>((size_t)B * (H + 2 * SRX_NPAD) * (W + 2 * SRX_NPAD));
     AxisTap<T> *ty = ar.take<AxisTap<T>>(H), *tx = ar.take<AxisTap<T>>(W);
@@ -126,6 +127,7 @@ static int zoom_cubic(const T *in, int B, int h, int w, int f, T *out, void *ws,
     if ((size_t)h * f >= ((size_t)1 << 30) || (size_t)w * f >= ((size_t)1 << 30) || !plane_fits(sizeof(T), 1, h, w, h * f, w * f))
         return SRX_E_UNSUPPORTED;
     Arena ar(ws, wsb);
+    ar.require(zoom_ws((int)sizeof(T), B, h, w, f));
     T *coef = ar.take<T>((size_t)B * h * w), *cscr = ar.take<T>((size_t)B * h * w);
     AxisTap<T> *ty = ar.take<AxisTap<T>>((size_t)h * f), *tx = ar.take<AxisTap<T>>((size_t)w * f);
     if (!ar.ok)
@@ -148,6 +150,7 @@ static int forward_model(const T *hr, int B, int H, int W, const double *k, int 
     if (!plane_fits(sizeof(T), 1, 1, 1, H, W))
         return SRX_E_UNSUPPORTED;
     Arena ar(ws, wsb);
+    ar.require(forward_ws((int)sizeof(T), B, H, W));
     T *b = ar.take<T>((size_t)B * H * W);
     T *pad = ar.take<T>((size_t)B * (H + 2 * SRX_NPAD) * (W + 2 * SRX_NPAD));
     T *scr = ar.take<T>((size_t)B * (H + 2 * SRX_NPAD) * (W + 2 * SRX_NPAD));
@@ -174,6 +177,7 @@ static int back_project(const T *err, int B, int eh, int ew, const double *k, in
     if (B > 65535 || !plane_fits(sizeof(T), 1, eh, ew, H, W))
         return SRX_E_UNSUPPORTED;
     Arena ar(ws, wsb);
+    ar.require(backproject_ws((int)sizeof(T), B, H, W));
     T *up = ar.take<T>((size_t)B * H * W), *s2 = ar.take<T>((size_t)B * H * W);
     T *pad = ar.take<T>((size_t)B * (H + 2 * SRX_NPAD) * (W + 2 * SRX_NPAD));
     T *scr = ar.take<T>((size_t)B * (H + 2 * SRX_NPAD) * (W + 2 * SRX_NPAD));
@@ -342,28 +346,22 @@ static Route route_ibp(int eb, int N, int h, int w, int H, int W, int f, const d
     return {SRX_OK, PATH_FUSED, nullptr, "fused"};
 }
 
-template <typename T>
-static int ibp_dispatch(const T *lr, int B, int N, int h, int w, const double *sh, const double *k, int kh, int kw,
-                        const T *hr_init, int H, int W, int f, int n_iter, double step, T *hr, double *errors, void *ws,
-                        size_t wsb, hipStream_t st, unsigned flags)
+// What a call on route `r` must bring: exactly what a mosaic implementation carves (the shape-only bound covers it by construction,
+// tests/test_abi.py sweeps shapes for need <= bound), the shape-only bound on every other path.
+static size_t ibp_need(const Route &r, int eb, int B, int N, int h, int w, int H, int W, int f, unsigned flags)
 {
-    if (!basic_ibp_args_ok(lr, B, N, h, w, sh, k, kh, kw, hr_init, H, W, f, n_iter, hr))
-        return SRX_E_INVALID;
-    if (N > SRX_MAX_FRAMES || kh * kw > SRX_MAX_KERNEL_TAPS || !plane_fits(sizeof(T), N, h, w, H, W))
-        return SRX_E_UNSUPPORTED;
-    if (B > SRX_MAX_BATCH_PER_LAUNCH) {  // the workspace is sized for one chunk and reused (stream order)
-        for (int b0 = 0; b0 < B; b0 += SRX_MAX_BATCH_PER_LAUNCH) {
-            const int bc = B - b0 < SRX_MAX_BATCH_PER_LAUNCH ? B - b0 : SRX_MAX_BATCH_PER_LAUNCH;
-            SRX_TRY(ibp_dispatch<T>(lr + (size_t)b0 * N * h * w, bc, N, h, w, sh, k, kh, kw, hr_init + (size_t)b0 * H * W, H, W,
-                                    f, n_iter, step, hr + (size_t)b0 * H * W, errors ? errors + (size_t)b0 * n_iter : nullptr,
-                                    ws, wsb, st, flags));
-        }
-        return SRX_OK;
-    }
-    const Route r = route_ibp((int)sizeof(T), N, h, w, H, W, f, sh, k, kh, kw, flags);
-    if (r.status != SRX_OK)
-        return r.status;
-    g_last_path = r.name;
+    if (B > SRX_MAX_BATCH_PER_LAUNCH)
+        B = SRX_MAX_BATCH_PER_LAUNCH;
+    if (r.status != SRX_OK || r.path != PATH_MOSAIC)
+        return srx_ibp_workspace_bytes(eb, B, N, h, w, H, W, f, flags);
+    return mosaic::ibp_ws_for(*r.impl, eb, B, N, H, W);
+}
+
+// one chunk (at most SRX_MAX_BATCH_PER_LAUNCH items) of a call on the route its entry point decided
+template <typename T>
+static int ibp_run(const Route &r, const T *lr, int B, int N, int h, int w, const double *sh, const double *k, int kh, int kw, const T *hr_init, int H,
+                   int W, int f, int n_iter, double step, T *hr, double *errors, void *ws, size_t wsb, hipStream_t st)
+{
     switch (r.path) {
     case PATH_MOSAIC:
         return mosaic::ibp<T>(*r.impl, lr, B, N, h, w, sh, k, kh, kw, hr_init, H, W, f, n_iter, step, hr, errors, ws, wsb, st);
@@ -380,6 +378,31 @@ static int ibp_dispatch(const T *lr, int B, int N, int h, int w, const double *s
 }
 
 template <typename T>
+static int ibp_dispatch(const T *lr, int B, int N, int h, int w, const double *sh, const double *k, int kh, int kw,
+                        const T *hr_init, int H, int W, int f, int n_iter, double step, T *hr, double *errors, void *ws,
+                        size_t wsb, hipStream_t st, unsigned flags)
+{
+    if (!basic_ibp_args_ok(lr, B, N, h, w, sh, k, kh, kw, hr_init, H, W, f, n_iter, hr))
+        return SRX_E_INVALID;
+    if (N > SRX_MAX_FRAMES || kh * kw > SRX_MAX_KERNEL_TAPS || !plane_fits(sizeof(T), N, h, w, H, W))
+        return SRX_E_UNSUPPORTED;
+    const Route r = route_ibp((int)sizeof(T), N, h, w, H, W, f, sh, k, kh, kw, flags);  // once per call: the batch size plays no part
+    if (r.status != SRX_OK)
+        return r.status;
+    // a short or misaligned workspace is refused before anything is queued
+    if (ws_short(ws, wsb, ibp_need(r, (int)sizeof(T), B, N, h, w, H, W, f, flags)))
+        return SRX_E_WORKSPACE;
+    g_last_path = r.name;
+    // batches beyond one launch's gridDim.z go through in chunks; the workspace is sized for one chunk and reused (stream order)
+    for (int b0 = 0; b0 < B; b0 += SRX_MAX_BATCH_PER_LAUNCH) {
+        const int bc = B - b0 < SRX_MAX_BATCH_PER_LAUNCH ? B - b0 : SRX_MAX_BATCH_PER_LAUNCH;
+        SRX_TRY(ibp_run<T>(r, lr + (size_t)b0 * N * h * w, bc, N, h, w, sh, k, kh, kw, hr_init + (size_t)b0 * H * W, H, W, f, n_iter, step,
+                           hr + (size_t)b0 * H * W, errors ? errors + (size_t)b0 * n_iter : nullptr, ws, wsb, st));
+    }
+    return SRX_OK;
+}
+
+template <typename T>
 static int saa_dispatch(const T *lr, int B, int N, int h, int w, const double *sh, int f, T *out, void *ws, size_t wsb,
                         hipStream_t st, unsigned flags)
 {
@@ -387,6 +410,8 @@ static int saa_dispatch(const T *lr, int B, int N, int h, int w, const double *s
         return SRX_E_INVALID;
     if (N > SRX_MAX_FRAMES || (size_t)h * f >= ((size_t)1 << 30) || (size_t)w * f >= ((size_t)1 << 30) || !plane_fits(sizeof(T), N, h, w, h * f, w * f))
         return SRX_E_UNSUPPORTED;
+    if (ws_short(ws, wsb, srx_saa_workspace_bytes((int)sizeof(T), B, N, h, w, f)))  // before anything is queued
+        return SRX_E_WORKSPACE;
     if ((long)B * N > SRX_MAX_BATCH_PER_LAUNCH) {
         const int step_b = SRX_MAX_BATCH_PER_LAUNCH / N > 0 ? SRX_MAX_BATCH_PER_LAUNCH / N : 1;
         for (int b0 = 0; b0 < B; b0 += step_b) {
@@ -438,6 +463,8 @@ static int plan_create(const T *lr, int B, int N, int h, int w, const double *sh
         return SRX_E_INVALID;
     if (N > SRX_MAX_FRAMES || kh * kw > SRX_MAX_KERNEL_TAPS || B > SRX_MAX_BATCH_PER_LAUNCH || !plane_fits(sizeof(T), N, h, w, H, W))
         return SRX_E_UNSUPPORTED;
+    if (ws_short(ws, wsb, srx_ibp_plan_workspace_bytes((int)sizeof(T), B, N, h, w, H, W, f, flags)))  // before anything is queued
+        return SRX_E_WORKSPACE;
     srx_plan_s *p = new srx_plan_s();
     p->eb = (int)sizeof(T), p->B = B, p->N = N, p->h = h, p->w = w, p->H = H, p->W = W, p->f = f, p->kh = kh, p->kw = kw, p->tr_lo = tr_lo, p->tr_hi = tr_hi;
     p->step = step, p->flags = flags, p->lr = lr, p->z = false, p->hr = nullptr, p->ws_rest = nullptr, p->wsb_rest = 0, p->path = "none";
@@ -586,7 +613,7 @@ const char *srx_strerror(int s)
     case SRX_OK: return "ok";
     case SRX_E_INVALID: return "invalid argument";
     case SRX_E_UNSUPPORTED: return "unsupported configuration";
-    case SRX_E_WORKSPACE: return "workspace missing or too small";
+    case SRX_E_WORKSPACE: return "workspace missing, not 256-byte aligned or too small";
     case SRX_E_HIP: return "HIP runtime error";
     default: return "unknown status";
     }
@@ -660,18 +687,21 @@ size_t srx_ibp_workspace_bytes(int eb, int B, int N, int h, int w, int H, int W,
 size_t srx_ibp_workspace_bytes_for(int eb, int B, int N, int h, int w, int H, int W, int f, const double *sh, const double *k, int kh,
                                    int kw, unsigned flags)
 {
-    const size_t bound = srx_ibp_workspace_bytes(eb, B, N, h, w, H, W, f, flags);
     if (!sh || !k || N <= 0 || N > SRX_MAX_FRAMES)
-        return bound;
-    if (B > SRX_MAX_BATCH_PER_LAUNCH)
-        B = SRX_MAX_BATCH_PER_LAUNCH;
+        return srx_ibp_workspace_bytes(eb, B, N, h, w, H, W, f, flags);
+    CallFlags cf(flags);
+    return ibp_need(route_ibp(eb, N, h, w, H, W, f, sh, k, kh, kw, flags), eb, B, N, h, w, H, W, f, flags);
+}
+
+const char *srx_ibp_path_for(int eb, int N, int h, int w, int H, int W, int f, const double *sh, const double *k, int kh, int kw, unsigned flags)
+{
+    int dummy = 0;  // (stands for the device pointers: only their presence is checked)
+    if ((eb != 4 && eb != 8) || !basic_ibp_args_ok(&dummy, 1, N, h, w, sh, k, kh, kw, &dummy, H, W, f, 1, &dummy) || N > SRX_MAX_FRAMES ||
+        kh * kw > SRX_MAX_KERNEL_TAPS || !plane_fits((size_t)eb, N, h, w, H, W))
+        return "none";
     CallFlags cf(flags);
     const Route r = route_ibp(eb, N, h, w, H, W, f, sh, k, kh, kw, flags);
-    if (r.status != SRX_OK || r.path != PATH_MOSAIC)
-        return bound;
-    // exactly what the call carves.  The shape-only bound covers it by construction (tests/test_abi.py sweeps shapes for need <= bound);
-    // should the two ever disagree, the call's own need is the answer that lets it run
-    return mosaic::ibp_ws_for(*r.impl, eb, B, N, H, W);
+    return r.status == SRX_OK ? r.name : "none";
 }
 
 int srx_interleave4_u8(const uint8_t *frames, int B, int h, int w, uint8_t *out, srx_stream_t s)
@@ -687,9 +717,7 @@ int srx_interleave4_u8(const uint8_t *frames, int B, int h, int w, uint8_t *out,
 
 size_t srx_metrics_workspace_bytes(int B, int H, int W, int nbin)
 {
-    const size_t a = metrics::moments_ws(B > 0 ? B : 1), b = metrics::rows_ws(H > 0 ? H : 1, nbin > 0 ? nbin : 1),
-                 c = 2 * align_up((size_t)(H > 0 ? H : 1) * (W > 0 ? W : 1) * sizeof(double));
-    return std::max(a, std::max(b, c));
+    return metrics::workspace_bytes(B, H, W, nbin);
 }
 
 int srx_edge_magnitude_f64(const double *roi, int H, int W, double sigma, double *mag, void *ws, size_t wsb, srx_stream_t s)

@@ -44,12 +44,24 @@ struct CallFlags {
 
 static inline size_t align_up(size_t x, size_t a = 256) { return (x + a - 1) / a * a; }
 
-// bump allocator over the caller's workspace
+// The one statement of the workspace rule (srx.h): the arena holds the call's documented size (its *_workspace_bytes) and lies on the
+// 256-byte grid, or the call is SRX_E_WORKSPACE on the host -- whether or not the path it takes would have carved less.
+static inline bool ws_short(const void *ws, size_t wsb, size_t need) { return (need && !ws) || ((uintptr_t)ws & 255) || wsb < need; }
+
+// bump allocator over the caller's workspace.  The base must be 256-byte aligned (srx.h): every plane starts on a multiple of 256 from
+// it and the kernels move arena planes 16 bytes at a time; a misaligned base is refused here, on the host, like a missing one.
 struct Arena {
     char *base;
     size_t cap, off;
     bool ok;
-    Arena(void *p, size_t n) : base((char *)p), cap(n), off(0), ok(p != nullptr || n == 0) {}
+    Arena(void *p, size_t n) : base((char *)p), cap(n), off(0), ok(!ws_short(p, n, n)) {}
+    // the documented size of the call (its *_workspace_bytes): a shorter arena is refused before anything is carved or queued, whether
+    // or not the path this call takes would have fitted
+    void require(size_t need)
+    {
+        if (ws_short(base, cap, need))
+            ok = false;
+    }
     template <typename U> U *take(size_t count)
     {
         size_t bytes = align_up(count * sizeof(U));

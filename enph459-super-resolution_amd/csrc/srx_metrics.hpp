@@ -370,6 +370,15 @@ __global__ void __launch_bounds__(64) k_mean_partials(const double *__restrict__
 
 // ---- host ---------------------------------------------------------------------------------------------------------------------------
 static inline size_t moments_ws(int B) { return align_up((size_t)B * RED_BLOCKS * NMOM * sizeof(double)); }
+static inline size_t rows_ws(int H, int nbin) { return align_up((size_t)H * 2 * nbin * sizeof(double)); }
+// srx_metrics_workspace_bytes: one size for every metric of a [B, H, W] batch with nbin bins.  A call is held to it at its own
+// arguments (B = 1 / nbin = 1 where it has none), so a caller that sized the arena for the whole set passes every call.
+static inline size_t workspace_bytes(int B, int H, int W, int nbin)
+{
+    const size_t a = moments_ws(B > 0 ? B : 1), b = rows_ws(H > 0 ? H : 1, nbin > 0 ? nbin : 1),
+                 c = 2 * align_up((size_t)(H > 0 ? H : 1) * (W > 0 ? W : 1) * sizeof(double));
+    return std::max(a, std::max(b, c));
+}
 
 template <typename T>
 static int pair_moments(const T *ref, const T *test, int B, int H, int W, int border, double *out, void *ws, size_t wsb, hipStream_t st)
@@ -379,6 +388,7 @@ static int pair_moments(const T *ref, const T *test, int B, int H, int W, int bo
     if (B > 65535)
         return SRX_E_UNSUPPORTED;
     Arena ar(ws, wsb);
+    ar.require(workspace_bytes(B, H, W, 1));
     const int nblk = std::min(RED_BLOCKS, H - 2 * border);
     double *part = ar.take<double>((size_t)B * nblk * NMOM);
     if (!ar.ok)
@@ -426,6 +436,7 @@ static int ssim(const T *ref, const T *test, int B, int H, int W, int border, in
     gy = cdiv(h, rows_per);
     const int nblk = gx * gy;
     Arena ar(ws, wsb);
+    ar.require(workspace_bytes(B, H, W, 1));
     double *part = ar.take<double>((size_t)B * nblk);
     if (!ar.ok)
         return SRX_E_WORKSPACE;
@@ -456,14 +467,13 @@ template <typename T> static int local_contrast(const T *prof, int B, int n, int
     return SRX_OK;
 }
 
-static inline size_t rows_ws(int H, int nbin) { return align_up((size_t)H * 2 * nbin * sizeof(double)); }
-
 template <typename T>
 static int ring_sums(const T *img, int H, int W, double cy, double cx, int nbin, double *out, void *ws, size_t wsb, hipStream_t st)
 {
     if (!img || !out || H <= 0 || W <= 0 || nbin <= 0 || nbin > 4096)
         return SRX_E_INVALID;
     Arena ar(ws, wsb);
+    ar.require(workspace_bytes(1, H, W, nbin));
     double *rows = ar.take<double>((size_t)H * 2 * nbin);
     if (!ar.ok)
         return SRX_E_WORKSPACE;
@@ -502,6 +512,7 @@ static int edge_magnitude(const double *roi, int H, int W, double sigma, double 
     for (int j = 2 * t.r + 1; j < 17; j++)
         t.k[j] = 0.0;
     Arena ar(ws, wsb);
+    ar.require(workspace_bytes(1, H, W, 1));
     double *a = ar.take<double>((size_t)H * W), *b = ar.take<double>((size_t)H * W);
     if (!ar.ok)
         return SRX_E_WORKSPACE;
@@ -521,6 +532,7 @@ static int edge_bins(const T *roi, int H, int W, EdgeLine e, double *out /*[2 nb
     if (!roi || !out || H <= 0 || W <= 0 || e.nbin <= 0 || e.nbin > 128 || !(e.norm > 0.0) || !(e.bw > 0.0))
         return SRX_E_INVALID;
     Arena ar(ws, wsb);
+    ar.require(workspace_bytes(1, H, W, e.nbin));
     double *rows = ar.take<double>((size_t)H * 2 * e.nbin);
     if (!ar.ok)
         return SRX_E_WORKSPACE;

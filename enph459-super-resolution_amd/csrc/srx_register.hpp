@@ -424,6 +424,7 @@ static int register_frames(const T *frames, int B, int N, int H, int W, int ref,
     const Plan p = make_plan(g.h, g.w, search);
     const int w0 = W - 2 * (search + 2);  // the crop width the workspace formula assumes (border 0)
     Arena ar(ws, wsb);
+    ar.require(workspace_bytes((int)sizeof(T), B, N, H, W, search));
     T *coef = ar.take<T>(nf * plane), *scratch = ar.take<T>(nf * plane);
     double *cpart = ar.take<double>((size_t)nf * coarse_blocks_max(w0) * p.nv);
     double *gpart = ar.take<double>((size_t)nf * gn_blocks_max(w0) * NG);

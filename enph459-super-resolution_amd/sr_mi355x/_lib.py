@@ -62,6 +62,7 @@ _PLAIN = {
     "srx_saa_workspace_bytes": (_Z, [_I, _I, _I, _I, _I, _I]),
     "srx_ibp_workspace_bytes": (_Z, [_I, _I, _I, _I, _I, _I, _I, _I, _U]),
     "srx_ibp_workspace_bytes_for": (_Z, [_I, _I, _I, _I, _I, _I, _I, _I, _HD, _HD, _I, _I, _U]),
+    "srx_ibp_path_for": (_c.c_char_p, [_I, _I, _I, _I, _I, _I, _I, _HD, _HD, _I, _I, _U]),
     "srx_ibp_plan_workspace_bytes": (_Z, [_I, _I, _I, _I, _I, _I, _I, _I, _U]),
     "srx_ibp_plan_run": (_I, [_P, _I, _P, _P]),
     "srx_ibp_plan_path": (_c.c_char_p, [_P]),

@@ -24,6 +24,22 @@
  *     enqueued on it; nothing synchronises the device.  No allocation happens inside a
  *     call: scratch comes from the caller's workspace (`*_workspace_bytes`, 256-B aligned
  *     device memory).  Inputs are never written; outputs never alias inputs unless stated.
+ *   - Memory contract (tests/test_gpu_memory_contract.py holds every entry point to it): a call
+ *     writes its outputs and bytes [0, ws_bytes) of its workspace, nothing else.  The workspace
+ *     may hold anything on entry (it is never assumed zero) and nothing is kept in it between
+ *     calls (plans excepted).  ws_bytes is checked on the host against the call's documented
+ *     size -- its `*_workspace_bytes` at the call's own arguments, srx_ibp_workspace_bytes_for
+ *     for srx_ibp -- and the pointer against the 256-byte grid: a shorter or misaligned
+ *     workspace is SRX_E_WORKSPACE before anything is queued, whether or not the path the call
+ *     takes would have carved less.  Image, output and errors pointers need only the alignment
+ *     of their element type (a frame sliced out of a batch of odd-sized frames is fine): no
+ *     kernel casts a caller pointer to a vector type, and only arena planes are moved as aligned
+ *     16-byte vectors.  One kernel does reach caller memory with 128-bit BUFFER accesses at
+ *     addresses that are then only 4-byte aligned (k_ibp_patch parks its state in hr_out, 16 bytes
+ *     per lane): that is legal because the HIP runtime runs gfx9 devices in unaligned-access mode
+ *     (SH_MEM_CONFIG.ALIGNMENT_MODE: multi-dword accesses need dword alignment), which is what
+ *     this guarantee rests on for that kernel; the element-aligned cases of the memory-contract
+ *     tests are its check on a given installation.
  *   - Streams and graphs: a call only queues kernels and device-to-device copies on `stream`
  *     (every fill is a kernel, the host arrays are read before the call returns and travel as
  *     kernel arguments or are expanded on the device), so it may be captured into a HIP graph
@@ -56,7 +72,7 @@ typedef enum {
     SRX_E_INVALID = -1,     /* null pointer, non-positive size, bad factor */
     SRX_E_UNSUPPORTED = -2, /* kernel larger than SRX_MAX_KERNEL_TAPS, N > SRX_MAX_FRAMES, or one image plane (with its 12-sample pad) /
                                one item's N frames of 2 GiB or more: planes are indexed with 32-bit offsets; the batch count is not limited */
-    SRX_E_WORKSPACE = -3,   /* workspace pointer null or smaller than *_workspace_bytes() */
+    SRX_E_WORKSPACE = -3,   /* workspace pointer null, not 256-byte aligned, or smaller than *_workspace_bytes() */
     SRX_E_HIP = -4          /* a HIP runtime call or kernel launch failed */
 } srx_status;
 
@@ -162,6 +178,10 @@ size_t srx_ibp_workspace_bytes(int elem_bytes, int B, int N, int h, int w, int H
  * every implementation the shape admits). */
 size_t srx_ibp_workspace_bytes_for(int elem_bytes, int B, int N, int h, int w, int H, int W, int factor, const double *shifts_yx,
                                    const double *kernel, int kh, int kw, unsigned flags);
+/* The name srx_last_path() reports after an srx_ibp call with these arguments ("none" for arguments the call refuses): the route
+ * is decided from shapes, shifts, PSF and flags on the host, so this needs no device and queues nothing. */
+const char *srx_ibp_path_for(int elem_bytes, int N, int h, int w, int H, int W, int factor, const double *shifts_yx, const double *kernel,
+                             int kh, int kw, unsigned flags);
 int srx_ibp_f32(const float *lr, int B, int N, int h, int w, const double *shifts_yx, const double *kernel, int kh,
                 int kw, const float *hr_init, int H, int W, int factor, int n_iter, double step, float *hr_out,
                 double *errors_out, void *ws, size_t ws_bytes, srx_stream_t stream, unsigned flags);
@@ -230,7 +250,8 @@ int srx_interleave4_u8(const uint8_t *frames, int B, int h, int w, uint8_t *out,
  * data_collection/psf_mtf_utils.py:67-95; the vendor GUI's PSNR, opt_materials/software/XPR_Software.py:735-745, 1215-1256).  These entry points
  * are the parts that are work on a frame or an ROI; sr_mi355x/metrics.py keeps the few-thousand-operation host parts (percentile, line fits,
  * 72-sample FFT, the 7-parameter fit, compute_mtf's 256^2 FFT).  All results are float64 DEVICE arrays; every sum is a fixed-order reduction
- * (bit-identical run to run).  Workspace: srx_metrics_workspace_bytes(B, H, W, nbin) covers every call below at those sizes.
+ * (bit-identical run to run).  Workspace: srx_metrics_workspace_bytes(B, H, W, nbin) covers every call below at those sizes
+ * (a call is held to it at its own arguments, with B = 1 / nbin = 1 where it has none).
  *   pair_moments : out[b] = {n, sum t, sum r, sum t^2, sum t r, sum r^2, sum (r - t)^2} over rows / columns [border, size - border) of
  *                  ref / test [B, H, W]: PSNR = 10 log10(peak^2 n / out[6]); the affine-fit PSNR follows from the other five.
  *   local_contrast: (max - min) / (max + min + 1e-9) of profile[i - w/2 : i + w/2], 0 within w/2 of either end.  [B, n] -> [B, n]
