@@ -191,7 +191,7 @@ __global__ void __launch_bounds__(NBY *NBX * 64, 2)
                double *__restrict__ epart, double scale)
 {
     using L = Lds<NBY, NBX>;
-    __shared__ float lds[L::WORDS];
+    __shared__ __attribute__((aligned(16))) float lds[L::WORDS];
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), s = wave / NBX, u = wave % NBX;
     int wx, wy, b;
@@ -342,7 +342,7 @@ __global__ void __launch_bounds__(NBY *NBX * 64, 2)
                double scale, double *__restrict__ errors, int errors_stride)
 {
     using L = Lds<NBY, NBX>;
-    __shared__ float lds[L::WORDS];
+    __shared__ __attribute__((aligned(16))) float lds[L::WORDS];
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), s = wave / NBX, u = wave % NBX;
     int wx, wy, b;

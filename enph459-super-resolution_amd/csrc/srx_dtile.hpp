@@ -776,7 +776,7 @@ __global__ void __launch_bounds__(256 * NSX)
     k_ibp_dtile(const float *__restrict__ hr_src, float *__restrict__ hr_dst, DTabs tb, DArgs da, double *__restrict__ epart,
                 const double *__restrict__ eprev, const double *__restrict__ Vtot, double scale, double *__restrict__ err_prev, int err_stride)
 {
-    __shared__ float lds[Lds<NSX>::WORDS];
+    __shared__ __attribute__((aligned(16))) float lds[Lds<NSX>::WORDS];
     if (__builtin_amdgcn_readfirstlane(tb.m8[blockIdx.y]) != 0)
         dtile_body<C01, true, NSX, PSF>(lds, hr_src, hr_dst, tb, da, epart, eprev, Vtot, scale, err_prev, err_stride);
     else

@@ -51,7 +51,8 @@ namespace patch {
                          // iteration): 8 -> 150, 2 -> 152, 8|2 -> 144, 8|2|1 -> 139, all -> 138: the memory operations are 14 % of the
                          // iteration; requesting the parked state or the near-band descriptors a chain earlier changes nothing.
 constexpr int PN = 256;        // patch edge (HR pixels)
-constexpr int TSD = 66;        // LDS row stride of a half-block transpose (even: 8-byte row reads, conflict-free)
+constexpr int TSD = 68;        // LDS row stride of a half-block transpose (a multiple of 4 words: 16-byte row reads; 17 quads: the 16
+                               // lanes the LDS serves together read 16 different quads of banks, conflict-free)
 constexpr int RW = 32 * TSD;   // LDS words of a wave's private region
 constexpr int SLOT0 = 0, SLOT1 = 1024;  // exchange slots inside the private region (<= 6 x 64 words each)
 constexpr int FIX = 16;        // samples over which a neighbour's carry is added
@@ -426,6 +427,11 @@ __device__ __forceinline__ void transpose64(const float (&a)[64], float (&r)[64]
     // pass 0 has parked a[0..31] in LDS, not before (an up-front definition keeps 128 registers live through the first 32 stores).
     // (SRX_TRANSPOSE_DEF 0: pass 0 reads unpredicated instead -- the upper half-wave re-reads the lower half's rows.  Same
     // registers, but a third more LDS read traffic in a phase the LDS bounds: C2 162 instead of 156 us per iteration.)
+    // The rows are read 16 bytes at a time (ds_read_b128, 4 LDS cycles per wave-instruction for 1 KB): with the 66-word pitch before,
+    // rows were only 8-byte aligned and hipcc fused the adjacent 8-byte reads into ds_read2_b64, which moves its 1 KB in 8 cycles.  Same-box
+    // A/B on C2: 132.5-133.5 -> 128.3-130.1 us per iteration.  Reading with the WHOLE wave instead (the half-waves exchange quadrants by
+    // v_permlane32_swap first, half as many reads, none predicated) shortens the transposes further and gains nothing: the swaps cost a
+    // SIMD's four waves 25 cycles each, and the time reappears at the barriers around the transposes.
     const unsigned m0v = __builtin_amdgcn_readfirstlane((unsigned)(uintptr_t)Tw);  // LDS byte address of the wave's region
     (void)m0v;
 #pragma unroll
@@ -434,45 +440,45 @@ __device__ __forceinline__ void transpose64(const float (&a)[64], float (&r)[64]
         // Tw[i * TSD + lane] = a[32 h + i] as ds_write_addtid_b32 (address = M0 + offset + 4 * lane, no address register): two LDS
         // cycles per wave-instruction, where ds_write_b32 takes four (its address and data registers travel to the LDS at two cycles
         // per dword) -- the transposes are bound by exactly that (C2: 154 -> 152 us per iteration).  M0 and the stores in one asm block:
-        // the compiler does not model M0 here.  M0 carries the full LDS byte address (the wave regions reach 135 KB; gfx950 honours more
+        // the compiler does not model M0 here.  M0 carries the full LDS byte address (the wave regions reach 139 KB; gfx950 honours more
         // than the 16 bits older ISA documents name -- with the address masked to 16 bits waves 8..15 wrote into the wrong regions and
         // tests/test_gpu_parity.py::test_patch_kernel_vs_oracle failed at once).
-        static_assert(TSD * 4 == 264, "offsets below");
+        static_assert(TSD * 4 == 272, "offsets below");
         asm volatile("s_mov_b32 m0, %16\n\t" SRX_M0_NOP
                      "ds_write_addtid_b32 %0 offset:0\n\t"
-                     "ds_write_addtid_b32 %1 offset:264\n\t"
-                     "ds_write_addtid_b32 %2 offset:528\n\t"
-                     "ds_write_addtid_b32 %3 offset:792\n\t"
-                     "ds_write_addtid_b32 %4 offset:1056\n\t"
-                     "ds_write_addtid_b32 %5 offset:1320\n\t"
-                     "ds_write_addtid_b32 %6 offset:1584\n\t"
-                     "ds_write_addtid_b32 %7 offset:1848\n\t"
-                     "ds_write_addtid_b32 %8 offset:2112\n\t"
-                     "ds_write_addtid_b32 %9 offset:2376\n\t"
-                     "ds_write_addtid_b32 %10 offset:2640\n\t"
-                     "ds_write_addtid_b32 %11 offset:2904\n\t"
-                     "ds_write_addtid_b32 %12 offset:3168\n\t"
-                     "ds_write_addtid_b32 %13 offset:3432\n\t"
-                     "ds_write_addtid_b32 %14 offset:3696\n\t"
-                     "ds_write_addtid_b32 %15 offset:3960\n\t"
+                     "ds_write_addtid_b32 %1 offset:272\n\t"
+                     "ds_write_addtid_b32 %2 offset:544\n\t"
+                     "ds_write_addtid_b32 %3 offset:816\n\t"
+                     "ds_write_addtid_b32 %4 offset:1088\n\t"
+                     "ds_write_addtid_b32 %5 offset:1360\n\t"
+                     "ds_write_addtid_b32 %6 offset:1632\n\t"
+                     "ds_write_addtid_b32 %7 offset:1904\n\t"
+                     "ds_write_addtid_b32 %8 offset:2176\n\t"
+                     "ds_write_addtid_b32 %9 offset:2448\n\t"
+                     "ds_write_addtid_b32 %10 offset:2720\n\t"
+                     "ds_write_addtid_b32 %11 offset:2992\n\t"
+                     "ds_write_addtid_b32 %12 offset:3264\n\t"
+                     "ds_write_addtid_b32 %13 offset:3536\n\t"
+                     "ds_write_addtid_b32 %14 offset:3808\n\t"
+                     "ds_write_addtid_b32 %15 offset:4080\n\t"
                      :: "v"(a[32 * h + 0]), "v"(a[32 * h + 1]), "v"(a[32 * h + 2]), "v"(a[32 * h + 3]), "v"(a[32 * h + 4]), "v"(a[32 * h + 5]), "v"(a[32 * h + 6]), "v"(a[32 * h + 7]), "v"(a[32 * h + 8]), "v"(a[32 * h + 9]), "v"(a[32 * h + 10]), "v"(a[32 * h + 11]), "v"(a[32 * h + 12]), "v"(a[32 * h + 13]), "v"(a[32 * h + 14]), "v"(a[32 * h + 15]), "s"(m0v) : "memory", "m0");
         asm volatile("s_mov_b32 m0, %16\n\t" SRX_M0_NOP
-                     "ds_write_addtid_b32 %0 offset:4224\n\t"
-                     "ds_write_addtid_b32 %1 offset:4488\n\t"
-                     "ds_write_addtid_b32 %2 offset:4752\n\t"
-                     "ds_write_addtid_b32 %3 offset:5016\n\t"
-                     "ds_write_addtid_b32 %4 offset:5280\n\t"
-                     "ds_write_addtid_b32 %5 offset:5544\n\t"
-                     "ds_write_addtid_b32 %6 offset:5808\n\t"
-                     "ds_write_addtid_b32 %7 offset:6072\n\t"
-                     "ds_write_addtid_b32 %8 offset:6336\n\t"
-                     "ds_write_addtid_b32 %9 offset:6600\n\t"
-                     "ds_write_addtid_b32 %10 offset:6864\n\t"
-                     "ds_write_addtid_b32 %11 offset:7128\n\t"
-                     "ds_write_addtid_b32 %12 offset:7392\n\t"
-                     "ds_write_addtid_b32 %13 offset:7656\n\t"
-                     "ds_write_addtid_b32 %14 offset:7920\n\t"
-                     "ds_write_addtid_b32 %15 offset:8184\n\t"
+                     "ds_write_addtid_b32 %0 offset:4352\n\t"
+                     "ds_write_addtid_b32 %1 offset:4624\n\t"
+                     "ds_write_addtid_b32 %2 offset:4896\n\t"
+                     "ds_write_addtid_b32 %3 offset:5168\n\t"
+                     "ds_write_addtid_b32 %4 offset:5440\n\t"
+                     "ds_write_addtid_b32 %5 offset:5712\n\t"
+                     "ds_write_addtid_b32 %6 offset:5984\n\t"
+                     "ds_write_addtid_b32 %7 offset:6256\n\t"
+                     "ds_write_addtid_b32 %8 offset:6528\n\t"
+                     "ds_write_addtid_b32 %9 offset:6800\n\t"
+                     "ds_write_addtid_b32 %10 offset:7072\n\t"
+                     "ds_write_addtid_b32 %11 offset:7344\n\t"
+                     "ds_write_addtid_b32 %12 offset:7616\n\t"
+                     "ds_write_addtid_b32 %13 offset:7888\n\t"
+                     "ds_write_addtid_b32 %14 offset:8160\n\t"
+                     "ds_write_addtid_b32 %15 offset:8432\n\t"
                      :: "v"(a[32 * h + 16]), "v"(a[32 * h + 17]), "v"(a[32 * h + 18]), "v"(a[32 * h + 19]), "v"(a[32 * h + 20]), "v"(a[32 * h + 21]), "v"(a[32 * h + 22]), "v"(a[32 * h + 23]), "v"(a[32 * h + 24]), "v"(a[32 * h + 25]), "v"(a[32 * h + 26]), "v"(a[32 * h + 27]), "v"(a[32 * h + 28]), "v"(a[32 * h + 29]), "v"(a[32 * h + 30]), "v"(a[32 * h + 31]), "s"(m0v) : "memory", "m0");
 #else
 #pragma unroll
@@ -490,11 +496,11 @@ __device__ __forceinline__ void transpose64(const float (&a)[64], float (&r)[64]
 #else
         if (h == 0 || (lane >> 5) == h) {
 #endif
-            const float2 *row = reinterpret_cast<const float2 *>(Tw + (lane & 31) * TSD);
+            const float4 *row = reinterpret_cast<const float4 *>(Tw + (lane & 31) * TSD);
 #pragma unroll
-            for (int k = 0; k < 32; k++) {
-                const float2 v = row[k];
-                r[2 * k] = v.x, r[2 * k + 1] = v.y;
+            for (int k = 0; k < 16; k++) {
+                const float4 v = row[k];
+                r[4 * k] = v.x, r[4 * k + 1] = v.y, r[4 * k + 2] = v.z, r[4 * k + 3] = v.w;
             }
         }
         __builtin_amdgcn_wave_barrier();
@@ -874,7 +880,7 @@ __global__ void __launch_bounds__(1024)
     k_ibp_patch(const float *__restrict__ hr_in, float *__restrict__ hr_out, PatchTabs tb, PatchArgs pa, const double *__restrict__ Vtot,
                 double scale, double *__restrict__ errors, int n_iter)
 {
-    __shared__ float lds[LDS_WORDS];
+    __shared__ __attribute__((aligned(16))) float lds[LDS_WORDS];
     const int tid0 = threadIdx.x;
     const int wave = __builtin_amdgcn_readfirstlane(tid0 >> 6), s = wave >> 2, u = wave & 3;
     const int b = blockIdx.x;

@@ -350,7 +350,7 @@ __global__ void __launch_bounds__(256, 2)
     k_ibp_sv(const T *__restrict__ hr_in, T *__restrict__ hr, T *P, const AxW<T> aw, int exy, T sn, int mode,
              const double *__restrict__ epart, const double *__restrict__ Vtot, double scale, double *__restrict__ errors, int n_iter, int it_done)
 {
-    __shared__ float lds[4 * RW];
+    __shared__ __attribute__((aligned(16))) float lds[4 * RW];
     const int tid = threadIdx.x, lane = tid & 63;
     const int s = __builtin_amdgcn_readfirstlane(tid >> 6), u = blockIdx.x, b = blockIdx.y;
     T *Rown = reinterpret_cast<T *>(lds + s * RW);
@@ -620,7 +620,7 @@ template <typename T, bool C01>
 __global__ void __launch_bounds__(256, 2)
     k_ibp_sh(T *P, const STabs<T> tb, const patch::PatchArgs pa, const AxW<T> aw, double *__restrict__ epart, int want_err)
 {
-    __shared__ float lds[4 * RW + STRIP_T * (sizeof(T) / 4) + 16];
+    __shared__ __attribute__((aligned(16))) float lds[4 * RW + STRIP_T * (sizeof(T) / 4) + 16];
     if (__builtin_amdgcn_readfirstlane(tb.m8[blockIdx.y]) != 0)
         sh_body<T, C01, true>(lds, P, tb, pa, aw, epart, want_err);
     else

@@ -9,7 +9,7 @@
 // layouts, wave-private LDS transposes, halo exchange through LDS) minus the recursions -- and writes the 52 x 244 pixels
 // whose 6-pixel dependency cone (3 for B, 3 for B') lies inside the region: 1.29x recompute, no intermediate plane.
 //
-// Tile shape (measured on one 3072 x 4096 frame / on eight): 256 threads = 4 waves side by side, 64 rows (NSY = 1), 33.9 KB of
+// Tile shape (measured on one 3072 x 4096 frame / on eight): 256 threads = 4 waves side by side, 64 rows (NSY = 1), 34.9 KB of
 // LDS.  With the pre-update state re-read for the update: 152 registers, three tiles per CU, 245 MB of HBM traffic per iteration
 // (PMC; 5.1 TB/s -- the kernel was bound by its own traffic), 48.4 / 301 us.  With the state HELD in 64 more registers
 // (SRX_ZTILE_HOLD, the default): 216 registers, two tiles per CU, 180 MB, 43.9 / 268 us.  Taller tiles recompute less but run
@@ -63,7 +63,7 @@ constexpr int SW = 4;             // strip pitch (rows of the top strip / column
 // The strips are four rows of RG words (top band) / RGY rows of four words (left band).  They live in the parts of the wave regions
 // that neither the exchange slots ([0, 384) and [1024, 1408)) nor anything else uses between the two transposes: row k of the top
 // strips in region k at 384 (Y) and 640 (G), the left strips in regions 0 and 1 at 1408 (RGY * 4 <= 704 words) -- which keeps a
-// one-block-high tile at 33.9 KB (the LDS would admit four tiles per CU; the register file admits three).
+// one-block-high tile at 34.9 KB (the LDS would admit four tiles per CU; the register file admits three).
 constexpr int YT_OFF = 384, GT_OFF = 640, YL_OFF = 1408, GL_OFF = patch::RW + 1408;
 static_assert(SW <= 4 * NSY && 4 * RGY <= 704 && GT_OFF + RG <= patch::SLOT1 && YT_OFF + RG <= GT_OFF, "strip placement");
 constexpr int OFF_PART = 4 * NSY * patch::RW, LDS_WORDS = OFF_PART + 32;
@@ -387,7 +387,7 @@ __global__ void __launch_bounds__(256 * NSY, SRX_ZTILE_WPE)
 {
     constexpr bool SEP = PSF == 0;
     constexpr int RAD = PSF == 2 ? 2 : 3;
-    __shared__ float lds[LDS_WORDS];
+    __shared__ __attribute__((aligned(16))) float lds[LDS_WORDS];
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), s = wave >> 2, u = wave & 3;
     int tx = blockIdx.x, ty = blockIdx.y, b = blockIdx.z;

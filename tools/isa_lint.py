@@ -1,12 +1,16 @@
 #!/usr/bin/env python3
 """Static lint of gfx950 machine code for the two hazards round 3 found on MI355X that neither the assembler nor the compiler's
-hazard recogniser covers (reproducers in tools/microbench/):
+hazard recogniser covers (reproducers in tools/microbench/), and for one the compiler does cover -- unless the
+instruction sits in an asm block:
 
   H1  a 96- or 128-bit buffer store whose scalar offset operand is a register (not the literal 0 / `off`), directly followed by a
       vector instruction that writes one of its data registers: GCNHazardRecognizer::createsVALUHazard exempts exactly this addressing
       form, and with many waves storing at once gfx950 does send the overwritten values (tools/microbench/store_data_war.hip).
   H2  a scalar write of M0 directly followed by an LDS add-TID access (ds_write_addtid_b32 / ds_read_addtid_b32): the ISA asks for one
       wait state; inside an asm block nobody inserts it (srx_patch.hpp: SRX_M0_NOP).
+  H3  a VALU write of either operand of v_permlane16_swap / v_permlane32_swap fewer than two wait states before the swap reads it
+      (every instruction in between is one wait state, s_nop N is N + 1).  The compiler's hazard recogniser pads the builtin;
+      a swap written in inline asm has to carry its own padding (tools/microbench/lane_shift_cost.hip does).
 
 Works on `hipcc -S --cuda-device-only` listings and on `llvm-objdump -d` output of the code object inside libsrx.so.
 
@@ -26,6 +30,7 @@ LLVM_BIN = os.environ.get("SRX_LLVM_BIN", "/opt/rocm/lib/llvm/bin")
 _REG = re.compile(r"^(v|a)(?:(\d+)|\[(\d+):(\d+)\])$")
 _WIDE_STORE = re.compile(r"^buffer_store_(dwordx3|dwordx4|b96|b128)\b")
 _ADDTID = re.compile(r"^ds_(write|read|store|load)_addtid_b32\b")
+_LANE_SWAP = re.compile(r"^v_permlane(16|32)_swap")
 
 
 def instructions(text):
@@ -60,7 +65,7 @@ def _regs(op):
 
 def _vector_dests(mn, ops):
     """registers a vector instruction writes (VALU: the first operand; v_swap: both; loads into VGPRs count as writers too)"""
-    if mn.startswith("v_swap"):
+    if mn.startswith("v_swap") or _LANE_SWAP.match(mn):
         return _regs(ops[0]) | _regs(ops[1])
     if mn.startswith(("v_cmp", "v_cmpx", "v_readlane", "v_readfirstlane", "v_nop")):
         return set()
@@ -100,6 +105,20 @@ def lint(text):
                 found.append(("H1", fn, ln, f"{mn} {', '.join(ops)}  ->  {mn2} {', '.join(ops2)} overwrites {sorted(hit)}"))
         if _writes_m0(mn, ops) and _ADDTID.match(mn2):
             found.append(("H2", fn, ln, f"{mn} {', '.join(ops)}  ->  {mn2} with no wait state"))
+    for i, (fn, ln, mn, ops) in enumerate(ins):
+        if not _LANE_SWAP.match(mn) or len(ops) < 2:
+            continue
+        read, ws, j = _regs(ops[0]) | _regs(ops[1]), 0, i - 1
+        while ws < 2 and j >= 0 and ins[j][0] == fn:
+            _, ln1, mn1, ops1 = ins[j]
+            if mn1 == "s_nop":
+                ws += int(ops1[0], 0) + 1 if ops1 else 1
+            else:
+                hit = read & _vector_dests(mn1, ops1) if mn1.startswith("v_") else set()
+                if hit:
+                    found.append(("H3", fn, ln1, f"{mn1} {', '.join(ops1)}  ->  {mn} {', '.join(ops)} reads {sorted(hit)} after {ws} wait state(s)"))
+                ws += 1
+            j -= 1
     return found
 
 

@@ -2,6 +2,9 @@
 //
 // k_ibp_ctile's blur along the lanes needs the six neighbours of every sample of a row.  Candidates: a whole-wave DPP shift
 // (v_mov_b32_dpp wave_shr:1), a row shift (row_shr:1, 16-lane rows), ds_bpermute, an LDS store + shifted read, v_fma_f64 for scale.
+// A half-wave exchange in front of patch::transpose64's stores was priced with v_permlane32_swap_b32 (each chain swaps a register pair
+// of its own; the two wait states the swap needs behind a VALU write of its operands are in the string, as for the DPP moves), also at
+// four waves per SIMD, which is how k_ibp_patch runs.
 // One workgroup per CU of 256 * W threads; every wave runs N instructions of a kind as C independent chains and times itself.
 //   hipcc -O3 --offload-arch=gfx950 tools/microbench/lane_shift_cost.hip -o lane_shift_cost && ./lane_shift_cost
 #include <hip/hip_runtime.h>
@@ -9,17 +12,17 @@
 #include <cstdio>
 #include <vector>
 
-enum Kind { WAVE_SHR, ROW_SHR, FMA64, FMA32, BPERMUTE, LDS_RT, LDS_BCAST };
+enum Kind { WAVE_SHR, ROW_SHR, FMA64, FMA32, BPERMUTE, LDS_RT, LDS_BCAST, SWAP32 };
 
 template <int KIND, int C>
 __global__ void k(float *out, unsigned long long *cyc, int n)
 {
     __shared__ double lds[1024 + 8];
-    int a[C];
+    int a[C], a2[C];
     double d[C];
 #pragma unroll
     for (int c = 0; c < C; c++)
-        a[c] = threadIdx.x + c, d[c] = (double)(threadIdx.x + c) * 1e-3;
+        a[c] = threadIdx.x + c, a2[c] = 3 * threadIdx.x + c, d[c] = (double)(threadIdx.x + c) * 1e-3;
     const double m = 0.999, b = 1e-4;
     const float mf = 0.999f, bf = 1e-4f;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -42,6 +45,8 @@ __global__ void k(float *out, unsigned long long *cyc, int n)
                     asm volatile("v_fma_f64 %0, %0, %1, %2" : "+v"(d[c]) : "v"(m), "v"(b));
                 else if (KIND == FMA32)
                     asm volatile("v_fma_f32 %0, %0, %1, %2" : "+v"(a[c]) : "v"(mf), "v"(bf));
+                else if (KIND == SWAP32)
+                    asm volatile("s_nop 1\n\tv_permlane32_swap_b32 %0, %1" : "+v"(a[c]), "+v"(a2[c]));
                 else if (KIND == BPERMUTE)
                     asm volatile("ds_bpermute_b32 %0, %1, %0\n\ts_waitcnt lgkmcnt(0)" : "+v"(a[c]) : "v"(perm));
                 else if (KIND == LDS_RT) {  // store the wave's 64 doubles, read them back one lane over
@@ -55,7 +60,7 @@ __global__ void k(float *out, unsigned long long *cyc, int n)
     double s = 0;
 #pragma unroll
     for (int c = 0; c < C; c++)
-        s += a[c] + d[c];
+        s += a[c] + a2[c] + d[c];
     out[blockIdx.x * blockDim.x + threadIdx.x] = (float)s;
     if ((threadIdx.x & 63) == 0)
         cyc[blockIdx.x * (blockDim.x / 64) + threadIdx.x / 64] = t1 - t0;
@@ -85,7 +90,11 @@ template <int KIND, int C> static void run(const char *name, int W, int n)
 int main()
 {
     const int n = 1 << 14;
-    for (int W = 1; W <= 2; W++) {
+    for (int W = 1; W <= 4; W *= 2) {
+        run<SWAP32, 1>("v_permlane32_swap_b32", W, n);
+        run<SWAP32, 8>("v_permlane32_swap_b32", W, n);
+        if (W == 4)
+            break;  // the other kinds were priced at one and two waves per SIMD
         run<WAVE_SHR, 1>("v_mov_b32_dpp wave_shr:1", W, n);
         run<WAVE_SHR, 8>("v_mov_b32_dpp wave_shr:1", W, n);
         run<ROW_SHR, 1>("v_mov_b32_dpp row_shr:1", W, n);
