@@ -11,6 +11,7 @@
 #include "srx_route.hpp"  // srx_mosaic.hpp and every implementation built on it
 #include "srx_btile.hpp"
 #include "srx_metrics.hpp"
+#include "srx_psf.hpp"
 #include "srx_register.hpp"
 
 using namespace srx;
@@ -777,6 +778,23 @@ int srx_register_f64(const double *frames, int B, int N, int H, int W, int ref, 
                      double tol, double *shifts, double *score, int *status, void *ws, size_t wsb, srx_stream_t s)
 {
     return reg::register_frames<double>(frames, B, N, H, W, ref, init_yx, search, border, n_iter, tol, shifts, score, status, ws, wsb, hs(s));
+}
+
+size_t srx_psf_estimate_workspace_bytes(int elem_bytes, int N, int H, int W, int halfwidth)
+{
+    return psf::workspace_bytes(elem_bytes, N, H, W, halfwidth);
+}
+int srx_psf_estimate_u8(const uint8_t *frames, int N, int H, int W, int halfwidth, double *out, int *info, void *ws, size_t wsb, srx_stream_t s)
+{
+    return psf::estimate<uint8_t>(frames, N, H, W, halfwidth, out, info, ws, wsb, hs(s));
+}
+int srx_psf_estimate_f32(const float *frames, int N, int H, int W, int halfwidth, double *out, int *info, void *ws, size_t wsb, srx_stream_t s)
+{
+    return psf::estimate<float>(frames, N, H, W, halfwidth, out, info, ws, wsb, hs(s));
+}
+int srx_psf_estimate_f64(const double *frames, int N, int H, int W, int halfwidth, double *out, int *info, void *ws, size_t wsb, srx_stream_t s)
+{
+    return psf::estimate<double>(frames, N, H, W, halfwidth, out, info, ws, wsb, hs(s));
 }
 
 #define SRX_DEFINE(SFX, T)                                                                                             \

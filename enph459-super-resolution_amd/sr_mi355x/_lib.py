@@ -45,6 +45,7 @@ _TYPED = {
     "srx_edge_bins_{T}": (_I, [_P, _I, _I, _D, _D, _D, _I, _D, _D, _I, _P, _P, _Z, _P]),
     "srx_ssim_{T}": (_I, [_P, _P, _I, _I, _I, _I, _I, _HD, _I, _D, _D, _D, _P, _P, _P, _P, _Z, _P]),
     "srx_register_{T}": (_I, [_P, _I, _I, _I, _I, _I, _HD, _I, _I, _I, _D, _P, _P, _P, _P, _Z, _P]),
+    "srx_psf_estimate_{T}": (_I, [_P, _I, _I, _I, _I, _P, _P, _P, _Z, _P]),
 }
 _PLAIN = {
     "srx_version": (_I, []),
@@ -72,6 +73,8 @@ _PLAIN = {
     "srx_edge_magnitude_f64": (_I, [_P, _I, _I, _D, _P, _P, _Z, _P]),
     "srx_edge_dist_range": (_I, [_I, _I, _D, _D, _D, _I, _P, _P]),
     "srx_register_workspace_bytes": (_Z, [_I, _I, _I, _I, _I, _I]),
+    "srx_psf_estimate_workspace_bytes": (_Z, [_I, _I, _I, _I, _I]),
+    "srx_psf_estimate_u8": (_I, [_P, _I, _I, _I, _I, _P, _P, _P, _Z, _P]),
 }
 
 

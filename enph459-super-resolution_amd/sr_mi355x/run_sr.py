@@ -36,6 +36,8 @@ def main(argv=None):
     ap.add_argument("--register", action="store_true",
                     help="estimate the frames' shifts on the device (table as the start) and reconstruct with them; "
                          "writes registration.json next to the PNGs")
+    ap.add_argument("--psf-on-device", action="store_true",
+                    help="with --psf measured: estimate the PSF from the pinhole frames on the device (uint8 frames uploaded as they are)")
     args = ap.parse_args(argv)
     rank, world, local_rank = int(os.environ.get("RANK", "0")), int(os.environ.get("WORLD_SIZE", "1")), int(os.environ.get("LOCAL_RANK", "0"))
     dist = None
@@ -50,9 +52,11 @@ def main(argv=None):
     if args.psf == "measured":
         if not args.psf_dir:
             ap.error("--psf measured needs --psf-dir")
-        psf = session.load_measured_psf(args.psf_dir)
-        print(f"  PSF: measured, kernel shape {psf.shape}")
+        psf = (session.load_measured_psf_device if args.psf_on_device else session.load_measured_psf)(args.psf_dir)
+        print(f"  PSF: measured{' on the device' if args.psf_on_device else ''}, kernel shape {psf.shape}")
     else:
+        if args.psf_on_device:
+            ap.error("--psf-on-device needs --psf measured")
         psf = api.make_gaussian_psf(session.PSF_SIZE, session.PSF_SIGMA)
         print(f"  PSF: Gaussian {session.PSF_SIZE}x{session.PSF_SIZE}, sigma={session.PSF_SIGMA}")
     sessions = session.discover_sessions(args.data_dir, args.kind)

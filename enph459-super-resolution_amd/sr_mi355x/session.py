@@ -595,3 +595,24 @@ def load_measured_psf(psf_dir):
     if not imgs:
         raise FileNotFoundError(f"No pos4_(0,0).png found under {psf_dir}")
     return psf_from_pinhole_images(imgs)
+
+
+def load_measured_psf_device(psf_dir):
+    """load_measured_psf with everything behind the PNG decode on the device: the same discovery, the files decoded side by side
+    (_decode_many), the uint8 frames uploaded as they are and handed to psf_device.estimate_psf (srx_psf_estimate_u8)."""
+    import torch
+    from . import psf_device
+    paths = []
+    for sweep in sorted(os.listdir(psf_dir)):
+        path = os.path.join(psf_dir, sweep, "pos4_(0,0).png")
+        if os.path.isdir(os.path.join(psf_dir, sweep)) and os.path.exists(path):
+            paths.append(path)
+    if not paths:
+        raise FileNotFoundError(f"No pos4_(0,0).png found under {psf_dir}")
+    imgs = _decode_many(paths)
+    if all(a.dtype == np.uint8 for a in imgs):
+        frames = torch.from_numpy(np.stack(imgs)).to(api._device())
+    else:  # colour files: load_gray's channel mean, float64
+        with _loader_precision():
+            return psf_device.estimate_psf([a.astype(np.float64) for a in imgs])
+    return psf_device.estimate_psf(frames)

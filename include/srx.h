@@ -33,8 +33,9 @@
  *     workspace is SRX_E_WORKSPACE before anything is queued, whether or not the path the call
  *     takes would have carved less.  Image, output and errors pointers need only the alignment
  *     of their element type (a frame sliced out of a batch of odd-sized frames is fine): no
- *     kernel casts a caller pointer to a vector type, and only arena planes are moved as aligned
- *     16-byte vectors.  One kernel does reach caller memory with 128-bit BUFFER accesses at
+ *     kernel casts a caller pointer to a vector type at an address it has not aligned itself (srx_psf_estimate
+ *     peels a scalar head and tail around its 16-byte reads of the frames), and otherwise only arena planes are
+ *     moved as aligned 16-byte vectors.  One kernel does reach caller memory with 128-bit BUFFER accesses at
  *     addresses that are then only 4-byte aligned (k_ibp_patch parks its state in hr_out, 16 bytes
  *     per lane): that is legal because the HIP runtime runs gfx9 devices in unaligned-access mode
  *     (SH_MEM_CONFIG.ALIGNMENT_MODE: multi-dword accesses need dword alignment), which is what
@@ -313,6 +314,33 @@ int srx_register_f32(const float *frames, int B, int N, int H, int W, int ref, c
                      double *shifts, double *score, int *status, void *ws, size_t ws_bytes, srx_stream_t stream);
 int srx_register_f64(const double *frames, int B, int N, int H, int W, int ref, const double *init_yx, int search, int border, int n_iter,
                      double tol, double *shifts, double *score, int *status, void *ws, size_t ws_bytes, srx_stream_t stream);
+
+/* ---- the measured PSF from pinhole frames (load_measured_psf, mono_cal_target/run_sr.py:114-152), on DEVICE frames ----
+ * frames [N, H, W] of uint8 (_u8: the camera's own samples, no conversion), float or double; reach = halfwidth + 6, side = 2 halfwidth + 1
+ * (the 6 is the reference's constant).  Per frame: the peak = the row-major first sample equal to the frame's maximum (np.argmax,
+ * run_sr.py:131); the frame is used if the window of +-reach around the peak lies inside it (reach <= row, row + reach < H, the same for the
+ * column; :133-135), dropped otherwise.  The used windows are added in frame order in float64 and divided by their number (:140, bit for bit
+ * numpy's stack.mean(axis=0)), cut to the central side x side (:141-142), the mean of the 36 samples at rows and columns
+ * {0, 1, 2, side-3, side-2, side-1} (repeats included when side < 6) is taken off as background (:145-147), negatives are clipped and the
+ * kernel is divided by its sum (:148-150).
+ *   psf   : [side][side] float64 DEVICE: what srx_ibp takes as `kernel` once copied to the host.
+ *   info  : [N][3] int32 DEVICE or NULL: {peak row, peak column, used (1 / 0)}; the peak is reported for dropped frames too.
+ *   ties  : samples tie by value equality (==: -0.0 and +0.0 tie), the smaller index wins.  Frames are expected NaN-free; if they are not, a
+ *           NaN never wins, and a frame with no winning sample (all NaN) reports the peak (0, 0).
+ *   no frame used: psf is all zeros.  Frames used but nothing left above the background: the division is done anyway (0 / 0 = NaN), as the
+ *           host form does.
+ * At most three kernel launches, no host synchronisation; sums and ties are fixed-order (bit-identical run to run).  The frame pointer needs
+ * only element alignment (frame k of a uint8 stack of odd H W starts at any byte: the kernels align their own 16-byte reads).
+ * SRX_E_INVALID: a null frames / psf, N, H or W <= 0, halfwidth outside [1, 7] (side 15: SRX_MAX_KERNEL_TAPS).  SRX_E_UNSUPPORTED: one frame
+ * of 2 GiB or more (indices inside a frame are 32-bit), N > 65535.  Workspace: srx_psf_estimate_workspace_bytes(sizeof(T), N, H, W,
+ * halfwidth) (0 for arguments no call accepts). */
+size_t srx_psf_estimate_workspace_bytes(int elem_bytes /* 1, 4, 8 */, int N, int H, int W, int halfwidth);
+int srx_psf_estimate_u8(const uint8_t *frames, int N, int H, int W, int halfwidth, double *psf, int *info, void *ws, size_t ws_bytes,
+                        srx_stream_t stream);
+int srx_psf_estimate_f32(const float *frames, int N, int H, int W, int halfwidth, double *psf, int *info, void *ws, size_t ws_bytes,
+                         srx_stream_t stream);
+int srx_psf_estimate_f64(const double *frames, int N, int H, int W, int halfwidth, double *psf, int *info, void *ws, size_t ws_bytes,
+                         srx_stream_t stream);
 
 #ifdef __cplusplus
 }
