@@ -24,6 +24,9 @@
 //
 // One iteration:  k_blur_pad -> k_fwd_mosaic -> k_bwd_mosaic, each an O(1)-per-pixel dense pass.
 #pragma once
+#include <algorithm>
+#include <type_traits>
+
 #include "srx_fused.hpp"
 
 namespace srx {
@@ -915,9 +918,14 @@ __global__ void __launch_bounds__(64) k_prefilter_64(const float *__restrict__ s
         dst[r * 64 + lane] = buf[r * LD + lane];
 }
 
+// By POSITION in k_saa_tile's frame order: the frames sorted by oy (stable, ascending), so that the frames sharing a row offset -- and with it
+// the y taps, jy0 and npy -- are neighbours and share one column pass.
 struct FrameOffsets {
     int oy[SRX_MAX_FRAMES], ox[SRX_MAX_FRAMES];
+    int frame[SRX_MAX_FRAMES];  // the caller's frame index at that position
+    unsigned last;              // bit k: position k is the last of its group (SRX_MAX_FRAMES <= 32)
 };
+static_assert(SRX_MAX_FRAMES <= 32, "FrameOffsets::last is one word");
 
 constexpr int SAA_ACC_TS = 96;  // edge of a W-plane tile of the two-pass form (k_saa_tile<T, F, true>)
 template <typename T, int F, bool ACC = false> struct SaaCfg {
@@ -936,6 +944,8 @@ template <typename T, int F, bool ACC = false> struct SaaCfg {
 // frame); row pass, lane = region column with its x tap in registers, rows wave-uniform; column pass, lane = region
 // ROW with its y tap in registers and the columns unrolled, so the four LR rows a lane combines are four base
 // addresses and every LDS read is base + immediate: 4 reads + 4 fma per output, no index arithmetic.  Two barriers.
+// The frames come sorted by their row offset and the column pass runs once per group of equal offsets, on the sum of the group's
+// row-pass images (FrameOffsets).
 // ACC (round 4, the two-pass form): the block's region IS a SAA_ACC_TS-square tile of the W plane [H + 27, W + 27] -- no halo, nothing
 // filtered: the accumulated sum goes to `out` (the plane) and k_saa_shift runs the fractional shift on regions of it.  The fused form
 // accumulates (TS + 2 R + 3)^2 samples per TS^2 outputs over all N frames: 2.07x the work in float32 (TS = 64, R = 11), 6.4x in float64
@@ -993,17 +1003,19 @@ __global__ void __launch_bounds__(256, sizeof(T) == 4 && F == 4 ? 4 : 1)  // flo
     int jy0, jx0, npy, npx;
     auto geometry = [&](int k) { jy0 = geo[k][0], jx0 = geo[k][1], npy = geo[k][2], npx = geo[k][3]; };
     T pre[PPT];
-    AxisTap<T> tX, tY, tXn, tYn;
-    auto fetch = [&](int k) {  // this thread's share of frame k's patch (fixed PD-wide mapping, clamped addresses) and its taps
-        const T *src = coef + ((size_t)b * N + k) * h * w;
+    AxisTap<T> tX, tY, tXn;
+    auto fetch = [&](int k) {  // this thread's share of the patch of the frame at position k (fixed PD-wide mapping, clamped addresses) and its taps
+        const T *src = coef + ((size_t)b * N + fo.frame[k]) * h * w;
 #pragma unroll
         for (int i = 0; i < PPT; i++) {
             const int idx = tid + 256 * i, py = idx / PD, px = idx - py * PD;
             pre[i] = src[(size_t)min(jy0 + py, h - 1) * w + min(jx0 + px, w - 1)];
         }
         tXn = zx[min(max(qa + cc + fo.ox[k] - SRX_NPAD, 0), W - 1)];
-        tYn = zy[min(max(pa + rr + fo.oy[k] - SRX_NPAD, 0), H - 1)];
     };
+    // the y tap of the group that starts at position k: loaded where the group before is done with its own (one load per group, and no
+    // second copy live during the row passes)
+    auto fetch_ty = [&](int k) { tY = zy[min(max(pa + rr + fo.oy[k] - SRX_NPAD, 0), H - 1)]; };
     auto stash = [&]() {
 #pragma unroll
         for (int i = 0; i < PPT; i++) {
@@ -1015,41 +1027,72 @@ __global__ void __launch_bounds__(256, sizeof(T) == 4 && F == 4 ? 4 : 1)  // flo
     SRX_STAMP(2, 0);
     geometry(0);
     fetch(0);
+    fetch_ty(0);
     stash();
     __syncthreads();
     SRX_STAMP(2, 1);
-    for (int k = 0; k < N; k++) {
-        tX = tXn, tY = tYn;
-        const int cjy0 = jy0, cjx0 = jx0, cnpy = npy;
-        if (k + 1 < N) {  // next frame's patch and taps: in flight during both passes of this one
+    // The column pass of a frame is Ay(oy) . rows: it depends on the frame through oy alone (tY, jy0, npy), so the frames of a group -- equal
+    // oy, neighbours in fo's order -- add up their row-pass images in registers and ONE column pass runs on the sum (a 4 x 4 phase grid: 4
+    // column passes for 16 frames).  A group of one is a frame of the per-frame form, operation for operation.  Every frame keeps its two
+    // barriers: with the patch double-buffered in LDS a frame inside a group needs one, and the kernel measured the same.
+    int cjy0, cjx0, cnpy;
+    auto begin_frame = [&](int k) {
+        tX = tXn;
+        cjy0 = jy0, cjx0 = jx0, cnpy = npy;
+        if (k + 1 < N) {  // next frame's patch and taps: in flight during the passes of this one, across a group's end as well
             geometry(k + 1);
             fetch(k + 1);
         }
-        // row pass: rows[py][cc] = sum_j zx[x(cc)].w[j] * patch[py][idx[j]]
-        {
-            const T *p0 = patch + tX.idx[0] - cjx0, *p1 = patch + tX.idx[1] - cjx0, *p2 = patch + tX.idx[2] - cjx0,
-                    *p3 = patch + tX.idx[3] - cjx0;
-            // all reads of the patch first: rows and patch share the LDS array, so hipcc would otherwise order each
-            // row's store before the next row's loads (one LDS round trip per row)
-            T v[(PD + 1) / 2];
+    };
+    // row pass: v[t] (+)= sum_j zx[x(cc)].w[j] * patch[py][idx[j]], py = half + 2 t
+    auto row_pass = [&](T(&v)[(PD + 1) / 2], auto first) {
+        const T *p0 = patch + tX.idx[0] - cjx0, *p1 = patch + tX.idx[1] - cjx0, *p2 = patch + tX.idx[2] - cjx0,
+                *p3 = patch + tX.idx[3] - cjx0;
 #pragma unroll
-            for (int t = 0; t < (PD + 1) / 2; t++) {
-                const int py = min(half + 2 * t, PD - 1);
+        for (int t = 0; t < (PD + 1) / 2; t++) {
+            const int py = min(half + 2 * t, PD - 1);
+            if constexpr (decltype(first)::value)
                 v[t] = tX.w[0] * p0[py * PD] + tX.w[1] * p1[py * PD] + tX.w[2] * p2[py * PD] + tX.w[3] * p3[py * PD];
-                if (t % 4 == 3)  // as in the column pass below: 16 reads in flight
-                    asm volatile("" : "+v"(v[t - 3]), "+v"(v[t - 2]), "+v"(v[t - 1]), "+v"(v[t])::"memory");
+            else  // four fmas onto the sum so far: no temporary beside the 16 reads in flight
+                v[t] = v[t] + tX.w[0] * p0[py * PD] + tX.w[1] * p1[py * PD] + tX.w[2] * p2[py * PD] + tX.w[3] * p3[py * PD];
+            if (t % 4 == 3)  // as in the column pass below: 16 reads in flight
+                asm volatile("" : "+v"(v[t - 3]), "+v"(v[t - 2]), "+v"(v[t - 1]), "+v"(v[t])::"memory");
+        }
+    };
+    for (int k = 0; k < N; k++) {  // one trip per group
+        [[maybe_unused]] const bool g0 = k == 0;  // the first group (stamps)
+        // all reads of the patch first: rows and patch share the LDS array, so hipcc would otherwise order each
+        // row's store before the next row's loads (one LDS round trip per row)
+        T v[(PD + 1) / 2];
+        begin_frame(k);
+        row_pass(v, std::true_type());
+        while (!(fo.last >> k & 1) && k + 1 < N) {  // wave-uniform: the group's other frames add to v
+            __syncthreads();  // every wave is done with the patch
+            if (k == 0) {
+                SRX_STAMP(2, 2);
+                SRX_STAMP(2, 3);
             }
+            stash();
+            __syncthreads();
+            if (k == 0)
+                SRX_STAMP(2, 4);
+            k++;
+            begin_frame(k);
+            row_pass(v, std::false_type());
+        }
 #pragma unroll
-            for (int t = 0; t < (PD + 1) / 2; t++) {
-                const int py = half + 2 * t;
-                if (py < cnpy && ccok)
-                    rows[py * RS + cc] = v[t];
-            }
+        for (int t = 0; t < (PD + 1) / 2; t++) {
+            const int py = half + 2 * t;
+            if (py < cnpy && ccok)
+                rows[py * RS + cc] = v[t];
         }
         __syncthreads();
         if (k == 0)
             SRX_STAMP(2, 2);
-        // column pass, accumulated over frames: up_k(y(rr), x) = sum_i zy[y].w[i] * rows[idx[i]][x]
+        if constexpr (ACC)
+            if (g0)
+                SRX_STAMP(2, 6);
+        // column pass of the group, accumulated over the groups: up(y(rr), x) = sum_i zy[y].w[i] * rows[idx[i]][x]
         {
             // four columns per LDS read: rows of pitch 4k from a column 4j, so every quad is 16-byte aligned.  ds_read_b128 moves 256 B
             // per LDS cycle, ds_read_b32 128, and this pass is bound by the LDS (4 reads per output, 1.2 MB per frame and CU).  (Pairs
@@ -1079,8 +1122,13 @@ __global__ void __launch_bounds__(256, sizeof(T) == 4 && F == 4 ? 4 : 1)  // flo
         }
         if (k == 0)
             SRX_STAMP(2, 3);
-        if (k + 1 < N)
+        if constexpr (ACC)
+            if (g0)
+                SRX_STAMP(2, 7);
+        if (k + 1 < N) {
+            fetch_ty(k + 1);
             stash();  // the row pass of this frame is done with the patch
+        }
         __syncthreads();
         if (k == 0)
             SRX_STAMP(2, 4);
@@ -1357,10 +1405,22 @@ static int saa(const T *lr, int B, int N, int h, int w, const double *sh, int f,
     SRX_TRY(build_taps(zx, W, w, TAP_ZOOM, 1, W > 1 ? (double)(w - 1) / (double)(W - 1) : 1.0, st));
     FrameOffsets fo;
     MosaicArgs<T> ma;
+    // shift(+d): the padded FIR reads U[p + floor(-d) - 1 + a]; -d = (-n - 1) + (1 - delta), or -n when delta = 0
+    int oy[SRX_MAX_FRAMES], ox[SRX_MAX_FRAMES], ord[SRX_MAX_FRAMES];
+    for (int q = 0; q < N; q++) {
+        oy[q] = -py.n[q] - (py.zero ? 1 : 2);
+        ox[q] = -px.n[q] - (px.zero ? 1 : 2);
+        ord[q] = q;
+    }
+    // k_saa_tile's frame order: by oy ascending, the caller's order inside a group (frames of one oy share a column pass)
+    std::stable_sort(ord, ord + N, [&](int a, int b) { return oy[a] < oy[b]; });
+    fo.last = 0;
     for (int q = 0; q < SRX_MAX_FRAMES; q++) {
-        // shift(+d): the padded FIR reads U[p + floor(-d) - 1 + a]; -d = (-n - 1) + (1 - delta), or -n when delta = 0
-        fo.oy[q] = q < N ? -py.n[q] - (py.zero ? 1 : 2) : 0;
-        fo.ox[q] = q < N ? -px.n[q] - (px.zero ? 1 : 2) : 0;
+        fo.oy[q] = q < N ? oy[ord[q]] : 0;
+        fo.ox[q] = q < N ? ox[ord[q]] : 0;
+        fo.frame[q] = q < N ? ord[q] : 0;
+        if (q < N && (q + 1 == N || oy[ord[q + 1]] != oy[ord[q]]))
+            fo.last |= 1u << q;
     }
     ma.Dy = ma.Dx = ma.PBy = ma.PBx = ma.RSy = ma.RSx = 0;
     double wv[4];

@@ -15,10 +15,16 @@ lib = _lib.load(); lib.srx_debug_stamps.argtypes = [ctypes.c_void_p]
 assert lib.srx_debug_stamps(buf.ctypes.data_as(ctypes.c_void_p)) == 0
 t = buf[2].astype(np.int64)
 nb = 9 * B
-names = ["geometry + frame 0 fetch + stash", "frame 0 row pass (+ barrier)", "frame 0 column pass", "frame 0 stash next (+ barrier)", "frames 1..N-1"]
+# stamps 2 -> 3 hold a column pass only where frame 0 closes its group (a group of one); the first group's column pass is between stamps 6 and 7
+names = ["geometry + frame 0 fetch + stash", "frame 0 row pass (+ barrier)", "frame 0 column pass (if it ends a group)", "frame 0 stash next (+ barrier)", "frames 1..N-1"]
 ok = (t[0, :nb] > 0) & (t[5, :nb] > t[0, :nb])
 tot = (t[5, :nb] - t[0, :nb])[ok]
 print(f"blocks {ok.sum()}, median cycles/block {np.median(tot):.0f} (p10 {np.percentile(tot, 10):.0f}, p90 {np.percentile(tot, 90):.0f})")
 for i in range(5):
     d = (t[i + 1, :nb] - t[i, :nb])[ok]
-    print(f"    {names[i]:34s} median {np.median(d):8.0f}  mean {d.mean():8.0f}  share {100 * d.mean() / tot.mean():5.1f} %")
+    print(f"    {names[i]:42s} median {np.median(d):8.0f}  mean {d.mean():8.0f}  share {100 * d.mean() / tot.mean():5.1f} %")
+print(f"    {'per frame (stamps 1 -> 5, / 16)':42s} median {np.median((t[5, :nb] - t[1, :nb])[ok]) / 16:8.0f}")
+ok67 = ok & (t[6, :nb] > 0) & (t[7, :nb] > t[6, :nb])
+if ok67.any():
+    d = (t[7, :nb] - t[6, :nb])[ok67]
+    print(f"    {'column pass of the first group':42s} median {np.median(d):8.0f}  mean {d.mean():8.0f}  share {100 * d.mean() / tot.mean():5.1f} % (one of 4)")
