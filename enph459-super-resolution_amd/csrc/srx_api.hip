@@ -358,14 +358,37 @@ static size_t ibp_need(const Route &r, int eb, int B, int N, int h, int w, int H
     return mosaic::ibp_ws_for(*r.impl, eb, B, N, H, W);
 }
 
+// The uint8 entry points (srx_ibp_u8lr_*, srx_saa_u8lr_*) off the mosaic family: the chunk's frames are converted to T at the front of the
+// workspace and the float driver runs on the rest.  (Those routes serve per-frame fractional shifts; the mosaic family reads the bytes itself.)
+static inline size_t u8_stage_bytes(int eb, int Bc, int N, int h, int w) { return align_up((size_t)Bc * N * h * w * eb); }
+
+template <typename T> static int u8_stage(const uint8_t *lr, size_t n, void *&ws, size_t &wsb, const T *&staged, hipStream_t st)
+{
+    const size_t bytes = align_up(n * sizeof(T));
+    if (wsb < bytes)
+        return SRX_E_WORKSPACE;
+    hipLaunchKernelGGL(k_u8_to<T>, dim3(grid1d(n)), dim3(256), 0, st, lr, n, (T *)ws);
+    SRX_CHECK_LAUNCH();
+    staged = (const T *)ws;
+    ws = (char *)ws + bytes, wsb -= bytes;
+    return SRX_OK;
+}
+
 // one chunk (at most SRX_MAX_BATCH_PER_LAUNCH items) of a call on the route its entry point decided
-template <typename T>
-static int ibp_run(const Route &r, const T *lr, int B, int N, int h, int w, const double *sh, const double *k, int kh, int kw, const T *hr_init, int H,
+template <typename T, typename S>
+static int ibp_run(const Route &r, const S *lr_, int B, int N, int h, int w, const double *sh, const double *k, int kh, int kw, const T *hr_init, int H,
                    int W, int f, int n_iter, double step, T *hr, double *errors, void *ws, size_t wsb, hipStream_t st)
 {
+    if (r.path == PATH_MOSAIC)
+        return mosaic::ibp<T, S>(*r.impl, lr_, B, N, h, w, sh, k, kh, kw, hr_init, H, W, f, n_iter, step, hr, errors, ws, wsb, st);
+    const T *lr;
+    if constexpr (std::is_same<S, T>::value)
+        lr = lr_;
+    else
+        SRX_TRY(u8_stage<T>(lr_, (size_t)B * N * h * w, ws, wsb, lr, st));
     switch (r.path) {
-    case PATH_MOSAIC:
-        return mosaic::ibp<T>(*r.impl, lr, B, N, h, w, sh, k, kh, kw, hr_init, H, W, f, n_iter, step, hr, errors, ws, wsb, st);
+    case PATH_MOSAIC:  // (taken above)
+        break;
     case PATH_BTILE:
         if constexpr (sizeof(T) == 4)
             return btile::ibp(lr, B, N, h, w, sh, k, kh, kw, hr_init, H, W, n_iter, step, hr, errors, ws, wsb, st);
@@ -378,8 +401,8 @@ static int ibp_run(const Route &r, const T *lr, int B, int N, int h, int w, cons
     return ibp_composed<T>(lr, B, N, h, w, sh, k, kh, kw, hr_init, H, W, f, n_iter, step, hr, errors, ws, wsb, st);
 }
 
-template <typename T>
-static int ibp_dispatch(const T *lr, int B, int N, int h, int w, const double *sh, const double *k, int kh, int kw,
+template <typename T, typename S = T>
+static int ibp_dispatch(const S *lr, int B, int N, int h, int w, const double *sh, const double *k, int kh, int kw,
                         const T *hr_init, int H, int W, int f, int n_iter, double step, T *hr, double *errors, void *ws,
                         size_t wsb, hipStream_t st, unsigned flags)
 {
@@ -391,34 +414,47 @@ static int ibp_dispatch(const T *lr, int B, int N, int h, int w, const double *s
     if (r.status != SRX_OK)
         return r.status;
     // a short or misaligned workspace is refused before anything is queued
-    if (ws_short(ws, wsb, ibp_need(r, (int)sizeof(T), B, N, h, w, H, W, f, flags)))
+    size_t need = ibp_need(r, (int)sizeof(T), B, N, h, w, H, W, f, flags);
+    if (!std::is_same<S, T>::value && r.path != PATH_MOSAIC)
+        need += u8_stage_bytes((int)sizeof(T), B < SRX_MAX_BATCH_PER_LAUNCH ? B : SRX_MAX_BATCH_PER_LAUNCH, N, h, w);
+    if (ws_short(ws, wsb, need))
         return SRX_E_WORKSPACE;
     g_last_path = r.name;
     // batches beyond one launch's gridDim.z go through in chunks; the workspace is sized for one chunk and reused (stream order)
     for (int b0 = 0; b0 < B; b0 += SRX_MAX_BATCH_PER_LAUNCH) {
         const int bc = B - b0 < SRX_MAX_BATCH_PER_LAUNCH ? B - b0 : SRX_MAX_BATCH_PER_LAUNCH;
-        SRX_TRY(ibp_run<T>(r, lr + (size_t)b0 * N * h * w, bc, N, h, w, sh, k, kh, kw, hr_init + (size_t)b0 * H * W, H, W, f, n_iter, step,
-                           hr + (size_t)b0 * H * W, errors ? errors + (size_t)b0 * n_iter : nullptr, ws, wsb, st));
+        SRX_TRY((ibp_run<T, S>(r, lr + (size_t)b0 * N * h * w, bc, N, h, w, sh, k, kh, kw, hr_init + (size_t)b0 * H * W, H, W, f, n_iter, step,
+                           hr + (size_t)b0 * H * W, errors ? errors + (size_t)b0 * n_iter : nullptr, ws, wsb, st)));
     }
     return SRX_OK;
 }
 
-template <typename T>
-static int saa_dispatch(const T *lr, int B, int N, int h, int w, const double *sh, int f, T *out, void *ws, size_t wsb,
-                        hipStream_t st, unsigned flags)
+static size_t saa_chunk_items(int B, int N)
 {
+    if ((long)B * N > SRX_MAX_BATCH_PER_LAUNCH)
+        return SRX_MAX_BATCH_PER_LAUNCH / N > 0 ? SRX_MAX_BATCH_PER_LAUNCH / N : 1;
+    return B;
+}
+
+template <typename T, typename S = T>
+static int saa_dispatch(const S *lr_, int B, int N, int h, int w, const double *sh, int f, T *out, void *ws, size_t wsb,
+                        hipStream_t st, unsigned flags, bool checked = false)
+{
+    constexpr bool u8 = !std::is_same<S, T>::value;
+    const S *lr = lr_;
     if (!lr || !sh || !out || B <= 0 || N <= 0 || h <= 0 || w <= 0 || f <= 0)
         return SRX_E_INVALID;
     if (N > SRX_MAX_FRAMES || (size_t)h * f >= ((size_t)1 << 30) || (size_t)w * f >= ((size_t)1 << 30) || !plane_fits(sizeof(T), N, h, w, h * f, w * f))
         return SRX_E_UNSUPPORTED;
-    if (ws_short(ws, wsb, srx_saa_workspace_bytes((int)sizeof(T), B, N, h, w, f)))  // before anything is queued
+    // before anything is queued (a chunk of a larger call was checked with it)
+    if (!checked && ws_short(ws, wsb, u8 ? srx_saa_u8lr_workspace_bytes((int)sizeof(T), B, N, h, w, f) : srx_saa_workspace_bytes((int)sizeof(T), B, N, h, w, f)))
         return SRX_E_WORKSPACE;
     if ((long)B * N > SRX_MAX_BATCH_PER_LAUNCH) {
         const int step_b = SRX_MAX_BATCH_PER_LAUNCH / N > 0 ? SRX_MAX_BATCH_PER_LAUNCH / N : 1;
         for (int b0 = 0; b0 < B; b0 += step_b) {
             const int bc = B - b0 < step_b ? B - b0 : step_b;
-            SRX_TRY(saa_dispatch<T>(lr + (size_t)b0 * N * h * w, bc, N, h, w, sh, f, out + (size_t)b0 * h * f * w * f, ws, wsb,
-                                    st, flags));
+            SRX_TRY((saa_dispatch<T, S>(lr + (size_t)b0 * N * h * w, bc, N, h, w, sh, f, out + (size_t)b0 * h * f * w * f, ws, wsb,
+                                        st, flags, true)));
         }
         return SRX_OK;
     }
@@ -428,13 +464,20 @@ static int saa_dispatch(const T *lr, int B, int N, int h, int w, const double *s
     if (can_fuse && !(flags & SRX_FLAG_COMPOSED)) {
         if (!(flags & SRX_FLAG_PER_FRAME) && mosaic::saa_eligible(N, h, w, sh, f)) {
             g_last_path = "mosaic";
-            return mosaic::saa<T>(lr, B, N, h, w, sh, f, out, ws, wsb, st);
+            return mosaic::saa<T, S>(lr, B, N, h, w, sh, f, out, ws, wsb, st);
         }
+    }
+    const T *lrT;
+    if constexpr (u8)
+        SRX_TRY(u8_stage<T>(lr, (size_t)B * N * h * w, ws, wsb, lrT, st));
+    else
+        lrT = lr;
+    if (can_fuse && !(flags & SRX_FLAG_COMPOSED)) {
         g_last_path = "fused";
-        return fused::saa<T>(lr, B, N, h, w, sh, f, out, ws, wsb, st);
+        return fused::saa<T>(lrT, B, N, h, w, sh, f, out, ws, wsb, st);
     }
     g_last_path = "composed";
-    return saa_composed<T>(lr, B, N, h, w, sh, f, out, ws, wsb, st);
+    return saa_composed<T>(lrT, B, N, h, w, sh, f, out, ws, wsb, st);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -669,6 +712,12 @@ size_t srx_saa_workspace_bytes(int eb, int B, int N, int h, int w, int f)
     return a > c ? a : c;
 }
 
+/* float figure + one staged copy (T) of a chunk's frames, whatever the route: the query has no shift table to tell the routes apart */
+size_t srx_saa_u8lr_workspace_bytes(int eb, int B, int N, int h, int w, int f)
+{
+    return srx_saa_workspace_bytes(eb, B, N, h, w, f) + u8_stage_bytes(eb, (int)saa_chunk_items(B, N), N, h, w);
+}
+
 size_t srx_ibp_workspace_bytes(int eb, int B, int N, int h, int w, int H, int W, int f, unsigned flags)
 {
     if (B > SRX_MAX_BATCH_PER_LAUNCH)
@@ -694,6 +743,25 @@ size_t srx_ibp_workspace_bytes_for(int eb, int B, int N, int h, int w, int H, in
     return ibp_need(route_ibp(eb, N, h, w, H, W, f, sh, k, kh, kw, flags), eb, B, N, h, w, H, W, f, flags);
 }
 
+/* uint8 frames: the float figure on a mosaic-family route (the kernels read the bytes; nothing is staged), plus the staged chunk elsewhere */
+size_t srx_ibp_u8lr_workspace_bytes(int eb, int B, int N, int h, int w, int H, int W, int f, unsigned flags)
+{
+    return srx_ibp_workspace_bytes(eb, B, N, h, w, H, W, f, flags) +
+           u8_stage_bytes(eb, B < SRX_MAX_BATCH_PER_LAUNCH ? (B > 0 ? B : 1) : SRX_MAX_BATCH_PER_LAUNCH, N, h, w);
+}
+size_t srx_ibp_u8lr_workspace_bytes_for(int eb, int B, int N, int h, int w, int H, int W, int f, const double *sh, const double *k, int kh,
+                                        int kw, unsigned flags)
+{
+    if (!sh || !k || N <= 0 || N > SRX_MAX_FRAMES)
+        return srx_ibp_u8lr_workspace_bytes(eb, B, N, h, w, H, W, f, flags);
+    CallFlags cf(flags);
+    const Route r = route_ibp(eb, N, h, w, H, W, f, sh, k, kh, kw, flags);
+    const size_t need = ibp_need(r, eb, B, N, h, w, H, W, f, flags);
+    if (r.status == SRX_OK && r.path == PATH_MOSAIC)
+        return need;
+    return need + u8_stage_bytes(eb, B < SRX_MAX_BATCH_PER_LAUNCH ? (B > 0 ? B : 1) : SRX_MAX_BATCH_PER_LAUNCH, N, h, w);
+}
+
 const char *srx_ibp_path_for(int eb, int N, int h, int w, int H, int W, int f, const double *sh, const double *k, int kh, int kw, unsigned flags)
 {
     int dummy = 0;  // (stands for the device pointers: only their presence is checked)
@@ -703,6 +771,18 @@ const char *srx_ibp_path_for(int eb, int N, int h, int w, int H, int W, int f, c
     CallFlags cf(flags);
     const Route r = route_ibp(eb, N, h, w, H, W, f, sh, k, kh, kw, flags);
     return r.status == SRX_OK ? r.name : "none";
+}
+
+int srx_decimate_u8(const uint8_t *in, int B, int H, int W, int f, int py, int px, uint8_t *out, srx_stream_t s)
+{
+    if (!in || !out || B <= 0 || f <= 0 || py < 0 || px < 0 || py >= H || px >= W)
+        return SRX_E_INVALID;
+    if (B > 65535)
+        return SRX_E_UNSUPPORTED;
+    const int h = cdiv(H - py, f), w = cdiv(W - px, f);
+    hipLaunchKernelGGL(k_decimate<uint8_t>, dim3(cdiv(w, 64), cdiv(h, 4), B), dim3(64, 4), 0, hs(s), in, H, W, f, py, px, h, w, out);
+    SRX_CHECK_LAUNCH();
+    return SRX_OK;
 }
 
 int srx_interleave4_u8(const uint8_t *frames, int B, int h, int w, uint8_t *out, srx_stream_t s)
@@ -834,6 +914,20 @@ int srx_psf_estimate_f64(const double *frames, int N, int H, int W, int halfwidt
         CallFlags cf(flags);                                                                                           \
         return ibp_dispatch<T>(lr, B, N, h, w, sh, k, kh, kw, hr_init, H, W, f, n_iter, step, hr_out, errors, ws, wsb, \
                                hs(s), flags);                                                                          \
+    }                                                                                                                  \
+    int srx_saa_u8lr_##SFX(const uint8_t *lr, int B, int N, int h, int w, const double *sh, int f, T *out, void *ws,    \
+                           size_t wsb, srx_stream_t s, unsigned flags)                                                 \
+    {                                                                                                                  \
+        CallFlags cf(flags);                                                                                           \
+        return saa_dispatch<T, uint8_t>(lr, B, N, h, w, sh, f, out, ws, wsb, hs(s), flags);                            \
+    }                                                                                                                  \
+    int srx_ibp_u8lr_##SFX(const uint8_t *lr, int B, int N, int h, int w, const double *sh, const double *k, int kh,   \
+                           int kw, const T *hr_init, int H, int W, int f, int n_iter, double step, T *hr_out,          \
+                           double *errors, void *ws, size_t wsb, srx_stream_t s, unsigned flags)                       \
+    {                                                                                                                  \
+        CallFlags cf(flags);                                                                                           \
+        return ibp_dispatch<T, uint8_t>(lr, B, N, h, w, sh, k, kh, kw, hr_init, H, W, f, n_iter, step, hr_out, errors, \
+                                        ws, wsb, hs(s), flags);                                                        \
     }                                                                                                                  \
     int srx_decimate_##SFX(const T *in, int B, int H, int W, int f, int py, int px, T *out, srx_stream_t s)             \
     {                                                                                                                  \

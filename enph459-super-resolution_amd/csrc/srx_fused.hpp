@@ -19,6 +19,7 @@
 // 8 launches whose cost does not grow with N except for the two gathers.
 #pragma once
 #include <cmath>
+#include <type_traits>
 
 #include "srx_prims.hpp"
 
@@ -207,20 +208,21 @@ __device__ __forceinline__ void corr7_strip8(const T *tile, int tx, int ty, cons
 // of 64 lanes: wave w takes rows w, w+4, ...; lanes take columns.  Loads are issued in batches of 8 rows
 // before the first LDS store, from clamped (always valid) addresses -- a per-element guarded load makes
 // hipcc wait for each load in turn, which was the single largest cost of the first tile kernels.
-template <typename T, int MAXR, int MAXC, int BATCH = 8>
-__device__ __forceinline__ void load_region(T *__restrict__ reg, int ld, const T *__restrict__ src, size_t pitch, int nr,
+// S: the plane's sample type (T, or uint8_t for the camera's frames: converted on the way into the LDS).
+template <typename T, int MAXR, int MAXC, int BATCH = 8, typename S = T>
+__device__ __forceinline__ void load_region(T *__restrict__ reg, int ld, const S *__restrict__ src, size_t pitch, int nr,
                                             int nc, int wave, int lane)
 {
     constexpr int RPW = (MAXR + 3) / 4, CPL = (MAXC + 63) / 64;
 #pragma unroll
     for (int j0 = 0; j0 < RPW; j0 += BATCH) {
-        T v[BATCH][CPL];
+        T v[BATCH][CPL];  // (bytes are converted as they arrive: kept as bytes they would share registers two by two)
 #pragma unroll
         for (int j = 0; j < BATCH; j++) {
             const int rr = min(wave + 4 * (j0 + j), nr - 1);
 #pragma unroll
             for (int cc = 0; cc < CPL; cc++)
-                v[j][cc] = src[(size_t)rr * pitch + min(lane + 64 * cc, nc - 1)];
+                v[j][cc] = (T)src[(size_t)rr * pitch + min(lane + 64 * cc, nc - 1)];
         }
 #pragma unroll
         for (int j = 0; j < BATCH; j++) {
@@ -989,9 +991,10 @@ __device__ __forceinline__ void tile_iir2d(T *reg, int nr, int nc, bool top_edge
 // condition (mode: MODE_MIRROR = zoom's prefilter, MODE_REFLECT = shift's on its pre-padded array) where the region
 // touches an array end.  Replaces k_prefilter_axis0 + k_prefilter_axis1 for float planes: those walk whole lines with 64
 // threads per block and a barrier per 64 samples (114 us for four 768 x 1024 frames; this: one read + one write).
-template <typename T>
+// S = uint8_t: the LR frames of srx_saa_u8lr_f32, read as bytes (a quarter of the float plane's read; the write is the same).
+template <typename T, typename S = T>
 __global__ void __launch_bounds__(256)
-    k_prefilter_tile(const T *__restrict__ src_, T *__restrict__ dst_, int Hc, int Wc, int mode)
+    k_prefilter_tile(const S *__restrict__ src_, T *__restrict__ dst_, int Hc, int Wc, int mode)
 {
     constexpr int TSP = 64, WU = Warmup<T>::n, FR = TSP + 2 * WU, LD = FR | 1;
     __shared__ T reg[FR * LD];
@@ -1001,8 +1004,8 @@ __global__ void __launch_bounds__(256)
     const int r0 = by * TSP, c0 = bx * TSP;
     const int pa = max(0, r0 - WU), pb = min(Hc, r0 + TSP + WU), qa = max(0, c0 - WU), qb = min(Wc, c0 + TSP + WU);
     const int nr = pb - pa, nc = qb - qa;
-    const T *src = src_ + (size_t)b * Hc * Wc;
-    load_region<T, FR, FR, 13>(reg, LD, src + (size_t)pa * Wc + qa, Wc, nr, nc, wave, lane);
+    const S *src = src_ + (size_t)b * Hc * Wc;
+    load_region<T, FR, FR, 13, S>(reg, LD, src + (size_t)pa * Wc + qa, Wc, nr, nc, wave, lane);
     __syncthreads();
     const bool mirror = mode == 0;  // MODE_MIRROR (srx_prims.hpp)
     const int bc_y = mirror ? ((pa == 0 ? SRX_BC_MIRROR_LO : 0) | (pb == Hc ? SRX_BC_MIRROR_HI : 0)) : 0;
@@ -1035,16 +1038,25 @@ template <typename T> static int prefilter2d_fast(T *a, T *scratch, int B, int H
 
 // The same out of place, src -> dst (the coefficients of a stack the caller may not write: the LR frames of shift_and_add).  The tile kernel
 // is out of place by nature, so this saves prefilter2d_fast's two copies of the stack (in, and back from the scratch plane).
-template <typename T> static int prefilter2d_from(const T *src, T *dst, T *scratch, int B, int Hc, int Wc, int mode, hipStream_t st)
+// S = uint8_t (the camera's samples): the tile kernel reads the bytes itself, and the copy that the in-place forms start with becomes the
+// conversion -- no pass and no plane beyond those of the float call.
+template <typename T, typename S> static int prefilter2d_from(const S *src, T *dst, T *scratch, int B, int Hc, int Wc, int mode, hipStream_t st)
 {
+    constexpr bool u8 = !std::is_same<S, T>::value;
+    static_assert(!u8 || std::is_same<S, uint8_t>::value, "LR samples: T or uint8_t");
+    const size_t n = (size_t)B * Hc * Wc;
     if constexpr (sizeof(T) == 4) {
         if (Hc >= 64 && Wc >= 64 && B <= 65535 && !(call_flags() & SRX_FLAG_DIAG_NO_PREFILTER_TILE)) {
-            SRX_LAUNCH(KID_PREFILTER_TILE, k_prefilter_tile<T>, dim3(cdiv(Wc, 64), cdiv(Hc, 64), B), dim3(256), 0, st, src, dst, Hc, Wc, mode);
+            SRX_LAUNCH(KID_PREFILTER_TILE, (k_prefilter_tile<T, S>), dim3(cdiv(Wc, 64), cdiv(Hc, 64), B), dim3(256), 0, st, src, dst, Hc, Wc, mode);
             return SRX_OK;
         }
     }
-    if (hipMemcpyAsync(dst, src, (size_t)B * Hc * Wc * sizeof(T), hipMemcpyDeviceToDevice, st) != hipSuccess)
+    if constexpr (u8) {
+        hipLaunchKernelGGL(k_u8_to<T>, dim3(grid1d(n)), dim3(256), 0, st, src, n, dst);
+        SRX_CHECK_LAUNCH();
+    } else if (hipMemcpyAsync(dst, src, n * sizeof(T), hipMemcpyDeviceToDevice, st) != hipSuccess) {
         return SRX_E_HIP;
+    }
     return prefilter2d_fast(dst, scratch, B, Hc, Wc, mode, st);
 }
 

@@ -138,9 +138,11 @@ __device__ __forceinline__ int near_index(int p, int q, int Wg, int PBy, int PBx
 // coordinate) and shared by all items, the row tap is wave-uniform (a scalar load; most frames miss a given row entirely),
 // and the PXT x IB sample loads of a frame are independent and issued together.  (8 items x 1 pixel for batches of patches,
 // 1 item x 4 pixels for a single full frame.)
-template <typename T, int IB, int PXT>
+// S: the type of the LR samples as the caller holds them -- T, or uint8_t (the camera's frames, srx_ibp_u8lr_*): (double)l is exact for
+// both, so the sums are the same bits.  A wave's read of one LR row segment is then 64 consecutive bytes, one per lane.
+template <typename T, int IB, int PXT, typename S = T>
 __global__ void __launch_bounds__(256)
-    k_mosaic_build(const T *__restrict__ lr, int B, int N, int h, int w, const MTap *__restrict__ tabY,
+    k_mosaic_build(const S *__restrict__ lr, int B, int N, int h, int w, const MTap *__restrict__ tabY,
                    const MTap *__restrict__ tabX, int Hg, int Wg, int PBy, int PBx, int Dy, int Dx, int NB,
                    T *__restrict__ Mg, T *__restrict__ Cg, T *__restrict__ Mu, double *__restrict__ Vpart, int tr_lo, int tr_hi)
 {
@@ -172,10 +174,10 @@ __global__ void __launch_bounds__(256)
                 tx[c] = tabX[(size_t)k * Wg + min(q0 + 64 * c, Wg - 1)];
             if (PXT == 1 && tx[0].i < 0)
                 continue;  // one pixel per thread: skipping beats issuing IB dropped loads
-            T l[PXT][IB];
+            S l[PXT][IB];
 #pragma unroll
             for (int c = 0; c < PXT; c++) {
-                const T *src = lr + (size_t)(k * h + ty.i) * w + max(tx[c].i, 0);  // a miss reads column 0 and is dropped
+                const S *src = lr + (size_t)(k * h + ty.i) * w + max(tx[c].i, 0);  // a miss reads column 0 and is dropped
 #pragma unroll
                 for (int i = 0; i < IB; i++)
                     l[c][i] = src[(size_t)min(b0 + i, B - 1) * item];  // clamped duplicate for a ragged last group
@@ -805,27 +807,27 @@ __global__ void __launch_bounds__(256)
 // stride 65: conflict-free both ways), lane = column for axis 0, lane = row for axis 1; whole lines, so SciPy's exact
 // boundary sums at both ends and no warm-up.  Replaces copy + k_prefilter_axis0 + k_prefilter_axis1 (out of place,
 // chunked, for long lines) on the LR stacks of shift_and_add.  grid ceil(frames / 4), block 256.
-template <typename T>
+template <typename T, typename S = T>
 __global__ void __launch_bounds__(256)
-    k_prefilter_small(const T *__restrict__ src_, T *__restrict__ dst_, int nframes, int Hc, int Wc, int mode)
+    k_prefilter_small(const S *__restrict__ src_, T *__restrict__ dst_, int nframes, int Hc, int Wc, int mode)
 {
     constexpr int LD = 65;
     __shared__ T buf[4][64 * LD];
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int fr = min((int)blockIdx.x * 4 + wave, nframes - 1);  // a ragged last block repeats the last frame
-    const T *src = src_ + (size_t)fr * Hc * Wc;
+    const S *src = src_ + (size_t)fr * Hc * Wc;  // (S = uint8_t: the camera's samples, converted on the way into the LDS)
     T *dst = dst_ + (size_t)fr * Hc * Wc;
     T *reg = buf[wave];
     const int cl = min(lane, Wc - 1);
     for (int r0 = 0; r0 < Hc; r0 += 16) {
-        T v[16];
+        S v[16];
 #pragma unroll
         for (int u = 0; u < 16; u++)
             v[u] = src[(size_t)min(r0 + u, Hc - 1) * Wc + cl];
 #pragma unroll
         for (int u = 0; u < 16; u++)
             if (r0 + u < Hc && lane < Wc)
-                reg[(r0 + u) * LD + lane] = v[u];
+                reg[(r0 + u) * LD + lane] = (T)v[u];
     }
     __syncthreads();
     fused::WalkState<T> st;
@@ -889,17 +891,31 @@ template <typename T> __device__ __forceinline__ void prefilter_line64(T (&v)[64
         v[i] = next;
     }
 }
-__global__ void __launch_bounds__(64) k_prefilter_64(const float *__restrict__ src_, float *__restrict__ dst_, int mode)
+// S = uint8_t (srx_saa_u8lr_f32): the 64 loads of a lane are bytes, a wave's request one 64-byte row of the frame; the stores are as before.
+// (Measured against a form that fetched the frame as 16 four-byte words per lane and spread them through the LDS: 57.9 us either way for the
+// 16 384 frames of a C2 batch, 62.4 against 59.9 on another box; the float frames take 88.  The one-byte form stays: it has no alignment case.)
+template <typename S = float>
+__global__ void __launch_bounds__(64) k_prefilter_64(const S *__restrict__ src_, float *__restrict__ dst_, int mode)
 {
     constexpr int LD = 65;
     __shared__ float buf[64 * LD];
     const int lane = threadIdx.x;
-    const float *src = src_ + (size_t)blockIdx.x * 4096;
+    const S *src = src_ + (size_t)blockIdx.x * 4096;
     float *dst = dst_ + (size_t)blockIdx.x * 4096;
     float v[64];
+    if constexpr (std::is_same<S, float>::value) {
 #pragma unroll
-    for (int r = 0; r < 64; r++)
-        v[r] = src[r * 64 + lane];
+        for (int r = 0; r < 64; r++)
+            v[r] = src[r * 64 + lane];
+    } else {
+        S raw[64];  // every load leaves before the first conversion
+#pragma unroll
+        for (int r = 0; r < 64; r++)
+            raw[r] = src[r * 64 + lane];
+#pragma unroll
+        for (int r = 0; r < 64; r++)
+            v[r] = (float)raw[r];
+    }
     prefilter_line64<float>(v, mode);  // axis 0: lane = column
 #pragma unroll
     for (int r = 0; r < 64; r++)
@@ -1202,7 +1218,8 @@ __global__ void __launch_bounds__(256)
 // What every implementation of formulation A shares -- the prepared call: its scalars, and what is built once per call (or once per
 // plan): the index maps, the LR mosaic M, the count map C, the near band's counted sums Mu and lists, the constant part V of the MSE trace.
 template <typename T> struct Common {
-    const T *lr;
+    const void *lr;  // T, or uint8_t when lr_u8 (the two kernels that read the frames have an instantiation for either)
+    bool lr_u8;
     int B, N, h, w, H, W, f;
     double step, scale;  // scale: 1 / (samples of an item), the MSE trace's normalisation
     AxisPlan py, px;
@@ -1230,12 +1247,13 @@ static inline size_t ws_common(int eb, int B, int N, int H, int W)
 
 // own_build: the implementation reads the LR frames itself and wants no M / C / Mu planes (a batch of patches on a full phase grid,
 // srx_patch.hpp's k_patch_build -- the M plane of 1024 patches is 328 MB written here and read back once by k_patch_prep)
-template <typename T>
-static int common_prep(Common<T> &c, bool own_build, const T *lr, int B, int N, int h, int w, const double *sh, const double *k, int kh, int kw, int H,
+template <typename T, typename S = T>
+static int common_prep(Common<T> &c, bool own_build, const S *lr, int B, int N, int h, int w, const double *sh, const double *k, int kh, int kw, int H,
                        int W, int f, double step, Arena &ar, hipStream_t st, int tr_lo, int tr_hi)
 {
     const int Hp = H + 2 * SRX_NPAD, Wp = W + 2 * SRX_NPAD, Hg = Hp + 3, Wg = Wp + 3;
-    c.lr = lr, c.B = B, c.N = N, c.h = h, c.w = w, c.H = H, c.W = W, c.f = f, c.step = step;
+    static_assert(std::is_same<S, T>::value || std::is_same<S, uint8_t>::value, "LR samples: T or uint8_t");
+    c.lr = lr, c.lr_u8 = !std::is_same<S, T>::value, c.B = B, c.N = N, c.h = h, c.w = w, c.H = H, c.W = W, c.f = f, c.step = step;
     c.scale = 1.0 / ((double)h * (double)w) / (double)N;
     AxisPlan &py = c.py, &px = c.px;
     if (!plan_axis(N, sh, 0, f, py) || !plan_axis(N, sh, 1, f, px))
@@ -1271,10 +1289,10 @@ static int common_prep(Common<T> &c, bool own_build, const T *lr, int B, int N, 
     c.own_build = own_build;
     if (!own_build) {
         if (B >= 8)
-            SRX_LAUNCH(KID_MOSAIC_BUILD, (k_mosaic_build<T, 8, 1>), dim3(cdiv(Wg, 64), cdiv(Hg, 4), cdiv(B, 8)), dim3(64, 4), 0, st, lr, B, N, h,
+            SRX_LAUNCH(KID_MOSAIC_BUILD, (k_mosaic_build<T, 8, 1, S>), dim3(cdiv(Wg, 64), cdiv(Hg, 4), cdiv(B, 8)), dim3(64, 4), 0, st, lr, B, N, h,
                        w, tabY, tabX, Hg, Wg, py.PB, px.PB, py.D, px.D, NB, Mg, Cg, Mu, Vpart, tr_lo, tr_hi);
         else
-            SRX_LAUNCH(KID_MOSAIC_BUILD, (k_mosaic_build<T, 1, 4>), dim3(cdiv(Wg, 256), cdiv(Hg, 4), B), dim3(64, 4), 0, st, lr, B, N, h, w,
+            SRX_LAUNCH(KID_MOSAIC_BUILD, (k_mosaic_build<T, 1, 4, S>), dim3(cdiv(Wg, 256), cdiv(Hg, 4), B), dim3(64, 4), 0, st, lr, B, N, h, w,
                        tabY, tabX, Hg, Wg, py.PB, px.PB, py.D, px.D, NB, Mg, Cg, Mu, Vpart, tr_lo, tr_hi);
         hipLaunchKernelGGL(k_vtot_reduce, dim3(B), dim3(256), 0, st, Vpart, (B >= 8 ? cdiv(Wg, 64) : cdiv(Wg, 256)) * cdiv(Hg, 4), Vtot);
         SRX_CHECK_LAUNCH();
@@ -1374,8 +1392,11 @@ static inline size_t saa_ws(int eb, int B, int N, int h, int w, int f)
            align_up((size_t)B * ((size_t)h * f + 2 * SRX_NPAD + 3) * ((size_t)w * f + 2 * SRX_NPAD + 3) * eb);  // the W plane of the two-pass form
 }
 
-template <typename T>
-static int saa(const T *lr, int B, int N, int h, int w, const double *sh, int f, T *out, void *ws, size_t wsb,
+// S: the type of the LR samples, T or uint8_t (srx_saa_u8lr_*).  The three prefilter forms are the only readers of the frames: the two
+// wave-per-frame kernels and the float32 tile kernel read bytes themselves; where the line kernels run (float64, or on request) the copy into
+// coef that the float call starts with is the conversion.  The workspace is the same for either sample type.
+template <typename T, typename S = T>
+static int saa(const S *lr, int B, int N, int h, int w, const double *sh, int f, T *out, void *ws, size_t wsb,
                hipStream_t st)
 {
     if ((long)B * N > 65535)
@@ -1394,9 +1415,9 @@ static int saa(const T *lr, int B, int N, int h, int w, const double *sh, int f,
         return SRX_E_WORKSPACE;
     if (h == 64 && w == 64 && sizeof(T) == 4) {
         if constexpr (sizeof(T) == 4)
-            SRX_LAUNCH(KID_PREFILTER_SMALL, k_prefilter_64, dim3(B * N), dim3(64), 0, st, lr, coef, (int)MODE_MIRROR);
+            SRX_LAUNCH(KID_PREFILTER_SMALL, k_prefilter_64<S>, dim3(B * N), dim3(64), 0, st, lr, coef, (int)MODE_MIRROR);
     } else if (h <= 64 && w <= 64) {
-        SRX_LAUNCH(KID_PREFILTER_SMALL, k_prefilter_small<T>, dim3(cdiv(B * N, 4)), dim3(256), 0, st, lr, coef, B * N, h, w,
+        SRX_LAUNCH(KID_PREFILTER_SMALL, (k_prefilter_small<T, S>), dim3(cdiv(B * N, 4)), dim3(256), 0, st, lr, coef, B * N, h, w,
                    (int)MODE_MIRROR);
     } else {
         SRX_TRY(fused::prefilter2d_from(lr, coef, cscr, B * N, h, w, MODE_MIRROR, st));

@@ -279,18 +279,28 @@ __global__ void k_patch_maps(BuildMaps v, BuildMaps *dst)  // (a lane-indexed by
 // PASS 1 writes the float plane of the patches so marked and returns at once for the others.  (Round 4's first form decided with a pass of
 // its own over the frames, k_patch_flags -- 63 us of a C2 step for a question this kernel answers on the way; frames of 8-bit integers,
 // the reference's data, now pay one empty launch instead, frames that are not pay the byte pass: +0.08 ms per 1024 patches.)
-template <int PASS>
+// S = uint8_t (the camera's frames, srx_ibp_u8lr_f32): the samples ARE bytes, so PASS 0 has nothing to test, never clears m8, and PASS 1
+// is not launched at all.  Two read shapes:
+//   WIDE (the default; frames on a 4-byte boundary -- a block-uniform test of `lr`: h w and w are multiples of 4): a wave fetches the LR rows
+//     behind one patch row WHOLE, as PN / 4 = 64 words (lane = frame of the row class x word of its row: one 4-byte load per lane and
+//     patch row, four per lane instead of sixteen), parks them in the LDS and every lane picks its four bytes there;
+//   one byte per lane (frames at other addresses, or SRX_FLAG_DIAG_U8_BYTE_LOADS): the float form's sixteen loads per lane, a wave's
+//     request 64 consecutive bytes of one LR row.
+// 1024 patches: 75 us wide, 101 us by bytes -- the kernel is bound by the loads it issues, not by their bytes -- against 79 + 7 us for the
+// two passes over float frames (tools/u8lr_time.py).
+template <int PASS, typename S = float, bool WIDE = false>
 __global__ void __launch_bounds__(256)
-    k_patch_build(const float *__restrict__ lr, int N, int h, int w, const BuildMaps *__restrict__ maps, int *__restrict__ m8,
+    k_patch_build(const S *__restrict__ lr, int N, int h, int w, const BuildMaps *__restrict__ maps, int *__restrict__ m8,
                   float *__restrict__ Mt, unsigned *__restrict__ Mt8)
 {
     __shared__ float4 tile[64][17];  // [column quad][row of the band] (+1: the write-out walks a quad's rows)
     const int b = blockIdx.y, gy0 = blockIdx.x * 16, cq = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    constexpr bool bytes = PASS == 0;
+    constexpr bool bytes = PASS == 0, test = PASS == 0 && std::is_same<S, float>::value;
+    static_assert(PASS == 0 || std::is_same<S, float>::value, "byte frames need no float plane");
     if (PASS == 1 && __builtin_amdgcn_readfirstlane(m8[b]) != 0)
         return;
     int bad = 0;
-    const float *src = lr + (size_t)b * N * h * w;
+    const S *src = lr + (size_t)b * N * h * w;
     int cx[4], jx[4];
 #pragma unroll
     for (int c = 0; c < 4; c++) {
@@ -302,6 +312,41 @@ __global__ void __launch_bounds__(256)
     const int *fw = reinterpret_cast<const int *>(&maps->frame[0][0]);
     const int fr0 = fw[0], fr1 = fw[1], fr2 = fw[2], fr3 = fw[3];
     float v[4][4];
+    bool done = false;
+    if constexpr (WIDE) {
+        __shared__ unsigned rowsw[4][4][64];  // [wave][patch row of the wave][frame of the row class x word]
+        if ((((size_t)lr) & 3) == 0) {  // (block-uniform: the barrier below is met by all or none)
+            const int nd = w >> 2, kx = cq / nd, dw = cq - kx * nd;  // words per LR row; this lane's column class and word
+            unsigned wd[4];
+#pragma unroll
+            for (int m = 0; m < 4; m++) {
+                const int gy = gy0 + wv + 4 * m;
+                const int cy = gy < maps->nby ? -1 : (int)maps->y.cls[gy], iy = maps->y.idx[gy];  // wave-uniform
+                const int fsel = cy == 0 ? fr0 : cy == 1 ? fr1 : cy == 2 ? fr2 : fr3;
+                wd[m] = 0;
+                if (cy >= 0)
+                    wd[m] = reinterpret_cast<const unsigned *>(src + ((size_t)((fsel >> (8 * kx)) & 0xff) * h + iy) * w)[dw];
+            }
+#pragma unroll
+            for (int m = 0; m < 4; m++)
+                rowsw[wv][m][cq] = wd[m];
+            __syncthreads();
+            const unsigned char *rb = reinterpret_cast<const unsigned char *>(&rowsw[wv][0][0]);
+#pragma unroll
+            for (int m = 0; m < 4; m++) {
+                const int gy = gy0 + wv + 4 * m;
+                const int cy = gy < maps->nby ? -1 : (int)maps->y.cls[gy];
+#pragma unroll
+                for (int c = 0; c < 4; c++) {
+                    v[m][c] = 0.f;
+                    if (cy >= 0 && cx[c] >= 0)
+                        v[m][c] = (float)rb[m * 256 + cx[c] * w + jx[c]];
+                }
+            }
+            done = true;
+        }
+    }
+    if (!done)
 #pragma unroll
     for (int m = 0; m < 4; m++) {  // all sixteen loads of a lane leave before the first one is looked at
         const int gy = gy0 + wv + 4 * m;
@@ -316,14 +361,14 @@ __global__ void __launch_bounds__(256)
     }
 #pragma unroll
     for (int m = 0; m < 4; m++) {
-        if (PASS == 0) {
+        if (test) {
 #pragma unroll
             for (int c = 0; c < 4; c++)  // (the zeros of absent samples pass)
                 bad |= !((int)(v[m][c] == rintf(v[m][c])) & (int)(v[m][c] >= 0.f) & (int)(v[m][c] <= 255.f));
         }
         tile[cq][wv + 4 * m] = make_float4(v[m][0], v[m][1], v[m][2], v[m][3]);
     }
-    if (PASS == 0) {
+    if (test) {
         if (__syncthreads_or(bad) && threadIdx.x == 0)
             atomicAnd(&m8[b], 0);
     } else {
@@ -349,8 +394,9 @@ __global__ void __launch_bounds__(256)
 }
 // (M, Mu) of the near-band pixels of every patch from the LR frames (k_mosaic_build's sums, on the near band only), and the patch's
 // share of the within-pixel scatter V (zero on a full phase grid; kept for the definition's sake).  grid (ceil(nn / 256), B)
+template <typename S = float>
 __global__ void __launch_bounds__(256)
-    k_patch_near_build(const float *__restrict__ lr, int N, int h, int w, const mosaic::MTap *__restrict__ tabY, const mosaic::MTap *__restrict__ tabX,
+    k_patch_near_build(const S *__restrict__ lr, int N, int h, int w, const mosaic::MTap *__restrict__ tabY, const mosaic::MTap *__restrict__ tabX,
                        int Hg, int Wg, int Dy, int Dx, int exy, int exx, int nby, int nbx, int nn, float2 *__restrict__ Mn, double *__restrict__ Vtot)
 {
     const int t = blockIdx.x * 256 + threadIdx.x, b = blockIdx.y;
@@ -359,7 +405,7 @@ __global__ void __launch_bounds__(256)
         int ngy, ngx, dst;
         near_coords(t, exy, exx, nby, nbx, ngy, ngx, dst);
         const int p = ngy + 13, q = ngx + 13;
-        const float *src = lr + (size_t)b * N * h * w;
+        const S *src = lr + (size_t)b * N * h * w;
         double M = 0.0, S1 = 0.0, S2 = 0.0;
         int cu = 0;
         for (int k = 0; k < N; k++) {
@@ -1456,8 +1502,15 @@ static int iterate(const mosaic::Common<float> &c, const float *hr_init, float *
         bm.nby = pa.y.nb, bm.nbx = pa.x.nb;
         hipLaunchKernelGGL(k_patch_maps, dim3(1), dim3(256), 0, st, bm, maps);
         SRX_CHECK_LAUNCH();
-        SRX_LAUNCH(KID_PATCH_BUILD, k_patch_build<0>, dim3(PN / 16, B), dim3(256), 0, st, c.lr, N, c.h, c.w, maps, m8, Mt, Mt8);
-        SRX_LAUNCH(KID_PATCH_FLAGS, k_patch_build<1>, dim3(PN / 16, B), dim3(256), 0, st, c.lr, N, c.h, c.w, maps, m8, Mt, Mt8);
+        if (c.lr_u8) {  // byte frames: the byte plane of every patch and nothing else (m8 keeps its preset: no patch asks for the float plane)
+            if (!(call_flags() & SRX_FLAG_DIAG_U8_BYTE_LOADS) && c.w % 4 == 0 && nx * c.w <= PN)  // (the column classes' rows fill at most 64 words)
+                SRX_LAUNCH(KID_PATCH_BUILD, (k_patch_build<0, uint8_t, true>), dim3(PN / 16, B), dim3(256), 0, st, (const uint8_t *)c.lr, N, c.h, c.w, maps, m8, Mt, Mt8);
+            else
+                SRX_LAUNCH(KID_PATCH_BUILD, (k_patch_build<0, uint8_t>), dim3(PN / 16, B), dim3(256), 0, st, (const uint8_t *)c.lr, N, c.h, c.w, maps, m8, Mt, Mt8);
+        } else {
+            SRX_LAUNCH(KID_PATCH_BUILD, k_patch_build<0>, dim3(PN / 16, B), dim3(256), 0, st, (const float *)c.lr, N, c.h, c.w, maps, m8, Mt, Mt8);
+            SRX_LAUNCH(KID_PATCH_FLAGS, k_patch_build<1>, dim3(PN / 16, B), dim3(256), 0, st, (const float *)c.lr, N, c.h, c.w, maps, m8, Mt, Mt8);
+        }
     } else {
         hipLaunchKernelGGL(k_patch_prep, dim3(PN / 32, PN / 32, B + 1), dim3(32, 8), 0, st, c.Mg, c.Cg, B, Hg, Wg, pa.y.nb, pa.x.nb, Mt, Ct, Mt8, m8);
         SRX_CHECK_LAUNCH();
@@ -1466,8 +1519,11 @@ static int iterate(const mosaic::Common<float> &c, const float *hr_init, float *
         hipLaunchKernelGGL(k_patch_near_tab, dim3(cdiv(pa.nn, 256)), dim3(256), 0, st, c.ncu, c.nyx, NS, py.PB, px.PB, pa.y.ex, pa.x.ex, pa.y.nb,
                            pa.x.nb, pa.y.E, pa.x.E, pa.nn, nrec, nent);
         SRX_CHECK_LAUNCH();
-        if (own)
-            hipLaunchKernelGGL(k_patch_near_build, dim3(cdiv(pa.nn, 256), B), dim3(256), 0, st, c.lr, N, c.h, c.w, c.tabY, c.tabX, Hg, Wg,
+        if (own && c.lr_u8)
+            hipLaunchKernelGGL(k_patch_near_build<uint8_t>, dim3(cdiv(pa.nn, 256), B), dim3(256), 0, st, (const uint8_t *)c.lr, N, c.h, c.w, c.tabY, c.tabX, Hg, Wg,
+                               py.D, px.D, pa.y.ex, pa.x.ex, pa.y.nb, pa.x.nb, pa.nn, Mn, c.Vtot);
+        else if (own)
+            hipLaunchKernelGGL(k_patch_near_build<float>, dim3(cdiv(pa.nn, 256), B), dim3(256), 0, st, (const float *)c.lr, N, c.h, c.w, c.tabY, c.tabX, Hg, Wg,
                                py.D, px.D, pa.y.ex, pa.x.ex, pa.y.nb, pa.x.nb, pa.nn, Mn, c.Vtot);
         else
             hipLaunchKernelGGL(k_patch_near_m, dim3(cdiv(pa.nn, 256), B), dim3(256), 0, st, c.Mg, c.Mu, c.NB, py.PB, px.PB, pa.y.ex, pa.x.ex, pa.y.nb,

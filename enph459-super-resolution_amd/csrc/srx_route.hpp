@@ -75,8 +75,10 @@ static inline size_t ibp_ws_for(const ImplRow &impl, int eb, int B, int N, int H
     return ws_common(eb, B, N, H, W) + impl.tabs_bytes(eb, B, N, H, W);
 }
 
-template <typename T>
-static int ibp(const ImplRow &impl, const T *lr, int B, int N, int h, int w, const double *sh, const double *k, int kh, int kw, const T *hr_init, int H,
+// S: the type of the LR samples, T or uint8_t (srx_ibp_u8lr_*).  Only the table building reads the frames (k_mosaic_build in common_prep,
+// the patch path's own build), so every implementation below is the same for either.
+template <typename T, typename S = T>
+static int ibp(const ImplRow &impl, const S *lr, int B, int N, int h, int w, const double *sh, const double *k, int kh, int kw, const T *hr_init, int H,
                int W, int f, int n_iter, double step, T *hr, double *errors, void *ws, size_t wsb, hipStream_t st)
 {
     if (n_iter == 0 && hr != hr_init && hipMemcpyAsync(hr, hr_init, (size_t)B * H * W * sizeof(T), hipMemcpyDeviceToDevice, st) != hipSuccess)
@@ -91,7 +93,7 @@ static int ibp(const ImplRow &impl, const T *lr, int B, int N, int h, int w, con
     }
     Arena ar(ws, wsb);
     Common<T> c;
-    SRX_TRY(common_prep<T>(c, own_build, lr, B, N, h, w, sh, k, kh, kw, H, W, f, step, ar, st, 0, H));
+    SRX_TRY((common_prep<T, S>(c, own_build, lr, B, N, h, w, sh, k, kh, kw, H, W, f, step, ar, st, 0, H)));
     switch (impl.id) {  // (the float32-only / float64-only drivers are not templates: eligible() admits them for their own type alone)
     case IMPL_STILE:  // float64 patches with a common fraction > 0: two launches per iteration on strips
         if constexpr (sizeof(T) == 8)

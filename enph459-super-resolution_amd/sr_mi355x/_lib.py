@@ -16,6 +16,7 @@ FLAG_AUTO, FLAG_COMPOSED, FLAG_FUSED, FLAG_PER_FRAME, FLAG_TILES = 0, 1, 2, 4, 8
 # diagnostic path switches (include/srx.h): implementations the tests hold to the same results
 FLAG_DIAG_NO_ZERO_FUSE, FLAG_DIAG_NO_SEPARABLE, FLAG_DIAG_NO_PREFILTER_TILE, FLAG_DIAG_V1 = 0x100, 0x200, 0x400, 0x800
 FLAG_DIAG_WIDE_WINDOWS, FLAG_DIAG_COLUMN_TILES, FLAG_DIAG_TWO_LAUNCH, FLAG_DIAG_SAA_ONE_PASS = 0x1000, 0x2000, 0x4000, 0x8000
+FLAG_DIAG_U8_BYTE_LOADS = 0x10000
 
 _c = ctypes
 _P, _I, _D, _Z, _U = _c.c_void_p, _c.c_int, _c.c_double, _c.c_size_t, _c.c_uint
@@ -30,6 +31,8 @@ _TYPED = {
     "srx_backproject_{T}": (_I, [_P, _I, _I, _I, _HD, _I, _I, _D, _D, _I, _I, _I, _P, _P, _Z, _P]),
     "srx_saa_{T}": (_I, [_P, _I, _I, _I, _I, _HD, _I, _P, _P, _Z, _P, _U]),
     "srx_ibp_{T}": (_I, [_P, _I, _I, _I, _I, _HD, _HD, _I, _I, _P, _I, _I, _I, _I, _D, _P, _P, _P, _Z, _P, _U]),
+    "srx_saa_u8lr_{T}": (_I, [_P, _I, _I, _I, _I, _HD, _I, _P, _P, _Z, _P, _U]),
+    "srx_ibp_u8lr_{T}": (_I, [_P, _I, _I, _I, _I, _HD, _HD, _I, _I, _P, _I, _I, _I, _I, _D, _P, _P, _P, _Z, _P, _U]),
     "srx_decimate_{T}": (_I, [_P, _I, _I, _I, _I, _I, _I, _P, _P]),
     "srx_zero_insert_{T}": (_I, [_P, _I, _I, _I, _I, _I, _I, _P, _P]),
     "srx_mean_frames_{T}": (_I, [_P, _I, _I, _Z, _P, _P]),
@@ -63,6 +66,10 @@ _PLAIN = {
     "srx_saa_workspace_bytes": (_Z, [_I, _I, _I, _I, _I, _I]),
     "srx_ibp_workspace_bytes": (_Z, [_I, _I, _I, _I, _I, _I, _I, _I, _U]),
     "srx_ibp_workspace_bytes_for": (_Z, [_I, _I, _I, _I, _I, _I, _I, _I, _HD, _HD, _I, _I, _U]),
+    "srx_saa_u8lr_workspace_bytes": (_Z, [_I, _I, _I, _I, _I, _I]),
+    "srx_ibp_u8lr_workspace_bytes": (_Z, [_I, _I, _I, _I, _I, _I, _I, _I, _U]),
+    "srx_ibp_u8lr_workspace_bytes_for": (_Z, [_I, _I, _I, _I, _I, _I, _I, _I, _HD, _HD, _I, _I, _U]),
+    "srx_decimate_u8": (_I, [_P, _I, _I, _I, _I, _I, _I, _P, _P]),
     "srx_ibp_path_for": (_c.c_char_p, [_I, _I, _I, _I, _I, _I, _I, _HD, _HD, _I, _I, _U]),
     "srx_ibp_plan_workspace_bytes": (_Z, [_I, _I, _I, _I, _I, _I, _I, _I, _U]),
     "srx_ibp_plan_run": (_I, [_P, _I, _P, _P]),

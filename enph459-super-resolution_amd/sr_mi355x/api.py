@@ -30,7 +30,7 @@ import torch
 from . import _lib
 from ._lib import (FLAG_AUTO, FLAG_COMPOSED, FLAG_FUSED, FLAG_PER_FRAME, FLAG_TILES, FLAG_DIAG_NO_ZERO_FUSE,  # noqa: F401  (re-exported)
                    FLAG_DIAG_NO_SEPARABLE, FLAG_DIAG_NO_PREFILTER_TILE, FLAG_DIAG_V1, FLAG_DIAG_WIDE_WINDOWS, FLAG_DIAG_COLUMN_TILES,
-                   FLAG_DIAG_TWO_LAUNCH, FLAG_DIAG_SAA_ONE_PASS)
+                   FLAG_DIAG_TWO_LAUNCH, FLAG_DIAG_SAA_ONE_PASS, FLAG_DIAG_U8_BYTE_LOADS)
 
 _TORCH_DT = {"f32": torch.float32, "f64": torch.float64}
 _ELEM = {"f32": 4, "f64": 8}
@@ -235,6 +235,65 @@ def ibp_batched(lr, shifts_yx, kernel, hr_init, factor=2, n_iter=80, step=0.5, p
     return hr, errors
 
 
+def _u8_dev(x, what, ndim):
+    """uint8 tensor / array -> contiguous uint8 CUDA tensor, uploaded as bytes; any other dtype is a TypeError (no silent cast)"""
+    if isinstance(x, torch.Tensor):
+        if x.dtype != torch.uint8:
+            raise TypeError(f"{what} must be uint8, not {x.dtype}")
+        t = x
+    else:
+        a = np.asarray(x)
+        if a.dtype != np.uint8:
+            raise TypeError(f"{what} must be uint8, not {a.dtype}")
+        t = torch.from_numpy(np.ascontiguousarray(a))
+    if t.dim() != ndim:
+        raise ValueError(f"{what} must have {ndim} dimensions")
+    return t.to(device=_device()).contiguous()
+
+
+def shift_and_add_u8_batched(lr_u8, shifts_yx, factor=2, precision=None, flags=FLAG_AUTO):
+    """shift_and_add_batched on the camera's own samples: lr_u8 uint8 [B, N, h, w] -> [B, h*f, w*f] of the compute precision; the same
+    bits as shift_and_add_batched on the converted frames (srx_saa_u8lr_*)."""
+    prec = precision or get_precision()
+    x = _u8_dev(lr_u8, "lr_u8", 4)
+    B, N, h, w = x.shape
+    f = int(factor)
+    sh, shp = _host_f64(shifts_yx, (N, 2))
+    out = torch.empty((B, h * f, w * f), dtype=_TORCH_DT[prec], device=x.device)
+    wt, wp, wn = _ws(_lib.load().srx_saa_u8lr_workspace_bytes(_ELEM[prec], B, N, h, w, f))
+    _lib.check(_fn("srx_saa_u8lr", prec)(_p(x), B, N, h, w, shp, f, _p(out), wp, wn, _stream(), flags), "srx_saa_u8lr")
+    return out
+
+
+def ibp_u8_batched(lr_u8, shifts_yx, kernel, hr_init, factor=2, n_iter=80, step=0.5, precision=None, flags=FLAG_AUTO,
+                   want_errors=True, out=None, exact_workspace=True):
+    """ibp_batched on the camera's own samples: lr_u8 uint8 [B, N, h, w], hr_init [B, H, W] -> (hr, errors); the same bits as
+    ibp_batched on the converted frames (srx_ibp_u8lr_*)."""
+    prec = precision or get_precision()
+    x = _u8_dev(lr_u8, "lr_u8", 4)
+    h0, _ = _to_dev(hr_init, prec)
+    B, N, h, w = x.shape
+    Bh, H, W = h0.shape
+    if Bh != B:
+        raise ValueError("lr_u8 and hr_init disagree on the batch size")
+    f = int(factor)
+    sh, shp = _host_f64(shifts_yx, (N, 2))
+    k, kp = _host_f64(kernel)
+    if out is not None:
+        if (not isinstance(out, torch.Tensor) or not out.is_cuda or out.dtype != _TORCH_DT[prec] or tuple(out.shape) != (B, H, W)
+                or not out.is_contiguous()):
+            raise ValueError(f"out must be a contiguous CUDA tensor of dtype {_TORCH_DT[prec]} and shape {(B, H, W)}")
+    hr = torch.empty_like(h0) if out is None else out
+    errors = torch.empty((B, int(n_iter)), dtype=torch.float64, device=x.device) if want_errors else None
+    lib = _lib.load()
+    wt, wp, wn = _ws(lib.srx_ibp_u8lr_workspace_bytes_for(_ELEM[prec], B, N, h, w, H, W, f, shp, kp, k.shape[0], k.shape[1], flags)
+                     if exact_workspace else lib.srx_ibp_u8lr_workspace_bytes(_ELEM[prec], B, N, h, w, H, W, f, flags))
+    _lib.check(_fn("srx_ibp_u8lr", prec)(_p(x), B, N, h, w, shp, kp, k.shape[0], k.shape[1], _p(h0), H, W, f, int(n_iter),
+                                         float(step), _p(hr), _p(errors) if want_errors else None, wp, wn, _stream(), flags),
+               "srx_ibp_u8lr")
+    return hr, errors
+
+
 class IbpPlan:
     """srx_ibp_plan_* (include/srx.h): the IBP loop of a batch in instalments -- the per-call tables built once, `run(n)` for n more
     iterations, rows of the state readable / replaceable in between.  `trace_rows=(lo, hi)`: the HR rows whose LR samples the MSE trace
@@ -359,6 +418,27 @@ def decimate(img, f, py=0, px=0):
 def extract_red(img):
     """Bayer RGGB red plane img[0::2, 0::2] (rgb_cal_target/run_sr.py:73-75)."""
     return decimate(img, 2, 0, 0)
+
+
+def decimate_u8(img_u8, f, py=0, px=0):
+    """img[..., py::f, px::f] on bytes: uint8 [H, W] or [B, H, W] -> uint8 (srx_decimate_u8); numpy in -> numpy out."""
+    was_np = not isinstance(img_u8, torch.Tensor)
+    if (img_u8.dim() if not was_np else np.ndim(img_u8)) not in (2, 3):
+        raise ValueError("img_u8 must be [H, W] or [B, H, W]")
+    single = (img_u8.dim() if not was_np else np.ndim(img_u8)) == 2
+    x = _u8_dev(img_u8, "img_u8", 2 if single else 3)
+    if single:
+        x = x[None]
+    B, H, W = x.shape
+    out = torch.empty((B, -(-(H - py) // f), -(-(W - px) // f)), dtype=torch.uint8, device=x.device)
+    _lib.check(_lib.load().srx_decimate_u8(_p(x), B, H, W, int(f), int(py), int(px), _p(out), _stream()), "srx_decimate_u8")
+    out = out[0] if single else out
+    return out.cpu().numpy() if was_np else out
+
+
+def extract_red_u8(img_u8):
+    """Bayer RGGB red plane of a raw uint8 frame, kept in bytes (rgb_cal_target/run_sr.py:73-75 without the cast)."""
+    return decimate_u8(img_u8, 2, 0, 0)
 
 
 def zero_insert(err, f, hr_shape):

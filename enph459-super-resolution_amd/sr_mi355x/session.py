@@ -81,6 +81,22 @@ def _to_dev_f(a):
     return api._to_dev(a, LOADER_PRECISION)[0]
 
 
+def _to_dev_frames(decoded, keep_u8):
+    """The decoded files of one frame set on the device: float64 (load_gray's cast), or -- keep_u8, and every file 8-bit greyscale -- the
+    bytes as they are (a quarter of the upload of float32 frames, an eighth of these; shift_and_add and ibp take them through
+    srx_saa_u8lr / srx_ibp_u8lr).  A colour file (load_gray's channel mean is not an integer) keeps the whole set in float64."""
+    if keep_u8 and all(a.dtype == np.uint8 for a in decoded):
+        import torch
+        return [torch.from_numpy(np.ascontiguousarray(a)).to(api._device()) for a in decoded]
+    return [_to_dev_f(a) for a in decoded]
+
+
+def _frames_f64(lr):
+    """float64 view of a frame stack for the loaders' arithmetic (the frame mean): the stack itself, or the bytes converted (exact)"""
+    import torch
+    return api.u8_to_float(lr, precision=LOADER_PRECISION) if lr.dtype == torch.uint8 else lr
+
+
 def load_gray_dev(path, decoded=None):
     """PNG -> float64 image on the device (load_gray, mono_cal_target/run_sr.py:73-75).  decoded: the file's pixels, if a caller
     already has them (_decode_many)."""
@@ -96,10 +112,10 @@ def detect_kind(session_dir):
     raise FileNotFoundError(f"no SR input images in {session_dir}")
 
 
-def load_mono_cal_session(session_dir):
-    """mono_cal_target/run_sr.py:78-99 -> (frames on device, shifts)."""
+def load_mono_cal_session(session_dir, keep_u8=False):
+    """mono_cal_target/run_sr.py:78-99 -> (frames on device, shifts).  keep_u8: the frames stay uint8 (_to_dev_frames)."""
     present = [(os.path.join(session_dir, fname), s) for fname, s in IMAGE_SHIFTS if os.path.exists(os.path.join(session_dir, fname))]
-    frames = [_to_dev_f(a) for a in _decode_many([p for p, _ in present])]
+    frames = _to_dev_frames(_decode_many([p for p, _ in present]), keep_u8)
     shifts = [s for _, s in present]
     if len(frames) < 2:
         raise FileNotFoundError(f"Need at least 2 images in {session_dir}")
@@ -132,8 +148,9 @@ def load_rgb_cal_combo(combo_dir):
     return frames, shifts
 
 
-def load_corner_reps(session_dir, red):
-    """mono_barcodes/run_sr.py:89-130 / rgb_barcodes/run_sr.py:102-143 -> (list over reps of 4 frames, shifts)."""
+def load_corner_reps(session_dir, red, keep_u8=False):
+    """mono_barcodes/run_sr.py:89-130 / rgb_barcodes/run_sr.py:102-143 -> (list over reps of 4 frames, shifts).
+    keep_u8: the frames stay uint8 (_to_dev_frames); the red plane is then cut out of the bytes (extract_red_u8)."""
     rep_indices = sorted({int(m.group(1)) for m in (re.match(r"corner\d+_rep(\d+)\.png", n) for n in os.listdir(session_dir))
                           if m})
     if not rep_indices:
@@ -143,11 +160,14 @@ def load_corner_reps(session_dir, red):
         if not os.path.exists(path):
             raise FileNotFoundError(f"Missing {path}")
     decoded = _decode_many(paths)
+    keep_u8 = keep_u8 and all(a.dtype == np.uint8 for a in decoded)  # (one colour file: the whole session in float64, as without the switch)
     all_reps = []
     for k in range(len(rep_indices)):
         frames = []
-        for ci in range(4):
-            img = _to_dev_f(decoded[4 * k + ci])
+        for img in _to_dev_frames(decoded[4 * k:4 * k + 4], keep_u8):
+            if keep_u8:
+                frames.append(api.extract_red_u8(img) if red else img)
+                continue
             with _loader_precision():
                 frames.append(api.extract_red(img) if red else img)
         all_reps.append(frames)
@@ -160,11 +180,16 @@ def reconstruct(frames, shifts, psf_kernel, n_iter, factor=UPSAMPLE_FACTOR, step
     row_bands: every rank of the process group calls this with the same frames; the IBP loop runs on row bands of the ONE image
     (rowband.ibp_row_bands: halo rows exchanged point to point), and only rank 0 gets "SAA_IBP" (None elsewhere)."""
     import torch
-    lr64 = torch.stack(frames)
+    lr64 = torch.stack(frames)  # float64, or uint8 frames (keep_u8 loaders): SAA and IBP then take the bytes themselves
+    u8 = lr64.dtype == torch.uint8
     with _loader_precision():
-        mean_lr = api.mean_frames(lr64)  # float64; also what LR_(red_)mean.png is quantised from
-    lr = lr64.to(api._TORCH_DT[api.get_precision()])
+        mean_lr = api.mean_frames(_frames_f64(lr64))  # float64; also what LR_(red_)mean.png is quantised from
     native = api.zoom_batched(mean_lr[None], factor)[0]
+    if u8 and not row_bands:
+        saa = api.shift_and_add_u8_batched(lr64[None], shifts, factor)
+        hr, errs = api.ibp_u8_batched(lr64[None], shifts, psf_kernel, saa.clone(), factor, n_iter, step)
+        return {"native_2x": native, "SAA": saa[0], "SAA_IBP": hr[0], "LR_mean": mean_lr}, [float(e) for e in errs[0].cpu()]
+    lr = api.u8_to_float(lr64) if u8 else lr64.to(api._TORCH_DT[api.get_precision()])  # (row bands run on plans: float frames)
     saa = api.shift_and_add_batched(lr[None], shifts, factor)
     if row_bands:
         from . import rowband
@@ -190,7 +215,7 @@ def register_shifts(frame_sets, shifts):
     import torch
     from . import register
     table = np.asarray(shifts, dtype=np.float64)
-    lr = torch.stack([torch.stack(list(fr)) for fr in frame_sets])
+    lr = _frames_f64(torch.stack([torch.stack(list(fr)) for fr in frame_sets]))  # (srx_register takes float frames)
     est, score, status = register.estimate_shifts(lr, init=table, full=True)
     out = []
     for b in range(len(frame_sets)):
@@ -208,14 +233,18 @@ def reconstruct_batch(frame_sets, shifts, psf_kernel, n_iter, factor=UPSAMPLE_FA
     -> list of (images dict, MSE trace), one per frame set.  lazy_errors: the traces stay device tensors (no wait for the IBP loop
     here; _save_outputs downloads them with the planes)."""
     import torch
-    lr64 = torch.stack([torch.stack(fr) for fr in frame_sets])  # [B, N, h, w] float64
+    lr64 = torch.stack([torch.stack(fr) for fr in frame_sets])  # [B, N, h, w] float64, or uint8 (keep_u8 loaders)
     B, N, h, w = lr64.shape
     with _loader_precision():
-        mean_lr = api.mean_frames_batched(lr64)
-    lr = lr64.to(api._TORCH_DT[api.get_precision()])
+        mean_lr = api.mean_frames_batched(_frames_f64(lr64))
     native = api.zoom_batched(mean_lr, factor)
-    saa = api.shift_and_add_batched(lr, shifts, factor)
-    hr, errs = api.ibp_batched(lr, shifts, psf_kernel, saa.clone(), factor, n_iter, step)
+    if lr64.dtype == torch.uint8:
+        saa = api.shift_and_add_u8_batched(lr64, shifts, factor)
+        hr, errs = api.ibp_u8_batched(lr64, shifts, psf_kernel, saa.clone(), factor, n_iter, step)
+    else:
+        lr = lr64.to(api._TORCH_DT[api.get_precision()])
+        saa = api.shift_and_add_batched(lr, shifts, factor)
+        hr, errs = api.ibp_batched(lr, shifts, psf_kernel, saa.clone(), factor, n_iter, step)
     if not lazy_errors:
         errs = errs.cpu()
     return [({"native_2x": native[i], "SAA": saa[i], "SAA_IBP": hr[i], "LR_mean": mean_lr[i]}, errs[i] if lazy_errors else [float(e) for e in errs[i]])
@@ -380,13 +409,14 @@ def _save_outputs(out_dir, images, errors, lr_name, extra=None):
 
 
 def process_session(session_dir, psf_kernel, output_base, kind=None, n_iter=None, verbose=True, batch_reps=True, loaded=None, flush=True,
-                    row_bands=False, on_images=None, register=False):
+                    row_bands=False, on_images=None, register=False, keep_u8=False):
     """Counterpart of process_session / process_combo.  Returns the list of output directories written
     (empty if everything was already done).  batch_reps: the reps of a barcode session that are still to do go through the
     library in one B = reps call (reconstruct_batch) instead of one call per rep; `loaded`: frames already decoded by a
     Prefetcher (what load_corner_reps / load_mono_cal_session / load_rgb_cal_combo would return).  row_bands (the two cal_target
     kinds: one large image per session): all ranks work on this one session (reconstruct(row_bands=True)), rank 0 writes.
-    register: reconstruct with shifts estimated from the frames (register_shifts) and write registration.json beside the PNGs."""
+    register: reconstruct with shifts estimated from the frames (register_shifts) and write registration.json beside the PNGs.
+    keep_u8 (run_sr --u8-frames): the frames this call loads itself stay uint8 on the device; the files written are the same."""
     kind = kind or detect_kind(session_dir)
     if kind not in IBP_ITERATIONS:
         raise ValueError("kind must be one of " + ", ".join(IBP_ITERATIONS))
@@ -400,7 +430,7 @@ def process_session(session_dir, psf_kernel, output_base, kind=None, n_iter=None
             say(f"  [skip] {name} - already done")
             return written
         if kind == "mono_cal_target":
-            frames, shifts = loaded or load_mono_cal_session(session_dir)
+            frames, shifts = loaded or load_mono_cal_session(session_dir, keep_u8=keep_u8)
             lr_name, extra = "LR_mean.png", None
         else:
             frames, shifts = loaded or load_rgb_cal_combo(session_dir)
@@ -421,7 +451,7 @@ def process_session(session_dir, psf_kernel, output_base, kind=None, n_iter=None
         written.append(out_dir)
         return written
     red = kind == "rgb_barcodes"
-    all_reps, shifts = loaded or load_corner_reps(session_dir, red)
+    all_reps, shifts = loaded or load_corner_reps(session_dir, red, keep_u8=keep_u8)
     todo = []
     for rep_idx, frames in enumerate(all_reps):
         out_dir = os.path.join(output_base, name, f"rep{rep_idx}")
@@ -449,17 +479,18 @@ def process_session(session_dir, psf_kernel, output_base, kind=None, n_iter=None
     return written
 
 
-def load_session(session_dir, kind):
-    """The host + upload half of process_session (what a Prefetcher runs ahead): decoded frames on the device."""
+def load_session(session_dir, kind, keep_u8=False):
+    """The host + upload half of process_session (what a Prefetcher runs ahead): decoded frames on the device.  keep_u8: as uint8 where
+    the kind's frames are the camera's samples (rgb_cal_target averages its reps: float64 either way)."""
     if kind == "mono_cal_target":
-        return load_mono_cal_session(session_dir)
+        return load_mono_cal_session(session_dir, keep_u8=keep_u8)
     if kind == "rgb_cal_target":
         return load_rgb_cal_combo(session_dir)
-    return load_corner_reps(session_dir, kind == "rgb_barcodes")
+    return load_corner_reps(session_dir, kind == "rgb_barcodes", keep_u8=keep_u8)
 
 
 def process_sessions(sessions, psf_kernel, output_base, kind, n_iter=None, verbose=True, rank=0, world=1, on_written=None, row_bands=False,
-                     on_images=None, register=False):
+                     on_images=None, register=False, keep_u8=False):
     """The reference's outer loop (mono_cal_target/run_sr.py:358-360, mono_barcodes/run_sr.py:301) over the sessions this
     rank owns (session i -> rank i mod world, parallel.map_sharded: independent items, no data-path collective), with the PNG
     decode and upload of session k + 1 overlapped with the device work of session k.  -> output directories written: by every
@@ -477,7 +508,7 @@ def process_sessions(sessions, psf_kernel, output_base, kind, n_iter=None, verbo
         name = os.path.basename(os.path.normpath(sessions[i]))
         if kind in ("mono_cal_target", "rgb_cal_target") and os.path.exists(os.path.join(output_base, name, "done.flag")):
             return None  # process_session will skip it: do not decode
-        return load_session(sessions[i], kind)
+        return load_session(sessions[i], kind, keep_u8=keep_u8)
 
     feed = iter(Prefetcher(owned, load))
     count = [0]

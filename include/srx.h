@@ -98,6 +98,8 @@ typedef enum {
 #define SRX_FLAG_DIAG_V1 0x800u                /* per-frame fused path with stand-alone prefilter passes (8 launches / iteration) */
 #define SRX_FLAG_DIAG_SAA_ONE_PASS 0x8000u   /* shift_and_add on a common fraction: the one-kernel form (accumulation over the frames with the
                                               * fractional shift's halo) instead of accumulate + shift (k_saa_tile<ACC> + k_saa_shift); same bits */
+#define SRX_FLAG_DIAG_U8_BYTE_LOADS 0x10000u /* srx_ibp_u8lr_f32, "patch" on a full phase grid: k_patch_build reads the frames one byte per lane also
+                                              * where they start on a 4-byte boundary (default there: whole LR rows as 4-byte words); same bits */
 
 int srx_version(void);
 const char *srx_strerror(int status);
@@ -190,6 +192,38 @@ int srx_ibp_f64(const double *lr, int B, int N, int h, int w, const double *shif
                 int kw, const double *hr_init, int H, int W, int factor, int n_iter, double step, double *hr_out,
                 double *errors_out, void *ws, size_t ws_bytes, srx_stream_t stream, unsigned flags);
 
+/* ---- shift_and_add / ibp on the camera's own samples: load_gray's uint8 frames (run_sr.py:73-75) without the astype(float64) ----
+ * The reference decodes 8-bit PNGs and converts them to float64 before anything else; these entry points take the bytes.  lr is
+ * uint8 [B, N, h, w]; _f32 / _f64 is the type of the state, the output and the arithmetic, as everywhere else.  (T)uint8 is exact, so a
+ * call returns the same bits as srx_saa_* / srx_ibp_* on the converted frames.  Everything else is the float call's: argument checks and
+ * limits (the 2 GiB rule counts the frames as T), flags, chunking of large batches, srx_last_path(), the MSE trace, hr_out == hr_init;
+ * the route is the float call's too (srx_ibp_path_for with elem_bytes = sizeof(T) answers for both).  lr needs byte alignment only (a
+ * frame of odd h w starts on an odd byte).
+ *   mosaic family ("patch", "stile", "ctile", "ztile", "dtile", "atile", "mosaic", and shift_and_add's "mosaic"): the kernels that build
+ *     the tables read the bytes themselves; no converted copy exists anywhere.  shift_and_add converts frames larger than 64 x 64 into a
+ *     plane the float call carves as well.
+ *   "btile", "fused", "composed": the frames of a chunk are converted to T at the front of the workspace and the float driver runs on the
+ *     rest.  These routes serve per-frame fractional shifts -- in the reference those belong to rep-averaged, hence non-integer, frames
+ *     (rgb_cal_target), so no real uint8 workload reaches them; they are there so that the entry points accept every shift table.
+ * Workspace: srx_ibp_u8lr_workspace_bytes_for = srx_ibp_workspace_bytes_for on a mosaic-family route, and that plus
+ * align_up(min(B, 32768) N h w sizeof(T)) (256-byte granules) on the others; srx_ibp_u8lr_workspace_bytes (shape only) covers both.
+ * srx_saa_u8lr_workspace_bytes = srx_saa_workspace_bytes + align_up(Bc N h w sizeof(T)), Bc = the items of one chunk (B, or
+ * max(32768 / N, 1) when B N > 32768), on every route: the query has no shift table to tell them apart. */
+size_t srx_saa_u8lr_workspace_bytes(int elem_bytes, int B, int N, int h, int w, int factor);
+int srx_saa_u8lr_f32(const uint8_t *lr, int B, int N, int h, int w, const double *shifts_yx, int factor, float *out, void *ws,
+                     size_t ws_bytes, srx_stream_t stream, unsigned flags);
+int srx_saa_u8lr_f64(const uint8_t *lr, int B, int N, int h, int w, const double *shifts_yx, int factor, double *out, void *ws,
+                     size_t ws_bytes, srx_stream_t stream, unsigned flags);
+size_t srx_ibp_u8lr_workspace_bytes(int elem_bytes, int B, int N, int h, int w, int H, int W, int factor, unsigned flags);
+size_t srx_ibp_u8lr_workspace_bytes_for(int elem_bytes, int B, int N, int h, int w, int H, int W, int factor, const double *shifts_yx,
+                                        const double *kernel, int kh, int kw, unsigned flags);
+int srx_ibp_u8lr_f32(const uint8_t *lr, int B, int N, int h, int w, const double *shifts_yx, const double *kernel, int kh, int kw,
+                     const float *hr_init, int H, int W, int factor, int n_iter, double step, float *hr_out, double *errors_out, void *ws,
+                     size_t ws_bytes, srx_stream_t stream, unsigned flags);
+int srx_ibp_u8lr_f64(const uint8_t *lr, int B, int N, int h, int w, const double *shifts_yx, const double *kernel, int kh, int kw,
+                     const double *hr_init, int H, int W, int factor, int n_iter, double step, double *hr_out, double *errors_out, void *ws,
+                     size_t ws_bytes, srx_stream_t stream, unsigned flags);
+
 /* ---- the same loop as a PLAN: tables built once, the iterations in several runs, rows of the state readable / replaceable in between ----
  * No reference counterpart (its ibp() is one call); this is what running ONE image on several GPUs needs (second row: row bands
  * with a halo exchange every few iterations, sr_mi355x/rowband.py), and what any caller that iterates in instalments saves: the ~0.5 ms of
@@ -222,6 +256,7 @@ void srx_ibp_plan_destroy(srx_plan_t *plan);
  * decimate:    out[i, j] = in[py + i*f, px + j*f]     `shifted[::f, ::f]` run_sr.py:165;
  *              with f=2, py=px=0 it is extract_red (rgb_cal_target/run_sr.py:73-75).
  *              in [B, H, W] -> out [B, ceil((H-py)/f), ceil((W-px)/f)].
+ *              _u8: the same index map on bytes -- the red plane of a raw Bayer frame stays uint8 (rgb_cal_target/run_sr.py:73-75).
  * zero_insert: out = 0; out[i*f, j*f] = in[i, j] for i*f < H, j*f < W   run_sr.py:170-175.
  *              in [B, eh, ew] -> out [B, H, W].
  * mean_frames: out = sum_r in[r] / R   (np.mean(axis=0)) run_sr.py:274, rgb_cal_target :107-108.
@@ -231,6 +266,7 @@ void srx_ibp_plan_destroy(srx_plan_t *plan);
  */
 int srx_decimate_f32(const float *in, int B, int H, int W, int f, int py, int px, float *out, srx_stream_t stream);
 int srx_decimate_f64(const double *in, int B, int H, int W, int f, int py, int px, double *out, srx_stream_t stream);
+int srx_decimate_u8(const uint8_t *in, int B, int H, int W, int f, int py, int px, uint8_t *out, srx_stream_t stream);
 int srx_zero_insert_f32(const float *in, int B, int eh, int ew, int f, int H, int W, float *out, srx_stream_t stream);
 int srx_zero_insert_f64(const double *in, int B, int eh, int ew, int f, int H, int W, double *out,
                         srx_stream_t stream);
