@@ -480,6 +480,8 @@ static int saa_dispatch(const S *lr_, int B, int N, int h, int w, const double *
     return saa_composed<T>(lrT, B, N, h, w, sh, f, out, ws, wsb, st);
 }
 
+#include "srx_items.hpp"  // one shift table per item: routing by runs on top of the dispatchers above
+
 // ---------------------------------------------------------------------------------------
 // plans: the per-call tables built ONCE, the iterations in several runs, rows of the state readable / replaceable in between
 // (what a row band of a larger image needs: sr_mi355x/rowband.py).  A plan keeps device state in the caller's workspace and a
@@ -762,6 +764,22 @@ size_t srx_ibp_u8lr_workspace_bytes_for(int eb, int B, int N, int h, int w, int 
     return need + u8_stage_bytes(eb, B < SRX_MAX_BATCH_PER_LAUNCH ? (B > 0 ? B : 1) : SRX_MAX_BATCH_PER_LAUNCH, N, h, w);
 }
 
+size_t srx_saa_items_workspace_bytes(int eb, int B, int N, int h, int w, int f) { return items::saa_ws_bound(eb, B, N, h, w, f); }
+size_t srx_ibp_items_workspace_bytes(int eb, int B, int N, int h, int w, int H, int W, int f, unsigned flags)
+{
+    return items::ibp_ws_bound(eb, B, N, h, w, H, W, f, flags);
+}
+/* what THIS call carves: the largest run's need (a per-item "btile" run: its route's plus the tables of its items) */
+size_t srx_ibp_items_workspace_bytes_for(int eb, int B, int N, int h, int w, int H, int W, int f, const double *sh, const double *k, int kh,
+                                         int kw, unsigned flags)
+{
+    if (!sh || !k || N <= 0 || N > SRX_MAX_FRAMES || B <= 0)
+        return srx_ibp_items_workspace_bytes(eb, B, N, h, w, H, W, f, flags);
+    CallFlags cf(flags);
+    const items::IbpPlan p = items::plan_ibp(eb, B, N, h, w, H, W, f, sh, k, kh, kw, flags);
+    return p.status == SRX_OK ? p.need : srx_ibp_items_workspace_bytes(eb, B, N, h, w, H, W, f, flags);
+}
+
 const char *srx_ibp_path_for(int eb, int N, int h, int w, int H, int W, int f, const double *sh, const double *k, int kh, int kw, unsigned flags)
 {
     int dummy = 0;  // (stands for the device pointers: only their presence is checked)
@@ -914,6 +932,20 @@ int srx_psf_estimate_f64(const double *frames, int N, int H, int W, int halfwidt
         CallFlags cf(flags);                                                                                           \
         return ibp_dispatch<T>(lr, B, N, h, w, sh, k, kh, kw, hr_init, H, W, f, n_iter, step, hr_out, errors, ws, wsb, \
                                hs(s), flags);                                                                          \
+    }                                                                                                                  \
+    int srx_saa_items_##SFX(const T *lr, int B, int N, int h, int w, const double *sh, int f, T *out, void *ws,         \
+                            size_t wsb, srx_stream_t s, unsigned flags)                                                \
+    {                                                                                                                  \
+        CallFlags cf(flags);                                                                                           \
+        return items::saa_dispatch_items<T>(lr, B, N, h, w, sh, f, out, ws, wsb, hs(s), flags);                        \
+    }                                                                                                                  \
+    int srx_ibp_items_##SFX(const T *lr, int B, int N, int h, int w, const double *sh, const double *k, int kh, int kw, \
+                            const T *hr_init, int H, int W, int f, int n_iter, double step, T *hr_out, double *errors, \
+                            void *ws, size_t wsb, srx_stream_t s, unsigned flags)                                      \
+    {                                                                                                                  \
+        CallFlags cf(flags);                                                                                           \
+        return items::ibp_dispatch_items<T>(lr, B, N, h, w, sh, k, kh, kw, hr_init, H, W, f, n_iter, step, hr_out,     \
+                                            errors, ws, wsb, hs(s), flags);                                            \
     }                                                                                                                  \
     int srx_saa_u8lr_##SFX(const uint8_t *lr, int B, int N, int h, int w, const double *sh, int f, T *out, void *ws,    \
                            size_t wsb, srx_stream_t s, unsigned flags)                                                 \

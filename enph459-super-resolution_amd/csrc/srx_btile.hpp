@@ -68,6 +68,11 @@ struct BFrame {  // 20 words
     float wyf[4], wxf[4];
     float wyb[4], wxb[4];  // times kq = -6 z each (the recursions run in srx_fused.hpp's scaled form)
 };
+// One table per item (the ITEMS instantiations of the kernels, srx_items.hpp): item b's table lies at frtab + b * frstride and starts with
+// TAB_HDR words oyf_min, oyf_max, oyb_min, oyb_max -- the range of ITS frames' row tap origins, so that every item makes the row-check
+// decisions it makes alone -- followed by its frames' records.  A call whose items share one table keeps the form it had: the records
+// alone in frtab, the ranges and the H-FIR weights in BArgs.
+constexpr int TAB_HDR = 4;
 struct BArgs {
     int N, h, w, H, W, nwx, nwy;
     int oyf_min, oyf_max, oyb_min, oyb_max;  // range of the frames' row tap origins (which blocks need no row checks)
@@ -575,6 +580,17 @@ __global__ void k_btile_params(BArgs A, int *__restrict__ dst)
     for (int i = threadIdx.x; i < MAXF * 20; i += blockDim.x)
         dst[i] = src[i];
 }
+// the tables of a call with one per item: the host's records by value, PARAM_WORDS at a time (a launch's arguments are limited to 4 KiB)
+constexpr int PARAM_WORDS = 960;
+struct ParamWords {
+    int n;
+    int w[PARAM_WORDS];
+};
+__global__ void k_param_words(ParamWords P, int *__restrict__ dst)
+{
+    for (int i = threadIdx.x; i < P.n; i += blockDim.x)
+        dst[i] = P.w[i];
+}
 
 // window geometry shared by the two kernels
 template <int NBY, int NBX> struct Geo {
@@ -587,10 +603,10 @@ template <int NBY, int NBX> struct Geo {
 // =========================================================================================================================
 // forward: err[b, k, i, j] = lr - (F_k P pad B hr)[2 i, 2 j];  epart[b, window] = sum err^2 * scale.  grid (nwx, nwy, B)
 // =========================================================================================================================
-template <int NBY, int NBX, int PSF>  // PSF: 0 = rank 1 (7 + 7 taps); 2, 3 = the 2-D form with a support of 5 x 5 / 7 x 7
+template <int NBY, int NBX, int PSF, bool ITEMS = false>  // PSF: 0 = rank 1 (7 + 7 taps); 2, 3 = the 2-D form with a support of 5 x 5 / 7 x 7
 __global__ void __launch_bounds__(NBY *NBX * 64, SRX_BT_MINB)
     k_ibp_bfwd(const float *__restrict__ S, const float *__restrict__ lr, float *__restrict__ err, BArgs A, const int *__restrict__ frtab,
-               double *__restrict__ epart, double scale)
+               double *__restrict__ epart, double scale, int frstride)  // (frstride last: the other arguments lie where they lay)
 {
     using L = Lds<NBY, NBX>;
     constexpr bool SEP = PSF == 0;
@@ -608,8 +624,13 @@ __global__ void __launch_bounds__(NBY *NBX * 64, SRX_BT_MINB)
     float *edge = lds + L::OFF_EDGE;
     int *frt = reinterpret_cast<int *>(lds + L::OFF_FR);
     double *part = reinterpret_cast<double *>(lds + L::OFF_PART);
+    // ITEMS: this item's table (b is wave-uniform: what is read through ftab directly are scalar loads, and the branches on it stay scalar)
+    const int *ftab = ITEMS ? frtab + b * frstride : frtab;
+    const BFrame *ffr = ITEMS ? reinterpret_cast<const BFrame *>(ftab + TAB_HDR) : nullptr;
     for (int i = tid; i < N * 20; i += L::NT)  // the frame table where a lane can index it
-        frt[i] = frtab[i];
+        frt[i] = ftab[(ITEMS ? TAB_HDR : 0) + i];
+    const int oyf_min = ITEMS ? __builtin_amdgcn_readfirstlane(ftab[0]) : A.oyf_min;
+    const int oyf_max = ITEMS ? __builtin_amdgcn_readfirstlane(ftab[1]) : A.oyf_max;
     const float *zero = lds + L::OFF_ZERO;
     if (!SEP) {
         for (int i = tid; i < 512; i += L::NT)
@@ -676,7 +697,7 @@ __global__ void __launch_bounds__(NBY *NBX * 64, SRX_BT_MINB)
         // owned rows of an interior block: i in [I0, I1) whatever the frame (Ya - Pb and Yb - Pb are even); blocks whose LR rows
         // may leave the image check every row
         constexpr int IA0 = HLO / 2, IB1 = 32 * NBY - HHI / 2 - 32 * (NBY - 1);
-        const bool interior = asr1(Pb - A.oyf_max) >= 0 && asr1(Pb + 1 - A.oyf_min) + 32 <= h;
+        const bool interior = asr1(Pb - oyf_max) >= 0 && asr1(Pb + 1 - oyf_min) + 32 <= h;
         const int rowsel = !interior ? 0 : (s == 0 ? 1 : (s == NBY - 1 ? 2 : 3));
         float lv[32];  // (ONE array for every variant: two would both count as live across the exchange)
 #if SRX_BT_PREFETCH
@@ -695,7 +716,7 @@ __global__ void __launch_bounds__(NBY *NBX * 64, SRX_BT_MINB)
             float w0 = 0.f, w1 = 0.f, w2 = 0.f, w3 = 0.f;
             int par = 0;
             if (kf < N) {
-                const BFrame &f = A.fr[kf];
+                const BFrame &f = ITEMS ? ffr[kf] : A.fr[kf];
                 w0 = f.wxf[0], w1 = f.wxf[1], w2 = f.wxf[2], w3 = f.wxf[3];
                 par = (f.oxf + Xb) & 1;
             }
@@ -775,10 +796,10 @@ __global__ void __launch_bounds__(NBY *NBX * 64, SRX_BT_MINB)
 // backward: hr_out = clip(hr_in + step * B'( crop P ( sum_k F'_k pad U err_k ) ) / N) on the window's owned pixels.
 // grid (nwx, nwy, B).  The window (0, 0) of an item also sums the forward kernel's per-window MSE partials.
 // =========================================================================================================================
-template <int NBY, int NBX, int PSF>
+template <int NBY, int NBX, int PSF, bool ITEMS = false>
 __global__ void __launch_bounds__(NBY *NBX * 64, SRX_BT_MINB)
     k_ibp_bbwd(const float *__restrict__ err, float *__restrict__ S, BArgs A, const int *__restrict__ frtab, const double *__restrict__ epart,
-               double *__restrict__ errors, int errors_stride)
+               double *__restrict__ errors, int errors_stride, int frstride)
 {
     using L = Lds<NBY, NBX>;
     constexpr bool SEP = PSF == 0;
@@ -795,8 +816,12 @@ __global__ void __launch_bounds__(NBY *NBX * 64, SRX_BT_MINB)
     const float *Xup = Xown - NBX * XW, *Xdn = Xown + NBX * XW, *Xlf = Xown - XW, *Xrt = Xown + XW;
     int *frt = reinterpret_cast<int *>(lds + L::OFF_FR);
     double *part = reinterpret_cast<double *>(lds + L::OFF_PART);
+    const int *ftab = ITEMS ? frtab + b * frstride : frtab;  // ITEMS: this item's table, as in k_ibp_bfwd
+    const BFrame *ffr = ITEMS ? reinterpret_cast<const BFrame *>(ftab + TAB_HDR) : nullptr;
     for (int i = tid; i < N * 20; i += L::NT)
-        frt[i] = frtab[i];
+        frt[i] = ftab[(ITEMS ? TAB_HDR : 0) + i];
+    const int oyb_min = ITEMS ? __builtin_amdgcn_readfirstlane(ftab[2]) : A.oyb_min;
+    const int oyb_max = ITEMS ? __builtin_amdgcn_readfirstlane(ftab[3]) : A.oyb_max;
     const float *zero = lds + L::OFF_ZERO;
     if (!SEP) {
         for (int i = tid; i < 512; i += L::NT)
@@ -832,7 +857,7 @@ __global__ void __launch_bounds__(NBY *NBX * 64, SRX_BT_MINB)
     // this pair cover the latency of the next pair's loads)
     float E[34];
     const int w4 = w * 4;
-    const bool lo_ok = asr1(Pb + A.oyb_min - SRX_NPAD) >= 0, hi_ok = asr1(Pb + A.oyb_max + 1 - SRX_NPAD) + 34 <= h;
+    const bool lo_ok = asr1(Pb + oyb_min - SRX_NPAD) >= 0, hi_ok = asr1(Pb + oyb_max + 1 - SRX_NPAD) + 34 <= h;
     auto request = [&](int kp) {
         const int k = 2 * kp + kk;
         const bool kok = k < N;
@@ -915,7 +940,7 @@ __global__ void __launch_bounds__(NBY *NBX * 64, SRX_BT_MINB)
         for (int half = 0; half < 2; half++) {
             const int k = 2 * kp + half;
             if (k < N) {
-                const BFrame &f = A.fr[k];
+                const BFrame &f = ITEMS ? ffr[k] : A.fr[k];
                 const float w0 = f.wxb[0], w1 = f.wxb[1], w2 = f.wxb[2], w3 = f.wxb[3];
                 const int par = (f.oxb + Xb) & 1;
                 if (half == 0) {
@@ -1028,6 +1053,36 @@ static inline size_t ws_bytes(int B, int N, int h, int w, int H, int W)
            align_up(MAXF * 20 * sizeof(int));
 }
 
+// one table per item: N records behind the header, item after item
+static inline int tab_stride(int N) { return TAB_HDR + 20 * N; }
+static inline size_t items_tab_bytes(int B, int N) { return align_up((size_t)B * tab_stride(N) * sizeof(int)); }
+
+// the records of one shift table and the range of their row tap origins: rng = oyf_min, oyf_max, oyb_min, oyb_max
+static inline void make_frames(const double *sh, int N, BFrame *fr, int nfr, int (&rng)[4])
+{
+    const double kq = -6.0 * patch::ZD;
+    rng[0] = rng[2] = 1 << 20, rng[1] = rng[3] = -(1 << 20);
+    for (int q = 0; q < nfr; q++) {
+        BFrame &f = fr[q];
+        f.oyf = f.oxf = f.oyb = f.oxb = 0;
+        for (int i = 0; i < 4; i++)
+            f.wyf[i] = f.wxf[i] = f.wyb[i] = f.wxb[i] = 0.f;
+        if (q >= N)
+            continue;
+        const double dy = sh[2 * q] * 2.0, dx = sh[2 * q + 1] * 2.0;
+        fused::FrameTap<double> tf, tb;
+        fused::make_tap<double>(-dy, -dx, SRX_NPAD, tf);  // forward_model: x = 2 i - d + 12 (srx_fused.hpp)
+        fused::make_tap<double>(+dy, +dx, 0, tb);         // back_project: the padded FIR reads Z[p + floor(d) - 1 + a]
+        f.oyf = tf.oy, f.oxf = tf.ox, f.oyb = tb.oy, f.oxb = tb.ox;
+        rng[0] = std::min(rng[0], f.oyf), rng[1] = std::max(rng[1], f.oyf);
+        rng[2] = std::min(rng[2], f.oyb), rng[3] = std::max(rng[3], f.oyb);
+        for (int i = 0; i < 4; i++) {
+            f.wyf[i] = (float)tf.wy[i], f.wxf[i] = (float)tf.wx[i];
+            f.wyb[i] = (float)(kq * tb.wy[i]), f.wxb[i] = (float)(kq * tb.wx[i]);
+        }
+    }
+}
+
 // Window shape: 2 x 2 waves (128 x 128 padded coordinates, 96 x 96 owned: 1.78x recompute), two or three workgroups per CU.  Measured
 // against 2 x 4 (128 x 256, 96 x 224 owned, 1.52x recompute, ONE workgroup of eight waves per CU) on 1536 x 2048: one frame 48.3
 // against 44.4 us per iteration, eight frames 211 against 185 -- eight waves that meet at every barrier wait for their slowest,
@@ -1035,9 +1090,12 @@ static inline size_t ws_bytes(int B, int N, int h, int w, int H, int W)
 // six waves: every window a compute unit of its own on one frame, tools/dev/bt_shape_ab.sh): one frame 2.087 / 2.16 against 2.06 ms per
 // step, eight frames 11.5 / 12.1 against 9.6, measured PSF 2.46 / 2.49 against 2.42 -- the six waves' barriers cost more than the idle
 // compute units.  The shape is fixed (SRX_BT_NBY x SRX_BT_NBX), so a batch gives every item the bits it gets alone.
+// per_item: sh is [B][N][2], one table per item.  The host builds every item's records with make_frames (the weights an item gets are the
+// ones it gets alone by construction) and ceil(B * tab_stride(N) / PARAM_WORDS) launches of k_param_words carry them to the device; the
+// workspace holds items_tab_bytes(B, N) more.
 template <int NBY, int NBX>
-static int ibp_t(const float *lr, int B, int N, int h, int w, const double *sh, const double *k, int kh, int kw, const float *hr_init, int H,
-                 int W, int n_iter, double step, float *hr, double *errors, void *ws, size_t wsb, hipStream_t st)
+static int ibp_t(const float *lr, int B, int N, int h, int w, const double *sh, bool per_item, const double *k, int kh, int kw,
+                 const float *hr_init, int H, int W, int n_iter, double step, float *hr, double *errors, void *ws, size_t wsb, hipStream_t st)
 {
     const int Hp = H + 2 * SRX_NPAD, Wp = W + 2 * SRX_NPAD;
     BArgs A;
@@ -1049,7 +1107,8 @@ static int ibp_t(const float *lr, int B, int N, int h, int w, const double *sh, 
     double *epart = ar.take<double>((size_t)B * A.nwy * A.nwx);
     const int H4 = (H + 3) / 4;
     float *S = ar.take<float>((size_t)B * H4 * W * 4);  // the state plane, four rows interleaved
-    int *frtab = ar.take<int>(MAXF * 20);
+    const int frstride = per_item ? tab_stride(N) : 0;
+    int *frtab = ar.take<int>(per_item ? (size_t)B * frstride : (size_t)(MAXF * 20));
     if (!ar.ok)
         return SRX_E_WORKSPACE;
     if (A.nwy > 65535 || B > 65535 || H4 > 65535)
@@ -1079,43 +1138,64 @@ static int ibp_t(const float *lr, int B, int N, int h, int w, const double *sh, 
             A.k2f[8 * v + q] = uu < 0 ? 0.f : (float)(kq * kq * (double)kc.k[7 * v + uu]);
             A.k2b[8 * v + q] = uu < 0 ? 0.f : kt.k[7 * v + uu];
         }
-    A.oyf_min = A.oyb_min = 1 << 20, A.oyf_max = A.oyb_max = -(1 << 20);
-    for (int q = 0; q < MAXF; q++) {
-        BFrame &f = A.fr[q];
-        f.oyf = f.oxf = f.oyb = f.oxb = 0;
-        for (int i = 0; i < 4; i++)
-            f.wyf[i] = f.wxf[i] = f.wyb[i] = f.wxb[i] = 0.f;
-        if (q >= N)
-            continue;
-        const double dy = sh[2 * q] * 2.0, dx = sh[2 * q + 1] * 2.0;
-        fused::FrameTap<double> tf, tb;
-        fused::make_tap<double>(-dy, -dx, SRX_NPAD, tf);  // forward_model: x = 2 i - d + 12 (srx_fused.hpp)
-        fused::make_tap<double>(+dy, +dx, 0, tb);         // back_project: the padded FIR reads Z[p + floor(d) - 1 + a]
-        f.oyf = tf.oy, f.oxf = tf.ox, f.oyb = tb.oy, f.oxb = tb.ox;
-        A.oyf_min = std::min(A.oyf_min, f.oyf), A.oyf_max = std::max(A.oyf_max, f.oyf);
-        A.oyb_min = std::min(A.oyb_min, f.oyb), A.oyb_max = std::max(A.oyb_max, f.oyb);
-        for (int i = 0; i < 4; i++) {
-            f.wyf[i] = (float)tf.wy[i], f.wxf[i] = (float)tf.wx[i];
-            f.wyb[i] = (float)(kq * tb.wy[i]), f.wxb[i] = (float)(kq * tb.wx[i]);
-        }
-    }
+    int rng[4];
+    make_frames(sh, N, A.fr, MAXF, rng);  // (per item: the first item's, which the ITEMS kernels do not read)
+    A.oyf_min = rng[0], A.oyf_max = rng[1], A.oyb_min = rng[2], A.oyb_max = rng[3];
     const size_t P = (size_t)B * H * W;
     if (n_iter == 0 && hr != hr_init && hipMemcpyAsync(hr, hr_init, P * sizeof(float), hipMemcpyDeviceToDevice, st) != hipSuccess)
         return SRX_E_HIP;
     const double scale = 1.0 / ((double)h * (double)w) / (double)N;
     if (n_iter == 0)
         return SRX_OK;
-    hipLaunchKernelGGL(k_btile_params, dim3(1), dim3(64), 0, st, A, frtab);
-    SRX_CHECK_LAUNCH();
+    if (!per_item) {
+        hipLaunchKernelGGL(k_btile_params, dim3(1), dim3(64), 0, st, A, frtab);
+        SRX_CHECK_LAUNCH();
+    } else {
+        ParamWords pw = {};  // (what lies past n travels too)
+        const size_t total = (size_t)B * frstride;
+        size_t sent = 0;
+        auto flush = [&]() -> int {
+            hipLaunchKernelGGL(k_param_words, dim3(1), dim3(256), 0, st, pw, frtab + sent);
+            SRX_CHECK_LAUNCH();
+            sent += pw.n, pw.n = 0;
+            return SRX_OK;
+        };
+        auto put = [&](const int *src, int n) -> int {
+            for (int i = 0; i < n; i++) {
+                pw.w[pw.n++] = src[i];
+                if (pw.n == PARAM_WORDS)
+                    SRX_TRY(flush());
+            }
+            return SRX_OK;
+        };
+        for (int b = 0; b < B; b++) {
+            BFrame fr[MAXF];
+            make_frames(sh + (size_t)b * 2 * N, N, fr, N, rng);
+            SRX_TRY(put(rng, TAB_HDR));
+            SRX_TRY(put(reinterpret_cast<const int *>(fr), 20 * N));
+        }
+        if (pw.n)
+            SRX_TRY(flush());
+        if (sent != total)
+            return SRX_E_INVALID;
+    }
     const dim3 cgrid(cdiv(W, 256), H4, B);
     hipLaunchKernelGGL(k_btile_copy_in, cgrid, dim3(256), 0, st, hr_init, H, W, H4, S);
     SRX_CHECK_LAUNCH();
     const dim3 grid(A.nwx, A.nwy, B), gridb(cdiv(Wp, Geo<NBY, NBX>::OWBX), cdiv(Hp, Geo<NBY, NBX>::OWBY), B), blk(NBY * NBX * 64);
     for (int it = 0; it < n_iter; it++) {
-#define SRX_BT_ITER(P_)                                                                                                                        \
-    do {                                                                                                                                       \
-        SRX_LAUNCH(KID_IBP_BFWD, (k_ibp_bfwd<NBY, NBX, P_>), grid, blk, 0, st, S, lr, err, A, frtab, errors ? epart : nullptr, scale);          \
-        SRX_LAUNCH(KID_IBP_BBWD, (k_ibp_bbwd<NBY, NBX, P_>), gridb, blk, 0, st, err, S, A, frtab, epart, errors ? errors + it : nullptr, n_iter); \
+#define SRX_BT_ITER2(P_, I_)                                                                                                                          \
+    do {                                                                                                                                              \
+        SRX_LAUNCH(KID_IBP_BFWD, (k_ibp_bfwd<NBY, NBX, P_, I_>), grid, blk, 0, st, S, lr, err, A, frtab, errors ? epart : nullptr, scale, frstride);   \
+        SRX_LAUNCH(KID_IBP_BBWD, (k_ibp_bbwd<NBY, NBX, P_, I_>), gridb, blk, 0, st, err, S, A, frtab, epart, errors ? errors + it : nullptr, n_iter, \
+                   frstride);                                                                                                                         \
+    } while (0)
+#define SRX_BT_ITER(P_)            \
+    do {                           \
+        if (per_item)              \
+            SRX_BT_ITER2(P_, true); \
+        else                       \
+            SRX_BT_ITER2(P_, false); \
     } while (0)
         if (psf_form == 0)
             SRX_BT_ITER(0);
@@ -1124,6 +1204,7 @@ static int ibp_t(const float *lr, int B, int N, int h, int w, const double *sh, 
         else
             SRX_BT_ITER(3);
 #undef SRX_BT_ITER
+#undef SRX_BT_ITER2
     }
     hipLaunchKernelGGL(k_btile_copy_out, cgrid, dim3(256), 0, st, S, H, W, H4, hr);
     SRX_CHECK_LAUNCH();
@@ -1133,7 +1214,14 @@ static int ibp_t(const float *lr, int B, int N, int h, int w, const double *sh, 
 static int ibp(const float *lr, int B, int N, int h, int w, const double *sh, const double *k, int kh, int kw, const float *hr_init, int H,
                int W, int n_iter, double step, float *hr, double *errors, void *ws, size_t wsb, hipStream_t st)
 {
-    return ibp_t<SRX_BT_NBY, SRX_BT_NBX>(lr, B, N, h, w, sh, k, kh, kw, hr_init, H, W, n_iter, step, hr, errors, ws, wsb, st);
+    return ibp_t<SRX_BT_NBY, SRX_BT_NBX>(lr, B, N, h, w, sh, false, k, kh, kw, hr_init, H, W, n_iter, step, hr, errors, ws, wsb, st);
+}
+
+// one table per item: sh is [B][N][2], every item routed to "btile" (srx_items.hpp)
+static int ibp_items(const float *lr, int B, int N, int h, int w, const double *sh, const double *k, int kh, int kw, const float *hr_init, int H,
+                     int W, int n_iter, double step, float *hr, double *errors, void *ws, size_t wsb, hipStream_t st)
+{
+    return ibp_t<SRX_BT_NBY, SRX_BT_NBX>(lr, B, N, h, w, sh, true, k, kh, kw, hr_init, H, W, n_iter, step, hr, errors, ws, wsb, st);
 }
 
 }  // namespace btile

@@ -1,0 +1,289 @@
+// srx_items.hpp -- one shift table PER ITEM of a batch (srx_saa_items_*, srx_ibp_items_*).  Included from srx_api.hip behind the
+// dispatchers of the shared-table calls: everything here is routing on the host plus the two per-item forms of kernels that exist.
+//
+// Registration measures a table per item (srx_register_* returns [B, N, 2]); the shared-table calls made such a caller leave the batch.
+// Here the driver walks the batch in maximal RUNS of consecutive items:
+//   - items that all route to "btile" (their tables may all differ): one batch through btile::ibp_items -- the ITEMS instantiations of
+//     k_ibp_bfwd / k_ibp_bbwd take the table of item b at frtab + b * stride, each with the range of ITS row tap origins in front of it;
+//   - any other run of bytewise-equal tables: the existing driver of its route, as a batch of the run's length (every table equal: this is
+//     the shared-table call, launch for launch);
+//   - items on "fused" / "composed" with pairwise different tables therefore run one by one.
+// shift_and_add does the same with "fused" in the place of "btile" (k_fir_pad_items reads the tap of (item, frame) from a device table).
+// The route of a table is decided once per DISTINCT table, on the host, before anything is queued; so is every refusal.
+//
+// The table's way to the device: the host builds every item's records with the code of the shared-table call (btile::make_frames,
+// fused::make_tap) and btile::k_param_words carries them, PARAM_WORDS = 960 words by value per launch: an ibp run of n items makes
+// ceil(n (4 + 20 N) / 960) such launches (N = 4: one per 11 items), a shift_and_add run ceil(n N sizeof(FrameTap<T>) / 3840).
+#pragma once
+#include <string>
+#include <unordered_map>
+#include <vector>
+
+namespace items {
+
+// which table every item has: id[b] indexes the distinct tables in order of first appearance; first[i] is the item that brought table i
+struct Tables {
+    std::vector<int> id, first;
+};
+static Tables distinct_tables(const double *sh, int B, int N)
+{
+    Tables t;
+    t.id.resize(B);
+    const size_t bytes = (size_t)2 * N * sizeof(double);
+    std::unordered_map<std::string, int> seen;
+    for (int b = 0; b < B; b++) {
+        const char *p = reinterpret_cast<const char *>(sh + (size_t)b * 2 * N);
+        if (b > 0 && memcmp(p, p - bytes, bytes) == 0) {
+            t.id[b] = t.id[b - 1];
+            continue;
+        }
+        const auto it = seen.emplace(std::string(p, bytes), (int)t.first.size());
+        if (it.second)
+            t.first.push_back(b);
+        t.id[b] = it.first->second;
+    }
+    return t;
+}
+
+struct Run {
+    int b0, n, table;
+    bool per_item;  // the per-item form of the run's route; else `n` items that share table `table`
+};
+
+// maximal runs: consecutive items whose route is the one with a per-item form (`batched[table]`), at most `cap` of them; else equal tables
+static std::vector<Run> make_runs(const Tables &t, const std::vector<char> &batched, int B, int cap)
+{
+    std::vector<Run> runs;
+    for (int b = 0; b < B;) {
+        int e = b + 1;
+        bool equal = true;
+        if (batched[t.id[b]]) {
+            for (; e < B && e - b < cap && batched[t.id[e]]; e++)
+                equal = equal && t.id[e] == t.id[b];
+        } else {
+            for (; e < B && t.id[e] == t.id[b]; e++) {
+            }
+        }
+        runs.push_back({b, e - b, t.id[b], batched[t.id[b]] && !equal});
+        b = e;
+    }
+    return runs;
+}
+
+static inline const char *common_name(const char *have, const char *name) { return !have || strcmp(have, name) == 0 ? name : "mixed"; }
+
+// ---------------------------------------------------------------------------------------
+// ibp
+// ---------------------------------------------------------------------------------------
+struct IbpPlan {
+    int status;
+    std::vector<Route> route;  // per distinct table
+    std::vector<Run> runs;
+    size_t need;
+    const char *name;
+};
+
+static IbpPlan plan_ibp(int eb, int B, int N, int h, int w, int H, int W, int f, const double *sh, const double *k, int kh, int kw, unsigned flags)
+{
+    IbpPlan p;
+    p.status = SRX_OK, p.need = 0, p.name = nullptr;
+    const Tables t = distinct_tables(sh, B, N);
+    std::vector<char> batched;
+    for (int b : t.first) {
+        p.route.push_back(route_ibp(eb, N, h, w, H, W, f, sh + (size_t)b * 2 * N, k, kh, kw, flags));
+        batched.push_back(p.route.back().path == PATH_BTILE);
+        if (p.route.back().status != SRX_OK && p.status == SRX_OK)
+            p.status = p.route.back().status;
+    }
+    if (p.status != SRX_OK)
+        return p;
+    p.runs = make_runs(t, batched, B, SRX_MAX_BATCH_PER_LAUNCH);
+    for (const Run &r : p.runs) {
+        size_t need = ibp_need(p.route[r.table], eb, r.n, N, h, w, H, W, f, flags);
+        if (r.per_item)
+            need += btile::items_tab_bytes(r.n, N);
+        p.need = need > p.need ? need : p.need;
+        p.name = common_name(p.name, p.route[r.table].name);
+    }
+    return p;
+}
+
+static size_t ibp_ws_bound(int eb, int B, int N, int h, int w, int H, int W, int f, unsigned flags)
+{
+    const int Bc = B < SRX_MAX_BATCH_PER_LAUNCH ? (B > 0 ? B : 1) : SRX_MAX_BATCH_PER_LAUNCH;
+    return srx_ibp_workspace_bytes(eb, B, N, h, w, H, W, f, flags) + btile::items_tab_bytes(Bc, N > 0 ? N : 1);
+}
+
+template <typename T>
+static int ibp_dispatch_items(const T *lr, int B, int N, int h, int w, const double *sh, const double *k, int kh, int kw, const T *hr_init, int H,
+                              int W, int f, int n_iter, double step, T *hr, double *errors, void *ws, size_t wsb, hipStream_t st, unsigned flags)
+{
+    if (!basic_ibp_args_ok(lr, B, N, h, w, sh, k, kh, kw, hr_init, H, W, f, n_iter, hr))
+        return SRX_E_INVALID;
+    if (N > SRX_MAX_FRAMES || kh * kw > SRX_MAX_KERNEL_TAPS || !plane_fits(sizeof(T), N, h, w, H, W))
+        return SRX_E_UNSUPPORTED;
+    const IbpPlan p = plan_ibp((int)sizeof(T), B, N, h, w, H, W, f, sh, k, kh, kw, flags);
+    if (p.status != SRX_OK)
+        return p.status;
+    if (ws_short(ws, wsb, p.need))
+        return SRX_E_WORKSPACE;
+    g_last_path = p.name;
+    const size_t fr = (size_t)N * h * w, P = (size_t)H * W;
+    for (const Run &r : p.runs) {
+        const double *shr = sh + (size_t)r.b0 * 2 * N;
+        const Route &rt = p.route[r.table];
+        if (r.per_item) {
+            if constexpr (sizeof(T) == 4)
+                SRX_TRY(btile::ibp_items(lr + r.b0 * fr, r.n, N, h, w, shr, k, kh, kw, hr_init + r.b0 * P, H, W, n_iter, step, hr + r.b0 * P,
+                                         errors ? errors + (size_t)r.b0 * n_iter : nullptr, ws, wsb, st));
+            else
+                return SRX_E_INVALID;  // (route_ibp gives float32 calls alone this path)
+            continue;
+        }
+        for (int b0 = r.b0; b0 < r.b0 + r.n; b0 += SRX_MAX_BATCH_PER_LAUNCH) {  // as ibp_dispatch
+            const int bc = r.b0 + r.n - b0 < SRX_MAX_BATCH_PER_LAUNCH ? r.b0 + r.n - b0 : SRX_MAX_BATCH_PER_LAUNCH;
+            SRX_TRY((ibp_run<T, T>(rt, lr + b0 * fr, bc, N, h, w, shr, k, kh, kw, hr_init + b0 * P, H, W, f, n_iter, step, hr + b0 * P,
+                                   errors ? errors + (size_t)b0 * n_iter : nullptr, ws, wsb, st)));
+        }
+    }
+    return SRX_OK;
+}
+
+// ---------------------------------------------------------------------------------------
+// shift_and_add
+// ---------------------------------------------------------------------------------------
+// k_fir_pad (srx_fused.hpp) with the tap of (item blockIdx.z, frame q) read from a device table [B][N]; the arithmetic is k_fir_pad's
+// statement for statement (contraction is decided per statement: the same statements round the same way)
+template <typename T, bool ACC>
+__global__ void __launch_bounds__(256)
+    k_fir_pad_items(const T *__restrict__ up, int H, int W, const fused::FrameTap<T> *__restrict__ tab, int N, int q, T *__restrict__ vpad)
+{
+    const int Hp = H + 2 * SRX_NPAD, Wp = W + 2 * SRX_NPAD;
+    const int qx = blockIdx.x * 64 + threadIdx.x, p = blockIdx.y * 4 + threadIdx.y, b = blockIdx.z;
+    if (p >= Hp || qx >= Wp)
+        return;
+    const fused::FrameTap<T> ft = tab[(size_t)b * N + q];
+    const T *u = up + (size_t)b * H * W;
+    T acc = 0;
+#pragma unroll
+    for (int a = 0; a < 4; a++) {
+        const int y = min(max(p + ft.oy + a - SRX_NPAD, 0), H - 1);
+        T racc = 0;
+#pragma unroll
+        for (int c = 0; c < 4; c++) {
+            const int x = min(max(qx + ft.ox + c - SRX_NPAD, 0), W - 1);
+            racc += ft.wx[c] * u[(size_t)y * W + x];
+        }
+        acc += ft.wy[a] * racc;
+    }
+    T *o = vpad + (size_t)b * Hp * Wp + (size_t)p * Wp + qx;
+    *o = ACC ? *o + acc : acc;
+}
+
+template <typename T> static inline size_t saa_tab_bytes(int B, int N) { return align_up((size_t)B * N * sizeof(fused::FrameTap<T>)); }
+
+static inline int saa_cap(int N) { return SRX_MAX_BATCH_PER_LAUNCH / N > 0 ? SRX_MAX_BATCH_PER_LAUNCH / N : 1; }
+
+static size_t saa_ws_bound(int eb, int B, int N, int h, int w, int f)
+{
+    const int n = N > 0 ? N : 1, cap = saa_cap(n), Bc = B < cap ? (B > 0 ? B : 1) : cap;
+    return srx_saa_workspace_bytes(eb, B, N, h, w, f) + (eb == 4 ? saa_tab_bytes<float>(Bc, n) : saa_tab_bytes<double>(Bc, n));
+}
+
+// fused::saa with one table per item: sh [B][N][2]; tab: B * N taps of device memory
+template <typename T>
+static int saa_fused_items(const T *lr, int B, int N, int h, int w, const double *sh, int f, T *out, fused::FrameTap<T> *tab, void *ws, size_t wsb,
+                           hipStream_t st)
+{
+    using namespace fused;
+    static_assert(sizeof(FrameTap<T>) % sizeof(int) == 0, "the taps travel as words");
+    if ((long)B * N > 65535)
+        return SRX_E_UNSUPPORTED;
+    const int H = h * f, W = w * f, Hp = H + 2 * SRX_NPAD, Wp = W + 2 * SRX_NPAD;
+    Arena ar(ws, wsb);
+    T *coef = ar.take<T>((size_t)B * N * h * w), *cscr = ar.take<T>((size_t)B * N * h * w);
+    T *up = ar.take<T>((size_t)B * H * W);
+    T *pad = ar.take<T>((size_t)B * Hp * Wp), *scr = ar.take<T>((size_t)B * Hp * Wp);
+    AxisTap<T> *zy = ar.take<AxisTap<T>>(H), *zx = ar.take<AxisTap<T>>(W);
+    if (!ar.ok)
+        return SRX_E_WORKSPACE;
+    {
+        btile::ParamWords pw = {};
+        int *dst = reinterpret_cast<int *>(tab);
+        constexpr int TW = (int)(sizeof(FrameTap<T>) / sizeof(int));
+        for (size_t i = 0; i < (size_t)B * N; i++) {
+            FrameTap<T> ft;
+            memset(&ft, 0, sizeof ft);
+            make_tap<T>(-sh[2 * i] * f, -sh[2 * i + 1] * f, 0, ft);  // shift(+d): out[r] = in[r - d]
+            int words[TW];
+            memcpy(words, &ft, sizeof ft);
+            for (int j = 0; j < TW; j++) {
+                pw.w[pw.n++] = words[j];
+                if (pw.n == btile::PARAM_WORDS || (j == TW - 1 && i + 1 == (size_t)B * N)) {
+                    hipLaunchKernelGGL(btile::k_param_words, dim3(1), dim3(256), 0, st, pw, dst);
+                    SRX_CHECK_LAUNCH();
+                    dst += pw.n, pw.n = 0;
+                }
+            }
+        }
+    }
+    SRX_TRY(prefilter2d_from(lr, coef, cscr, B * N, h, w, MODE_MIRROR, st));
+    const double zy_ = H > 1 ? (double)(h - 1) / (double)(H - 1) : 1.0;
+    const double zx_ = W > 1 ? (double)(w - 1) / (double)(W - 1) : 1.0;
+    SRX_TRY(build_taps(zy, H, h, TAP_ZOOM, 1, zy_, st));
+    SRX_TRY(build_taps(zx, W, w, TAP_ZOOM, 1, zx_, st));
+    for (int q = 0; q < N; q++) {
+        SRX_TRY(interp_strided(coef + (size_t)q * h * w, (size_t)N * h * w, B, h, w, zy, zx, H, W, up, st));
+        const dim3 grd(cdiv(Wp, 64), cdiv(Hp, 4), B), blk(64, 4);
+        if (q == 0)
+            SRX_LAUNCH(KID_FIR_PAD, (k_fir_pad_items<T, false>), grd, blk, 0, st, up, H, W, tab, N, q, pad);
+        else
+            SRX_LAUNCH(KID_FIR_PAD, (k_fir_pad_items<T, true>), grd, blk, 0, st, up, H, W, tab, N, q, pad);
+    }
+    SRX_TRY(prefilter2d_fast(pad, scr, B, Hp, Wp, MODE_REFLECT, st));
+    SRX_LAUNCH(KID_CROP_DIV, k_crop_div<T>, dim3(cdiv(W, 64), cdiv(H, 4), B), dim3(64, 4), 0, st, pad, H, W, (T)N, out);
+    return SRX_OK;
+}
+
+template <typename T>
+static int saa_dispatch_items(const T *lr, int B, int N, int h, int w, const double *sh, int f, T *out, void *ws, size_t wsb, hipStream_t st,
+                              unsigned flags)
+{
+    if (!lr || !sh || !out || B <= 0 || N <= 0 || h <= 0 || w <= 0 || f <= 0)
+        return SRX_E_INVALID;
+    if (N > SRX_MAX_FRAMES || (size_t)h * f >= ((size_t)1 << 30) || (size_t)w * f >= ((size_t)1 << 30) || !plane_fits(sizeof(T), N, h, w, h * f, w * f))
+        return SRX_E_UNSUPPORTED;
+    // the route of every distinct table (saa_dispatch's decision), and every refusal, before anything is queued
+    const Tables t = distinct_tables(sh, B, N);
+    std::vector<char> batched;
+    for (int b : t.first) {
+        const double *s = sh + (size_t)b * 2 * N;
+        const bool can_fuse = fused::saa_eligible(N, h, w, s, f);
+        if ((flags & SRX_FLAG_FUSED) && !can_fuse)
+            return SRX_E_UNSUPPORTED;
+        const bool fuse = can_fuse && !(flags & SRX_FLAG_COMPOSED);
+        batched.push_back(fuse && !(!(flags & SRX_FLAG_PER_FRAME) && mosaic::saa_eligible(N, h, w, s, f)));
+    }
+    if (ws_short(ws, wsb, saa_ws_bound((int)sizeof(T), B, N, h, w, f)))
+        return SRX_E_WORKSPACE;
+    const int cap = saa_cap(N);
+    const size_t tabb = saa_tab_bytes<T>(B < cap ? B : cap, N);
+    fused::FrameTap<T> *tab = reinterpret_cast<fused::FrameTap<T> *>(ws);
+    void *wsr = (char *)ws + tabb;
+    const size_t wsrb = wsb - tabb;
+    const size_t fr = (size_t)N * h * w, P = (size_t)h * f * w * f;
+    const char *name = nullptr;
+    for (const Run &r : make_runs(t, batched, B, cap)) {
+        const double *shr = sh + (size_t)r.b0 * 2 * N;
+        if (r.per_item) {
+            g_last_path = "fused";
+            SRX_TRY(saa_fused_items<T>(lr + r.b0 * fr, r.n, N, h, w, shr, f, out + r.b0 * P, tab, wsr, wsrb, st));
+        } else
+            SRX_TRY((saa_dispatch<T, T>(lr + r.b0 * fr, r.n, N, h, w, shr, f, out + r.b0 * P, wsr, wsrb, st, flags)));
+        name = common_name(name, g_last_path);
+    }
+    g_last_path = name;
+    return SRX_OK;
+}
+
+}  // namespace items

@@ -32,6 +32,8 @@ _TYPED = {
     "srx_saa_{T}": (_I, [_P, _I, _I, _I, _I, _HD, _I, _P, _P, _Z, _P, _U]),
     "srx_ibp_{T}": (_I, [_P, _I, _I, _I, _I, _HD, _HD, _I, _I, _P, _I, _I, _I, _I, _D, _P, _P, _P, _Z, _P, _U]),
     "srx_saa_u8lr_{T}": (_I, [_P, _I, _I, _I, _I, _HD, _I, _P, _P, _Z, _P, _U]),
+    "srx_saa_items_{T}": (_I, [_P, _I, _I, _I, _I, _HD, _I, _P, _P, _Z, _P, _U]),
+    "srx_ibp_items_{T}": (_I, [_P, _I, _I, _I, _I, _HD, _HD, _I, _I, _P, _I, _I, _I, _I, _D, _P, _P, _P, _Z, _P, _U]),
     "srx_ibp_u8lr_{T}": (_I, [_P, _I, _I, _I, _I, _HD, _HD, _I, _I, _P, _I, _I, _I, _I, _D, _P, _P, _P, _Z, _P, _U]),
     "srx_decimate_{T}": (_I, [_P, _I, _I, _I, _I, _I, _I, _P, _P]),
     "srx_zero_insert_{T}": (_I, [_P, _I, _I, _I, _I, _I, _I, _P, _P]),
@@ -69,6 +71,9 @@ _PLAIN = {
     "srx_saa_u8lr_workspace_bytes": (_Z, [_I, _I, _I, _I, _I, _I]),
     "srx_ibp_u8lr_workspace_bytes": (_Z, [_I, _I, _I, _I, _I, _I, _I, _I, _U]),
     "srx_ibp_u8lr_workspace_bytes_for": (_Z, [_I, _I, _I, _I, _I, _I, _I, _I, _HD, _HD, _I, _I, _U]),
+    "srx_saa_items_workspace_bytes": (_Z, [_I, _I, _I, _I, _I, _I]),
+    "srx_ibp_items_workspace_bytes": (_Z, [_I, _I, _I, _I, _I, _I, _I, _I, _U]),
+    "srx_ibp_items_workspace_bytes_for": (_Z, [_I, _I, _I, _I, _I, _I, _I, _I, _HD, _HD, _I, _I, _U]),
     "srx_decimate_u8": (_I, [_P, _I, _I, _I, _I, _I, _I, _P, _P]),
     "srx_ibp_path_for": (_c.c_char_p, [_I, _I, _I, _I, _I, _I, _I, _HD, _HD, _I, _I, _U]),
     "srx_ibp_plan_workspace_bytes": (_Z, [_I, _I, _I, _I, _I, _I, _I, _I, _U]),

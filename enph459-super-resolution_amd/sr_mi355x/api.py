@@ -110,6 +110,25 @@ def _host_f64(a, shape=None):
     return a, a.ctypes.data_as(_lib._HD)
 
 
+def _shape4(x, what):
+    """(B, N, h, w) of a frame stack before it is moved anywhere"""
+    shp = tuple(x.shape) if hasattr(x, "shape") else np.shape(x)
+    if len(shp) != 4:
+        raise ValueError(f"{what} must have 4 dimensions [B, N, h, w]")
+    return tuple(int(v) for v in shp)
+
+
+def _shift_tables(shifts_yx, B, N):
+    """shifts_yx [N, 2] (one table shared by the batch) or [B, N, 2] (one per item: the *_items_* entry points) ->
+    (array, ctypes pointer, per_item); any other shape is a ValueError."""
+    a = np.ascontiguousarray(np.asarray(shifts_yx, dtype=np.float64))
+    if a.shape == (N, 2):
+        return a, a.ctypes.data_as(_lib._HD), False
+    if a.shape == (B, N, 2):
+        return a, a.ctypes.data_as(_lib._HD), True
+    raise ValueError(f"shifts_yx must have shape {(N, 2)} or {(B, N, 2)}, not {a.shape}")
+
+
 def _ws(nbytes):
     t = torch.empty(max(int(nbytes), 256), dtype=torch.uint8, device=_device())
     return t, ctypes.c_void_p(t.data_ptr()), ctypes.c_size_t(t.numel())
@@ -193,15 +212,16 @@ def back_project_batched(error_lr, kernel, shift_yx, factor, hr_shape, precision
 
 
 def shift_and_add_batched(lr, shifts_yx, factor=2, precision=None, flags=FLAG_AUTO):
-    """lr [B, N, h, w] -> [B, h*f, w*f]."""
+    """lr [B, N, h, w] -> [B, h*f, w*f].  shifts_yx [N, 2], or [B, N, 2] for one table per item (srx_saa_items_*)."""
     prec = precision or get_precision()
+    B, N, h, w = _shape4(lr, "lr")
+    sh, shp, per_item = _shift_tables(shifts_yx, B, N)
     x, _ = _to_dev(lr, prec)
-    B, N, h, w = x.shape
     f = int(factor)
-    sh, shp = _host_f64(shifts_yx, (N, 2))
     out = torch.empty((B, h * f, w * f), dtype=x.dtype, device=x.device)
-    wt, wp, wn = _ws(_lib.load().srx_saa_workspace_bytes(_ELEM[prec], B, N, h, w, f))
-    _lib.check(_fn("srx_saa", prec)(_p(x), B, N, h, w, shp, f, _p(out), wp, wn, _stream(), flags), "srx_saa")
+    name = "srx_saa_items" if per_item else "srx_saa"
+    wt, wp, wn = _ws(getattr(_lib.load(), name + "_workspace_bytes")(_ELEM[prec], B, N, h, w, f))
+    _lib.check(_fn(name, prec)(_p(x), B, N, h, w, shp, f, _p(out), wp, wn, _stream(), flags), name)
     return out
 
 
@@ -209,17 +229,19 @@ def ibp_batched(lr, shifts_yx, kernel, hr_init, factor=2, n_iter=80, step=0.5, p
                 want_errors=True, out=None, exact_workspace=True):
     """lr [B, N, h, w], hr_init [B, H, W] -> (hr [B, H, W], errors float64 [B, n_iter] or None).
     `exact_workspace=False` sizes the arena by the shape-only bound (srx_ibp_workspace_bytes), as a caller without the shift table
-    at hand would."""
+    at hand would.  shifts_yx [N, 2], or [B, N, 2] for one table per item (srx_ibp_items_*: item b gets the bits of a B = 1 call
+    on shifts_yx[b])."""
     prec = precision or get_precision()
+    B, N, h, w = _shape4(lr, "lr")
+    sh, shp, per_item = _shift_tables(shifts_yx, B, N)
     x, _ = _to_dev(lr, prec)
     h0, _ = _to_dev(hr_init, prec)
-    B, N, h, w = x.shape
     Bh, H, W = h0.shape
     if Bh != B:
         raise ValueError("lr and hr_init disagree on the batch size")
     f = int(factor)
-    sh, shp = _host_f64(shifts_yx, (N, 2))
     k, kp = _host_f64(kernel)
+    name = "srx_ibp_items" if per_item else "srx_ibp"
     if out is not None:  # the library writes B*H*W elements of the call's precision straight through this pointer
         if (not isinstance(out, torch.Tensor) or not out.is_cuda or out.dtype != _TORCH_DT[prec] or tuple(out.shape) != (B, H, W)
                 or not out.is_contiguous()):
@@ -227,11 +249,11 @@ def ibp_batched(lr, shifts_yx, kernel, hr_init, factor=2, n_iter=80, step=0.5, p
     hr = torch.empty_like(h0) if out is None else out
     errors = torch.empty((B, int(n_iter)), dtype=torch.float64, device=x.device) if want_errors else None
     lib = _lib.load()
-    wt, wp, wn = _ws(lib.srx_ibp_workspace_bytes_for(_ELEM[prec], B, N, h, w, H, W, f, shp, kp, k.shape[0], k.shape[1], flags)
-                     if exact_workspace else lib.srx_ibp_workspace_bytes(_ELEM[prec], B, N, h, w, H, W, f, flags))
-    _lib.check(_fn("srx_ibp", prec)(_p(x), B, N, h, w, shp, kp, k.shape[0], k.shape[1], _p(h0), H, W, f, int(n_iter),
-                                    float(step), _p(hr), _p(errors) if want_errors else None, wp, wn, _stream(), flags),
-               "srx_ibp")
+    wt, wp, wn = _ws(getattr(lib, name + "_workspace_bytes_for")(_ELEM[prec], B, N, h, w, H, W, f, shp, kp, k.shape[0], k.shape[1], flags)
+                     if exact_workspace else getattr(lib, name + "_workspace_bytes")(_ELEM[prec], B, N, h, w, H, W, f, flags))
+    _lib.check(_fn(name, prec)(_p(x), B, N, h, w, shp, kp, k.shape[0], k.shape[1], _p(h0), H, W, f, int(n_iter),
+                               float(step), _p(hr), _p(errors) if want_errors else None, wp, wn, _stream(), flags),
+               name)
     return hr, errors
 
 
@@ -255,10 +277,12 @@ def shift_and_add_u8_batched(lr_u8, shifts_yx, factor=2, precision=None, flags=F
     """shift_and_add_batched on the camera's own samples: lr_u8 uint8 [B, N, h, w] -> [B, h*f, w*f] of the compute precision; the same
     bits as shift_and_add_batched on the converted frames (srx_saa_u8lr_*)."""
     prec = precision or get_precision()
+    B, N, h, w = _shape4(lr_u8, "lr_u8")
+    sh, shp, per_item = _shift_tables(shifts_yx, B, N)
     x = _u8_dev(lr_u8, "lr_u8", 4)
-    B, N, h, w = x.shape
+    if per_item:  # no uint8 items entry point: the frames are converted on the device ((T)uint8 is exact: the same bits)
+        return shift_and_add_batched(u8_to_float(x, prec), sh, factor, prec, flags)
     f = int(factor)
-    sh, shp = _host_f64(shifts_yx, (N, 2))
     out = torch.empty((B, h * f, w * f), dtype=_TORCH_DT[prec], device=x.device)
     wt, wp, wn = _ws(_lib.load().srx_saa_u8lr_workspace_bytes(_ELEM[prec], B, N, h, w, f))
     _lib.check(_fn("srx_saa_u8lr", prec)(_p(x), B, N, h, w, shp, f, _p(out), wp, wn, _stream(), flags), "srx_saa_u8lr")
@@ -270,14 +294,16 @@ def ibp_u8_batched(lr_u8, shifts_yx, kernel, hr_init, factor=2, n_iter=80, step=
     """ibp_batched on the camera's own samples: lr_u8 uint8 [B, N, h, w], hr_init [B, H, W] -> (hr, errors); the same bits as
     ibp_batched on the converted frames (srx_ibp_u8lr_*)."""
     prec = precision or get_precision()
+    B, N, h, w = _shape4(lr_u8, "lr_u8")
+    sh, shp, per_item = _shift_tables(shifts_yx, B, N)
     x = _u8_dev(lr_u8, "lr_u8", 4)
+    if per_item:  # as in shift_and_add_u8_batched
+        return ibp_batched(u8_to_float(x, prec), sh, kernel, hr_init, factor, n_iter, step, prec, flags, want_errors, out, exact_workspace)
     h0, _ = _to_dev(hr_init, prec)
-    B, N, h, w = x.shape
     Bh, H, W = h0.shape
     if Bh != B:
         raise ValueError("lr_u8 and hr_init disagree on the batch size")
     f = int(factor)
-    sh, shp = _host_f64(shifts_yx, (N, 2))
     k, kp = _host_f64(kernel)
     if out is not None:
         if (not isinstance(out, torch.Tensor) or not out.is_cuda or out.dtype != _TORCH_DT[prec] or tuple(out.shape) != (B, H, W)

@@ -35,7 +35,8 @@ def main(argv=None):
                     help="several GPUs on ONE image: split every image's IBP loop into row bands (cal_target kinds; under torchrun)")
     ap.add_argument("--register", action="store_true",
                     help="estimate the frames' shifts on the device (table as the start) and reconstruct with them; "
-                         "writes registration.json next to the PNGs")
+                         "writes registration.json next to the PNGs (barcode kinds: the reps of a session still go through the "
+                         "library as one batch, every rep under its own table)")
     ap.add_argument("--psf-on-device", action="store_true",
                     help="with --psf measured: estimate the PSF from the pinhole frames on the device (uint8 frames uploaded as they are)")
     ap.add_argument("--u8-frames", action="store_true",

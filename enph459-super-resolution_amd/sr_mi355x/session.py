@@ -230,11 +230,16 @@ def reconstruct_batch(frame_sets, shifts, psf_kernel, n_iter, factor=UPSAMPLE_FA
     """`reconstruct` for B frame sets of one shape and one shift table in ONE library call per stage (B = the reps of a
     barcode session, mono_barcodes/run_sr.py:301-351: independent work items).  Every item's result is bit-identical to
     reconstruct() on that item alone (the kernels treat batch entries independently; tests/test_gpu_session.py).
+    shifts: one table [N, 2] for every frame set, or a list of B tables (register=True measures one per rep): still one call per
+    stage, through the library's per-item entry points (srx_saa_items_* / srx_ibp_items_*), every item as on its own.
     -> list of (images dict, MSE trace), one per frame set.  lazy_errors: the traces stay device tensors (no wait for the IBP loop
     here; _save_outputs downloads them with the planes)."""
     import torch
     lr64 = torch.stack([torch.stack(fr) for fr in frame_sets])  # [B, N, h, w] float64, or uint8 (keep_u8 loaders)
     B, N, h, w = lr64.shape
+    shifts = np.asarray(shifts, dtype=np.float64)
+    if shifts.shape not in ((N, 2), (B, N, 2)):
+        raise ValueError(f"shifts must be one table {(N, 2)} or one per frame set {(B, N, 2)}, not {shifts.shape}")
     with _loader_precision():
         mean_lr = api.mean_frames_batched(_frames_f64(lr64))
     native = api.zoom_batched(mean_lr, factor)
@@ -412,7 +417,7 @@ def process_session(session_dir, psf_kernel, output_base, kind=None, n_iter=None
                     row_bands=False, on_images=None, register=False, keep_u8=False):
     """Counterpart of process_session / process_combo.  Returns the list of output directories written
     (empty if everything was already done).  batch_reps: the reps of a barcode session that are still to do go through the
-    library in one B = reps call (reconstruct_batch) instead of one call per rep; `loaded`: frames already decoded by a
+    library in one B = reps call (reconstruct_batch) instead of one call per rep (with register, every rep under its own table); `loaded`: frames already decoded by a
     Prefetcher (what load_corner_reps / load_mono_cal_session / load_rgb_cal_combo would return).  row_bands (the two cal_target
     kinds: one large image per session): all ranks work on this one session (reconstruct(row_bands=True)), rank 0 writes.
     register: reconstruct with shifts estimated from the frames (register_shifts) and write registration.json beside the PNGs.
@@ -464,7 +469,10 @@ def process_session(session_dir, psf_kernel, output_base, kind=None, n_iter=None
     extras = [None] * len(todo)
     if register:  # one registration item per rep (one batched call); each rep then reconstructs with its own shifts
         regs = register_shifts([fr for _, fr in todo], shifts)
-        results = [reconstruct(fr, used, psf_kernel, n_iter) for (_, fr), (used, _) in zip(todo, regs)]
+        if batch_reps:  # ... in one library call per stage, each with its own table
+            results = reconstruct_batch([fr for _, fr in todo], [used for used, _ in regs], psf_kernel, n_iter, lazy_errors=True)
+        else:
+            results = [reconstruct(fr, used, psf_kernel, n_iter) for (_, fr), (used, _) in zip(todo, regs)]
         extras = [{"registration.json": reg} for _, reg in regs]
     elif batch_reps:
         results = reconstruct_batch([fr for _, fr in todo], shifts, psf_kernel, n_iter, lazy_errors=True)

@@ -19,7 +19,7 @@
  *   - Small parameter arrays (PSF kernel, shift table) are HOST pointers, float64:
  *     `kernel` [kh, kw] row-major, `shifts_yx` [N, 2] = (dy, dx) in LR pixels, positive =
  *     content moves toward +index -- exactly the reference's `shift_yx`/`shifts_yx`.
- *     They are shared by all B items of a call.
+ *     They are shared by all B items of a call (the *_items_* entry points take one table per item).
  *   - `stream` is a hipStream_t passed as void* (NULL = the default stream).  All work is
  *     enqueued on it; nothing synchronises the device.  No allocation happens inside a
  *     call: scratch comes from the caller's workspace (`*_workspace_bytes`, 256-B aligned
@@ -223,6 +223,42 @@ int srx_ibp_u8lr_f32(const uint8_t *lr, int B, int N, int h, int w, const double
 int srx_ibp_u8lr_f64(const uint8_t *lr, int B, int N, int h, int w, const double *shifts_yx, const double *kernel, int kh, int kw,
                      const double *hr_init, int H, int W, int factor, int n_iter, double step, double *hr_out, double *errors_out, void *ws,
                      size_t ws_bytes, srx_stream_t stream, unsigned flags);
+
+/* ---- shift_and_add / ibp with one shift table PER ITEM: what registration measures (srx_register_* returns [B, N, 2]) ----
+ * shifts_byx is HOST float64 [B, N, 2]; everything else is the shared-table call's.  Item b returns exactly the bits of srx_saa_* /
+ * srx_ibp_* with B = 1 on item b's frames, hr_init and table shifts_byx[b] under the same flags: the output, the MSE trace, hr_out ==
+ * hr_init.  The header's conventions hold: the tables are read before the call returns, nothing is allocated on the device, only kernels
+ * and device-to-device copies are queued, the memory contract holds, and the argument checks and limits of the shared-table calls apply
+ * per item -- a refusal for any item (SRX_FLAG_FUSED on an item that cannot fuse) is decided on the host before anything is queued.
+ * Routing: the route is decided once per DISTINCT table (what srx_ibp_path_for answers on shifts_byx[b]) and the batch is walked in
+ * maximal runs of consecutive items:
+ *   items that all route to "btile" (float32, x2, per-frame fractional shifts; their tables may all differ): one batch, the kernels take
+ *     each item's table and the range of ITS tap origins from a device array;
+ *   any other run of bytewise-equal tables: the driver of its route as a batch of the run's length.  Every table equal: the call IS the
+ *     shared-table call -- same route, same bits, same launches;
+ *   items on "fused" / "composed" with pairwise different tables run one by one (batching those routes' tile kernels per item is not done).
+ *   shift_and_add: the same with "fused" in the place of "btile".
+ * srx_last_path() reports the common route name if every run took the same one, else "mixed".  Batches above 32768 items go through in
+ * chunks, as everywhere.  The per-item tables travel as kernel arguments, 960 words per launch: a "btile" run of n items makes
+ * ceil(n (4 + 20 N) / 960) parameter launches, a "fused" shift_and_add run ceil(n N sizeof(tap) / 3840) (tap: 40 bytes f32, 72 f64).
+ * Workspace: srx_ibp_items_workspace_bytes_for = the largest run's srx_ibp_workspace_bytes_for at the run's length, plus
+ * align_up(n (4 + 20 N) 4) for a per-item "btile" run of n items; srx_ibp_items_workspace_bytes (shape only) covers it for every table.
+ * srx_saa_items_workspace_bytes = srx_saa_workspace_bytes + align_up(Bc N sizeof(tap)), Bc = min(B, max(32768 / N, 1)).
+ * There are no uint8 forms: the per-frame routes stage the bytes to T anyway (convert with srx_u8_to_*; the result is the same bits). */
+size_t srx_saa_items_workspace_bytes(int elem_bytes, int B, int N, int h, int w, int factor);
+int srx_saa_items_f32(const float *lr, int B, int N, int h, int w, const double *shifts_byx, int factor, float *out, void *ws,
+                      size_t ws_bytes, srx_stream_t stream, unsigned flags);
+int srx_saa_items_f64(const double *lr, int B, int N, int h, int w, const double *shifts_byx, int factor, double *out, void *ws,
+                      size_t ws_bytes, srx_stream_t stream, unsigned flags);
+size_t srx_ibp_items_workspace_bytes(int elem_bytes, int B, int N, int h, int w, int H, int W, int factor, unsigned flags);
+size_t srx_ibp_items_workspace_bytes_for(int elem_bytes, int B, int N, int h, int w, int H, int W, int factor, const double *shifts_byx,
+                                         const double *kernel, int kh, int kw, unsigned flags);
+int srx_ibp_items_f32(const float *lr, int B, int N, int h, int w, const double *shifts_byx, const double *kernel, int kh, int kw,
+                      const float *hr_init, int H, int W, int factor, int n_iter, double step, float *hr_out, double *errors_out, void *ws,
+                      size_t ws_bytes, srx_stream_t stream, unsigned flags);
+int srx_ibp_items_f64(const double *lr, int B, int N, int h, int w, const double *shifts_byx, const double *kernel, int kh, int kw,
+                      const double *hr_init, int H, int W, int factor, int n_iter, double step, double *hr_out, double *errors_out, void *ws,
+                      size_t ws_bytes, srx_stream_t stream, unsigned flags);
 
 /* ---- the same loop as a PLAN: tables built once, the iterations in several runs, rows of the state readable / replaceable in between ----
  * No reference counterpart (its ibp() is one call); this is what running ONE image on several GPUs needs (second row: row bands
