@@ -1,8 +1,9 @@
 // srx_api.hip -- C ABI of libsrx.so (include/srx.h): primitive entry points, the composed
 // (literal, per-frame) SAA / IBP built from the primitive kernels, and the route of a call:
 // route_ibp() decides once which of composed / fused / btile / mosaic (and which row of
-// srx_route.hpp's table of mosaic implementations) takes it; the call, a plan and the exact
-// workspace query all read that one record.
+// srx_route.hpp's table of mosaic implementations) takes an srx_ibp call, route_saa() which of
+// composed / fused / mosaic takes an srx_saa call; the call, its per-item form, a plan, the exact
+// workspace query and the host's route queries all read that one record.
 #include <cstdio>
 #include <cstring>
 
@@ -319,15 +320,24 @@ static bool basic_ibp_args_ok(const void *lr, int B, int N, int h, int w, const 
 }
 
 #define SRX_MAX_BATCH_PER_LAUNCH 32768  // gridDim.z <= 65535; larger batches go through in chunks of this many items
+// The items of one chunk (shift_and_add's kernels take an (item, frame) pair per gridDim.z).  The workspace queries accept any B and N, so
+// these do: B <= 0 passes through, and a query that sizes a table or a staged copy for at least one item says so with std::max.
+static inline int ibp_chunk_items(int B) { return B > SRX_MAX_BATCH_PER_LAUNCH ? SRX_MAX_BATCH_PER_LAUNCH : B; }
+static inline int saa_chunk_items(int B, int N)
+{
+    if ((long)B * N > SRX_MAX_BATCH_PER_LAUNCH)
+        return SRX_MAX_BATCH_PER_LAUNCH / N > 0 ? SRX_MAX_BATCH_PER_LAUNCH / N : 1;
+    return B;
+}
 
-// The route of one srx_ibp call (valid arguments within the library's limits), decided here and nowhere else: the call itself, a plan and the
-// exact workspace query read it.  The batch size plays no part.  Precondition: runs under the entry point's CallFlags guard, like everything
+// The route of one srx_ibp / srx_saa call (valid arguments within the library's limits), decided here and nowhere else: the call itself, its
+// per-item form, a plan, the exact workspace query and srx_*_path_for read it.  The batch size plays no part.  Precondition: runs under the entry point's CallFlags guard, like everything
 // below it -- the eligibility predicates and fused::make_kernel7 read the path-forcing flags through call_flags().  Pure host arithmetic.
-enum Path { PATH_COMPOSED, PATH_FUSED, PATH_BTILE, PATH_MOSAIC };
+enum Path { PATH_COMPOSED, PATH_FUSED, PATH_BTILE, PATH_MOSAIC };  // (shift_and_add has no PATH_BTILE)
 struct Route {
     int status;                    // an early answer (SRX_FLAG_FUSED on a call that cannot fuse), else SRX_OK
     Path path;
-    const mosaic::ImplRow *impl;   // PATH_MOSAIC: the row of srx_route.hpp's table
+    const mosaic::ImplRow *impl;   // ibp on PATH_MOSAIC: the row of srx_route.hpp's table
     const char *name;              // what srx_last_path() reports
 };
 
@@ -347,12 +357,23 @@ static Route route_ibp(int eb, int N, int h, int w, int H, int W, int f, const d
     return {SRX_OK, PATH_FUSED, nullptr, "fused"};
 }
 
+static Route route_saa(int N, int h, int w, int f, const double *sh, unsigned flags)
+{
+    const bool can_fuse = fused::saa_eligible(N, h, w, sh, f);
+    if ((flags & SRX_FLAG_FUSED) && !can_fuse)
+        return {SRX_E_UNSUPPORTED, PATH_COMPOSED, nullptr, "none"};
+    if (!can_fuse || (flags & SRX_FLAG_COMPOSED))
+        return {SRX_OK, PATH_COMPOSED, nullptr, "composed"};
+    if (!(flags & SRX_FLAG_PER_FRAME) && mosaic::saa_eligible(N, h, w, sh, f))
+        return {SRX_OK, PATH_MOSAIC, nullptr, "mosaic"};
+    return {SRX_OK, PATH_FUSED, nullptr, "fused"};
+}
+
 // What a call on route `r` must bring: exactly what a mosaic implementation carves (the shape-only bound covers it by construction,
 // tests/test_abi.py sweeps shapes for need <= bound), the shape-only bound on every other path.
 static size_t ibp_need(const Route &r, int eb, int B, int N, int h, int w, int H, int W, int f, unsigned flags)
 {
-    if (B > SRX_MAX_BATCH_PER_LAUNCH)
-        B = SRX_MAX_BATCH_PER_LAUNCH;
+    B = ibp_chunk_items(B);
     if (r.status != SRX_OK || r.path != PATH_MOSAIC)
         return srx_ibp_workspace_bytes(eb, B, N, h, w, H, W, f, flags);
     return mosaic::ibp_ws_for(*r.impl, eb, B, N, H, W);
@@ -416,68 +437,65 @@ static int ibp_dispatch(const S *lr, int B, int N, int h, int w, const double *s
     // a short or misaligned workspace is refused before anything is queued
     size_t need = ibp_need(r, (int)sizeof(T), B, N, h, w, H, W, f, flags);
     if (!std::is_same<S, T>::value && r.path != PATH_MOSAIC)
-        need += u8_stage_bytes((int)sizeof(T), B < SRX_MAX_BATCH_PER_LAUNCH ? B : SRX_MAX_BATCH_PER_LAUNCH, N, h, w);
+        need += u8_stage_bytes((int)sizeof(T), ibp_chunk_items(B), N, h, w);
     if (ws_short(ws, wsb, need))
         return SRX_E_WORKSPACE;
     g_last_path = r.name;
     // batches beyond one launch's gridDim.z go through in chunks; the workspace is sized for one chunk and reused (stream order)
     for (int b0 = 0; b0 < B; b0 += SRX_MAX_BATCH_PER_LAUNCH) {
-        const int bc = B - b0 < SRX_MAX_BATCH_PER_LAUNCH ? B - b0 : SRX_MAX_BATCH_PER_LAUNCH;
+        const int bc = ibp_chunk_items(B - b0);
         SRX_TRY((ibp_run<T, S>(r, lr + (size_t)b0 * N * h * w, bc, N, h, w, sh, k, kh, kw, hr_init + (size_t)b0 * H * W, H, W, f, n_iter, step,
                            hr + (size_t)b0 * H * W, errors ? errors + (size_t)b0 * n_iter : nullptr, ws, wsb, st)));
     }
     return SRX_OK;
 }
 
-static size_t saa_chunk_items(int B, int N)
+// argument and limit checks of every srx_saa entry point (and of srx_saa_path_for); lr / out: the device pointers, only their presence counts
+static int saa_check(size_t eb, const void *lr, int B, int N, int h, int w, const double *sh, int f, const void *out)
 {
-    if ((long)B * N > SRX_MAX_BATCH_PER_LAUNCH)
-        return SRX_MAX_BATCH_PER_LAUNCH / N > 0 ? SRX_MAX_BATCH_PER_LAUNCH / N : 1;
-    return B;
+    if (!lr || !sh || !out || B <= 0 || N <= 0 || h <= 0 || w <= 0 || f <= 0)
+        return SRX_E_INVALID;
+    if (N > SRX_MAX_FRAMES || (size_t)h * f >= ((size_t)1 << 30) || (size_t)w * f >= ((size_t)1 << 30) || !plane_fits(eb, N, h, w, h * f, w * f))
+        return SRX_E_UNSUPPORTED;
+    return SRX_OK;
+}
+
+// one chunk (at most saa_chunk_items items) of a call on the route its entry point decided
+template <typename T, typename S>
+static int saa_run(const Route &r, const S *lr_, int B, int N, int h, int w, const double *sh, int f, T *out, void *ws, size_t wsb, hipStream_t st)
+{
+    if (r.path == PATH_MOSAIC)
+        return mosaic::saa<T, S>(lr_, B, N, h, w, sh, f, out, ws, wsb, st);
+    const T *lr;
+    if constexpr (std::is_same<S, T>::value)
+        lr = lr_;
+    else
+        SRX_TRY(u8_stage<T>(lr_, (size_t)B * N * h * w, ws, wsb, lr, st));
+    if (r.path == PATH_FUSED)
+        return fused::saa<T>(lr, B, N, h, w, sh, f, out, ws, wsb, st);
+    return saa_composed<T>(lr, B, N, h, w, sh, f, out, ws, wsb, st);
 }
 
 template <typename T, typename S = T>
-static int saa_dispatch(const S *lr_, int B, int N, int h, int w, const double *sh, int f, T *out, void *ws, size_t wsb,
-                        hipStream_t st, unsigned flags, bool checked = false)
+static int saa_dispatch(const S *lr, int B, int N, int h, int w, const double *sh, int f, T *out, void *ws, size_t wsb,
+                        hipStream_t st, unsigned flags)
 {
+    SRX_TRY(saa_check(sizeof(T), lr, B, N, h, w, sh, f, out));
+    const Route r = route_saa(N, h, w, f, sh, flags);  // once per call: the batch size plays no part
+    // Every refusal comes before anything is queued (the uint8 staging included).  These entry points answer a short workspace BEFORE
+    // SRX_FLAG_FUSED on a table that cannot fuse, items::saa_dispatch_items the other way round: callers have met both orders, both stay.
     constexpr bool u8 = !std::is_same<S, T>::value;
-    const S *lr = lr_;
-    if (!lr || !sh || !out || B <= 0 || N <= 0 || h <= 0 || w <= 0 || f <= 0)
-        return SRX_E_INVALID;
-    if (N > SRX_MAX_FRAMES || (size_t)h * f >= ((size_t)1 << 30) || (size_t)w * f >= ((size_t)1 << 30) || !plane_fits(sizeof(T), N, h, w, h * f, w * f))
-        return SRX_E_UNSUPPORTED;
-    // before anything is queued (a chunk of a larger call was checked with it)
-    if (!checked && ws_short(ws, wsb, u8 ? srx_saa_u8lr_workspace_bytes((int)sizeof(T), B, N, h, w, f) : srx_saa_workspace_bytes((int)sizeof(T), B, N, h, w, f)))
+    if (ws_short(ws, wsb, u8 ? srx_saa_u8lr_workspace_bytes((int)sizeof(T), B, N, h, w, f) : srx_saa_workspace_bytes((int)sizeof(T), B, N, h, w, f)))
         return SRX_E_WORKSPACE;
-    if ((long)B * N > SRX_MAX_BATCH_PER_LAUNCH) {
-        const int step_b = SRX_MAX_BATCH_PER_LAUNCH / N > 0 ? SRX_MAX_BATCH_PER_LAUNCH / N : 1;
-        for (int b0 = 0; b0 < B; b0 += step_b) {
-            const int bc = B - b0 < step_b ? B - b0 : step_b;
-            SRX_TRY((saa_dispatch<T, S>(lr + (size_t)b0 * N * h * w, bc, N, h, w, sh, f, out + (size_t)b0 * h * f * w * f, ws, wsb,
-                                        st, flags, true)));
-        }
-        return SRX_OK;
+    if (r.status != SRX_OK)
+        return r.status;
+    g_last_path = r.name;
+    // batches beyond one launch's gridDim.z go through in chunks; the workspace is sized for one chunk and reused (stream order)
+    for (int b0 = 0, bc; b0 < B; b0 += bc) {
+        bc = saa_chunk_items(B - b0, N);
+        SRX_TRY((saa_run<T, S>(r, lr + (size_t)b0 * N * h * w, bc, N, h, w, sh, f, out + (size_t)b0 * h * f * w * f, ws, wsb, st)));
     }
-    const bool can_fuse = fused::saa_eligible(N, h, w, sh, f);
-    if ((flags & SRX_FLAG_FUSED) && !can_fuse)
-        return SRX_E_UNSUPPORTED;
-    if (can_fuse && !(flags & SRX_FLAG_COMPOSED)) {
-        if (!(flags & SRX_FLAG_PER_FRAME) && mosaic::saa_eligible(N, h, w, sh, f)) {
-            g_last_path = "mosaic";
-            return mosaic::saa<T, S>(lr, B, N, h, w, sh, f, out, ws, wsb, st);
-        }
-    }
-    const T *lrT;
-    if constexpr (u8)
-        SRX_TRY(u8_stage<T>(lr, (size_t)B * N * h * w, ws, wsb, lrT, st));
-    else
-        lrT = lr;
-    if (can_fuse && !(flags & SRX_FLAG_COMPOSED)) {
-        g_last_path = "fused";
-        return fused::saa<T>(lrT, B, N, h, w, sh, f, out, ws, wsb, st);
-    }
-    g_last_path = "composed";
-    return saa_composed<T>(lrT, B, N, h, w, sh, f, out, ws, wsb, st);
+    return SRX_OK;
 }
 
 #include "srx_items.hpp"  // one shift table per item: routing by runs on top of the dispatchers above
@@ -706,8 +724,7 @@ size_t srx_backproject_workspace_bytes(int eb, int B, int H, int W) { return bac
 
 size_t srx_saa_workspace_bytes(int eb, int B, int N, int h, int w, int f)
 {
-    if ((long)B * N > SRX_MAX_BATCH_PER_LAUNCH)
-        B = SRX_MAX_BATCH_PER_LAUNCH / N > 0 ? SRX_MAX_BATCH_PER_LAUNCH / N : 1;
+    B = saa_chunk_items(B, N);
     size_t a = saa_ws_composed(eb, B, N, h, w, f), b = fused::saa_ws(eb, B, N, h, w, f);
     const size_t c = mosaic::saa_ws(eb, B, N, h, w, f);
     a = a > b ? a : b;
@@ -717,13 +734,12 @@ size_t srx_saa_workspace_bytes(int eb, int B, int N, int h, int w, int f)
 /* float figure + one staged copy (T) of a chunk's frames, whatever the route: the query has no shift table to tell the routes apart */
 size_t srx_saa_u8lr_workspace_bytes(int eb, int B, int N, int h, int w, int f)
 {
-    return srx_saa_workspace_bytes(eb, B, N, h, w, f) + u8_stage_bytes(eb, (int)saa_chunk_items(B, N), N, h, w);
+    return srx_saa_workspace_bytes(eb, B, N, h, w, f) + u8_stage_bytes(eb, saa_chunk_items(B, N), N, h, w);
 }
 
 size_t srx_ibp_workspace_bytes(int eb, int B, int N, int h, int w, int H, int W, int f, unsigned flags)
 {
-    if (B > SRX_MAX_BATCH_PER_LAUNCH)
-        B = SRX_MAX_BATCH_PER_LAUNCH;
+    B = ibp_chunk_items(B);
     size_t a = ibp_ws_composed(eb, B, N, h, w, H, W, f), b = fused::ibp_ws(eb, B, N, h, w, H, W, f);
     const size_t c = mosaic::ibp_ws(eb, B, N, H, W);
     b = b > c ? b : c;
@@ -749,7 +765,7 @@ size_t srx_ibp_workspace_bytes_for(int eb, int B, int N, int h, int w, int H, in
 size_t srx_ibp_u8lr_workspace_bytes(int eb, int B, int N, int h, int w, int H, int W, int f, unsigned flags)
 {
     return srx_ibp_workspace_bytes(eb, B, N, h, w, H, W, f, flags) +
-           u8_stage_bytes(eb, B < SRX_MAX_BATCH_PER_LAUNCH ? (B > 0 ? B : 1) : SRX_MAX_BATCH_PER_LAUNCH, N, h, w);
+           u8_stage_bytes(eb, std::max(ibp_chunk_items(B), 1), N, h, w);
 }
 size_t srx_ibp_u8lr_workspace_bytes_for(int eb, int B, int N, int h, int w, int H, int W, int f, const double *sh, const double *k, int kh,
                                         int kw, unsigned flags)
@@ -761,7 +777,7 @@ size_t srx_ibp_u8lr_workspace_bytes_for(int eb, int B, int N, int h, int w, int 
     const size_t need = ibp_need(r, eb, B, N, h, w, H, W, f, flags);
     if (r.status == SRX_OK && r.path == PATH_MOSAIC)
         return need;
-    return need + u8_stage_bytes(eb, B < SRX_MAX_BATCH_PER_LAUNCH ? (B > 0 ? B : 1) : SRX_MAX_BATCH_PER_LAUNCH, N, h, w);
+    return need + u8_stage_bytes(eb, std::max(ibp_chunk_items(B), 1), N, h, w);
 }
 
 size_t srx_saa_items_workspace_bytes(int eb, int B, int N, int h, int w, int f) { return items::saa_ws_bound(eb, B, N, h, w, f); }
@@ -776,7 +792,7 @@ size_t srx_ibp_items_workspace_bytes_for(int eb, int B, int N, int h, int w, int
     if (!sh || !k || N <= 0 || N > SRX_MAX_FRAMES || B <= 0)
         return srx_ibp_items_workspace_bytes(eb, B, N, h, w, H, W, f, flags);
     CallFlags cf(flags);
-    const items::IbpPlan p = items::plan_ibp(eb, B, N, h, w, H, W, f, sh, k, kh, kw, flags);
+    const items::Plan p = items::plan_ibp(eb, B, N, h, w, H, W, f, sh, k, kh, kw, flags);
     return p.status == SRX_OK ? p.need : srx_ibp_items_workspace_bytes(eb, B, N, h, w, H, W, f, flags);
 }
 
@@ -788,6 +804,16 @@ const char *srx_ibp_path_for(int eb, int N, int h, int w, int H, int W, int f, c
         return "none";
     CallFlags cf(flags);
     const Route r = route_ibp(eb, N, h, w, H, W, f, sh, k, kh, kw, flags);
+    return r.status == SRX_OK ? r.name : "none";
+}
+
+const char *srx_saa_path_for(int eb, int N, int h, int w, int f, const double *sh, unsigned flags)
+{
+    int dummy = 0;  // (stands for the device pointers: only their presence is checked)
+    if ((eb != 4 && eb != 8) || saa_check((size_t)eb, &dummy, 1, N, h, w, sh, f, &dummy) != SRX_OK)
+        return "none";
+    CallFlags cf(flags);
+    const Route r = route_saa(N, h, w, f, sh, flags);
     return r.status == SRX_OK ? r.name : "none";
 }
 

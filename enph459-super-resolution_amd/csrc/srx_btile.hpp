@@ -591,6 +591,29 @@ __global__ void k_param_words(ParamWords P, int *__restrict__ dst)
     for (int i = threadIdx.x; i < P.n; i += blockDim.x)
         dst[i] = P.w[i];
 }
+// host side: words put() one after the other land at dst, a launch every PARAM_WORDS of them and one more at finish() for the rest
+struct ParamUpload {
+    hipStream_t st;
+    int *dst;
+    ParamWords pw = {};  // (what lies past n travels too)
+    int flush()
+    {
+        hipLaunchKernelGGL(k_param_words, dim3(1), dim3(256), 0, st, pw, dst);
+        SRX_CHECK_LAUNCH();
+        dst += pw.n, pw.n = 0;
+        return SRX_OK;
+    }
+    int put(const int *src, int n)
+    {
+        for (int i = 0; i < n; i++) {
+            pw.w[pw.n++] = src[i];
+            if (pw.n == PARAM_WORDS)
+                SRX_TRY(flush());
+        }
+        return SRX_OK;
+    }
+    int finish() { return pw.n ? flush() : SRX_OK; }
+};
 
 // window geometry shared by the two kernels
 template <int NBY, int NBX> struct Geo {
@@ -1151,32 +1174,15 @@ static int ibp_t(const float *lr, int B, int N, int h, int w, const double *sh, 
         hipLaunchKernelGGL(k_btile_params, dim3(1), dim3(64), 0, st, A, frtab);
         SRX_CHECK_LAUNCH();
     } else {
-        ParamWords pw = {};  // (what lies past n travels too)
-        const size_t total = (size_t)B * frstride;
-        size_t sent = 0;
-        auto flush = [&]() -> int {
-            hipLaunchKernelGGL(k_param_words, dim3(1), dim3(256), 0, st, pw, frtab + sent);
-            SRX_CHECK_LAUNCH();
-            sent += pw.n, pw.n = 0;
-            return SRX_OK;
-        };
-        auto put = [&](const int *src, int n) -> int {
-            for (int i = 0; i < n; i++) {
-                pw.w[pw.n++] = src[i];
-                if (pw.n == PARAM_WORDS)
-                    SRX_TRY(flush());
-            }
-            return SRX_OK;
-        };
+        ParamUpload up{st, frtab};
         for (int b = 0; b < B; b++) {
             BFrame fr[MAXF];
             make_frames(sh + (size_t)b * 2 * N, N, fr, N, rng);
-            SRX_TRY(put(rng, TAB_HDR));
-            SRX_TRY(put(reinterpret_cast<const int *>(fr), 20 * N));
+            SRX_TRY(up.put(rng, TAB_HDR));
+            SRX_TRY(up.put(reinterpret_cast<const int *>(fr), 20 * N));
         }
-        if (pw.n)
-            SRX_TRY(flush());
-        if (sent != total)
+        SRX_TRY(up.finish());
+        if (up.dst != frtab + (size_t)B * frstride)
             return SRX_E_INVALID;
     }
     const dim3 cgrid(cdiv(W, 256), H4, B);

@@ -1523,9 +1523,10 @@ static inline size_t saa_ws(int eb, int B, int N, int h, int w, int f)
            2 * align_up((H > W ? H : W) * sizeof(AxisTap<double>));
 }
 
-template <typename T>
-static int saa(const T *lr, int B, int N, int h, int w, const double *sh, int f, T *out, void *ws, size_t wsb,
-               hipStream_t st)
+// The driver body of shift_and_add on this route.  fir(q, grid, block, up, pad) makes frame q's FIR launch: where its tap comes from is
+// all that differs between one table for the batch (saa below) and one per item (items::saa_fused_items).
+template <typename T, typename Fir>
+static int saa_with(Fir fir, const T *lr, int B, int N, int h, int w, int f, T *out, void *ws, size_t wsb, hipStream_t st)
 {
     if ((long)B * N > 65535)
         return SRX_E_UNSUPPORTED;
@@ -1545,17 +1546,28 @@ static int saa(const T *lr, int B, int N, int h, int w, const double *sh, int f,
     SRX_TRY(build_taps(zx, W, w, TAP_ZOOM, 1, zx_, st));
     for (int q = 0; q < N; q++) {
         SRX_TRY(interp_strided(coef + (size_t)q * h * w, (size_t)N * h * w, B, h, w, zy, zx, H, W, up, st));
-        FrameTap<T> ft;
-        make_tap<T>(-sh[2 * q] * f, -sh[2 * q + 1] * f, 0, ft);  // shift(+d): out[r] = in[r - d]
-        const dim3 grd(cdiv(Wp, 64), cdiv(Hp, 4), B), blk(64, 4);
-        if (q == 0)
-            SRX_LAUNCH(KID_FIR_PAD, (k_fir_pad<T, false>), grd, blk, 0, st, up, H, W, ft, pad);
-        else
-            SRX_LAUNCH(KID_FIR_PAD, (k_fir_pad<T, true>), grd, blk, 0, st, up, H, W, ft, pad);
+        SRX_TRY(fir(q, dim3(cdiv(Wp, 64), cdiv(Hp, 4), B), dim3(64, 4), up, pad));
     }
     SRX_TRY(prefilter2d_fast(pad, scr, B, Hp, Wp, MODE_REFLECT, st));
     SRX_LAUNCH(KID_CROP_DIV, k_crop_div<T>, dim3(cdiv(W, 64), cdiv(H, 4), B), dim3(64, 4), 0, st, pad, H, W, (T)N, out);
     return SRX_OK;
+}
+
+template <typename T>
+static int saa(const T *lr, int B, int N, int h, int w, const double *sh, int f, T *out, void *ws, size_t wsb,
+               hipStream_t st)
+{
+    const int H = h * f, W = w * f;
+    auto fir = [&](int q, dim3 grd, dim3 blk, const T *up, T *pad) -> int {
+        FrameTap<T> ft;
+        make_tap<T>(-sh[2 * q] * f, -sh[2 * q + 1] * f, 0, ft);  // shift(+d): out[r] = in[r - d]
+        if (q == 0)
+            SRX_LAUNCH(KID_FIR_PAD, (k_fir_pad<T, false>), grd, blk, 0, st, up, H, W, ft, pad);
+        else
+            SRX_LAUNCH(KID_FIR_PAD, (k_fir_pad<T, true>), grd, blk, 0, st, up, H, W, ft, pad);
+        return SRX_OK;
+    };
+    return saa_with<T>(fir, lr, B, N, h, w, f, out, ws, wsb, st);
 }
 
 }  // namespace fused

@@ -9,10 +9,11 @@
 //     the shared-table call, launch for launch);
 //   - items on "fused" / "composed" with pairwise different tables therefore run one by one.
 // shift_and_add does the same with "fused" in the place of "btile" (k_fir_pad_items reads the tap of (item, frame) from a device table).
-// The route of a table is decided once per DISTINCT table, on the host, before anything is queued; so is every refusal.
+// The route of a table is decided once per DISTINCT table (route_ibp / route_saa, the records the shared-table calls read), on the host,
+// before anything is queued; so is every refusal.  A plan (plan_ibp / plan_saa) holds those records and the runs; the drivers read it.
 //
 // The table's way to the device: the host builds every item's records with the code of the shared-table call (btile::make_frames,
-// fused::make_tap) and btile::k_param_words carries them, PARAM_WORDS = 960 words by value per launch: an ibp run of n items makes
+// fused::make_tap) and btile::ParamUpload carries them, PARAM_WORDS = 960 words by value per launch: an ibp run of n items makes
 // ceil(n (4 + 20 N) / 960) such launches (N = 4: one per 11 items), a shift_and_add run ceil(n N sizeof(FrameTap<T>) / 3840).
 #pragma once
 #include <string>
@@ -72,46 +73,55 @@ static std::vector<Run> make_runs(const Tables &t, const std::vector<char> &batc
 
 static inline const char *common_name(const char *have, const char *name) { return !have || strcmp(have, name) == 0 ? name : "mixed"; }
 
-// ---------------------------------------------------------------------------------------
-// ibp
-// ---------------------------------------------------------------------------------------
-struct IbpPlan {
-    int status;
+// what a per-item call does, decided before anything is queued
+struct Plan {
+    int status;                // the first refusal among the tables, else SRX_OK
     std::vector<Route> route;  // per distinct table
     std::vector<Run> runs;
-    size_t need;
-    const char *name;
+    size_t need;               // the workspace the call must bring
+    const char *name;          // what srx_last_path() reports: the runs' common route name, else "mixed"
 };
 
-static IbpPlan plan_ibp(int eb, int B, int N, int h, int w, int H, int W, int f, const double *sh, const double *k, int kh, int kw, unsigned flags)
+// route(table) of every distinct table, the first refusal, and the runs: `per_item` is the path that has a per-item form, `cap` its longest run
+template <typename RouteFn> static Plan plan_runs(const double *sh, int B, int N, Path per_item, int cap, RouteFn route)
 {
-    IbpPlan p;
+    Plan p;
     p.status = SRX_OK, p.need = 0, p.name = nullptr;
     const Tables t = distinct_tables(sh, B, N);
     std::vector<char> batched;
     for (int b : t.first) {
-        p.route.push_back(route_ibp(eb, N, h, w, H, W, f, sh + (size_t)b * 2 * N, k, kh, kw, flags));
-        batched.push_back(p.route.back().path == PATH_BTILE);
+        p.route.push_back(route(sh + (size_t)b * 2 * N));
+        batched.push_back(p.route.back().path == per_item);
         if (p.route.back().status != SRX_OK && p.status == SRX_OK)
             p.status = p.route.back().status;
     }
     if (p.status != SRX_OK)
         return p;
-    p.runs = make_runs(t, batched, B, SRX_MAX_BATCH_PER_LAUNCH);
+    p.runs = make_runs(t, batched, B, cap);
+    for (const Run &r : p.runs)
+        p.name = common_name(p.name, p.route[r.table].name);
+    return p;
+}
+
+// ---------------------------------------------------------------------------------------
+// ibp
+// ---------------------------------------------------------------------------------------
+static Plan plan_ibp(int eb, int B, int N, int h, int w, int H, int W, int f, const double *sh, const double *k, int kh, int kw, unsigned flags)
+{
+    Plan p = plan_runs(sh, B, N, PATH_BTILE, SRX_MAX_BATCH_PER_LAUNCH,
+                       [&](const double *s) { return route_ibp(eb, N, h, w, H, W, f, s, k, kh, kw, flags); });
     for (const Run &r : p.runs) {
         size_t need = ibp_need(p.route[r.table], eb, r.n, N, h, w, H, W, f, flags);
         if (r.per_item)
             need += btile::items_tab_bytes(r.n, N);
         p.need = need > p.need ? need : p.need;
-        p.name = common_name(p.name, p.route[r.table].name);
     }
     return p;
 }
 
 static size_t ibp_ws_bound(int eb, int B, int N, int h, int w, int H, int W, int f, unsigned flags)
 {
-    const int Bc = B < SRX_MAX_BATCH_PER_LAUNCH ? (B > 0 ? B : 1) : SRX_MAX_BATCH_PER_LAUNCH;
-    return srx_ibp_workspace_bytes(eb, B, N, h, w, H, W, f, flags) + btile::items_tab_bytes(Bc, N > 0 ? N : 1);
+    return srx_ibp_workspace_bytes(eb, B, N, h, w, H, W, f, flags) + btile::items_tab_bytes(std::max(ibp_chunk_items(B), 1), N > 0 ? N : 1);
 }
 
 template <typename T>
@@ -122,7 +132,7 @@ static int ibp_dispatch_items(const T *lr, int B, int N, int h, int w, const dou
         return SRX_E_INVALID;
     if (N > SRX_MAX_FRAMES || kh * kw > SRX_MAX_KERNEL_TAPS || !plane_fits(sizeof(T), N, h, w, H, W))
         return SRX_E_UNSUPPORTED;
-    const IbpPlan p = plan_ibp((int)sizeof(T), B, N, h, w, H, W, f, sh, k, kh, kw, flags);
+    const Plan p = plan_ibp((int)sizeof(T), B, N, h, w, H, W, f, sh, k, kh, kw, flags);
     if (p.status != SRX_OK)
         return p.status;
     if (ws_short(ws, wsb, p.need))
@@ -141,7 +151,7 @@ static int ibp_dispatch_items(const T *lr, int B, int N, int h, int w, const dou
             continue;
         }
         for (int b0 = r.b0; b0 < r.b0 + r.n; b0 += SRX_MAX_BATCH_PER_LAUNCH) {  // as ibp_dispatch
-            const int bc = r.b0 + r.n - b0 < SRX_MAX_BATCH_PER_LAUNCH ? r.b0 + r.n - b0 : SRX_MAX_BATCH_PER_LAUNCH;
+            const int bc = ibp_chunk_items(r.b0 + r.n - b0);
             SRX_TRY((ibp_run<T, T>(rt, lr + b0 * fr, bc, N, h, w, shr, k, kh, kw, hr_init + b0 * P, H, W, f, n_iter, step, hr + b0 * P,
                                    errors ? errors + (size_t)b0 * n_iter : nullptr, ws, wsb, st)));
         }
@@ -182,107 +192,78 @@ __global__ void __launch_bounds__(256)
 
 template <typename T> static inline size_t saa_tab_bytes(int B, int N) { return align_up((size_t)B * N * sizeof(fused::FrameTap<T>)); }
 
-static inline int saa_cap(int N) { return SRX_MAX_BATCH_PER_LAUNCH / N > 0 ? SRX_MAX_BATCH_PER_LAUNCH / N : 1; }
-
 static size_t saa_ws_bound(int eb, int B, int N, int h, int w, int f)
 {
-    const int n = N > 0 ? N : 1, cap = saa_cap(n), Bc = B < cap ? (B > 0 ? B : 1) : cap;
+    const int n = N > 0 ? N : 1, Bc = std::max(saa_chunk_items(B, n), 1);
     return srx_saa_workspace_bytes(eb, B, N, h, w, f) + (eb == 4 ? saa_tab_bytes<float>(Bc, n) : saa_tab_bytes<double>(Bc, n));
 }
 
-// fused::saa with one table per item: sh [B][N][2]; tab: B * N taps of device memory
+// fused::saa with one table per item: sh [B][N][2]; tab: B * N taps of device memory.  The taps go up before the body runs; its own
+// refusals cannot follow them, the dispatcher having held the workspace to the bound and the run to one chunk.
 template <typename T>
 static int saa_fused_items(const T *lr, int B, int N, int h, int w, const double *sh, int f, T *out, fused::FrameTap<T> *tab, void *ws, size_t wsb,
                            hipStream_t st)
 {
     using namespace fused;
     static_assert(sizeof(FrameTap<T>) % sizeof(int) == 0, "the taps travel as words");
-    if ((long)B * N > 65535)
-        return SRX_E_UNSUPPORTED;
-    const int H = h * f, W = w * f, Hp = H + 2 * SRX_NPAD, Wp = W + 2 * SRX_NPAD;
-    Arena ar(ws, wsb);
-    T *coef = ar.take<T>((size_t)B * N * h * w), *cscr = ar.take<T>((size_t)B * N * h * w);
-    T *up = ar.take<T>((size_t)B * H * W);
-    T *pad = ar.take<T>((size_t)B * Hp * Wp), *scr = ar.take<T>((size_t)B * Hp * Wp);
-    AxisTap<T> *zy = ar.take<AxisTap<T>>(H), *zx = ar.take<AxisTap<T>>(W);
-    if (!ar.ok)
-        return SRX_E_WORKSPACE;
-    {
-        btile::ParamWords pw = {};
-        int *dst = reinterpret_cast<int *>(tab);
-        constexpr int TW = (int)(sizeof(FrameTap<T>) / sizeof(int));
-        for (size_t i = 0; i < (size_t)B * N; i++) {
-            FrameTap<T> ft;
-            memset(&ft, 0, sizeof ft);
-            make_tap<T>(-sh[2 * i] * f, -sh[2 * i + 1] * f, 0, ft);  // shift(+d): out[r] = in[r - d]
-            int words[TW];
-            memcpy(words, &ft, sizeof ft);
-            for (int j = 0; j < TW; j++) {
-                pw.w[pw.n++] = words[j];
-                if (pw.n == btile::PARAM_WORDS || (j == TW - 1 && i + 1 == (size_t)B * N)) {
-                    hipLaunchKernelGGL(btile::k_param_words, dim3(1), dim3(256), 0, st, pw, dst);
-                    SRX_CHECK_LAUNCH();
-                    dst += pw.n, pw.n = 0;
-                }
-            }
-        }
+    constexpr int TW = (int)(sizeof(FrameTap<T>) / sizeof(int));
+    btile::ParamUpload words{st, reinterpret_cast<int *>(tab)};
+    for (size_t i = 0; i < (size_t)B * N; i++) {
+        FrameTap<T> ft;
+        memset(&ft, 0, sizeof ft);
+        make_tap<T>(-sh[2 * i] * f, -sh[2 * i + 1] * f, 0, ft);  // shift(+d): out[r] = in[r - d]
+        int ftw[TW];
+        memcpy(ftw, &ft, sizeof ft);
+        SRX_TRY(words.put(ftw, TW));
     }
-    SRX_TRY(prefilter2d_from(lr, coef, cscr, B * N, h, w, MODE_MIRROR, st));
-    const double zy_ = H > 1 ? (double)(h - 1) / (double)(H - 1) : 1.0;
-    const double zx_ = W > 1 ? (double)(w - 1) / (double)(W - 1) : 1.0;
-    SRX_TRY(build_taps(zy, H, h, TAP_ZOOM, 1, zy_, st));
-    SRX_TRY(build_taps(zx, W, w, TAP_ZOOM, 1, zx_, st));
-    for (int q = 0; q < N; q++) {
-        SRX_TRY(interp_strided(coef + (size_t)q * h * w, (size_t)N * h * w, B, h, w, zy, zx, H, W, up, st));
-        const dim3 grd(cdiv(Wp, 64), cdiv(Hp, 4), B), blk(64, 4);
+    SRX_TRY(words.finish());
+    const int H = h * f, W = w * f;
+    auto fir = [&](int q, dim3 grd, dim3 blk, const T *up, T *pad) -> int {
         if (q == 0)
             SRX_LAUNCH(KID_FIR_PAD, (k_fir_pad_items<T, false>), grd, blk, 0, st, up, H, W, tab, N, q, pad);
         else
             SRX_LAUNCH(KID_FIR_PAD, (k_fir_pad_items<T, true>), grd, blk, 0, st, up, H, W, tab, N, q, pad);
-    }
-    SRX_TRY(prefilter2d_fast(pad, scr, B, Hp, Wp, MODE_REFLECT, st));
-    SRX_LAUNCH(KID_CROP_DIV, k_crop_div<T>, dim3(cdiv(W, 64), cdiv(H, 4), B), dim3(64, 4), 0, st, pad, H, W, (T)N, out);
-    return SRX_OK;
+        return SRX_OK;
+    };
+    return saa_with<T>(fir, lr, B, N, h, w, f, out, ws, wsb, st);
+}
+
+// (what the call must bring is the shape-only bound: there is no exact query for shift_and_add)
+static Plan plan_saa(int eb, int B, int N, int h, int w, int f, const double *sh, unsigned flags)
+{
+    Plan p = plan_runs(sh, B, N, PATH_FUSED, saa_chunk_items(B, N), [&](const double *s) { return route_saa(N, h, w, f, s, flags); });
+    p.need = saa_ws_bound(eb, B, N, h, w, f);
+    return p;
 }
 
 template <typename T>
 static int saa_dispatch_items(const T *lr, int B, int N, int h, int w, const double *sh, int f, T *out, void *ws, size_t wsb, hipStream_t st,
                               unsigned flags)
 {
-    if (!lr || !sh || !out || B <= 0 || N <= 0 || h <= 0 || w <= 0 || f <= 0)
-        return SRX_E_INVALID;
-    if (N > SRX_MAX_FRAMES || (size_t)h * f >= ((size_t)1 << 30) || (size_t)w * f >= ((size_t)1 << 30) || !plane_fits(sizeof(T), N, h, w, h * f, w * f))
-        return SRX_E_UNSUPPORTED;
-    // the route of every distinct table (saa_dispatch's decision), and every refusal, before anything is queued
-    const Tables t = distinct_tables(sh, B, N);
-    std::vector<char> batched;
-    for (int b : t.first) {
-        const double *s = sh + (size_t)b * 2 * N;
-        const bool can_fuse = fused::saa_eligible(N, h, w, s, f);
-        if ((flags & SRX_FLAG_FUSED) && !can_fuse)
-            return SRX_E_UNSUPPORTED;
-        const bool fuse = can_fuse && !(flags & SRX_FLAG_COMPOSED);
-        batched.push_back(fuse && !(!(flags & SRX_FLAG_PER_FRAME) && mosaic::saa_eligible(N, h, w, s, f)));
-    }
-    if (ws_short(ws, wsb, saa_ws_bound((int)sizeof(T), B, N, h, w, f)))
+    SRX_TRY(saa_check(sizeof(T), lr, B, N, h, w, sh, f, out));
+    const Plan p = plan_saa((int)sizeof(T), B, N, h, w, f, sh, flags);
+    if (p.status != SRX_OK)  // (before the workspace, unlike saa_dispatch: see there)
+        return p.status;
+    if (ws_short(ws, wsb, p.need))
         return SRX_E_WORKSPACE;
-    const int cap = saa_cap(N);
-    const size_t tabb = saa_tab_bytes<T>(B < cap ? B : cap, N);
+    g_last_path = p.name;
+    // the head of the workspace holds the taps of one per-item run, every run's driver gets the rest
+    const size_t tabb = saa_tab_bytes<T>(saa_chunk_items(B, N), N);
     fused::FrameTap<T> *tab = reinterpret_cast<fused::FrameTap<T> *>(ws);
     void *wsr = (char *)ws + tabb;
     const size_t wsrb = wsb - tabb;
     const size_t fr = (size_t)N * h * w, P = (size_t)h * f * w * f;
-    const char *name = nullptr;
-    for (const Run &r : make_runs(t, batched, B, cap)) {
+    for (const Run &r : p.runs) {
         const double *shr = sh + (size_t)r.b0 * 2 * N;
         if (r.per_item) {
-            g_last_path = "fused";
             SRX_TRY(saa_fused_items<T>(lr + r.b0 * fr, r.n, N, h, w, shr, f, out + r.b0 * P, tab, wsr, wsrb, st));
-        } else
-            SRX_TRY((saa_dispatch<T, T>(lr + r.b0 * fr, r.n, N, h, w, shr, f, out + r.b0 * P, wsr, wsrb, st, flags)));
-        name = common_name(name, g_last_path);
+            continue;
+        }
+        for (int b0 = r.b0, bc; b0 < r.b0 + r.n; b0 += bc) {  // as saa_dispatch
+            bc = saa_chunk_items(r.b0 + r.n - b0, N);
+            SRX_TRY((saa_run<T, T>(p.route[r.table], lr + b0 * fr, bc, N, h, w, shr, f, out + b0 * P, wsr, wsrb, st)));
+        }
     }
-    g_last_path = name;
     return SRX_OK;
 }
 

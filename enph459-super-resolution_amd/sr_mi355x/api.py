@@ -143,7 +143,8 @@ def _fn(name, prec):
 
 
 def last_path():
-    """Which code path the last shift_and_add/ibp call took: 'fused' or 'composed'."""
+    """The name of the code path the last shift_and_add / ibp call on this thread took (include/srx.h, srx_last_path): 'mosaic', 'fused',
+    'composed', ibp's kernel names such as 'patch' or 'btile', or 'mixed' after a per-item call whose runs took different ones."""
     return _lib.load().srx_last_path().decode()
 
 

@@ -167,6 +167,10 @@ int srx_backproject_f64(const double *err, int B, int eh, int ew, const double *
 /* ---- shift_and_add(lr_list, shifts_yx, factor, order=3): run_sr.py:181-187.
  * lr [B, N, h, w] -> out [B, h*f, w*f]. */
 size_t srx_saa_workspace_bytes(int elem_bytes, int B, int N, int h, int w, int factor);
+/* The name srx_last_path() reports after an srx_saa call with these arguments: "mosaic", "fused" or "composed" ("none" for arguments the
+ * call refuses, SRX_FLAG_FUSED on a table that cannot fuse included).  Decided from shape, shifts and flags on the host: no device,
+ * nothing queued. */
+const char *srx_saa_path_for(int elem_bytes, int N, int h, int w, int factor, const double *shifts_yx, unsigned flags);
 int srx_saa_f32(const float *lr, int B, int N, int h, int w, const double *shifts_yx, int factor, float *out,
                 void *ws, size_t ws_bytes, srx_stream_t stream, unsigned flags);
 int srx_saa_f64(const double *lr, int B, int N, int h, int w, const double *shifts_yx, int factor, double *out,
@@ -197,7 +201,7 @@ int srx_ibp_f64(const double *lr, int B, int N, int h, int w, const double *shif
  * uint8 [B, N, h, w]; _f32 / _f64 is the type of the state, the output and the arithmetic, as everywhere else.  (T)uint8 is exact, so a
  * call returns the same bits as srx_saa_* / srx_ibp_* on the converted frames.  Everything else is the float call's: argument checks and
  * limits (the 2 GiB rule counts the frames as T), flags, chunking of large batches, srx_last_path(), the MSE trace, hr_out == hr_init;
- * the route is the float call's too (srx_ibp_path_for with elem_bytes = sizeof(T) answers for both).  lr needs byte alignment only (a
+ * the route is the float call's too (srx_ibp_path_for / srx_saa_path_for with elem_bytes = sizeof(T) answer for both).  lr needs byte alignment only (a
  * frame of odd h w starts on an odd byte).
  *   mosaic family ("patch", "stile", "ctile", "ztile", "dtile", "atile", "mosaic", and shift_and_add's "mosaic"): the kernels that build
  *     the tables read the bytes themselves; no converted copy exists anywhere.  shift_and_add converts frames larger than 64 x 64 into a
@@ -230,7 +234,7 @@ int srx_ibp_u8lr_f64(const uint8_t *lr, int B, int N, int h, int w, const double
  * hr_init.  The header's conventions hold: the tables are read before the call returns, nothing is allocated on the device, only kernels
  * and device-to-device copies are queued, the memory contract holds, and the argument checks and limits of the shared-table calls apply
  * per item -- a refusal for any item (SRX_FLAG_FUSED on an item that cannot fuse) is decided on the host before anything is queued.
- * Routing: the route is decided once per DISTINCT table (what srx_ibp_path_for answers on shifts_byx[b]) and the batch is walked in
+ * Routing: the route is decided once per DISTINCT table (what srx_ibp_path_for / srx_saa_path_for answer on shifts_byx[b]) and the batch is walked in
  * maximal runs of consecutive items:
  *   items that all route to "btile" (float32, x2, per-frame fractional shifts; their tables may all differ): one batch, the kernels take
  *     each item's table and the range of ITS tap origins from a device array;

@@ -46,6 +46,11 @@ def path_for(prec, table, psf, h, w, f, flags=0):
                                         k.shape[0], k.shape[1], flags).decode()
 
 
+def saa_path_for(prec, table, h, w, f, flags=0):
+    sh = np.ascontiguousarray(np.asarray(table, dtype=np.float64))
+    return _lib.load().srx_saa_path_for(EB[prec], len(sh), h, w, f, sh.ctypes.data_as(_lib._HD), flags).decode()
+
+
 _frames_cache = {}
 
 
@@ -182,6 +187,35 @@ def test_shift_and_add_per_item(prec, f):
         name = S.last_path()
         out = S.shift_and_add_batched(lr, np.stack([t] * 3), f, precision=prec)
         assert S.last_path() == name and torch.equal(out, ref)
+
+
+@pytest.mark.parametrize("prec", ["f32", "f64"])
+def test_shift_and_add_routes_match_the_host_query(prec):
+    f, h, w = 2, 40, 56
+    tables = np.stack([N4, jitter(N4, 21), LARGE])
+    lr = frames(3, 4, h, w, prec, seed=4)
+    want = [saa_path_for(prec, t, h, w, f) for t in tables]
+    assert len(set(want)) == 3, want
+    for b in range(3):
+        S.shift_and_add_batched(lr[b:b + 1], tables[b], f, precision=prec)
+        assert S.last_path() == want[b], b
+    S.shift_and_add_batched(lr, tables, f, precision=prec)
+    assert S.last_path() == "mixed"
+
+
+def test_shift_and_add_per_item_run_crosses_the_chunk():
+    """2100 items of 16 frames, every table different and on "fused": a chunk is 32768 // 16 = 2048 items, so the batch is walked as
+    2048 + 52 (about 350 parameter launches for the 336 000 words of taps)"""
+    prec, f, h, w, B, N = "f32", 2, 8, 8, 2100, 16
+    tables = np.stack([jitter(synth.phase_shifts(4), 1000 + b) for b in range(B)])
+    assert all(not np.array_equal(tables[b], tables[b + 1]) for b in range(B - 1))
+    assert {saa_path_for(prec, t, h, w, f) for t in tables} == {"fused"}
+    lr = torch.from_numpy(np.random.default_rng(31).uniform(0.0, 255.0, (B, N, h, w))).to("cuda", DT[prec])
+    out = S.shift_and_add_batched(lr, tables, f, precision=prec)
+    assert S.last_path() == "fused"
+    for b in (0, 2047, 2048, 2099):
+        ref = S.shift_and_add_batched(lr[b:b + 1], tables[b], f, precision=prec)[0]
+        assert torch.equal(out[b], ref), (b, float((out[b] - ref).abs().max()))
 
 
 def test_uint8_frames_with_per_item_tables():
