@@ -896,12 +896,22 @@ size_t srx_register_workspace_bytes(int elem_bytes, int B, int N, int H, int W, 
 int srx_register_f32(const float *frames, int B, int N, int H, int W, int ref, const double *init_yx, int search, int border, int n_iter, double tol,
                      double *shifts, double *score, int *status, void *ws, size_t wsb, srx_stream_t s)
 {
-    return reg::register_frames<float>(frames, B, N, H, W, ref, init_yx, search, border, n_iter, tol, shifts, score, status, ws, wsb, hs(s));
+    return reg::register_frames<float, float>(frames, B, N, H, W, ref, init_yx, search, border, n_iter, tol, shifts, score, status, ws, wsb, hs(s));
 }
 int srx_register_f64(const double *frames, int B, int N, int H, int W, int ref, const double *init_yx, int search, int border, int n_iter,
                      double tol, double *shifts, double *score, int *status, void *ws, size_t wsb, srx_stream_t s)
 {
-    return reg::register_frames<double>(frames, B, N, H, W, ref, init_yx, search, border, n_iter, tol, shifts, score, status, ws, wsb, hs(s));
+    return reg::register_frames<double, double>(frames, B, N, H, W, ref, init_yx, search, border, n_iter, tol, shifts, score, status, ws, wsb, hs(s));
+}
+int srx_register_u8_f32(const uint8_t *frames, int B, int N, int H, int W, int ref, const double *init_yx, int search, int border, int n_iter,
+                        double tol, double *shifts, double *score, int *status, void *ws, size_t wsb, srx_stream_t s)
+{
+    return reg::register_frames<float, uint8_t>(frames, B, N, H, W, ref, init_yx, search, border, n_iter, tol, shifts, score, status, ws, wsb, hs(s));
+}
+int srx_register_u8_f64(const uint8_t *frames, int B, int N, int H, int W, int ref, const double *init_yx, int search, int border, int n_iter,
+                        double tol, double *shifts, double *score, int *status, void *ws, size_t wsb, srx_stream_t s)
+{
+    return reg::register_frames<double, uint8_t>(frames, B, N, H, W, ref, init_yx, search, border, n_iter, tol, shifts, score, status, ws, wsb, hs(s));
 }
 
 size_t srx_psf_estimate_workspace_bytes(int elem_bytes, int N, int H, int W, int halfwidth)

@@ -18,6 +18,13 @@
 //               steps; a singular matrix (det <= 1e-6 trace^2, or trace <= 1e-10 sum w^2) restores the coarse shift.
 //   finish      one more k_reg_gn pass at the final shifts gives the score (zero-mean NCC, what metrics.ecc gives for the crop);
 //               k_reg_finish writes shifts / score / status, the reference rows exactly (0, 0), 1, 0.
+//
+// uint8 frames (srx_register_u8_*: F = uint8_t, T the type of the coefficients and of the arithmetic) run the same launches on the same
+// grids and return the bits of the float call on the converted frames.  (T)uint8 is exact, so k_reg_pad writes the float call's plane and
+// k_reg_gn reads the float call's reference samples.  The coarse stage is k_reg_coarse_u8, in integers: samples are <= 255 and a crop has
+// fewer than 2^29 pixels (a plane is below 2 GiB even as float), so sum t, t^2, t r, r, r^2 are all below 2^29 255^2 < 2^45 -- integers a
+// float64 holds exactly, with every partial sum of them.  The float kernel's float64 sums are therefore those integers whatever the order,
+// and the integer kernel's, converted to double per block, are the same `part` words; k_reg_pick reads them unchanged.
 #pragma once
 #include "srx_common.h"
 #include "srx_metrics.hpp"
@@ -90,15 +97,15 @@ static inline Plan make_plan(int h, int w, int search)
 }
 
 // ---- 'nearest' edge pad of the moving frames: [nf][H + 24][W + 24] ------------------------------------------------------------------
-template <typename T>
-__global__ void __launch_bounds__(256) k_reg_pad(const T *__restrict__ frames, Geo g, T *__restrict__ out)
+template <typename T, typename F>
+__global__ void __launch_bounds__(256) k_reg_pad(const F *__restrict__ frames, Geo g, T *__restrict__ out)
 {
     const int Hp = g.H + 2 * SRX_NPAD, Wp = g.W + 2 * SRX_NPAD;
     const int c = blockIdx.x * 64 + threadIdx.x, r = blockIdx.y * 4 + threadIdx.y, f = blockIdx.z;
     if (r >= Hp || c >= Wp)
         return;
     const int rr = min(max(r - SRX_NPAD, 0), g.H - 1), cc = min(max(c - SRX_NPAD, 0), g.W - 1);
-    out[(size_t)f * Hp * Wp + (size_t)r * Wp + c] = frames[g.plane(f) * g.H * g.W + (size_t)rr * g.W + cc];
+    out[(size_t)f * Hp * Wp + (size_t)r * Wp + c] = (T)frames[g.plane(f) * g.H * g.W + (size_t)rr * g.W + cc];
 }
 
 // ---- coarse search, stage 1: grid (cgx, cgy, nf), block 256 ---------------------------------------------------------------------------
@@ -174,6 +181,133 @@ __global__ void __launch_bounds__(256) k_reg_coarse(const T *__restrict__ frames
     }
 }
 
+// ---- coarse search, stage 1 on bytes: the same grid, blocks and `part` layout; the sums in integers ------------------------------------
+// four consecutive samples p[0..3] of the frame stack [lo, hi) as one word (p[0] in bits 0-7), p on any byte: two aligned word loads and
+// a byte align where both words lie inside the stack, byte loads at its two ends
+__device__ __forceinline__ unsigned load4_u8(const uint8_t *p, const uint8_t *lo, const uint8_t *hi)
+{
+    const uintptr_t a = (uintptr_t)p, a0 = a & ~(uintptr_t)3;
+    if (a0 >= (uintptr_t)lo && a0 + 8 <= (uintptr_t)hi) {
+        const unsigned *q = (const unsigned *)a0;
+        return __builtin_amdgcn_alignbyte(q[1], q[0], (unsigned)(a & 3));
+    }
+    return (unsigned)p[0] | (unsigned)p[1] << 8 | (unsigned)p[2] << 16 | (unsigned)p[3] << 24;
+}
+
+// The chunk and its window are staged as packed bytes, 16 words per chunk row and TWW = 19 per window row (64 + 2 * 4 bytes and the word
+// the byte align reads behind them; 19 is odd, so the rows a wave's offsets read fall on different banks).  Thread (offset o, group g)
+// takes the words g, g + G, ... of the chunk: the four moving samples at offset o come from two aligned LDS words and a byte align, and
+// three dot4 add t, t t and t r of the four pixels.  r and r r are added by the thread that stages the reference word.  Samples right of a
+// partial chunk are zero in the reference word and masked out of the moving word.
+// Overflow: the 32-bit accumulators hold the products of ONE 64 x 16 chunk, at most 1024 * 255^2 < 2^27, and are added into 64-bit ones
+// after every chunk; a block's 64-bit totals stay below 2^45 (head comment) and convert to double exactly.
+__global__ void __launch_bounds__(256) k_reg_coarse_u8(const uint8_t *__restrict__ frames, Geo g, int search, int rows_per, Start c0,
+                                                       double *__restrict__ part)
+{
+    constexpr int CWW = CW / 4, TWW = (CW + 2 * MAX_SEARCH) / 4 + 1, TH = CH + 2 * MAX_SEARCH;
+    __shared__ unsigned sr[CH][CWW];
+    __shared__ unsigned stl[TH][TWW];
+    __shared__ unsigned long long red[256 * 3];  // [group][offset][3]: G noff <= 256
+    __shared__ unsigned long long redr[4][2];    // [wave]
+    const int f = blockIdx.z, tid = threadIdx.x;
+    const int D = 2 * search + 1, noff = D * D, G = 256 / noff;
+    const int o = tid % noff, grp = tid / noff;  // grp == G: idle
+    const int oy = o / D, ox = o - oy * D;       // offset + search
+    const int x0 = blockIdx.x * CW, cols = min(CW, g.w - x0), nw = (cols + 3) >> 2;
+    const int y0 = blockIdx.y * rows_per, y1 = min(y0 + rows_per, g.h);
+    const uint8_t *lo = frames, *hi = frames + (size_t)g.B * g.N * g.H * g.W;
+    const uint8_t *t = frames + g.plane(f) * g.H * g.W, *r = frames + g.ref_plane(f) * g.H * g.W;
+    const int k = g.moving(f), cy = c0.c[k][0] - search, cx = c0.c[k][1] - search;
+    const int wsh = ox >> 2;
+    const unsigned bsh = ox & 3;
+    unsigned long long st = 0, stt = 0, str = 0, s_r = 0, s_rr = 0;
+    for (int ya = y0; ya < y1; ya += CH) {
+        const int rows = min(CH, y1 - ya), th = rows + 2 * search;
+        __syncthreads();
+        for (int i = tid; i < rows * CWW; i += 256) {
+            const int py = i / CWW, wx = i - py * CWW, n = min(cols - 4 * wx, 4);  // samples of this word inside the crop
+            const uint8_t *p = r + (size_t)(g.m + ya + py) * g.W + g.m + x0 + 4 * wx;
+            unsigned v = 0;
+            if (n == 4)
+                v = load4_u8(p, lo, hi);
+            else
+                for (int b = 0; b < n; b++)
+                    v |= (unsigned)p[b] << (8 * b);
+            sr[py][wx] = v;
+            s_r += __builtin_amdgcn_udot4(v, 0x01010101u, 0u, false), s_rr += __builtin_amdgcn_udot4(v, v, 0u, false);
+        }
+        for (int i = tid; i < th * TWW; i += 256) {
+            const int py = i / TWW, wx = i - py * TWW;
+            const int yy = min(max(g.m + ya + py + cy, 0), g.H - 1), xs = g.m + x0 + 4 * wx + cx;
+            const uint8_t *p = t + (size_t)yy * g.W;
+            unsigned v = 0;
+            if (xs >= 0 && xs + 3 < g.W)
+                v = load4_u8(p + xs, lo, hi);
+            else
+                for (int b = 0; b < 4; b++)
+                    v |= (unsigned)p[min(max(xs + b, 0), g.W - 1)] << (8 * b);
+            stl[py][wx] = v;
+        }
+        __syncthreads();
+        if (grp < G) {
+            unsigned a_t = 0, a_tt = 0, a_tr = 0;  // one chunk: < 2^27
+            for (int q = grp; q < rows * CWW; q += G) {
+                const int py = q / CWW, wx = q - py * CWW;
+                if (wx >= nw)
+                    continue;
+                const unsigned rv = sr[py][wx];
+                const unsigned *mw = &stl[py + oy][wx + wsh];
+                unsigned tv = __builtin_amdgcn_alignbyte(mw[1], mw[0], bsh);
+                const int n = cols - 4 * wx;
+                if (n < 4)
+                    tv &= (1u << (8 * n)) - 1u;
+                a_t = __builtin_amdgcn_udot4(tv, 0x01010101u, a_t, false);
+                a_tt = __builtin_amdgcn_udot4(tv, tv, a_tt, false);
+                a_tr = __builtin_amdgcn_udot4(tv, rv, a_tr, false);
+            }
+            st += a_t, stt += a_tt, str += a_tr;
+        }
+    }
+    // the groups' sums, added by thread o < noff; the reference's, by wave and then by thread 0
+    s_r = wave_sum(s_r), s_rr = wave_sum(s_rr);
+    __syncthreads();
+    if (grp < G)
+        red[3 * tid] = st, red[3 * tid + 1] = stt, red[3 * tid + 2] = str;
+    if ((tid & 63) == 0)
+        redr[tid >> 6][0] = s_r, redr[tid >> 6][1] = s_rr;
+    __syncthreads();
+    double *out = part + ((size_t)f * gridDim.x * gridDim.y + blockIdx.y * gridDim.x + blockIdx.x) * (3 * noff + 2);
+    if (tid < noff) {
+        unsigned long long a0 = 0, a1 = 0, a2 = 0;
+        for (int q = 0; q < G; q++) {
+            const unsigned long long *e = red + 3 * (q * noff + tid);
+            a0 += e[0], a1 += e[1], a2 += e[2];
+        }
+        out[3 * tid] = (double)a0, out[3 * tid + 1] = (double)a1, out[3 * tid + 2] = (double)a2;
+    }
+    if (tid == 0) {
+        unsigned long long b0 = 0, b1 = 0;
+        for (int q = 0; q < 4; q++)
+            b0 += redr[q][0], b1 += redr[q][1];
+        out[3 * noff] = (double)b0, out[3 * noff + 1] = (double)b1;
+    }
+}
+
+// the coarse kernel of frames of type F.  SRX_REG_COARSE_PLAIN (a development build: profiles/README.md) runs uint8 frames through the
+// float kernel's structure with F = uint8_t in its loads and LDS planes instead: the ablation k_reg_coarse_u8 was measured against.
+template <typename F>
+static inline void launch_coarse(const F *frames, const Geo &g, int search, const Plan &p, const Start &c0, double *part, hipStream_t st)
+{
+    hipLaunchKernelGGL(k_reg_coarse<F>, dim3(p.cgx, p.cgy, g.nf()), dim3(256), 0, st, frames, g, search, p.crow, c0, part);
+}
+#ifndef SRX_REG_COARSE_PLAIN
+template <>
+inline void launch_coarse<uint8_t>(const uint8_t *frames, const Geo &g, int search, const Plan &p, const Start &c0, double *part, hipStream_t st)
+{
+    hipLaunchKernelGGL(k_reg_coarse_u8, dim3(p.cgx, p.cgy, g.nf()), dim3(256), 0, st, frames, g, search, p.crow, c0, part);
+}
+#endif
+
 __device__ __forceinline__ double zm_ncc(double n, double st, double stt, double sr, double srr, double str)
 {
     const double vt = stt - st * st / n, vr = srr - sr * sr / n;
@@ -245,8 +379,8 @@ __device__ __forceinline__ void taps_d(double u, double w[4], double dw[4])
 
 // ---- refinement / score pass: grid (ggx, ggy, nf), block 256 (one crop column per thread, rows_per rows) -----------------------------
 // all = 0: frozen frames are skipped (their partials are never read); all = 1: every frame (the score pass)
-template <typename T>
-__global__ void __launch_bounds__(256) k_reg_gn(const T *__restrict__ coef, const T *__restrict__ frames, Geo g, int rows_per,
+template <typename T, typename F>
+__global__ void __launch_bounds__(256) k_reg_gn(const T *__restrict__ coef, const F *__restrict__ frames, Geo g, int rows_per,
                                                 const double *__restrict__ sd, const int *__restrict__ si, int all, double *__restrict__ part)
 {
     __shared__ double sh[4 * NG];
@@ -271,7 +405,7 @@ __global__ void __launch_bounds__(256) k_reg_gn(const T *__restrict__ coef, cons
         v[i] = 0.0;
     if (x < g.w) {
         const T *c = coef + (size_t)f * Hp * Wp;
-        const T *r = frames + g.ref_plane(f) * g.H * g.W + g.m + x;
+        const F *r = frames + g.ref_plane(f) * g.H * g.W + g.m + x;
         // clamped tap columns ('nearest' on the padded coefficients; never taken for shifts inside the margin)
         int cx[4];
         const int bx = g.m + x + (int)fx - 1 + SRX_NPAD;
@@ -399,8 +533,9 @@ static inline size_t workspace_bytes(int elem_bytes, int B, int N, int H, int W,
            align_up(nf * gn_blocks_max(w) * NG * sizeof(double)) + align_up(nf * SD * sizeof(double)) + align_up(nf * SI * sizeof(int));
 }
 
-template <typename T>
-static int register_frames(const T *frames, int B, int N, int H, int W, int ref, const double *init, int search, int border, int n_iter,
+// F: the frames' type (T, or uint8_t: srx_register_u8_*); T: the coefficients and the arithmetic
+template <typename T, typename F>
+static int register_frames(const F *frames, int B, int N, int H, int W, int ref, const double *init, int search, int border, int n_iter,
                            double tol, double *shifts, double *score, int *status, void *ws, size_t wsb, hipStream_t st)
 {
     if (!frames || !shifts || B <= 0 || N < 2 || H <= 0 || W <= 0 || ref < 0 || ref >= N || search < 0 || search > MAX_SEARCH || border < 0 ||
@@ -432,21 +567,21 @@ static int register_frames(const T *frames, int B, int N, int H, int W, int ref,
     int *si = ar.take<int>((size_t)nf * SI);
     if (!ar.ok)
         return SRX_E_WORKSPACE;
-    hipLaunchKernelGGL(k_reg_pad<T>, dim3(cdiv(W + 2 * SRX_NPAD, 64), cdiv(H + 2 * SRX_NPAD, 4), nf), dim3(64, 4), 0, st, frames, g, coef);
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_reg_pad<T, F>), dim3(cdiv(W + 2 * SRX_NPAD, 64), cdiv(H + 2 * SRX_NPAD, 4), nf), dim3(64, 4), 0, st, frames, g, coef);
     SRX_CHECK_LAUNCH();
     SRX_TRY(prefilter2d(coef, scratch, nf, H + 2 * SRX_NPAD, W + 2 * SRX_NPAD, MODE_REFLECT, st));
-    hipLaunchKernelGGL(k_reg_coarse<T>, dim3(p.cgx, p.cgy, nf), dim3(256), 0, st, frames, g, search, p.crow, c0, cpart);
+    launch_coarse<F>(frames, g, search, p, c0, cpart, st);
     SRX_CHECK_LAUNCH();
     hipLaunchKernelGGL(k_reg_pick, dim3(nf), dim3(256), 0, st, cpart, p.cgx * p.cgy, g, search, c0, sd, si);
     SRX_CHECK_LAUNCH();
     const dim3 gg(p.ggx, p.ggy, nf);
     for (int it = 0; it < n_iter; it++) {
-        hipLaunchKernelGGL(k_reg_gn<T>, gg, dim3(GW), 0, st, coef, frames, g, p.grow, sd, si, 0, gpart);
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_reg_gn<T, F>), gg, dim3(GW), 0, st, coef, frames, g, p.grow, sd, si, 0, gpart);
         SRX_CHECK_LAUNCH();
         hipLaunchKernelGGL(k_reg_solve, dim3(nf), dim3(64), 0, st, gpart, p.ggx * p.ggy, n_iter, tol, sd, si);
         SRX_CHECK_LAUNCH();
     }
-    hipLaunchKernelGGL(k_reg_gn<T>, gg, dim3(GW), 0, st, coef, frames, g, p.grow, sd, si, 1, gpart);
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_reg_gn<T, F>), gg, dim3(GW), 0, st, coef, frames, g, p.grow, sd, si, 1, gpart);
     SRX_CHECK_LAUNCH();
     hipLaunchKernelGGL(k_reg_finish, dim3(B * N), dim3(64), 0, st, gpart, p.ggx * p.ggy, g, n_iter, tol, sd, si, shifts, score, status);
     SRX_CHECK_LAUNCH();

@@ -50,6 +50,7 @@ _TYPED = {
     "srx_edge_bins_{T}": (_I, [_P, _I, _I, _D, _D, _D, _I, _D, _D, _I, _P, _P, _Z, _P]),
     "srx_ssim_{T}": (_I, [_P, _P, _I, _I, _I, _I, _I, _HD, _I, _D, _D, _D, _P, _P, _P, _P, _Z, _P]),
     "srx_register_{T}": (_I, [_P, _I, _I, _I, _I, _I, _HD, _I, _I, _I, _D, _P, _P, _P, _P, _Z, _P]),
+    "srx_register_u8_{T}": (_I, [_P, _I, _I, _I, _I, _I, _HD, _I, _I, _I, _D, _P, _P, _P, _P, _Z, _P]),
     "srx_psf_estimate_{T}": (_I, [_P, _I, _I, _I, _I, _P, _P, _P, _Z, _P]),
 }
 _PLAIN = {

@@ -1,4 +1,5 @@
-"""Sub-pixel frame registration on the device (translation only), on top of libsrx.so's `srx_register_*` (include/srx.h).
+"""Sub-pixel frame registration on the device (translation only), on top of libsrx.so's `srx_register_*` and, for uint8 frames,
+`srx_register_u8_*` (include/srx.h).
 
 Every reconstruction needs the frames' shifts_yx; estimate_shifts measures them from the frames themselves: an integer NCC search
 around the caller's table, then Gauss-Newton on the cubic B-spline interpolant of each frame, all on the device with one
@@ -52,6 +53,25 @@ def _check(shape, ref, init, anchor, search, border, n_iter, tol):
     return B, N, H, W, batched, init, anchor
 
 
+def _is_u8(frames):
+    """every frame is uint8 (a numpy array, a torch tensor, or a list of either): the stack goes to srx_register_u8_* as bytes"""
+    def u8(a):
+        return a.dtype == torch.uint8 if isinstance(a, torch.Tensor) else isinstance(a, np.ndarray) and a.dtype == np.uint8
+    return u8(frames) if isinstance(frames, (torch.Tensor, np.ndarray)) else all(u8(f) for f in frames)
+
+
+def _stack_u8(frames):
+    """uint8 frames -> one contiguous uint8 CUDA tensor; host arrays are uploaded as bytes"""
+    if isinstance(frames, np.ndarray):
+        frames = torch.from_numpy(np.ascontiguousarray(frames))
+    elif not isinstance(frames, torch.Tensor):
+        if isinstance(frames[0], torch.Tensor):
+            frames = torch.stack([f.to(api._device()) for f in frames])
+        else:
+            frames = torch.from_numpy(np.stack(frames))
+    return frames.to(api._device()).contiguous()
+
+
 def workspace_bytes(elem_bytes, B, N, H, W, search):
     """srx_register_workspace_bytes (no GPU needed)"""
     return int(_lib.load().srx_register_workspace_bytes(int(elem_bytes), int(B), int(N), int(H), int(W), int(search)))
@@ -64,10 +84,13 @@ def estimate_shifts(frames, ref=0, init=None, anchor=None, search=2, border=8, n
     the frames were taken with (the coarse search starts at rint(init[k] - init[ref])); anchor: the reference frame's known shift
     (default init[ref], or (0, 0)).  Returns host float64 anchor + d_k, [N, 2] (or [B, N, 2]); with full=True also the zero-mean
     NCC score at the returned shift and the status per frame (0 ok, 1 singular, 2 coarse argmax on the search boundary, 3 not
-    converged; see STATUS), float64 and int32 [N] (or [B, N]).  Frames with a nonzero status are best replaced by the table."""
+    converged; see STATUS), float64 and int32 [N] (or [B, N]).  Frames with a nonzero status are best replaced by the table.
+    uint8 frames (the camera's own samples) are uploaded and registered as bytes (srx_register_u8_*): the same bits as the frames
+    converted to the compute precision give, with no float copy of them anywhere."""
     B, N, H, W, batched, init, anchor = _check(_shape(frames), ref, init, anchor, search, border, n_iter, tol)
     prec = precision or api.get_precision()
-    x, _ = api._stack_dev(frames, prec)
+    name = "srx_register_u8" if _is_u8(frames) else "srx_register"
+    x = _stack_u8(frames) if name == "srx_register_u8" else api._stack_dev(frames, prec)[0]
     x = x.reshape(B, N, H, W)
     dev = x.device
     shifts = torch.empty((B, N, 2), dtype=torch.float64, device=dev)
@@ -75,8 +98,8 @@ def estimate_shifts(frames, ref=0, init=None, anchor=None, search=2, border=8, n
     status = torch.empty((B, N), dtype=torch.int32, device=dev)
     wt, wp, wn = api._ws(workspace_bytes(api._ELEM[prec], B, N, H, W, search))
     hinit = None if init is None else init.ctypes.data_as(_lib._HD)
-    _lib.check(api._fn("srx_register", prec)(api._p(x), B, N, H, W, int(ref), hinit, int(search), int(border), int(n_iter), float(tol),
-                                             api._p(shifts), api._p(score), api._p(status), wp, wn, api._stream()), "srx_register")
+    _lib.check(api._fn(name, prec)(api._p(x), B, N, H, W, int(ref), hinit, int(search), int(border), int(n_iter), float(tol),
+                                   api._p(shifts), api._p(score), api._p(status), wp, wn, api._stream()), name)
     d = shifts.cpu().numpy() + anchor
     sc, st = score.cpu().numpy(), status.cpu().numpy()
     if not batched:

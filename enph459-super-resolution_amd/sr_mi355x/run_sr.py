@@ -41,7 +41,8 @@ def main(argv=None):
                     help="with --psf measured: estimate the PSF from the pinhole frames on the device (uint8 frames uploaded as they are)")
     ap.add_argument("--u8-frames", action="store_true",
                     help="keep the 8-bit frames as bytes on the device (mono_cal_target, mono_barcodes, rgb_barcodes): shift_and_add and ibp "
-                         "read them through srx_saa_u8lr / srx_ibp_u8lr; the files written are the same")
+                         "read them through srx_saa_u8lr / srx_ibp_u8lr and, with --register, registration through srx_register_u8; the "
+                         "files written are the same")
     args = ap.parse_args(argv)
     rank, world, local_rank = int(os.environ.get("RANK", "0")), int(os.environ.get("WORLD_SIZE", "1")), int(os.environ.get("LOCAL_RANK", "0"))
     dist = None

@@ -18,7 +18,7 @@ written as `convergence.json` instead.
 
 register=True (run_sr --register) measures the shifts from the loaded frames (sr_mi355x.register.estimate_shifts, with the
 table above as init and anchor: one item per rep for the barcode kinds, the rep-averaged red planes for rgb_cal_target) and
-reconstructs with them; frames whose estimate has a nonzero status keep their table shift.  registration.json records the table,
+reconstructs with them (uint8 frames, keep_u8, are measured as bytes); frames whose estimate has a nonzero status keep their table shift.  registration.json records the table,
 the estimates, the shifts used, the scores and the status codes.  Without it, nothing differs.
 """
 import json
@@ -84,7 +84,7 @@ def _to_dev_f(a):
 def _to_dev_frames(decoded, keep_u8):
     """The decoded files of one frame set on the device: float64 (load_gray's cast), or -- keep_u8, and every file 8-bit greyscale -- the
     bytes as they are (a quarter of the upload of float32 frames, an eighth of these; shift_and_add and ibp take them through
-    srx_saa_u8lr / srx_ibp_u8lr).  A colour file (load_gray's channel mean is not an integer) keeps the whole set in float64."""
+    srx_saa_u8lr / srx_ibp_u8lr, registration through srx_register_u8).  A colour file (load_gray's channel mean is not an integer) keeps the whole set in float64."""
     if keep_u8 and all(a.dtype == np.uint8 for a in decoded):
         import torch
         return [torch.from_numpy(np.ascontiguousarray(a)).to(api._device()) for a in decoded]
@@ -211,11 +211,13 @@ def reconstruct(frames, shifts, psf_kernel, n_iter, factor=UPSAMPLE_FACTOR, step
 
 def register_shifts(frame_sets, shifts):
     """register=True: estimate_shifts on B frame sets of one shape (a batch of B items) with the table as init and anchor.
-    -> one (shifts used, registration.json content) per frame set; a frame with a nonzero status keeps its table shift."""
+    -> one (shifts used, registration.json content) per frame set; a frame with a nonzero status keeps its table shift.
+    uint8 frame sets (keep_u8 loaders) are registered as bytes (srx_register_u8: the same bits, no float copy of the frames); float sets
+    (rgb_cal_target's rep-averaged planes) go on as they are."""
     import torch
     from . import register
     table = np.asarray(shifts, dtype=np.float64)
-    lr = _frames_f64(torch.stack([torch.stack(list(fr)) for fr in frame_sets]))  # (srx_register takes float frames)
+    lr = torch.stack([torch.stack(list(fr)) for fr in frame_sets])  # float64, or uint8 (keep_u8 loaders): registered as bytes, the same bits
     est, score, status = register.estimate_shifts(lr, init=table, full=True)
     out = []
     for b in range(len(frame_sets)):

@@ -34,7 +34,8 @@
  *     takes would have carved less.  Image, output and errors pointers need only the alignment
  *     of their element type (a frame sliced out of a batch of odd-sized frames is fine): no
  *     kernel casts a caller pointer to a vector type at an address it has not aligned itself (srx_psf_estimate
- *     peels a scalar head and tail around its 16-byte reads of the frames), and otherwise only arena planes are
+ *     peels a scalar head and tail around its 16-byte reads of the frames, srx_register_u8's coarse kernel reads aligned words inside the
+ *     stack and single bytes at its ends), and otherwise only arena planes are
  *     moved as aligned 16-byte vectors.  One kernel does reach caller memory with 128-bit BUFFER accesses at
  *     addresses that are then only 4-byte aligned (k_ibp_patch parks its state in hr_out, 16 bytes
  *     per lane): that is legal because the HIP runtime runs gfx9 devices in unaligned-access mode
@@ -212,7 +213,9 @@ int srx_ibp_f64(const double *lr, int B, int N, int h, int w, const double *shif
  * Workspace: srx_ibp_u8lr_workspace_bytes_for = srx_ibp_workspace_bytes_for on a mosaic-family route, and that plus
  * align_up(min(B, 32768) N h w sizeof(T)) (256-byte granules) on the others; srx_ibp_u8lr_workspace_bytes (shape only) covers both.
  * srx_saa_u8lr_workspace_bytes = srx_saa_workspace_bytes + align_up(Bc N h w sizeof(T)), Bc = the items of one chunk (B, or
- * max(32768 / N, 1) when B N > 32768), on every route: the query has no shift table to tell them apart. */
+ * max(32768 / N, 1) when B N > 32768), on every route: the query has no shift table to tell them apart.
+ * Registration reads the bytes as well (srx_register_u8_*, with srx_register_* below) and srx_psf_estimate_u8 the pinhole frames: every
+ * stage that touches the camera's frames has a uint8 form. */
 size_t srx_saa_u8lr_workspace_bytes(int elem_bytes, int B, int N, int h, int w, int factor);
 int srx_saa_u8lr_f32(const uint8_t *lr, int B, int N, int h, int w, const double *shifts_yx, int factor, float *out, void *ws,
                      size_t ws_bytes, srx_stream_t stream, unsigned flags);
@@ -390,6 +393,22 @@ int srx_register_f32(const float *frames, int B, int N, int H, int W, int ref, c
                      double *shifts, double *score, int *status, void *ws, size_t ws_bytes, srx_stream_t stream);
 int srx_register_f64(const double *frames, int B, int N, int H, int W, int ref, const double *init_yx, int search, int border, int n_iter,
                      double tol, double *shifts, double *score, int *status, void *ws, size_t ws_bytes, srx_stream_t stream);
+
+/* ---- registration on the camera's own samples: load_gray's uint8 frames (run_sr.py:73-75) without the astype(float64) ----
+ * frames is uint8 [B, N, H, W]; _f32 / _f64 is the type T of the spline coefficients and of the arithmetic, as in srx_saa_u8lr_*.  A call
+ * returns exactly the bits of srx_register_T on the frames converted with srx_u8_to_T: shifts, score and status, the reference rows, frozen
+ * and singular frames, a batch item against the same item alone.  (T)uint8 is exact, so the coefficients and the Gauss-Newton sums are the
+ * float call's; the coarse sums are formed in integers on packed bytes (four samples per dot instruction) -- sums of 8-bit samples and
+ * their products over a crop stay below 2^53, so the float call's float64 sums are those integers, in any order.  Everything else is the
+ * float call's: the argument checks and their order, the limits (the 2 GiB rule counts a padded plane as T), init_yx, the launches, no
+ * allocation and no host synchronisation.  frames needs byte alignment only (frame k of a stack of odd H W starts on any byte, a row of
+ * odd W likewise): the kernel that reads words aligns its own reads and takes single bytes at the two ends of the stack.
+ * Workspace: srx_register_workspace_bytes(sizeof(T), B, N, H, W, search), the float call's -- the coefficient and scratch planes stay T;
+ * no converted copy of the frames exists anywhere. */
+int srx_register_u8_f32(const uint8_t *frames, int B, int N, int H, int W, int ref, const double *init_yx, int search, int border, int n_iter,
+                        double tol, double *shifts, double *score, int *status, void *ws, size_t ws_bytes, srx_stream_t stream);
+int srx_register_u8_f64(const uint8_t *frames, int B, int N, int H, int W, int ref, const double *init_yx, int search, int border, int n_iter,
+                        double tol, double *shifts, double *score, int *status, void *ws, size_t ws_bytes, srx_stream_t stream);
 
 /* ---- the measured PSF from pinhole frames (load_measured_psf, mono_cal_target/run_sr.py:114-152), on DEVICE frames ----
  * frames [N, H, W] of uint8 (_u8: the camera's own samples, no conversion), float or double; reach = halfwidth + 6, side = 2 halfwidth + 1
