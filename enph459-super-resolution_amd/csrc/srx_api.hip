@@ -77,11 +77,46 @@ static int shift_sampled(const T *in, int B, int H, int W, double sy, double sx,
     return interp(pad, B, Hp, Wp, ty, tx, Ho, Wo, out, accumulate, st);
 }
 
-static size_t shift_ws(int eb, int B, int H, int W)
+// ---- workspace layouts of the primitives.  Each is one function: on the call's arena it is the carve, on a counting one (measured())
+// the size its *_workspace_bytes query returns.  The counts: the planes of a [B, H, W] batch and the entries of the two tap tables --
+// H and W in a call, the longer side for both in the bound (tap_bound) ----
+struct ShiftDims {
+    size_t B, H, W, ty, tx;
+};
+static ShiftDims shift_dims(int B, int H, int W) { return {(size_t)B, (size_t)H, (size_t)W, (size_t)H, (size_t)W}; }
+static ShiftDims shift_bound(int eb, int B, int H, int W)
 {
-    const size_t Hp = H + 2 * SRX_NPAD, Wp = W + 2 * SRX_NPAD;
-    return 2 * align_up((size_t)B * Hp * Wp * eb) + 2 * align_up((size_t)(H > W ? H : W) * sizeof(AxisTap<double>));
+    const size_t tl = tap_bound(eb, (size_t)(H > W ? H : W));
+    return {(size_t)B, (size_t)H, (size_t)W, tl, tl};
 }
+template <typename T> struct ShiftTabs {
+    T *pad, *scr;
+    AxisTap<T> *ty, *tx;
+};
+template <typename T> static ShiftTabs<T> carve_shift(Arena &ar, const ShiftDims &d)
+{
+    const size_t Hp = d.H + 2 * SRX_NPAD, Wp = d.W + 2 * SRX_NPAD;
+    return {ar.take<T>(d.B * Hp * Wp), ar.take<T>(d.B * Hp * Wp), ar.take<AxisTap<T>>(d.ty), ar.take<AxisTap<T>>(d.tx)};
+}
+// forward_model: the blurred batch in front; back_project: the zero-inserted and the shifted batch (`planes` of them)
+template <typename T, int planes> struct PlanesShiftTabs {
+    T *p[planes];
+    ShiftTabs<T> s;
+};
+template <typename T, int planes> static PlanesShiftTabs<T, planes> carve_planes_shift(Arena &ar, const ShiftDims &d)
+{
+    PlanesShiftTabs<T, planes> t;
+    for (int i = 0; i < planes; i++)
+        t.p[i] = ar.take<T>(d.B * d.H * d.W);
+    t.s = carve_shift<T>(ar, d);
+    return t;
+}
+template <int planes> static size_t planes_shift_ws(int eb, int B, int H, int W)
+{
+    const ShiftDims d = shift_bound(eb, B, H, W);
+    return measured([&](Arena &m) { eb == 8 ? (void)carve_planes_shift<double, planes>(m, d) : (void)carve_planes_shift<float, planes>(m, d); });
+}
+static size_t shift_ws(int eb, int B, int H, int W) { return planes_shift_ws<0>(eb, B, H, W); }
 
 template <typename T>
 static int shift_cubic(const T *in, int B, int H, int W, double sy, double sx, T *out, void *ws, size_t wsb,
@@ -93,9 +128,7 @@ static int shift_cubic(const T *in, int B, int H, int W, double sy, double sx, T
         return SRX_E_UNSUPPORTED;
     Arena ar(ws, wsb);
     ar.require(shift_ws((int)sizeof(T), B, H, W));
-    T *pad = ar.take<T>((size_t)B * (H + 2 * SRX_NPAD) * (W + 2 * SRX_NPAD));
-    T *scr = ar.take<T>((size_t)B * (H + 2 * SRX_NPAD) * (W + 2 * SRX_NPAD));
-    AxisTap<T> *ty = ar.take<AxisTap<T>>(H), *tx = ar.take<AxisTap<T>>(W);
+    const auto [pad, scr, ty, tx] = carve_shift<T>(ar, shift_dims(B, H, W));
     if (!ar.ok)
         return SRX_E_WORKSPACE;
     return shift_sampled(in, B, H, W, sy, sx, 1, H, W, out, false, pad, scr, ty, tx, false, st);
@@ -115,10 +148,23 @@ static int zoom_into(const T *in, size_t in_stride, int B, int h, int w, int Ho,
     return interp(coef, B, h, w, ty, tx, Ho, Wo, out, false, st);
 }
 
+// zoom: the coefficient planes of a [B, h, w] batch and the two tap tables, h f and w f entries in a call
+struct ZoomDims {
+    size_t B, h, w, ty, tx;
+};
+template <typename T> struct ZoomTabs {
+    T *coef, *cscr;
+    AxisTap<T> *ty, *tx;
+};
+template <typename T> static ZoomTabs<T> carve_zoom(Arena &ar, const ZoomDims &d)
+{
+    return {ar.take<T>(d.B * d.h * d.w), ar.take<T>(d.B * d.h * d.w), ar.take<AxisTap<T>>(d.ty), ar.take<AxisTap<T>>(d.tx)};
+}
 static size_t zoom_ws(int eb, int B, int h, int w, int f)
 {
-    const size_t m = (size_t)(h > w ? h : w) * f;
-    return 2 * align_up((size_t)B * h * w * eb) + 2 * align_up(m * sizeof(AxisTap<double>));
+    const size_t tl = tap_bound(eb, (size_t)(h > w ? h : w) * f);
+    const ZoomDims d{(size_t)B, (size_t)h, (size_t)w, tl, tl};
+    return measured([&](Arena &m) { eb == 8 ? (void)carve_zoom<double>(m, d) : (void)carve_zoom<float>(m, d); });
 }
 
 template <typename T>
@@ -130,18 +176,14 @@ static int zoom_cubic(const T *in, int B, int h, int w, int f, T *out, void *ws,
         return SRX_E_UNSUPPORTED;
     Arena ar(ws, wsb);
     ar.require(zoom_ws((int)sizeof(T), B, h, w, f));
-    T *coef = ar.take<T>((size_t)B * h * w), *cscr = ar.take<T>((size_t)B * h * w);
-    AxisTap<T> *ty = ar.take<AxisTap<T>>((size_t)h * f), *tx = ar.take<AxisTap<T>>((size_t)w * f);
+    const auto [coef, cscr, ty, tx] = carve_zoom<T>(ar, ZoomDims{(size_t)B, (size_t)h, (size_t)w, (size_t)h * f, (size_t)w * f});
     if (!ar.ok)
         return SRX_E_WORKSPACE;
     return zoom_into(in, (size_t)h * w, B, h, w, h * f, w * f, out, coef, cscr, ty, tx, st);
 }
 
 // forward_model = decimate(shift(blur(hr)))
-static size_t forward_ws(int eb, int B, int H, int W)
-{
-    return align_up((size_t)B * H * W * eb) + shift_ws(eb, B, H, W);
-}
+static size_t forward_ws(int eb, int B, int H, int W) { return planes_shift_ws<1>(eb, B, H, W); }
 
 template <typename T>
 static int forward_model(const T *hr, int B, int H, int W, const double *k, int kh, int kw, double sy, double sx, int f,
@@ -153,11 +195,10 @@ static int forward_model(const T *hr, int B, int H, int W, const double *k, int 
         return SRX_E_UNSUPPORTED;
     Arena ar(ws, wsb);
     ar.require(forward_ws((int)sizeof(T), B, H, W));
-    T *b = ar.take<T>((size_t)B * H * W);
-    T *pad = ar.take<T>((size_t)B * (H + 2 * SRX_NPAD) * (W + 2 * SRX_NPAD));
-    T *scr = ar.take<T>((size_t)B * (H + 2 * SRX_NPAD) * (W + 2 * SRX_NPAD));
+    const auto t = carve_planes_shift<T, 1>(ar, shift_dims(B, H, W));
+    T *const b = t.p[0], *const pad = t.s.pad, *const scr = t.s.scr;
+    AxisTap<T> *const ty = t.s.ty, *const tx = t.s.tx;
     const int sh = cdiv(H, f), sw = cdiv(W, f);
-    AxisTap<T> *ty = ar.take<AxisTap<T>>(H), *tx = ar.take<AxisTap<T>>(W);
     if (!ar.ok)
         return SRX_E_WORKSPACE;
     SRX_TRY(blur(hr, B, H, W, k, kh, kw, false, b, st));
@@ -165,10 +206,7 @@ static int forward_model(const T *hr, int B, int H, int W, const double *k, int 
 }
 
 // back_project = blur_flipped(shift(zero_insert(err), -s f))
-static size_t backproject_ws(int eb, int B, int H, int W)
-{
-    return 2 * align_up((size_t)B * H * W * eb) + shift_ws(eb, B, H, W);
-}
+static size_t backproject_ws(int eb, int B, int H, int W) { return planes_shift_ws<2>(eb, B, H, W); }
 
 template <typename T>
 static int back_project(const T *err, int B, int eh, int ew, const double *k, int kh, int kw, double sy, double sx,
@@ -180,10 +218,9 @@ static int back_project(const T *err, int B, int eh, int ew, const double *k, in
         return SRX_E_UNSUPPORTED;
     Arena ar(ws, wsb);
     ar.require(backproject_ws((int)sizeof(T), B, H, W));
-    T *up = ar.take<T>((size_t)B * H * W), *s2 = ar.take<T>((size_t)B * H * W);
-    T *pad = ar.take<T>((size_t)B * (H + 2 * SRX_NPAD) * (W + 2 * SRX_NPAD));
-    T *scr = ar.take<T>((size_t)B * (H + 2 * SRX_NPAD) * (W + 2 * SRX_NPAD));
-    AxisTap<T> *ty = ar.take<AxisTap<T>>(H), *tx = ar.take<AxisTap<T>>(W);
+    const auto t = carve_planes_shift<T, 2>(ar, shift_dims(B, H, W));
+    T *const up = t.p[0], *const s2 = t.p[1], *const pad = t.s.pad, *const scr = t.s.scr;
+    AxisTap<T> *const ty = t.s.ty, *const tx = t.s.tx;
     if (!ar.ok)
         return SRX_E_WORKSPACE;
     hipLaunchKernelGGL(k_zero_insert<T>, dim3(cdiv(W, 64), cdiv(H, 4), B), dim3(64, 4), 0, st, err, eh, ew, f, H, W, up);
@@ -195,13 +232,26 @@ static int back_project(const T *err, int B, int eh, int ew, const double *k, in
 // ---------------------------------------------------------------------------------------
 // composed shift_and_add
 // ---------------------------------------------------------------------------------------
+// the counts: a [B, h, w] frame batch, its [B, H, W] zoom, and two pairs of tap tables (zoom, shift) of ty / tx entries
+struct SaaComposedDims {
+    size_t B, h, w, H, W, ty, tx;
+};
+template <typename T> struct SaaComposedTabs {
+    T *coef, *cscr, *up, *pad, *scr;
+    AxisTap<T> *zy, *zx, *ty, *tx;
+};
+template <typename T> static SaaComposedTabs<T> carve_saa_composed(Arena &ar, const SaaComposedDims &d)
+{
+    const size_t Pp = d.B * (d.H + 2 * SRX_NPAD) * (d.W + 2 * SRX_NPAD);
+    return {ar.take<T>(d.B * d.h * d.w), ar.take<T>(d.B * d.h * d.w), ar.take<T>(d.B * d.H * d.W), ar.take<T>(Pp), ar.take<T>(Pp),
+            ar.take<AxisTap<T>>(d.ty), ar.take<AxisTap<T>>(d.tx), ar.take<AxisTap<T>>(d.ty), ar.take<AxisTap<T>>(d.tx)};
+}
 static size_t saa_ws_composed(int eb, int B, int N, int h, int w, int f)
 {
     (void)N;
-    const size_t H = (size_t)h * f, W = (size_t)w * f;
-    return 2 * align_up((size_t)B * h * w * eb) + align_up((size_t)B * H * W * eb) +
-           2 * align_up((size_t)B * (H + 2 * SRX_NPAD) * (W + 2 * SRX_NPAD) * eb) +
-           4 * align_up((H > W ? H : W) * sizeof(AxisTap<double>));
+    const size_t H = (size_t)h * f, W = (size_t)w * f, tl = tap_bound(eb, H > W ? H : W);
+    const SaaComposedDims d{(size_t)B, (size_t)h, (size_t)w, H, W, tl, tl};
+    return measured([&](Arena &m) { eb == 8 ? (void)carve_saa_composed<double>(m, d) : (void)carve_saa_composed<float>(m, d); });
 }
 
 template <typename T>
@@ -210,12 +260,8 @@ static int saa_composed(const T *lr, int B, int N, int h, int w, const double *s
 {
     const int H = h * f, W = w * f;
     Arena ar(ws, wsb);
-    T *coef = ar.take<T>((size_t)B * h * w), *cscr = ar.take<T>((size_t)B * h * w);
-    T *up = ar.take<T>((size_t)B * H * W);
-    T *pad = ar.take<T>((size_t)B * (H + 2 * SRX_NPAD) * (W + 2 * SRX_NPAD));
-    T *scr = ar.take<T>((size_t)B * (H + 2 * SRX_NPAD) * (W + 2 * SRX_NPAD));
-    AxisTap<T> *zy = ar.take<AxisTap<T>>(H), *zx = ar.take<AxisTap<T>>(W);
-    AxisTap<T> *ty = ar.take<AxisTap<T>>(H), *tx = ar.take<AxisTap<T>>(W);
+    const auto [coef, cscr, up, pad, scr, zy, zx, ty, tx] =
+        carve_saa_composed<T>(ar, SaaComposedDims{(size_t)B, (size_t)h, (size_t)w, (size_t)H, (size_t)W, (size_t)H, (size_t)W});
     if (!ar.ok)
         return SRX_E_WORKSPACE;
     const size_t n = (size_t)B * H * W;
@@ -235,15 +281,37 @@ static int saa_composed(const T *lr, int B, int N, int h, int w, const double *s
 // composed ibp: the reference's loop, frame by frame (run_sr.py:190-209).  blur(hr) is taken
 // once per iteration (it is the same array for every frame); everything else is literal.
 // ---------------------------------------------------------------------------------------
+// the counts: [B, H, W] planes, the [B, sh, sw] simulated frames, 4 N tap tables of tl entries, rblk block partials of k_residual per item
+struct IbpComposedDims {
+    size_t B, N, H, W, sh, sw, tl, rblk;
+};
+template <typename T> struct IbpComposedTabs {
+    T *b, *up, *s2, *bp, *corr, *pad, *scr, *sim, *err;
+    AxisTap<T> *taps[4 * SRX_MAX_FRAMES];
+    double *rpart;
+};
+template <typename T> static IbpComposedTabs<T> carve_ibp_composed(Arena &ar, const IbpComposedDims &d)
+{
+    const size_t P = d.B * d.H * d.W, Pp = d.B * (d.H + 2 * SRX_NPAD) * (d.W + 2 * SRX_NPAD);
+    IbpComposedTabs<T> t{ar.take<T>(P), ar.take<T>(P), ar.take<T>(P), ar.take<T>(P), ar.take<T>(P), ar.take<T>(Pp), ar.take<T>(Pp),
+                         ar.take<T>(d.B * d.sh * d.sw), ar.take<T>(d.B * d.sh * d.sw), {}, nullptr};
+    for (size_t i = 0; i < 4 * d.N; i++) {  // (a query accepts N beyond what a call does: counted, not kept)
+        AxisTap<T> *const p = ar.take<AxisTap<T>>(d.tl);
+        if (i < 4 * SRX_MAX_FRAMES)
+            t.taps[i] = p;
+    }
+    t.rpart = ar.take<double>(d.B * d.rblk);
+    return t;
+}
+// the bound: the block partials of whole simulated frames (a call's residual covers min(sh, h) x min(sw, w) of them)
 static size_t ibp_ws_composed(int eb, int B, int N, int h, int w, int H, int W, int f)
 {
     (void)h;
     (void)w;
-    const size_t P = align_up((size_t)B * H * W * eb);
-    const size_t sh = cdiv(H, f), sw = cdiv(W, f);
-    return 5 * P + 2 * align_up((size_t)B * (H + 2 * SRX_NPAD) * (W + 2 * SRX_NPAD) * eb) +
-           2 * align_up((size_t)B * sh * sw * eb) + (size_t)4 * N * align_up((size_t)(H > W ? H : W) * sizeof(AxisTap<double>)) +
-           align_up((size_t)B * cdiv((int)sw, 64) * cdiv((int)sh, 4) * sizeof(double));  // k_residual's block partials
+    const int sh = cdiv(H, f), sw = cdiv(W, f);
+    const IbpComposedDims d{(size_t)B, (size_t)(N > 0 ? N : 0), (size_t)H, (size_t)W, (size_t)sh, (size_t)sw, tap_bound(eb, (size_t)(H > W ? H : W)),
+                            (size_t)cdiv(sw, 64) * cdiv(sh, 4)};
+    return measured([&](Arena &m) { eb == 8 ? (void)carve_ibp_composed<double>(m, d) : (void)carve_ibp_composed<float>(m, d); });
 }
 
 template <typename T>
@@ -255,16 +323,9 @@ static int ibp_composed(const T *lr, int B, int N, int h, int w, const double *s
     const int mh = sh < h ? sh : h, mw = sw < w ? sw : w;
     const size_t P = (size_t)B * H * W;
     Arena ar(ws, wsb);
-    T *b = ar.take<T>(P), *up = ar.take<T>(P), *s2 = ar.take<T>(P), *bp = ar.take<T>(P), *corr = ar.take<T>(P);
-    T *pad = ar.take<T>((size_t)B * (H + 2 * SRX_NPAD) * (W + 2 * SRX_NPAD));
-    T *scr = ar.take<T>((size_t)B * (H + 2 * SRX_NPAD) * (W + 2 * SRX_NPAD));
-    T *sim = ar.take<T>((size_t)B * sh * sw), *err = ar.take<T>((size_t)B * sh * sw);
-    AxisTap<T> *taps[4 * SRX_MAX_FRAMES];
-    const size_t tl = (size_t)(H > W ? H : W);
-    for (int i = 0; i < 4 * N; i++)
-        taps[i] = ar.take<AxisTap<T>>(tl);
     const int rblk = cdiv(mw, 64) * cdiv(mh, 4);
-    double *rpart = ar.take<double>((size_t)B * rblk);
+    const auto [b, up, s2, bp, corr, pad, scr, sim, err, taps, rpart] = carve_ibp_composed<T>(
+        ar, IbpComposedDims{(size_t)B, (size_t)N, (size_t)H, (size_t)W, (size_t)sh, (size_t)sw, (size_t)(H > W ? H : W), (size_t)rblk});
     if (!ar.ok)
         return SRX_E_WORKSPACE;
     const int Hp = H + 2 * SRX_NPAD, Wp = W + 2 * SRX_NPAD;
@@ -381,17 +442,23 @@ static size_t ibp_need(const Route &r, int eb, int B, int N, int h, int w, int H
 
 // The uint8 entry points (srx_ibp_u8lr_*, srx_saa_u8lr_*) off the mosaic family: the chunk's frames are converted to T at the front of the
 // workspace and the float driver runs on the rest.  (Those routes serve per-frame fractional shifts; the mosaic family reads the bytes itself.)
-static inline size_t u8_stage_bytes(int eb, int Bc, int N, int h, int w) { return align_up((size_t)Bc * N * h * w * eb); }
+template <typename T> static T *carve_u8_stage(Arena &ar, size_t n) { return ar.take<T>(n); }
+static inline size_t u8_stage_bytes(int eb, int Bc, int N, int h, int w)
+{
+    const size_t n = (size_t)Bc * N * h * w;
+    return measured([&](Arena &m) { eb == 8 ? (void)carve_u8_stage<double>(m, n) : (void)carve_u8_stage<float>(m, n); });
+}
 
 template <typename T> static int u8_stage(const uint8_t *lr, size_t n, void *&ws, size_t &wsb, const T *&staged, hipStream_t st)
 {
-    const size_t bytes = align_up(n * sizeof(T));
-    if (wsb < bytes)
+    Arena ar(ws, wsb);
+    T *const dst = carve_u8_stage<T>(ar, n);
+    if (!ar.ok)
         return SRX_E_WORKSPACE;
-    hipLaunchKernelGGL(k_u8_to<T>, dim3(grid1d(n)), dim3(256), 0, st, lr, n, (T *)ws);
+    hipLaunchKernelGGL(k_u8_to<T>, dim3(grid1d(n)), dim3(256), 0, st, lr, n, dst);
     SRX_CHECK_LAUNCH();
-    staged = (const T *)ws;
-    ws = (char *)ws + bytes, wsb -= bytes;
+    staged = dst;
+    ws = (char *)ws + ar.off, wsb -= ar.off;
     return SRX_OK;
 }
 
@@ -519,6 +586,9 @@ struct srx_plan_s {
     const char *path;
 };
 
+// a plan off the hoisted-table path keeps its state as a plain [B, H, W] plane at the head of the workspace
+template <typename T> static T *carve_plan_state(Arena &ar, size_t B, int H, int W) { return ar.take<T>(B * H * W); }
+
 template <typename T>
 static int plan_create(const T *lr, int B, int N, int h, int w, const double *sh, const double *k, int kh, int kw, const T *hr_init, int H, int W, int f,
                        double step, int tr_lo, int tr_hi, void *ws, size_t wsb, hipStream_t st, unsigned flags, srx_plan_s **out)
@@ -548,7 +618,7 @@ static int plan_create(const T *lr, int B, int N, int h, int w, const double *sh
         }
     }
     if (!z) {
-        T *hr = ar.take<T>((size_t)B * H * W);
+        T *hr = carve_plan_state<T>(ar, B, H, W);
         if (!ar.ok)
             rc = SRX_E_WORKSPACE;
         else if (hipMemcpyAsync(hr, hr_init, (size_t)B * H * W * sizeof(T), hipMemcpyDeviceToDevice, st) != hipSuccess)
@@ -601,7 +671,9 @@ extern "C" {
 
 size_t srx_ibp_plan_workspace_bytes(int eb, int B, int N, int h, int w, int H, int W, int f, unsigned flags)
 {
-    return align_up((size_t)(B > 0 ? B : 1) * H * W * eb) + srx_ibp_workspace_bytes(eb, B, N, h, w, H, W, f, flags);
+    const size_t b1 = B > 0 ? B : 1;
+    return measured([&](Arena &m) { eb == 8 ? (void)carve_plan_state<double>(m, b1, H, W) : (void)carve_plan_state<float>(m, b1, H, W); }) +
+           srx_ibp_workspace_bytes(eb, B, N, h, w, H, W, f, flags);
 }
 
 int srx_ibp_plan_create_f32(const float *lr, int B, int N, int h, int w, const double *sh, const double *k, int kh, int kw, const float *hr_init, int H,

@@ -463,14 +463,27 @@ static inline bool eligible(int elem_bytes, int N, int H, int W, const double *s
     return kc.separable != 0;
 }
 
+// the counts the workspace layout depends on (the planes follow from H and W); nnear: blocks of k_atile_near, cdiv(NB, 256)
+struct Dims {
+    size_t B, H, W, nnear;
+};
+static inline int windows_y(int Hp) { return cdiv(Hp + 1, Geo<2, 2>::OWNY); }
+static inline int windows_x(int Wp) { return cdiv(Wp + 1, Geo<2, 2>::OWNX); }
+struct Carved {
+    float *S, *G, *MCq, *Yb;  // G: four rows interleaved; MCq: (M, C), four rows interleaved
+    double *epart;
+};
+// the layout: on the call's arena it is the carve, on a counting one the size (a braced list is evaluated left to right)
+static Carved carve(Arena &ar, const Dims &d)
+{
+    const size_t Hp = d.H + 2 * SRX_NPAD, Wp = d.W + 2 * SRX_NPAD, Hg = Hp + 3, Wg = Wp + 3, Qn = (Hg + 3) / 4;
+    return {ar.take<float>(d.B * ((d.W + 3) / 4) * d.H * 4), ar.take<float>(d.B * Qn * Wg * 4), ar.take<float>(d.B * Qn * Wg * 8),
+            ar.take<float>(d.B * (Hp + 4) * (Wp + 4)), ar.take<double>(d.B * ((size_t)windows_y((int)Hp) * windows_x((int)Wp) + d.nnear))};
+}
 static inline size_t tabs_bytes(int, int B, int, int H, int W)
 {
-    const size_t Hp = H + 2 * SRX_NPAD, Wp = W + 2 * SRX_NPAD, Hg = Hp + 3, Wg = Wp + 3;
-    const size_t nwin = (size_t)cdiv((int)Hp + 1, Geo<2, 2>::OWNY) * cdiv((int)Wp + 1, Geo<2, 2>::OWNX), nnear = cdiv((int)(20 * (Hg + Wg)), 256);
-    const size_t Qn = (Hg + 3) / 4;
-    return align_up((size_t)B * ((W + 3) / 4) * H * 16) + align_up((size_t)B * Qn * Wg * 16) + align_up((size_t)B * Qn * Wg * 32) +
-           align_up((size_t)B * (Hp + 4) * (Wp + 4) * 4) +
-           align_up((size_t)B * (nwin + nnear) * sizeof(double));
+    const size_t Hg = H + 2 * SRX_NPAD + 3, Wg = W + 2 * SRX_NPAD + 3;
+    return measured([&](Arena &m) { carve(m, Dims{(size_t)B, (size_t)H, (size_t)W, (size_t)cdiv((int)mosaic::near_bound(Hg, Wg), 256)}); });
 }
 
 static int iterate(const mosaic::Common<float> &c, const float *hr_init, float *hr, int n_iter, double *errors, Arena &ar, hipStream_t st)
@@ -482,16 +495,12 @@ static int iterate(const mosaic::Common<float> &c, const float *hr_init, float *
     const int Hp = H + 2 * SRX_NPAD, Wp = W + 2 * SRX_NPAD, Hg = Hp + 3, Wg = Wp + 3, W4 = (W + 3) / 4;
     AArgs A;
     A.H = H, A.W = W, A.Hg = Hg, A.Wg = Wg;
-    A.nwy = cdiv(Hp + 1, Geo<NBY, NBX>::OWNY), A.nwx = cdiv(Wp + 1, Geo<NBY, NBX>::OWNX);
+    A.nwy = windows_y(Hp), A.nwx = windows_x(Wp);
     A.Dy = py.D, A.Dx = px.D, A.PBy = py.PB, A.PBx = px.PB;
     A.nnear = cdiv(NB, 256);
     A.sn = (float)c.step / (float)c.N;
-    float *S = ar.take<float>((size_t)B * W4 * H * 4);
     const int Qn = (Hg + 3) / 4;
-    float *G = ar.take<float>((size_t)B * Qn * Wg * 4);       // four rows interleaved
-    float *MCq = ar.take<float>((size_t)B * Qn * Wg * 8);     // (M, C), four rows interleaved
-    float *Yb = ar.take<float>((size_t)B * (Hp + 4) * (Wp + 4));
-    double *epart = ar.take<double>((size_t)B * (A.nwx * A.nwy + A.nnear));
+    const auto [S, G, MCq, Yb, epart] = carve(ar, Dims{(size_t)B, (size_t)H, (size_t)W, (size_t)A.nnear});
     if (!ar.ok)
         return SRX_E_WORKSPACE;
     if (A.nwy > 65535 || B > 65535 || cdiv(H, 4) > 65535)

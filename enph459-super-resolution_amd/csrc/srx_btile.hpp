@@ -1069,16 +1069,41 @@ static inline bool eligible(int elem_bytes, int N, int h, int w, const double *s
     return kh <= 7 && kw <= 7;  // a rank-1 PSF as 7 + 7 taps, any other 7 x 7 along registers and lanes (blur2d_cross)
 }
 
-static inline size_t ws_bytes(int B, int N, int h, int w, int H, int W)
-{
-    const int nwy = cdiv(H + 2 * SRX_NPAD, Geo<2, 2>::OWNY), nwx = cdiv(W + 2 * SRX_NPAD, Geo<2, 2>::OWNX);
-    return align_up((size_t)B * N * h * w * 4) + align_up((size_t)B * nwy * nwx * sizeof(double)) + align_up((size_t)B * ((H + 3) / 4) * W * 16) +
-           align_up(MAXF * 20 * sizeof(int));
-}
-
 // one table per item: N records behind the header, item after item
 static inline int tab_stride(int N) { return TAB_HDR + 20 * N; }
-static inline size_t items_tab_bytes(int B, int N) { return align_up((size_t)B * tab_stride(N) * sizeof(int)); }
+
+// the counts the workspace layout depends on.  per_item: one table of records per item in the place of the call's one (MAXF records)
+struct Dims {
+    size_t B, N, h, w, H, W, nwin;
+    bool per_item;
+};
+static inline size_t windows(int H, int W)
+{
+    return (size_t)cdiv(H + 2 * SRX_NPAD, Geo<SRX_BT_NBY, SRX_BT_NBX>::OWNY) * cdiv(W + 2 * SRX_NPAD, Geo<SRX_BT_NBY, SRX_BT_NBX>::OWNX);
+}
+struct Carved {
+    float *err;
+    double *epart;
+    float *S;  // the state plane, four rows interleaved
+    int *frtab;
+};
+static inline int *carve_table(Arena &ar, const Dims &d) { return ar.take<int>(d.per_item ? d.B * tab_stride((int)d.N) : (size_t)(MAXF * 20)); }
+// the layout: on the call's arena it is the carve, on a counting one the size (a braced list is evaluated left to right)
+static Carved carve(Arena &ar, const Dims &d)
+{
+    return {ar.take<float>(d.B * d.N * d.h * d.w), ar.take<double>(d.B * d.nwin), ar.take<float>(d.B * ((d.H + 3) / 4) * d.W * 4), carve_table(ar, d)};
+}
+// a call on one shared table ...
+static inline size_t ws_bytes(int B, int N, int h, int w, int H, int W)
+{
+    return measured([&](Arena &m) { carve(m, Dims{(size_t)B, (size_t)N, (size_t)h, (size_t)w, (size_t)H, (size_t)W, windows(H, W), false}); });
+}
+// ... and what srx_items.hpp's queries add to it for a run with one table per item: those tables (more than the run carves, which
+// takes them in the place of the shared one)
+static inline size_t items_tab_bytes(int B, int N)
+{
+    return measured([&](Arena &m) { carve_table(m, Dims{(size_t)B, (size_t)N, 0, 0, 0, 0, 0, true}); });
+}
 
 // the records of one shift table and the range of their row tap origins: rng = oyf_min, oyf_max, oyb_min, oyb_max
 static inline void make_frames(const double *sh, int N, BFrame *fr, int nfr, int (&rng)[4])
@@ -1126,12 +1151,10 @@ static int ibp_t(const float *lr, int B, int N, int h, int w, const double *sh, 
     A.nwy = cdiv(Hp, Geo<NBY, NBX>::OWNY), A.nwx = cdiv(Wp, Geo<NBY, NBX>::OWNX);
     A.sn = (float)step / (float)N;
     Arena ar(ws, wsb);
-    float *err = ar.take<float>((size_t)B * N * h * w);
-    double *epart = ar.take<double>((size_t)B * A.nwy * A.nwx);
     const int H4 = (H + 3) / 4;
-    float *S = ar.take<float>((size_t)B * H4 * W * 4);  // the state plane, four rows interleaved
     const int frstride = per_item ? tab_stride(N) : 0;
-    int *frtab = ar.take<int>(per_item ? (size_t)B * frstride : (size_t)(MAXF * 20));
+    const auto [err, epart, S, frtab] =
+        carve(ar, Dims{(size_t)B, (size_t)N, (size_t)h, (size_t)w, (size_t)H, (size_t)W, (size_t)A.nwy * A.nwx, per_item});
     if (!ar.ok)
         return SRX_E_WORKSPACE;
     if (A.nwy > 65535 || B > 65535 || H4 > 65535)

@@ -24,6 +24,13 @@ template <typename T> struct AxisTap {
     T w[4];      // cubic B-spline weights (all zero = sample is cval 0)
 };
 
+// The shape-only workspace queries size a tap table of n entries as float64's (48 bytes a tap) whatever the element type.  In entries of
+// the query's own type (32 bytes in float32) that is this many -- rounded up, which never reaches another 256-byte granule.
+static inline size_t tap_bound(int eb, size_t n)
+{
+    return eb == 8 ? n : (n * sizeof(AxisTap<double>) + sizeof(AxisTap<float>) - 1) / sizeof(AxisTap<float>);
+}
+
 template <typename T> struct KernelArg {
     T k[SRX_MAX_KERNEL_TAPS];
 };
@@ -55,6 +62,14 @@ struct Arena {
     size_t cap, off;
     bool ok;
     Arena(void *p, size_t n) : base((char *)p), cap(n), off(0), ok(!ws_short(p, n, n)) {}
+    // counting mode: no base, no limit.  A layout function run on this arena leaves its size in `off`; the pointers it hands out are
+    // never dereferenced.
+    static Arena measure()
+    {
+        Arena a(nullptr, 0);
+        a.cap = SIZE_MAX;
+        return a;
+    }
     // the documented size of the call (its *_workspace_bytes): a shorter arena is refused before anything is carved or queued, whether
     // or not the path this call takes would have fitted
     void require(size_t need)
@@ -69,11 +84,20 @@ struct Arena {
             ok = false;
             return nullptr;
         }
-        U *r = (U *)(base + off);
+        U *r = (U *)((uintptr_t)base + off);
         off += bytes;
         return r;
     }
 };
+
+// The size of a layout: `carve`, the function that takes a driver's planes and tables from its arena, run on a counting one.  A driver's
+// *_bytes query and its call are the same sequence of take<>() this way, at the query's bound of the counts and at the call's own.
+template <typename F> static inline size_t measured(F &&carve)
+{
+    Arena m = Arena::measure();
+    carve(m);
+    return m.off;
+}
 
 __host__ __device__ static inline int cdiv(int a, int b) { return (a + b - 1) / b; }
 

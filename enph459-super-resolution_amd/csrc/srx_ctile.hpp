@@ -524,14 +524,32 @@ __global__ void __launch_bounds__(256, 2)
 }
 
 // ---- host ----------------------------------------------------------------------------------------------------------
+// The frame geometry, its counts and their bound are srx_ztile.hpp's (frame_geometry, Dims), with this kernel's rows per tile.
+static_assert(VT == ztile::VT && HALO == ztile::HALO, "k_ibp_ctile shares k_ibp_ztile's padded-plane geometry");
+
+// what a call carves, in this order; CTabs is its read-only view for the kernel
+template <typename T> struct Carved {
+    T *Mp, *s0, *s1, *Cp;  // s0, s1: the two padded state planes
+    uint2 *CM4;
+    int *cmok;
+    T *kw;
+    unsigned *nrec;
+    uint4 *nent;
+    T2<T> *Mn;
+    double *ep0, *ep1;     // per-tile MSE partials, alternating
+};
+// the layout: on the call's arena it is the carve, on a counting one the size (a braced list is evaluated left to right)
+template <typename T> static Carved<T> carve(Arena &ar, const ztile::Dims &d)
+{
+    const size_t splane = (d.HP + 2) * d.WP;
+    return {ar.take<T>(d.B * d.HP * d.WP), ar.take<T>(d.B * splane), ar.take<T>(d.B * splane), ar.take<T>(d.HP * d.WP),
+            ar.take<uint2>(d.B * (d.HP / 4) * d.WP), ar.take<int>(d.B), ar.take<T>(32), ar.take<unsigned>(d.NT), ar.take<uint4>(d.ngrp * d.NT),
+            ar.take<T2<T>>(d.B * d.NT), ar.take<double>(d.B * d.ntiles), ar.take<double>(d.B * d.ntiles)};
+}
 static inline size_t tabs_bytes(int eb, int B, int N, int H, int W)
 {
-    const size_t ngrp = ((size_t)N + 3) / 4, NT = (size_t)6 * (W + 4) + (size_t)H * 6;
-    const int VTY = rows_for(eb) - 2 * HALO;
-    const size_t ty = cdiv(H, VTY), tx = cdiv(W, VT), HP = ty * VTY + 2 * HALO, WP = tx * VT + 2 * HALO;
-    return align_up((size_t)B * HP * WP * eb) + 2 * align_up((size_t)B * (HP + 2) * WP * eb) + align_up(HP * WP * eb) +
-           align_up((size_t)B * (HP / 4) * WP * 8) + align_up((size_t)B * 4) + align_up(32 * eb) + align_up(NT * 4) + align_up(ngrp * NT * 16) +
-           align_up((size_t)B * NT * 2 * eb) + 2 * align_up((size_t)B * ty * tx * 8);
+    const ztile::Dims d = ztile::dims_bound(B, N, H, W, rows_for(eb) - 2 * HALO);
+    return measured([&](Arena &m) { eb == 8 ? (void)carve<double>(m, d) : (void)carve<float>(m, d); });
 }
 
 template <typename T>
@@ -542,55 +560,45 @@ static int iterate(const mosaic::Common<T> &c, const T *hr_init, T *hr, int n_it
     const double step = c.step, scale = c.scale, *Vtot = c.Vtot;
     constexpr int VTY = Rows<T>::NR - 2 * HALO;
     ztile::ZArgs za;  // the near-band enumeration and its table builder are srx_ztile.hpp's
-    za.H = H, za.W = W, za.tiles_x = cdiv(W, VT), za.tiles_y = cdiv(H, VTY);
-    za.HP = za.tiles_y * VTY + 2 * HALO, za.WP = za.tiles_x * VT + 2 * HALO;
+    ztile::frame_geometry(za, H, W, VTY, py, px, NS);
     const int HP = za.HP, WP = za.WP;
-    za.exy = py.nmax, za.nby = -py.nmin, za.exx = px.nmax, za.nbx = -px.nmin;
-    za.Ey = py.E, za.Ex = px.E;
-    za.WT = W + za.exx, za.LN = za.exx + za.nbx, za.TOPN = (za.exy + za.nby) * za.WT;
-    za.ngrp = NS / 4;
     za.sn = (float)step / (float)N;
     CArgs ca;
     ca.H = H, ca.W = W, ca.tiles_x = za.tiles_x, ca.tiles_y = za.tiles_y, ca.HP = HP, ca.WP = WP;
     ca.exy = za.exy, ca.exx = za.exx, ca.nby = za.nby, ca.nbx = za.nbx, ca.Ey = za.Ey, ca.Ex = za.Ex;
     ca.WT = za.WT, ca.LN = za.LN, ca.TOPN = za.TOPN, ca.ngrp = za.ngrp;
     ca.sn = sizeof(T) == 4 ? (double)((float)step / (float)N) : step / (double)N;
-    const int NT = za.TOPN + (H - za.nby) * za.LN, ntiles = za.tiles_x * za.tiles_y;
-    const size_t splane = (size_t)(HP + 2) * WP;
-    T *Mp = ar.take<T>((size_t)B * HP * WP), *s0 = ar.take<T>(B * splane), *s1 = ar.take<T>(B * splane), *Cp = ar.take<T>((size_t)HP * WP);
-    uint2 *CM4 = ar.take<uint2>((size_t)B * (HP / 4) * WP);
-    int *cmok = ar.take<int>(B);
-    T *kw = ar.take<T>(32);
-    unsigned *nrec = ar.take<unsigned>(NT);
-    uint4 *nent = ar.take<uint4>((size_t)za.ngrp * NT);
-    T2<T> *Mn = ar.take<T2<T>>((size_t)B * NT);
-    double *ep0 = ar.take<double>((size_t)B * ntiles), *ep1 = ar.take<double>((size_t)B * ntiles);
+    const ztile::Dims d = ztile::dims_of(B, za);
+    const int NT = (int)d.NT, ntiles = (int)d.ntiles;
+    const Carved<T> t = carve<T>(ar, d);
     if (!ar.ok)
         return SRX_E_WORKSPACE;
+    T *const s0 = t.s0, *const s1 = t.s1;
+    double *const ep0 = t.ep0, *const ep1 = t.ep1;
     KwTab kv;
     for (int i = 0; i < 8; i++) {
         kv.v[i] = i < 7 ? (double)c.kc.cy[i] : 0.0, kv.v[8 + i] = i < 7 ? (double)c.kc.cx[i] : 0.0;
         kv.v[16 + i] = i < 7 ? (double)c.kt.cy[i] : 0.0, kv.v[24 + i] = i < 7 ? (double)c.kt.cx[i] : 0.0;
     }
-    hipLaunchKernelGGL(k_ctile_kw<T>, dim3(1), dim3(64), 0, st, kv, kw);
+    hipLaunchKernelGGL(k_ctile_kw<T>, dim3(1), dim3(64), 0, st, kv, t.kw);
     SRX_CHECK_LAUNCH();
-    hipLaunchKernelGGL(k_ctile_prep<T>, dim3(cdiv(WP, 256), HP / 2, B + 1), dim3(256), 0, st, c.Mg, c.Cg, B, H, W, HP, WP, za.nby, za.nbx, Mp, Cp);
+    hipLaunchKernelGGL(k_ctile_prep<T>, dim3(cdiv(WP, 256), HP / 2, B + 1), dim3(256), 0, st, c.Mg, c.Cg, B, H, W, HP, WP, za.nby, za.nbx, t.Mp, t.Cp);
     SRX_CHECK_LAUNCH();
-    if (fill_bytes(cmok, 0xff, (size_t)B * sizeof(int), st) != hipSuccess)
+    if (fill_bytes(t.cmok, 0xff, (size_t)B * sizeof(int), st) != hipSuccess)
         return SRX_E_HIP;
-    hipLaunchKernelGGL(k_ctile_pack<T>, dim3(cdiv(WP, 256), HP / 4, B), dim3(256), 0, st, Mp, Cp, HP, WP, CM4, cmok);
+    hipLaunchKernelGGL(k_ctile_pack<T>, dim3(cdiv(WP, 256), HP / 4, B), dim3(256), 0, st, t.Mp, t.Cp, HP, WP, t.CM4, t.cmok);
     SRX_CHECK_LAUNCH();
     hipLaunchKernelGGL(ztile::k_ztile_zero_border<T>, dim3(HP / 2 + 1, B), dim3(256), 0, st, s0, s1, H, W, HP, WP);  // (only what the image does not cover)
     SRX_CHECK_LAUNCH();
     hipLaunchKernelGGL(k_ctile_copy_in<T>, dim3(cdiv(W, 256), H, B), dim3(256), 0, st, hr_init, H, W, HP, WP, s0);
     SRX_CHECK_LAUNCH();
     if (NT > 0) {
-        hipLaunchKernelGGL(ztile::k_ztile_near_tab, dim3(cdiv(NT, 256)), dim3(256), 0, st, c.ncu, c.nyx, NS, py.PB, px.PB, za, NT, nrec, nent);
+        hipLaunchKernelGGL(ztile::k_ztile_near_tab, dim3(cdiv(NT, 256)), dim3(256), 0, st, c.ncu, c.nyx, NS, py.PB, px.PB, za, NT, t.nrec, t.nent);
         SRX_CHECK_LAUNCH();
-        hipLaunchKernelGGL(k_ctile_near_m<T>, dim3(cdiv(NT, 256), B), dim3(256), 0, st, c.Mg, c.Mu, c.NB, py.PB, px.PB, za, NT, Mn);
+        hipLaunchKernelGGL(k_ctile_near_m<T>, dim3(cdiv(NT, 256), B), dim3(256), 0, st, c.Mg, c.Mu, c.NB, py.PB, px.PB, za, NT, t.Mn);
         SRX_CHECK_LAUNCH();
     }
-    CTabs<T> tb{Mp, Cp, CM4, cmok, kw, nrec, nent, Mn};
+    CTabs<T> tb{t.Mp, t.Cp, t.CM4, t.cmok, t.kw, t.nrec, t.nent, t.Mn};
     const dim3 grid(za.tiles_x, za.tiles_y, B);
     for (int it = 0; it < n_iter; it++) {
         const T *src = (it & 1) ? s1 : s0;

@@ -116,6 +116,10 @@ static inline bool plan_axis_tiles(int L, int RL, int align, AxisTiles &at)
     }
 }
 
+// what plan() admits at most: the bounds of the shape-only workspace query
+constexpr int MAX_TILES = 1024;       // windows of a frame
+constexpr int MAX_TABS = 64 + 64;     // near-band tables, one per window of the first row and column: tx.n + ty.n - 1 with at most 64 windows per axis
+
 struct Plan {
     int nsx;
     AxisTiles ty, tx;
@@ -133,7 +137,7 @@ static inline bool plan(int H, int W, Plan &pl)
     p.nsx = (call_flags() & SRX_FLAG_DIAG_WIDE_WINDOWS) ? 4 : 3;
     if (!plan_axis_tiles(H, RY, ALIGN_Y, p.ty) || !plan_axis_tiles(W, 64 * p.nsx, ALIGN_X, p.tx))
         return false;
-    if ((long)p.ty.n * p.tx.n > 1024)
+    if ((long)p.ty.n * p.tx.n > MAX_TILES)
         return false;
     pl = p;
     return true;
@@ -784,13 +788,37 @@ __global__ void __launch_bounds__(256 * NSX)
 }
 
 // ---- host ----------------------------------------------------------------------------------------------------------
+// the counts the workspace layout depends on
+struct Dims {
+    size_t B, H, W, ntabs, ntiles, ngrp;
+};
+// what a call carves, in this order; DTabs is its read-only view for the kernel
+struct Carved {
+    float *s0, *s1, *Mt;  // s0, s1: the two state planes
+    unsigned *Mt8;
+    int *m8;
+    float *Ct;
+    AxisW *aw;
+    TileD *tiles;
+    unsigned long long *rowm, *colm;
+    int *nnt;
+    uint2 *nrec, *nent;
+    float2 *Mn;
+    double *ep0, *ep1;    // per-window MSE partials, alternating
+    float *k2;
+};
+// the layout: on the call's arena it is the carve, on a counting one the size (a braced list is evaluated left to right)
+static Carved carve(Arena &ar, const Dims &d)
+{
+    const size_t plane = d.H * d.W;
+    return {ar.take<float>(d.B * plane), ar.take<float>(d.B * plane), ar.take<float>(d.B * plane), ar.take<unsigned>(d.B * (d.W / 4) * d.H),
+            ar.take<int>(d.B), ar.take<float>(plane), ar.take<AxisW>(2), ar.take<TileD>(d.ntiles), ar.take<unsigned long long>(64 * 4),
+            ar.take<unsigned long long>(64 * 4), ar.take<int>(d.ntabs), ar.take<uint2>(d.ntabs * NN_PAD), ar.take<uint2>(d.ngrp * d.ntabs * NN_PAD),
+            ar.take<float2>(d.B * d.ntabs * NN_PAD), ar.take<double>(d.B * d.ntiles), ar.take<double>(d.B * d.ntiles), ar.take<float>(112)};
+}
 static inline size_t tabs_bytes(int, int B, int N, int H, int W)
 {
-    const size_t ngrp = ((size_t)N + 3) / 4, plane = (size_t)H * W, ntabs = 128, ntiles = 1024;
-    return 3 * align_up((size_t)B * plane * 4) + align_up((size_t)B * (W / 4) * H * 4) + align_up((size_t)B * 4) + align_up(plane * 4) +
-           align_up(2 * sizeof(AxisW)) + align_up(ntiles * sizeof(TileD)) + 2 * align_up(64 * 4 * 8) + align_up(ntabs * 4) +
-           align_up(ntabs * NN_PAD * 8) + align_up(ngrp * ntabs * NN_PAD * 8) + align_up((size_t)B * ntabs * NN_PAD * 8) +
-           2 * align_up((size_t)B * ntiles * 8) + align_up(112 * 4);
+    return measured([&](Arena &m) { carve(m, Dims{(size_t)B, (size_t)H, (size_t)W, MAX_TABS, MAX_TILES, ((size_t)N + 3) / 4}); });
 }
 
 // windows and 0/1 count masks, built on the device from the two axis plans (by-value arguments: no host buffer, no copy)
@@ -850,19 +878,8 @@ static int iterate(const mosaic::Common<float> &c, const float *hr_init, float *
     if (!plan(H, W, pl))
         return SRX_E_UNSUPPORTED;
     const int ntiles = pl.ty.n * pl.tx.n, RX = 64 * pl.nsx, ngrp = NS / 4, ntabs = pl.tx.n + pl.ty.n - 1;
-    const size_t plane = (size_t)H * W;
-    float *s0 = ar.take<float>(B * plane), *s1 = ar.take<float>(B * plane), *Mt = ar.take<float>(B * plane);
-    unsigned *Mt8 = ar.take<unsigned>((size_t)B * (W / 4) * H);
-    int *m8 = ar.take<int>(B);
-    float *Ct = ar.take<float>(plane);
-    AxisW *aw = ar.take<AxisW>(2);
-    TileD *tiles = ar.take<TileD>(ntiles);
-    unsigned long long *rowm = ar.take<unsigned long long>(64 * 4), *colm = ar.take<unsigned long long>(64 * 4);
-    int *nnt = ar.take<int>(ntabs);
-    uint2 *nrec = ar.take<uint2>((size_t)ntabs * NN_PAD), *nent = ar.take<uint2>((size_t)ngrp * ntabs * NN_PAD);
-    float2 *Mn = ar.take<float2>((size_t)B * ntabs * NN_PAD);
-    double *ep0 = ar.take<double>((size_t)B * ntiles), *ep1 = ar.take<double>((size_t)B * ntiles);
-    float *k2 = ar.take<float>(112);
+    const auto [s0, s1, Mt, Mt8, m8, Ct, aw, tiles, rowm, colm, nnt, nrec, nent, Mn, ep0, ep1, k2] =
+        carve(ar, Dims{(size_t)B, (size_t)H, (size_t)W, (size_t)ntabs, (size_t)ntiles, (size_t)ngrp});
     if (!ar.ok)
         return SRX_E_WORKSPACE;
     const int psf = fused::psf_form(c.kc, c.kt);

@@ -1399,13 +1399,31 @@ __global__ void __launch_bounds__(256, sizeof(T) == 4 ? 3 : 1)  // float: three 
 // ---------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------
+// the counts ibp's layout depends on.  v2 (the default iteration) adds the lattice-tap tables, ty and tx entries, and the per-tile MSE
+// partial sums to what v1 (SRX_FLAG_DIAG_V1) carves
+struct IbpDims {
+    size_t B, N, h, w, H, W, ty, tx;
+    bool v2;
+};
+template <typename T, typename Tap> struct IbpTabs {
+    T *pad, *scr, *err;
+    Tap *tyT, *txT;
+    double *epart;
+};
+// the layout: on the call's arena it is the carve, on a counting one the size (a braced list is evaluated left to right)
+template <typename T, typename Tap> static IbpTabs<T, Tap> carve_ibp(Arena &ar, const IbpDims &d)
+{
+    const size_t Hp = d.H + 2 * SRX_NPAD, Wp = d.W + 2 * SRX_NPAD;
+    return {ar.take<T>(d.B * Hp * Wp), ar.take<T>(d.B * Hp * Wp), ar.take<T>(d.B * d.N * d.h * d.w), d.v2 ? ar.take<Tap>(d.ty) : nullptr,
+            d.v2 ? ar.take<Tap>(d.tx) : nullptr, d.v2 ? ar.take<double>(d.B * cdiv((int)d.H, 16) * cdiv((int)d.W, 16)) : nullptr};
+}
+// the bound: v2, each tap table as (N + 8) (H + W + 48) entries of the widest form, two float64 lattice taps
 static inline size_t ibp_ws(int eb, int B, int N, int h, int w, int H, int W, int f)
 {
     (void)f;
-    const size_t padb = align_up((size_t)B * (H + 2 * SRX_NPAD) * (W + 2 * SRX_NPAD) * eb);
-    return 2 * padb + align_up((size_t)B * N * h * w * eb) +
-           2 * align_up((size_t)(N + 8) * (H + W + 4 * SRX_NPAD) * sizeof(LTap<double, 2>)) +
-           align_up((size_t)B * cdiv(H, 16) * cdiv(W, 16) * sizeof(double));  // per-tile MSE partial sums
+    const size_t nt = (size_t)(N + 8) * (H + W + 4 * SRX_NPAD);
+    const IbpDims d{(size_t)B, (size_t)N, (size_t)h, (size_t)w, (size_t)H, (size_t)W, nt, nt, true};
+    return measured([&](Arena &m) { eb == 8 ? (void)carve_ibp<double, LTap<double, 2>>(m, d) : (void)carve_ibp<float, LTap<double, 2>>(m, d); });
 }
 
 // SRX_FLAG_DIAG_V1 selects the 8-launch iteration (stand-alone exact prefilter passes); default v2.
@@ -1416,14 +1434,17 @@ template <typename T, int F>
 static int ibp_v2_loop(const T *lr, int B, int N, int h, int w, const FrameSet<T> &fwd, const FrameSet<T> &bwd,
                        int omin_y, int omax_y, int omin_x, int omax_x, const Kernel7<T> &kc, const Kernel7<T> &kt,
                        const T *hr_init, int H, int W, int n_iter, double step, T *hr, double *errors, double scale,
-                       T *pad, T *err, Arena &ar, hipStream_t st)
+                       Arena &ar, hipStream_t st)
 {
     using C = BwdCfg<T, F>;
     constexpr int L = C::L, KS = C::KS, f = F;
     const int Hp = H + 2 * SRX_NPAD, Wp = W + 2 * SRX_NPAD;
     const int KP = (N + KS - 1) / KS * KS;
-    LTap<T, L> *tyT = ar.take<LTap<T, L>>((size_t)KP * Hp), *txT = ar.take<LTap<T, L>>((size_t)N * Wp);
-    double *epart = ar.take<double>((size_t)B * cdiv(H, 16) * cdiv(W, 16));
+    const IbpTabs<T, LTap<T, L>> t =
+        carve_ibp<T, LTap<T, L>>(ar, IbpDims{(size_t)B, (size_t)N, (size_t)h, (size_t)w, (size_t)H, (size_t)W, (size_t)KP * Hp, (size_t)N * Wp, true});
+    T *const pad = t.pad, *const err = t.err;
+    LTap<T, L> *const tyT = t.tyT, *const txT = t.txT;
+    double *const epart = t.epart;
     if (!ar.ok)
         return SRX_E_WORKSPACE;
     hipLaunchKernelGGL((k_build_ltaps<T, L>), dim3(cdiv(Hp, 64), KP), dim3(64), 0, st, tyT, Hp, H, h, f, bwd, KP, 0);
@@ -1463,10 +1484,6 @@ static int ibp(const T *lr, int B, int N, int h, int w, const double *sh, const 
 {
     const int Hp = H + 2 * SRX_NPAD, Wp = W + 2 * SRX_NPAD;
     Arena ar(ws, wsb);
-    T *pad = ar.take<T>((size_t)B * Hp * Wp), *scr = ar.take<T>((size_t)B * Hp * Wp);
-    T *err = ar.take<T>((size_t)B * N * h * w);
-    if (!ar.ok)
-        return SRX_E_WORKSPACE;
     FrameSet<T> fwd, bwd;
     fwd.n = bwd.n = N;
     int omin_y = 1 << 30, omin_x = 1 << 30, omax_y = -(1 << 30), omax_x = -(1 << 30);
@@ -1492,7 +1509,7 @@ static int ibp(const T *lr, int B, int N, int h, int w, const double *sh, const 
         // ---- v2: blur_pad -> fwd_tile -> bwd_tile ----
 #define SRX_V2(FF)                                                                                                  \
     return ibp_v2_loop<T, FF>(lr, B, N, h, w, fwd, bwd, omin_y, omax_y, omin_x, omax_x, kc, kt, hr_init, H, W, n_iter, \
-                              step, hr, errors, scale, pad, err, ar, st)
+                              step, hr, errors, scale, ar, st)
         if (f == 4)
             SRX_V2(4);
         if (f == 3)
@@ -1500,6 +1517,10 @@ static int ibp(const T *lr, int B, int N, int h, int w, const double *sh, const 
         SRX_V2(2);
 #undef SRX_V2
     }
+    const IbpTabs<T, LTap<T, 1>> t = carve_ibp<T, LTap<T, 1>>(ar, IbpDims{(size_t)B, (size_t)N, (size_t)h, (size_t)w, (size_t)H, (size_t)W, 0, 0, false});
+    T *const pad = t.pad, *const scr = t.scr, *const err = t.err;
+    if (!ar.ok)
+        return SRX_E_WORKSPACE;
     for (int it = 0; it < n_iter; it++) {
         const T *cur = it == 0 ? hr_init : hr;
         SRX_LAUNCH(KID_BLUR_PAD, (k_blur_pad<T, false>), bgrid, bblk, 0, st, cur, H, W, kc, pad);
@@ -1515,12 +1536,25 @@ static int ibp(const T *lr, int B, int N, int h, int w, const double *sh, const 
     return SRX_OK;
 }
 
+// the counts shift_and_add's layout depends on.  zy, zx: entries of the zoom tap tables (H and W in a call, the longer side in the bound)
+struct SaaDims {
+    size_t B, N, h, w, f, zy, zx;
+};
+template <typename T> struct SaaTabs {
+    T *coef, *cscr, *up, *pad, *scr;
+    AxisTap<T> *zy, *zx;
+};
+template <typename T> static SaaTabs<T> carve_saa(Arena &ar, const SaaDims &d)
+{
+    const size_t H = d.h * d.f, W = d.w * d.f, Hp = H + 2 * SRX_NPAD, Wp = W + 2 * SRX_NPAD;
+    return {ar.take<T>(d.B * d.N * d.h * d.w), ar.take<T>(d.B * d.N * d.h * d.w), ar.take<T>(d.B * H * W), ar.take<T>(d.B * Hp * Wp), ar.take<T>(d.B * Hp * Wp),
+            ar.take<AxisTap<T>>(d.zy), ar.take<AxisTap<T>>(d.zx)};
+}
 static inline size_t saa_ws(int eb, int B, int N, int h, int w, int f)
 {
-    const size_t H = (size_t)h * f, W = (size_t)w * f;
-    return 2 * align_up((size_t)B * N * h * w * eb) + align_up((size_t)B * H * W * eb) +
-           2 * align_up((size_t)B * (H + 2 * SRX_NPAD) * (W + 2 * SRX_NPAD) * eb) +
-           2 * align_up((H > W ? H : W) * sizeof(AxisTap<double>));
+    const size_t tl = tap_bound(eb, (size_t)(h > w ? h : w) * f);
+    const SaaDims d{(size_t)B, (size_t)N, (size_t)h, (size_t)w, (size_t)f, tl, tl};
+    return measured([&](Arena &m) { eb == 8 ? (void)carve_saa<double>(m, d) : (void)carve_saa<float>(m, d); });
 }
 
 // The driver body of shift_and_add on this route.  fir(q, grid, block, up, pad) makes frame q's FIR launch: where its tap comes from is
@@ -1532,10 +1566,7 @@ static int saa_with(Fir fir, const T *lr, int B, int N, int h, int w, int f, T *
         return SRX_E_UNSUPPORTED;
     const int H = h * f, W = w * f, Hp = H + 2 * SRX_NPAD, Wp = W + 2 * SRX_NPAD;
     Arena ar(ws, wsb);
-    T *coef = ar.take<T>((size_t)B * N * h * w), *cscr = ar.take<T>((size_t)B * N * h * w);
-    T *up = ar.take<T>((size_t)B * H * W);
-    T *pad = ar.take<T>((size_t)B * Hp * Wp), *scr = ar.take<T>((size_t)B * Hp * Wp);
-    AxisTap<T> *zy = ar.take<AxisTap<T>>(H), *zx = ar.take<AxisTap<T>>(W);
+    const auto [coef, cscr, up, pad, scr, zy, zx] = carve_saa<T>(ar, SaaDims{(size_t)B, (size_t)N, (size_t)h, (size_t)w, (size_t)f, (size_t)H, (size_t)W});
     if (!ar.ok)
         return SRX_E_WORKSPACE;
     // spline coefficients of every LR frame at once: [B*N, h, w], 'mirror' ends (scipy.ndimage.zoom)

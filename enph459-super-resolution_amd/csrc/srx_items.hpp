@@ -190,7 +190,12 @@ __global__ void __launch_bounds__(256)
     *o = ACC ? *o + acc : acc;
 }
 
-template <typename T> static inline size_t saa_tab_bytes(int B, int N) { return align_up((size_t)B * N * sizeof(fused::FrameTap<T>)); }
+// the taps of one per-item run, at the head of the workspace: the carve, and measured, what the queries add for it
+template <typename T> static fused::FrameTap<T> *carve_saa_tab(Arena &ar, int B, int N) { return ar.take<fused::FrameTap<T>>((size_t)B * N); }
+template <typename T> static inline size_t saa_tab_bytes(int B, int N)
+{
+    return measured([&](Arena &m) { carve_saa_tab<T>(m, B, N); });
+}
 
 static size_t saa_ws_bound(int eb, int B, int N, int h, int w, int f)
 {
@@ -248,10 +253,10 @@ static int saa_dispatch_items(const T *lr, int B, int N, int h, int w, const dou
         return SRX_E_WORKSPACE;
     g_last_path = p.name;
     // the head of the workspace holds the taps of one per-item run, every run's driver gets the rest
-    const size_t tabb = saa_tab_bytes<T>(saa_chunk_items(B, N), N);
-    fused::FrameTap<T> *tab = reinterpret_cast<fused::FrameTap<T> *>(ws);
-    void *wsr = (char *)ws + tabb;
-    const size_t wsrb = wsb - tabb;
+    Arena ar(ws, wsb);
+    fused::FrameTap<T> *tab = carve_saa_tab<T>(ar, saa_chunk_items(B, N), N);
+    void *wsr = (char *)ws + ar.off;
+    const size_t wsrb = wsb - ar.off;
     const size_t fr = (size_t)N * h * w, P = (size_t)h * f * w * f;
     for (const Run &r : p.runs) {
         const double *shr = sh + (size_t)r.b0 * 2 * N;

@@ -268,7 +268,7 @@ __global__ void __launch_bounds__(256) k_edge_dist_range(int H, int W, EdgeLine 
 constexpr int SSIM_MAX_R = 7;
 constexpr int SSIM_TW = 256;                         // crop columns per block
 constexpr int SSIM_TARGET_BLOCKS = 1024;             // 4096 waves: 16 per CU
-constexpr int SSIM_MAX_BLOCKS = RED_BLOCKS * NMOM;   // per item: the partials fit in moments_ws(B)
+constexpr int SSIM_MAX_BLOCKS = RED_BLOCKS * NMOM;   // per item: what srx_metrics_workspace_bytes sizes the partials for
 template <typename T> struct SsimArgs {
     T k[2 * SSIM_MAX_R + 1];  // correlation taps, 2R + 1 used
     T c1, c2, cov_norm;
@@ -369,14 +369,23 @@ __global__ void __launch_bounds__(64) k_mean_partials(const double *__restrict__
 }
 
 // ---- host ---------------------------------------------------------------------------------------------------------------------------
-static inline size_t moments_ws(int B) { return align_up((size_t)B * RED_BLOCKS * NMOM * sizeof(double)); }
-static inline size_t rows_ws(int H, int nbin) { return align_up((size_t)H * 2 * nbin * sizeof(double)); }
+// The three layouts of this file, each the carve of the calls that use it and, measured, a term of the size below:
+// block partials per item (pair_moments: nblk * NMOM, ssim: nblk; at most SSIM_MAX_BLOCKS = RED_BLOCKS * NMOM either way) ...
+static double *carve_partials(Arena &ar, size_t B, size_t per_item) { return ar.take<double>(B * per_item); }
+// ... per-row sums and counts of nbin bins (ring_sums, edge_bins) ...
+static double *carve_rows(Arena &ar, size_t H, size_t nbin) { return ar.take<double>(H * 2 * nbin); }
+// ... and two float64 planes (edge_magnitude)
+struct Planes {
+    double *a, *b;
+};
+static Planes carve_planes(Arena &ar, size_t H, size_t W) { return {ar.take<double>(H * W), ar.take<double>(H * W)}; }
 // srx_metrics_workspace_bytes: one size for every metric of a [B, H, W] batch with nbin bins.  A call is held to it at its own
 // arguments (B = 1 / nbin = 1 where it has none), so a caller that sized the arena for the whole set passes every call.
 static inline size_t workspace_bytes(int B, int H, int W, int nbin)
 {
-    const size_t a = moments_ws(B > 0 ? B : 1), b = rows_ws(H > 0 ? H : 1, nbin > 0 ? nbin : 1),
-                 c = 2 * align_up((size_t)(H > 0 ? H : 1) * (W > 0 ? W : 1) * sizeof(double));
+    const size_t b1 = B > 0 ? B : 1, h1 = H > 0 ? H : 1, w1 = W > 0 ? W : 1, n1 = nbin > 0 ? nbin : 1;
+    const size_t a = measured([&](Arena &m) { carve_partials(m, b1, SSIM_MAX_BLOCKS); }), b = measured([&](Arena &m) { carve_rows(m, h1, n1); }),
+                 c = measured([&](Arena &m) { carve_planes(m, h1, w1); });
     return std::max(a, std::max(b, c));
 }
 
@@ -390,7 +399,7 @@ static int pair_moments(const T *ref, const T *test, int B, int H, int W, int bo
     Arena ar(ws, wsb);
     ar.require(workspace_bytes(B, H, W, 1));
     const int nblk = std::min(RED_BLOCKS, H - 2 * border);
-    double *part = ar.take<double>((size_t)B * nblk * NMOM);
+    double *part = carve_partials(ar, B, (size_t)nblk * NMOM);
     if (!ar.ok)
         return SRX_E_WORKSPACE;
     hipLaunchKernelGGL(k_pair_moments<T>, dim3(nblk, B), dim3(256), 0, st, ref, test, H, W, border, part);
@@ -437,7 +446,7 @@ static int ssim(const T *ref, const T *test, int B, int H, int W, int border, in
     const int nblk = gx * gy;
     Arena ar(ws, wsb);
     ar.require(workspace_bytes(B, H, W, 1));
-    double *part = ar.take<double>((size_t)B * nblk);
+    double *part = carve_partials(ar, B, nblk);
     if (!ar.ok)
         return SRX_E_WORKSPACE;
     const dim3 grid(gx, gy, B);
@@ -474,7 +483,7 @@ static int ring_sums(const T *img, int H, int W, double cy, double cx, int nbin,
         return SRX_E_INVALID;
     Arena ar(ws, wsb);
     ar.require(workspace_bytes(1, H, W, nbin));
-    double *rows = ar.take<double>((size_t)H * 2 * nbin);
+    double *rows = carve_rows(ar, H, nbin);
     if (!ar.ok)
         return SRX_E_WORKSPACE;
     hipLaunchKernelGGL(k_ring_rows<T>, dim3(H), dim3(256), (size_t)2 * nbin * sizeof(double), st, img, H, W, cy, cx, nbin, rows);
@@ -513,7 +522,7 @@ static int edge_magnitude(const double *roi, int H, int W, double sigma, double 
         t.k[j] = 0.0;
     Arena ar(ws, wsb);
     ar.require(workspace_bytes(1, H, W, 1));
-    double *a = ar.take<double>((size_t)H * W), *b = ar.take<double>((size_t)H * W);
+    const auto [a, b] = carve_planes(ar, H, W);
     if (!ar.ok)
         return SRX_E_WORKSPACE;
     const dim3 grid(cdiv(W, 64), cdiv(H, 4)), blk(64, 4);
@@ -533,7 +542,7 @@ static int edge_bins(const T *roi, int H, int W, EdgeLine e, double *out /*[2 nb
         return SRX_E_INVALID;
     Arena ar(ws, wsb);
     ar.require(workspace_bytes(1, H, W, e.nbin));
-    double *rows = ar.take<double>((size_t)H * 2 * e.nbin);
+    double *rows = carve_rows(ar, H, e.nbin);
     if (!ar.ok)
         return SRX_E_WORKSPACE;
     hipLaunchKernelGGL(k_edge_bins_rows<T>, dim3(H), dim3(128), 0, st, roi, H, W, e, rows);

@@ -1233,16 +1233,30 @@ template <typename T> struct Common {
     bool sep, zero, own_build;
 };
 
-// what common_prep carves
+// ---- what common_prep carves ----
+// the counts its layout depends on.  ty, tx: entries per frame of tabY / tabX -- Hg and Wg in a call, the longer side for both in the bound
+struct CommonDims {
+    size_t B, N, Hg, Wg, ty, tx, NB, NS;
+};
+static inline size_t near_slots(int N) { return (N + 3) & ~3; }                       // slots per near-band pixel
+static inline size_t near_bound(size_t Hg, size_t Wg) { return 20 * (Hg + Wg); }     // NB <= this: PB <= 18 rows + 18 columns of the plane
+template <typename T> struct CommonTabs {
+    T *Mg, *Cg, *Mu;
+    MTap *tabY, *tabX;
+    double *Vtot, *Vpart;  // Vpart: k_mosaic_build's block partials of V
+    int *ncu, *nyx;
+};
+// the layout: on the call's arena it is the carve, on a counting one the size (a braced list is evaluated left to right)
+template <typename T> static CommonTabs<T> carve_common(Arena &ar, const CommonDims &d)
+{
+    return {ar.take<T>(d.B * d.Hg * d.Wg), ar.take<T>(d.Hg * d.Wg), ar.take<T>(d.B * d.NB), ar.take<MTap>(d.N * d.ty), ar.take<MTap>(d.N * d.tx),
+            ar.take<double>(d.B), ar.take<double>(d.B * cdiv((int)d.Wg, 64) * cdiv((int)d.Hg, 4)), ar.take<int>(d.NB), ar.take<int>(d.NB * d.NS)};
+}
 static inline size_t ws_common(int eb, int B, int N, int H, int W)
 {
-    const size_t Hg = H + 2 * SRX_NPAD + 3, Wg = W + 2 * SRX_NPAD + 3;
-    const size_t NBmax = 20 * (Hg + Wg);  // near band: PB <= 18 rows + 18 columns of the plane
-    const size_t NS = (N + 3) & ~3;
-    return align_up((size_t)B * Hg * Wg * eb) + align_up(Hg * Wg * eb) + align_up((size_t)B * NBmax * eb) +
-           2 * align_up((size_t)N * (Hg > Wg ? Hg : Wg) * sizeof(MTap)) + align_up((size_t)B * sizeof(double)) +
-           align_up((size_t)B * cdiv((int)Wg, 64) * cdiv((int)Hg, 4) * sizeof(double)) +  // k_mosaic_build's block partials of V
-           align_up(NBmax * sizeof(int)) + align_up(NBmax * NS * sizeof(int));
+    const size_t Hg = H + 2 * SRX_NPAD + 3, Wg = W + 2 * SRX_NPAD + 3, tl = Hg > Wg ? Hg : Wg;
+    const CommonDims d{(size_t)B, (size_t)N, Hg, Wg, tl, tl, near_bound(Hg, Wg), near_slots(N)};
+    return measured([&](Arena &m) { eb == 8 ? (void)carve_common<double>(m, d) : (void)carve_common<float>(m, d); });
 }
 
 // own_build: the implementation reads the LR frames itself and wants no M / C / Mu planes (a batch of patches on a full phase grid,
@@ -1259,16 +1273,13 @@ static int common_prep(Common<T> &c, bool own_build, const S *lr, int B, int N, 
     if (!plan_axis(N, sh, 0, f, py) || !plan_axis(N, sh, 1, f, px))
         return SRX_E_UNSUPPORTED;
     const int NB = py.PB * Wg + (Hg - py.PB) * px.PB;  // pixels of the near band
-    const int NS = (N + 3) & ~3;                        // slots per near-band pixel
+    const int NS = (int)near_slots(N);
     c.NB = NB, c.NS = NS, c.Hg = Hg, c.Wg = Wg;
-    T *Mg = c.Mg = ar.take<T>((size_t)B * Hg * Wg), *Cg = c.Cg = ar.take<T>((size_t)Hg * Wg);
-    T *Mu = c.Mu = ar.take<T>((size_t)B * NB);
-    MTap *tabY = c.tabY = ar.take<MTap>((size_t)N * Hg), *tabX = c.tabX = ar.take<MTap>((size_t)N * Wg);
-    double *Vtot = c.Vtot = ar.take<double>(B);
-    double *Vpart = ar.take<double>((size_t)B * cdiv(Wg, 64) * cdiv(Hg, 4));
-    int *ncu = c.ncu = ar.take<int>(NB), *nyx = c.nyx = ar.take<int>((size_t)NB * NS);
+    const auto [Mg, Cg, Mu, tabY, tabX, Vtot, Vpart, ncu, nyx] =
+        carve_common<T>(ar, CommonDims{(size_t)B, (size_t)N, (size_t)Hg, (size_t)Wg, (size_t)Hg, (size_t)Wg, (size_t)NB, (size_t)NS});
     if (!ar.ok)
         return SRX_E_WORKSPACE;
+    c.Mg = Mg, c.Cg = Cg, c.Mu = Mu, c.tabY = tabY, c.tabX = tabX, c.Vtot = Vtot, c.ncu = ncu, c.nyx = nyx;
     AxisDev dy, dx;
     dy.E = py.E, dy.D = py.D, dx.E = px.E, dx.D = px.D;
     for (int q = 0; q < SRX_MAX_FRAMES; q++)
@@ -1305,20 +1316,25 @@ static int common_prep(Common<T> &c, bool own_build, const S *lr, int B, int N, 
 
 // ---- the tile kernels of this file: every mosaic call no register-resident implementation (srx_route.hpp's table) takes ----
 // behind the common tables: the blurred plane, G, per-tile MSE partials
+template <typename T> struct TileTabs {
+    T *pad, *G;
+    double *epart;  // per-tile MSE partial sums of one iteration
+};
+template <typename T> static TileTabs<T> carve_tiles(Arena &ar, size_t B, int H, int W)
+{
+    const int Hp = H + 2 * SRX_NPAD, Wp = W + 2 * SRX_NPAD, Hg = Hp + 3, Wg = Wp + 3;
+    return {ar.take<T>(B * Hp * Wp), ar.take<T>(B * Hg * Wg), ar.take<double>(B * cdiv(Hg, 32) * cdiv(Wg, 32))};
+}
 static inline size_t tiles_bytes(int eb, int B, int, int H, int W)
 {
-    const size_t Hp = H + 2 * SRX_NPAD, Wp = W + 2 * SRX_NPAD, Hg = Hp + 3, Wg = Wp + 3;
-    return align_up((size_t)B * Hp * Wp * eb) + align_up((size_t)B * Hg * Wg * eb) +
-           align_up((size_t)B * cdiv((int)Hg, 32) * cdiv((int)Wg, 32) * sizeof(double));
+    return measured([&](Arena &m) { eb == 8 ? (void)carve_tiles<double>(m, B, H, W) : (void)carve_tiles<float>(m, B, H, W); });
 }
 
 template <typename T>
 static int iterate(const Common<T> &c, const T *hr_init, T *hr, int n_iter, double *errors, Arena &ar, hipStream_t st)
 {
     const int B = c.B, H = c.H, W = c.W, Hp = H + 2 * SRX_NPAD, Wp = W + 2 * SRX_NPAD, Hg = c.Hg, Wg = c.Wg;
-    T *pad = ar.take<T>((size_t)B * Hp * Wp);
-    T *G = ar.take<T>((size_t)B * Hg * Wg);
-    double *epart = ar.take<double>((size_t)B * cdiv(Hg, 32) * cdiv(Wg, 32));  // per-tile MSE partial sums of one iteration
+    const auto [pad, G, epart] = carve_tiles<T>(ar, B, H, W);
     if (!ar.ok)
         return SRX_E_WORKSPACE;
     constexpr int TS = TileCfg<T>::T_HR;
@@ -1386,10 +1402,28 @@ static inline bool saa_eligible(int N, int h, int w, const double *sh, int f)
     return plan_axis(N, sh, 0, f, a) && plan_axis(N, sh, 1, f, a);
 }
 
+// the counts shift_and_add's layout depends on.  zy, zx: entries of the two zoom tap tables (H and W in a call); two_pass: the W plane
+struct SaaDims {
+    size_t B, N, h, w, f, zy, zx;
+    bool two_pass;
+};
+template <typename T> struct SaaTabs {
+    T *coef, *cscr;
+    AxisTap<T> *zy, *zx;
+    T *Wpl;  // the accumulated plane of the two-pass form (or null)
+};
+template <typename T> static SaaTabs<T> carve_saa(Arena &ar, const SaaDims &d)
+{
+    const size_t Hw = d.h * d.f + 2 * SRX_NPAD + 3, Ww = d.w * d.f + 2 * SRX_NPAD + 3;
+    return {ar.take<T>(d.B * d.N * d.h * d.w), ar.take<T>(d.B * d.N * d.h * d.w), ar.take<AxisTap<T>>(d.zy), ar.take<AxisTap<T>>(d.zx),
+            d.two_pass ? ar.take<T>(d.B * Hw * Ww) : nullptr};
+}
+// the bound: the two-pass form, and both tap tables at the longer side
 static inline size_t saa_ws(int eb, int B, int N, int h, int w, int f)
 {
-    return 2 * align_up((size_t)B * N * h * w * eb) + 2 * align_up((size_t)(h > w ? h : w) * f * sizeof(AxisTap<double>)) +
-           align_up((size_t)B * ((size_t)h * f + 2 * SRX_NPAD + 3) * ((size_t)w * f + 2 * SRX_NPAD + 3) * eb);  // the W plane of the two-pass form
+    const size_t tl = (size_t)(h > w ? h : w) * f;
+    const SaaDims d{(size_t)B, (size_t)N, (size_t)h, (size_t)w, (size_t)f, tap_bound(eb, tl), tap_bound(eb, tl), true};
+    return measured([&](Arena &m) { eb == 8 ? (void)carve_saa<double>(m, d) : (void)carve_saa<float>(m, d); });
 }
 
 // S: the type of the LR samples, T or uint8_t (srx_saa_u8lr_*).  The three prefilter forms are the only readers of the frames: the two
@@ -1406,11 +1440,9 @@ static int saa(const S *lr, int B, int N, int h, int w, const double *sh, int f,
     if (!plan_axis(N, sh, 0, f, py) || !plan_axis(N, sh, 1, f, px))
         return SRX_E_UNSUPPORTED;
     Arena ar(ws, wsb);
-    T *coef = ar.take<T>((size_t)B * N * h * w), *cscr = ar.take<T>((size_t)B * N * h * w);
-    AxisTap<T> *zy = ar.take<AxisTap<T>>(H), *zx = ar.take<AxisTap<T>>(W);
     const bool two_pass = !(call_flags() & SRX_FLAG_DIAG_SAA_ONE_PASS);
     const int Hw = H + 2 * SRX_NPAD + 3, Ww = W + 2 * SRX_NPAD + 3;
-    T *Wpl = two_pass ? ar.take<T>((size_t)B * Hw * Ww) : nullptr;
+    const auto [coef, cscr, zy, zx, Wpl] = carve_saa<T>(ar, SaaDims{(size_t)B, (size_t)N, (size_t)h, (size_t)w, (size_t)f, (size_t)H, (size_t)W, two_pass});
     if (!ar.ok)
         return SRX_E_WORKSPACE;
     if (h == 64 && w == 64 && sizeof(T) == 4) {

@@ -1435,11 +1435,31 @@ static inline bool builds_itself(const mosaic::AxisPlan &py, const mosaic::AxisP
     return axis_map(py, N, f, bm.y, cy, ny) && axis_map(px, N, f, bm.x, cx, nx) && ny * nx == N;
 }
 
+// the counts the workspace layout depends on (a patch is PN x PN; its near band has at most NN_PAD pixels)
+struct Dims {
+    size_t B, ngrp;
+};
+// what a call carves, in this order; PatchTabs is its read-only view for the kernel
+struct Carved {
+    BuildMaps *maps;
+    float *Mt;
+    unsigned *Mt8;
+    int *m8;
+    float *Ct;
+    uint2 *nrec, *nent;
+    float2 *Mn;
+    AxisW *aw;
+    float *k2;
+};
+// the layout: on the call's arena it is the carve, on a counting one the size (a braced list is evaluated left to right)
+static Carved carve(Arena &ar, const Dims &d)
+{
+    return {ar.take<BuildMaps>(1), ar.take<float>(d.B * PN * PN), ar.take<unsigned>(d.B * (PN / 4) * PN), ar.take<int>(d.B), ar.take<float>((size_t)PN * PN),
+            ar.take<uint2>(NN_PAD), ar.take<uint2>(d.ngrp * NN_PAD), ar.take<float2>(d.B * NN_PAD), ar.take<AxisW>(2), ar.take<float>(112)};
+}
 static inline size_t tabs_bytes(int, int B, int N, int, int)
 {
-    const size_t ngrp = ((size_t)N + 3) / 4;
-    return align_up(sizeof(BuildMaps)) + align_up((size_t)B * PN * PN * 4) + align_up((size_t)B * (PN / 4) * PN * 4) + align_up((size_t)B * 4) + align_up((size_t)PN * PN * 4) +
-           align_up((size_t)NN_PAD * 8) + align_up(ngrp * NN_PAD * 8) + align_up((size_t)B * NN_PAD * 8) + align_up(2 * sizeof(AxisW)) + align_up(112 * 4);
+    return measured([&](Arena &m) { carve(m, Dims{(size_t)B, ((size_t)N + 3) / 4}); });
 }
 
 // a PSF that is not rank 1: the 7 x 7 weights in column layout (lane-direction tap, then register-direction tap), the forward ones times
@@ -1464,15 +1484,7 @@ static int iterate(const mosaic::Common<float> &c, const float *hr_init, float *
     const int B = c.B, N = c.N, f = c.f, NS = c.NS;
     const mosaic::AxisPlan &py = c.py, &px = c.px;
     const int Hg = PN + 27, Wg = PN + 27, ngrp = NS / 4;
-    BuildMaps *maps = ar.take<BuildMaps>(1);
-    float *Mt = ar.take<float>((size_t)B * PN * PN);
-    unsigned *Mt8 = ar.take<unsigned>((size_t)B * (PN / 4) * PN);
-    int *m8 = ar.take<int>(B);
-    float *Ct = ar.take<float>((size_t)PN * PN);
-    uint2 *nrec = ar.take<uint2>(NN_PAD), *nent = ar.take<uint2>((size_t)ngrp * NN_PAD);
-    float2 *Mn = ar.take<float2>((size_t)B * NN_PAD);
-    AxisW *aw = ar.take<AxisW>(2);
-    float *k2 = ar.take<float>(112);
+    const auto [maps, Mt, Mt8, m8, Ct, nrec, nent, Mn, aw, k2] = carve(ar, Dims{(size_t)B, (size_t)ngrp});
     if (!ar.ok)
         return SRX_E_WORKSPACE;
     PatchArgs pa;

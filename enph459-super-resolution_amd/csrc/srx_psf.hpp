@@ -349,12 +349,19 @@ static inline int check_args(int elem_bytes, int N, int H, int W, int halfwidth)
     return SRX_OK;
 }
 
+// what a call carves: one candidate (value, index) per chunk of every frame, and the frames' peaks; np = N * chunks of a frame
+struct Tabs {
+    double *pval;
+    unsigned *pidx;
+    int *peaks;
+};
+static Tabs carve(Arena &ar, size_t N, size_t np) { return {ar.take<double>(np), ar.take<unsigned>(np), ar.take<int>(N * 3)}; }
+
 static inline size_t workspace_bytes(int elem_bytes, int N, int H, int W, int halfwidth)
 {
     if (check_args(elem_bytes, N, H, W, halfwidth) != SRX_OK)
         return 0;
-    const size_t np = (size_t)N * chunks_of((size_t)H * W * elem_bytes);
-    return align_up(np * sizeof(double)) + align_up(np * sizeof(unsigned)) + align_up((size_t)N * 3 * sizeof(int));
+    return measured([&](Arena &m) { carve(m, N, (size_t)N * chunks_of((size_t)H * W * elem_bytes)); });
 }
 
 template <typename T>
@@ -367,9 +374,7 @@ static int estimate(const T *frames, int N, int H, int W, int halfwidth, double 
     const size_t np = (size_t)N * chunks;
     Arena ar(ws, wsb);
     ar.require(workspace_bytes((int)sizeof(T), N, H, W, halfwidth));
-    double *pval = ar.take<double>(np);
-    unsigned *pidx = ar.take<unsigned>(np);
-    int *peaks = ar.take<int>((size_t)N * 3);
+    const auto [pval, pidx, peaks] = carve(ar, N, np);
     if (!ar.ok)
         return SRX_E_WORKSPACE;
     const int reach = halfwidth + EXTRA_REACH, win = 2 * reach + 1;

@@ -521,6 +521,27 @@ static inline bool geometry(int B, int N, int H, int W, int search, int border, 
     return h >= MIN_CROP && w >= MIN_CROP;
 }
 
+// the counts the workspace layout depends on: the moving frames, their padded plane, and the block partials per frame of the coarse
+// search and of a Gauss-Newton step -- both at the widest crop, border 0, whatever the call's border
+struct Dims {
+    size_t nf, plane, cpart, gpart;
+};
+static inline Dims dims(int B, int N, int H, int W, int search)
+{
+    const int w0 = W - 2 * (search + 2), D = 2 * search + 1;
+    return {(size_t)B * (N - 1), (size_t)(H + 2 * SRX_NPAD) * (W + 2 * SRX_NPAD), (size_t)coarse_blocks_max(w0) * (3 * D * D + 2), (size_t)gn_blocks_max(w0) * NG};
+}
+template <typename T> struct Tabs {
+    T *coef, *scratch;
+    double *cpart, *gpart, *sd;
+    int *si;
+};
+// the layout: on the call's arena it is the carve, on a counting one the size (a braced list is evaluated left to right)
+template <typename T> static Tabs<T> carve(Arena &ar, const Dims &d)
+{
+    return {ar.take<T>(d.nf * d.plane), ar.take<T>(d.nf * d.plane), ar.take<double>(d.nf * d.cpart), ar.take<double>(d.nf * d.gpart),
+            ar.take<double>(d.nf * SD), ar.take<int>(d.nf * SI)};
+}
 static inline size_t workspace_bytes(int elem_bytes, int B, int N, int H, int W, int search)
 {
     if ((elem_bytes != 4 && elem_bytes != 8) || B <= 0 || N < 2 || H <= 0 || W <= 0 || search < 0 || search > MAX_SEARCH)
@@ -528,9 +549,8 @@ static inline size_t workspace_bytes(int elem_bytes, int B, int N, int H, int W,
     int m, h, w;
     if (!geometry(B, N, H, W, search, 0, m, h, w))  // border 0: the widest crop
         return 0;
-    const size_t nf = (size_t)B * (N - 1), plane = (size_t)(H + 2 * SRX_NPAD) * (W + 2 * SRX_NPAD), noff = (size_t)(2 * search + 1) * (2 * search + 1);
-    return 2 * align_up(nf * plane * elem_bytes) + align_up(nf * coarse_blocks_max(w) * (3 * noff + 2) * sizeof(double)) +
-           align_up(nf * gn_blocks_max(w) * NG * sizeof(double)) + align_up(nf * SD * sizeof(double)) + align_up(nf * SI * sizeof(int));
+    const Dims d = dims(B, N, H, W, search);
+    return measured([&](Arena &a) { elem_bytes == 8 ? (void)carve<double>(a, d) : (void)carve<float>(a, d); });
 }
 
 // F: the frames' type (T, or uint8_t: srx_register_u8_*); T: the coefficients and the arithmetic
@@ -557,14 +577,9 @@ static int register_frames(const F *frames, int B, int N, int H, int W, int ref,
     if (nf > 65535 || plane * sizeof(T) >= ((size_t)1 << 31))
         return SRX_E_UNSUPPORTED;
     const Plan p = make_plan(g.h, g.w, search);
-    const int w0 = W - 2 * (search + 2);  // the crop width the workspace formula assumes (border 0)
     Arena ar(ws, wsb);
     ar.require(workspace_bytes((int)sizeof(T), B, N, H, W, search));
-    T *coef = ar.take<T>(nf * plane), *scratch = ar.take<T>(nf * plane);
-    double *cpart = ar.take<double>((size_t)nf * coarse_blocks_max(w0) * p.nv);
-    double *gpart = ar.take<double>((size_t)nf * gn_blocks_max(w0) * NG);
-    double *sd = ar.take<double>((size_t)nf * SD);
-    int *si = ar.take<int>((size_t)nf * SI);
+    const auto [coef, scratch, cpart, gpart, sd, si] = carve<T>(ar, dims(B, N, H, W, search));
     if (!ar.ok)
         return SRX_E_WORKSPACE;
     hipLaunchKernelGGL(HIP_KERNEL_NAME(k_reg_pad<T, F>), dim3(cdiv(W + 2 * SRX_NPAD, 64), cdiv(H + 2 * SRX_NPAD, 4), nf), dim3(64, 4), 0, st, frames, g, coef);

@@ -1,6 +1,8 @@
 // srx_route.hpp -- the implementations of the mosaic formulation (srx_mosaic.hpp) as ONE table: which of them a call takes, what each
 // carves from the workspace, and the driver that prepares the call and runs the one chosen.  Included after every implementation header;
-// a new implementation is a header with shape_admits / eligible / tabs_bytes / iterate, a row here and a case in ibp()'s switch.
+// a new implementation is a header with shape_admits / eligible / iterate, a dims bound and a carve (its workspace layout as ONE function:
+// iterate runs it on the call's arena with the call's counts, tabs_bytes measures it on a counting arena with the shape-only bound of
+// those counts), a row here and a case in ibp()'s switch.
 #pragma once
 #include "srx_mosaic.hpp"
 #include "srx_patch.hpp"
@@ -22,7 +24,7 @@ struct ImplRow {
     bool (*shape_admits)(int eb, int H, int W);      // may a call of this shape EVER take it (the shape-only workspace bound's question);
                                                      // each header's eligible() asks its own first, so bound and dispatch cannot disagree
     bool (*eligible)(int eb, int N, int H, int W, const double *sh, const double *k, int kh, int kw, int f);  // reads call_flags()
-    size_t (*tabs_bytes)(int eb, int B, int N, int H, int W);
+    size_t (*tabs_bytes)(int eb, int B, int N, int H, int W);  // the implementation's carve, measured at its dims bound
 };
 
 // (thin wrappers, not conditions of patch::eligible itself: stile::eligible calls that and must not inherit the flag exclusions -- a

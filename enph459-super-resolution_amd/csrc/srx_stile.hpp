@@ -643,11 +643,26 @@ template <typename T> static inline void fill_axis(const mosaic::AxisPlan &pl, c
     ax.ex = pl.nmax, ax.nb = -pl.nmin, ax.E = pl.E;
 }
 
+// what a call carves, in this order (the counts are srx_patch.hpp's: the batch and the near band's slot groups)
+template <typename T> struct Carved {
+    T *Mt, *P;
+    unsigned *Mt8;
+    int *m8;
+    T *Ct;
+    uint2 *nrec, *nent;
+    T2<T> *Mn;
+    double *epart;
+};
+// the layout: on the call's arena it is the carve, on a counting one the size (a braced list is evaluated left to right)
+template <typename T> static Carved<T> carve(Arena &ar, const patch::Dims &d)
+{
+    return {ar.take<T>(d.B * PN * PN), ar.take<T>(d.B * PN * PN), ar.take<unsigned>(d.B * (PN / 4) * PN), ar.take<int>(d.B), ar.take<T>((size_t)PN * PN),
+            ar.take<uint2>(NN_PAD), ar.take<uint2>(d.ngrp * NN_PAD), ar.take<T2<T>>(d.B * NN_PAD), ar.take<double>(d.B * 4)};
+}
 static inline size_t tabs_bytes(int eb, int B, int N, int, int)
 {
-    const size_t ngrp = ((size_t)N + 3) / 4, plane = (size_t)B * PN * PN * eb;
-    return 2 * align_up(plane) + align_up((size_t)B * (PN / 4) * PN * 4) + align_up((size_t)B * 4) + align_up((size_t)PN * PN * eb) + align_up((size_t)NN_PAD * 8) +
-           align_up(ngrp * NN_PAD * 8) + align_up((size_t)B * NN_PAD * 2 * eb) + align_up((size_t)B * 4 * sizeof(double));
+    const patch::Dims d{(size_t)B, ((size_t)N + 3) / 4};
+    return measured([&](Arena &m) { eb == 8 ? (void)carve<double>(m, d) : (void)carve<float>(m, d); });
 }
 
 template <typename T>
@@ -657,13 +672,7 @@ static int iterate(const mosaic::Common<T> &c, const T *hr_init, T *hr, int n_it
     const mosaic::AxisPlan &py = c.py, &px = c.px;
     const double scale = c.scale;
     const int Hg = PN + 27, Wg = PN + 27, ngrp = NS / 4;
-    T *Mt = ar.take<T>((size_t)B * PN * PN), *P = ar.take<T>((size_t)B * PN * PN);
-    unsigned *Mt8 = ar.take<unsigned>((size_t)B * (PN / 4) * PN);
-    int *m8 = ar.take<int>(B);
-    T *Ct = ar.take<T>((size_t)PN * PN);
-    uint2 *nrec = ar.take<uint2>(NN_PAD), *nent = ar.take<uint2>((size_t)ngrp * NN_PAD);
-    T2<T> *Mn = ar.take<T2<T>>((size_t)B * NN_PAD);
-    double *epart = ar.take<double>((size_t)B * 4);
+    const auto [Mt, P, Mt8, m8, Ct, nrec, nent, Mn, epart] = carve<T>(ar, patch::Dims{(size_t)B, (size_t)ngrp});
     if (!ar.ok)
         return SRX_E_WORKSPACE;
     patch::PatchArgs pa;

@@ -675,14 +675,55 @@ __global__ void __launch_bounds__(256 * NSY, SRX_ZTILE_WPE)
 }
 
 // ---- host ----------------------------------------------------------------------------------------------------------
+// The geometry of an H x W frame in tiles of vty x VT owned pixels, written once for k_ibp_ztile and k_ibp_ctile (vty: its own rows): the
+// padded planes, and the near band's rows above and columns left of the image with the table of their NT entries.
+static inline int padded(int n, int v) { return cdiv(n, v) * v + 2 * HALO; }
+static inline void frame_geometry(ZArgs &za, int H, int W, int vty, const mosaic::AxisPlan &py, const mosaic::AxisPlan &px, int NS)
+{
+    za.H = H, za.W = W, za.tiles_x = cdiv(W, VT), za.tiles_y = cdiv(H, vty);
+    za.HP = padded(H, vty), za.WP = padded(W, VT);
+    za.exy = py.nmax, za.nby = -py.nmin, za.exx = px.nmax, za.nbx = -px.nmin;
+    za.Ey = py.E, za.Ex = px.E;
+    za.WT = W + za.exx, za.LN = za.exx + za.nbx, za.TOPN = (za.exy + za.nby) * za.WT;
+    za.ngrp = NS / 4;
+}
+// the counts the workspace layout depends on: of a call, and their shape-only bound (NT <= 6 (W + 4) + 6 H)
+struct Dims {
+    size_t B, HP, WP, NT, ngrp, ntiles;
+};
+static inline Dims dims_of(int B, const ZArgs &za)
+{
+    return {(size_t)B, (size_t)za.HP, (size_t)za.WP, (size_t)(za.TOPN + (za.H - za.nby) * za.LN), (size_t)za.ngrp, (size_t)za.tiles_x * za.tiles_y};
+}
+static inline Dims dims_bound(int B, int N, int H, int W, int vty)
+{
+    return {(size_t)B, (size_t)padded(H, vty), (size_t)padded(W, VT), (size_t)6 * (W + 4) + (size_t)H * 6, ((size_t)N + 3) / 4,
+            (size_t)cdiv(H, vty) * cdiv(W, VT)};
+}
+
+// what a call carves, in this order; ZTabs is its read-only view for the kernel
+struct Carved {
+    float *Mt, *s0, *s1, *Ct;  // s0, s1: the two padded state planes
+    unsigned *CM;
+    int *cmok;
+    patch::AxisW *aw;
+    float *k2;
+    unsigned *nrec;
+    uint4 *nent;
+    float2 *Mn;
+    double *ep0, *ep1;         // per-tile MSE partials, alternating
+};
+// the layout: on the call's arena it is the carve, on a counting one the size (a braced list is evaluated left to right)
+static Carved carve(Arena &ar, const Dims &d)
+{
+    const size_t splane = (d.HP + 2) * d.WP;
+    return {ar.take<float>(d.B * d.HP * d.WP), ar.take<float>(d.B * splane), ar.take<float>(d.B * splane), ar.take<float>(d.HP * d.WP),
+            ar.take<unsigned>(d.B * (d.WP / 2) * d.HP), ar.take<int>(d.B), ar.take<patch::AxisW>(2), ar.take<float>(112), ar.take<unsigned>(d.NT),
+            ar.take<uint4>(d.ngrp * d.NT), ar.take<float2>(d.B * d.NT), ar.take<double>(d.B * d.ntiles), ar.take<double>(d.B * d.ntiles)};
+}
 static inline size_t tabs_bytes(int, int B, int N, int H, int W)
 {
-    const size_t ngrp = ((size_t)N + 3) / 4, NT = (size_t)6 * (W + 4) + (size_t)H * 6;
-    const size_t ty = cdiv(H, VTY), tx = cdiv(W, VT), HP = ty * VTY + 2 * HALO, WP = tx * VT + 2 * HALO;
-    return align_up((size_t)B * HP * WP * 4) + 2 * align_up((size_t)B * (HP + 2) * WP * 4) + align_up(HP * WP * 4) +
-           align_up((size_t)B * (WP / 2) * HP * 4) + align_up((size_t)B * 4) +
-           align_up(2 * sizeof(patch::AxisW)) + align_up(112 * 4) + align_up(NT * 4) + align_up(ngrp * NT * 16) + align_up((size_t)B * NT * 8) +
-           2 * align_up((size_t)B * ty * tx * 8);
+    return measured([&](Arena &m) { carve(m, dims_bound(B, N, H, W, VTY)); });
 }
 
 // The state of a call between its launches: what iterate() keeps on its stack, and what a plan (srx_ibp_plan_*: the per-call tables built
@@ -705,27 +746,13 @@ static int setup(State &zs, const mosaic::Common<float> &c, const float *hr_init
     const int B = c.B, H = c.H, W = c.W, NS = c.NS;
     const mosaic::AxisPlan &py = c.py, &px = c.px;
     ZArgs &za = zs.za;
-    za.H = H, za.W = W, za.tiles_x = cdiv(W, VT), za.tiles_y = cdiv(H, VTY);
-    za.HP = za.tiles_y * VTY + 2 * HALO, za.WP = za.tiles_x * VT + 2 * HALO;
+    frame_geometry(za, H, W, VTY, py, px, NS);
     const int HP = za.HP, WP = za.WP;
-    za.exy = py.nmax, za.nby = -py.nmin, za.exx = px.nmax, za.nbx = -px.nmin;
-    za.Ey = py.E, za.Ex = px.E;
-    za.WT = W + za.exx, za.LN = za.exx + za.nbx, za.TOPN = (za.exy + za.nby) * za.WT;
-    za.ngrp = NS / 4;
     za.sn = (float)c.step / (float)c.N;
     za.tr_lo = tr_lo, za.tr_hi = tr_hi;
-    const int NT = za.TOPN + (H - za.nby) * za.LN, ntiles = za.tiles_x * za.tiles_y;
-    const size_t splane = (size_t)(HP + 2) * WP;
-    float *Mt = ar.take<float>((size_t)B * HP * WP), *s0 = ar.take<float>(B * splane), *s1 = ar.take<float>(B * splane),
-          *Ct = ar.take<float>((size_t)HP * WP);
-    unsigned *CM = ar.take<unsigned>((size_t)B * (WP / 2) * HP);
-    int *cmok = ar.take<int>(B);
-    patch::AxisW *aw = ar.take<patch::AxisW>(2);
-    float *k2 = ar.take<float>(112);
-    unsigned *nrec = ar.take<unsigned>(NT);
-    uint4 *nent = ar.take<uint4>((size_t)za.ngrp * NT);
-    float2 *Mn = ar.take<float2>((size_t)B * NT);
-    double *ep0 = ar.take<double>((size_t)B * ntiles), *ep1 = ar.take<double>((size_t)B * ntiles);
+    const Dims d = dims_of(B, za);
+    const int NT = (int)d.NT, ntiles = (int)d.ntiles;
+    const Carved t = carve(ar, d);
     if (!ar.ok)
         return SRX_E_WORKSPACE;
     patch::AxisWPair awp;
@@ -733,7 +760,7 @@ static int setup(State &zs, const mosaic::Common<float> &c, const float *hr_init
         awp.y.kb[i] = i < 7 ? c.kc.cy[i] : 0.f, awp.y.kt[i] = i < 7 ? c.kt.cy[i] : 0.f, awp.y.wfb[i] = 0.f;
         awp.x.kb[i] = i < 7 ? c.kc.cx[i] : 0.f, awp.x.kt[i] = i < 7 ? c.kt.cx[i] : 0.f, awp.x.wfb[i] = 0.f;
     }
-    hipLaunchKernelGGL(patch::k_patch_params, dim3(1), dim3(1), 0, st, awp, aw);
+    hipLaunchKernelGGL(patch::k_patch_params, dim3(1), dim3(1), 0, st, awp, t.aw);
     SRX_CHECK_LAUNCH();
     zs.psf = fused::psf_form(c.kc, c.kt);
     if (!c.sep) {
@@ -741,28 +768,28 @@ static int setup(State &zs, const mosaic::Common<float> &c, const float *hr_init
         for (int u = 0; u < 7; u++)
             for (int v = 0; v < 8; v++)
                 kv.v[8 * u + v] = v < 7 ? c.kc.k[7 * u + v] : 0.f, kv.v[56 + 8 * u + v] = v < 7 ? c.kt.k[7 * u + v] : 0.f;
-        hipLaunchKernelGGL(k_ztile_k2, dim3(1), dim3(128), 0, st, kv, k2);
+        hipLaunchKernelGGL(k_ztile_k2, dim3(1), dim3(128), 0, st, kv, t.k2);
         SRX_CHECK_LAUNCH();
     }
-    hipLaunchKernelGGL(k_ztile_prep, dim3(cdiv(WP, 32), cdiv(HP, 32), B + 1), dim3(32, 8), 0, st, c.Mg, c.Cg, B, H, W, HP, WP, za.nby, za.nbx, Mt, Ct);
+    hipLaunchKernelGGL(k_ztile_prep, dim3(cdiv(WP, 32), cdiv(HP, 32), B + 1), dim3(32, 8), 0, st, c.Mg, c.Cg, B, H, W, HP, WP, za.nby, za.nbx, t.Mt, t.Ct);
     SRX_CHECK_LAUNCH();
-    if (fill_bytes(cmok, 0xff, (size_t)B * sizeof(int), st) != hipSuccess)
+    if (fill_bytes(t.cmok, 0xff, (size_t)B * sizeof(int), st) != hipSuccess)
         return SRX_E_HIP;
-    hipLaunchKernelGGL(k_ztile_pack, dim3(cdiv(HP, 256), WP / 2, B), dim3(256), 0, st, Mt, Ct, HP, WP, CM, cmok);
+    hipLaunchKernelGGL(k_ztile_pack, dim3(cdiv(HP, 256), WP / 2, B), dim3(256), 0, st, t.Mt, t.Ct, HP, WP, t.CM, t.cmok);
     SRX_CHECK_LAUNCH();
     // padded state planes: zero borders (and trash rows) once, then the image
-    hipLaunchKernelGGL(k_ztile_zero_border<float>, dim3(HP / 2 + 1, B), dim3(256), 0, st, s0, s1, H, W, HP, WP);
+    hipLaunchKernelGGL(k_ztile_zero_border<float>, dim3(HP / 2 + 1, B), dim3(256), 0, st, t.s0, t.s1, H, W, HP, WP);
     SRX_CHECK_LAUNCH();
-    hipLaunchKernelGGL(k_ztile_copy_in, dim3(cdiv(W, 256), H, B), dim3(256), 0, st, hr_init, H, W, HP, WP, s0, 0);
+    hipLaunchKernelGGL(k_ztile_copy_in, dim3(cdiv(W, 256), H, B), dim3(256), 0, st, hr_init, H, W, HP, WP, t.s0, 0);
     SRX_CHECK_LAUNCH();
     if (NT > 0) {
-        hipLaunchKernelGGL(k_ztile_near_tab, dim3(cdiv(NT, 256)), dim3(256), 0, st, c.ncu, c.nyx, NS, py.PB, px.PB, za, NT, nrec, nent);
+        hipLaunchKernelGGL(k_ztile_near_tab, dim3(cdiv(NT, 256)), dim3(256), 0, st, c.ncu, c.nyx, NS, py.PB, px.PB, za, NT, t.nrec, t.nent);
         SRX_CHECK_LAUNCH();
-        hipLaunchKernelGGL(k_ztile_near_m, dim3(cdiv(NT, 256), B), dim3(256), 0, st, c.Mg, c.Mu, c.NB, py.PB, px.PB, za, NT, Mn);
+        hipLaunchKernelGGL(k_ztile_near_m, dim3(cdiv(NT, 256), B), dim3(256), 0, st, c.Mg, c.Mu, c.NB, py.PB, px.PB, za, NT, t.Mn);
         SRX_CHECK_LAUNCH();
     }
-    zs.tb = ZTabs{Mt, Ct, CM, cmok, aw, k2, nrec, nent, Mn};
-    zs.s0 = s0, zs.s1 = s1, zs.ep0 = ep0, zs.ep1 = ep1, zs.Vtot = c.Vtot, zs.scale = c.scale, zs.B = B, zs.ntiles = ntiles, zs.it = 0, zs.sep = c.sep;
+    zs.tb = ZTabs{t.Mt, t.Ct, t.CM, t.cmok, t.aw, t.k2, t.nrec, t.nent, t.Mn};
+    zs.s0 = t.s0, zs.s1 = t.s1, zs.ep0 = t.ep0, zs.ep1 = t.ep1, zs.Vtot = c.Vtot, zs.scale = c.scale, zs.B = B, zs.ntiles = ntiles, zs.it = 0, zs.sep = c.sep;
     return SRX_OK;
 }
 

@@ -706,6 +706,14 @@ def test_register(prec, case):
 
 
 # =====================================================================================================================================
+# the test files that declare memory-contract cases of their own through ids() above
+REGISTERING_FILES = ("test_gpu_items", "test_gpu_register_u8", "test_gpu_psf", "test_gpu_u8lr")
+
+
 def all_case_ids():
-    """every test id of this file, as the parametrize calls above registered them"""
+    """every memory-contract test id: those the parametrize calls above registered and those of REGISTERING_FILES, which register theirs on
+    import (imported here, not at the top: they import this module)"""
+    import importlib
+    for name in REGISTERING_FILES:
+        importlib.import_module(name)
     return list(TEST_IDS)
