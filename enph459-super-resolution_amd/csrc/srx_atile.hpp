@@ -42,7 +42,7 @@ using btile::transpose64;
 using btile::VOFF_OUT;
 using btile::XW;
 using btile::zero_outside;
-using patch::RW;
+using blk::RW;
 
 #ifndef SRX_AT_DBG
 #define SRX_AT_DBG 0  // timing ablations of a development build (results are wrong): 1 no operand loads, 2 no G stores, 4 no G loads (backward)
@@ -505,7 +505,7 @@ static int iterate(const mosaic::Common<float> &c, const float *hr_init, float *
         return SRX_E_WORKSPACE;
     if (A.nwy > 65535 || B > 65535 || cdiv(H, 4) > 65535)
         return SRX_E_UNSUPPORTED;
-    const double kq = -6.0 * patch::ZD;
+    const double kq = -6.0 * blk::ZD;
     A.kby[7] = A.kbx[7] = A.kty[7] = A.ktx[7] = 0.f;
     for (int i = 0; i < 7; i++) {
         A.kby[i] = (float)(kq * (double)c.kc.cy[i]), A.kbx[i] = (float)(kq * (double)c.kc.cx[i]);

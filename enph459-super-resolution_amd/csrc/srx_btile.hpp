@@ -28,13 +28,11 @@
 namespace srx {
 namespace btile {
 
-using patch::chain64;
-using patch::f8;
-using patch::FIX;
-using patch::K2;
-using patch::PZ;
-using patch::RW;
-using patch::ZP;
+using blk::add_carry;
+using blk::chain64;
+using blk::f8;
+using blk::RW;
+constexpr float K2 = blk::Cn<float>::K2;
 
 #ifdef SRX_STAMPS_INNER  // stamps inside prefilter_block (the last call of a kernel wins)
 #define SRX_PSTAMP2(PH) SRX_PSTAMP(PH)
@@ -115,12 +113,8 @@ __device__ __forceinline__ void prefilter_block(float (&a)[64], bool first, bool
     SRX_PSTAMP2(17);
     __syncthreads();
     SRX_PSTAMP2(18);
-    if (!first) {
-        const float carry = Rprev[slot + lane];
-#pragma unroll
-        for (int i = 0; i < FIX; i++)
-            a[i] = fmaf(ZP.v[i], carry, a[i]);
-    }
+    if (!first)
+        add_carry<false>(a, Rprev[slot + lane]);
     const float cb = last ? a[63] * K2 : 0.f;
     chain64<true>(a, cb);
     Rown[slot + 64 + lane] = a[0];
@@ -132,9 +126,7 @@ __device__ __forceinline__ void prefilter_block(float (&a)[64], bool first, bool
     hi[0] = hi[1] = hi[2] = cb;
     if (!last) {
         const float hb = Rnext[slot + 64 + lane];
-#pragma unroll
-        for (int i = 0; i < FIX; i++)
-            a[63 - i] = fmaf(ZP.v[i], hb, a[63 - i]);
+        add_carry<true>(a, hb);
         hi[0] = hb, hi[1] = Rnext[slot + 128 + lane], hi[2] = Rnext[slot + 192 + lane];
     }
 }
@@ -179,7 +171,7 @@ __device__ __forceinline__ void zero_outside(float (&a)[64], int c0, int hi)
     }
 }
 
-// 7-tap correlation along the registers with three samples from either neighbour block: srx_patch.hpp's blur_block with TWO adjacent
+// 7-tap correlation along the registers with three samples from either neighbour block: srx_block.hpp's blur_block with TWO adjacent
 // outputs per instruction (v_pk_fma_f32).  These kernels run one or two waves per SIMD, where a wave issues an instruction every
 // ~5 cycles whatever it does (profiles/README.md): what counts is the number of instructions, and a packed fma is one.
 typedef float v2f __attribute__((ext_vector_type(2)));
@@ -190,7 +182,7 @@ __device__ __forceinline__ void blur_block(float (&a)[64], bool first, bool last
                                            const f8 kb)
 {
 #if !SRX_BT_PK
-    patch::blur_block(a, first, last, Xown, Xprev, Xnext, s6, lane, kb);
+    blk::blur_block(a, first, last, Xown, Xprev, Xnext, s6, lane, kb);
 #else
     Xown[s6 + lane] = a[0];
     Xown[s6 + 64 + lane] = a[1];
@@ -247,8 +239,6 @@ __device__ __forceinline__ void blur_block(float (&a)[64], bool first, bool last
 // operand, one 16-byte LDS read per row (every wave publishes its columns 0..2 and 63..61 for all 64 rows before the one barrier;
 // a window's outer waves read zeros, as blur_block does).  Rows come from the blocks above / below as in blur_block, their edge
 // columns from the diagonal neighbours' published rows.
-__device__ __forceinline__ float dpp_up(float v, float fill) { return __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(fill), __float_as_int(v), 0x138, 0xf, 0xf, false)); }
-__device__ __forceinline__ float dpp_dn(float v, float fill) { return __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(fill), __float_as_int(v), 0x130, 0xf, 0xf, false)); }
 
 // Input rows R = -RAD .. 63 + RAD of the block, one step each (a template recursion: `#pragma unroll` gave up part-way and indexed the
 // registers dynamically).  The edge columns of a row are requested three steps ahead of their use.  RAD: the PSF's support is (2 RAD + 1)^2 -- 3 for a full 7 x 7; 2 when its outer ring is zero, which
@@ -271,11 +261,11 @@ __device__ __forceinline__ B2Row blur2d_shift(const float (&a)[64], const float 
     B2Row w;
     const float in = R < 0 ? hl[R < 0 ? R + 3 : 0] : (R < 64 ? a[R >= 0 && R < 64 ? R : 0] : hr[R >= 64 ? R - 64 : 0]);
     w.s[3] = in;
-    w.s[2] = dpp_up(in, e.x), w.s[1] = dpp_up(w.s[2], e.y);
-    w.s[4] = dpp_dn(in, e.x), w.s[5] = dpp_dn(w.s[4], e.y);
+    w.s[2] = blk::shift_up(in, e.x), w.s[1] = blk::shift_up(w.s[2], e.y);
+    w.s[4] = blk::shift_dn(in, e.x), w.s[5] = blk::shift_dn(w.s[4], e.y);
     w.s[0] = w.s[6] = 0.f;
     if constexpr (RAD == 3)
-        w.s[0] = dpp_up(w.s[1], e.z), w.s[6] = dpp_dn(w.s[5], e.z);
+        w.s[0] = blk::shift_up(w.s[1], e.z), w.s[6] = blk::shift_dn(w.s[5], e.z);
     return w;
 }
 // One step = the multiply-adds of input row R (its shifted copies `cur` were made a step earlier) + the shifts of row R + 1 + the LDS
@@ -427,7 +417,7 @@ __device__ __forceinline__ void transpose64(const float (&a)[64], float (&r)[64]
     for (int i = 0; i < 64; i++)
         r[i] = a[i];
 #else
-    patch::transpose64(a, r, Tw, lane);
+    blk::transpose64(a, r, Tw, lane);
 #endif
 }
 
@@ -492,7 +482,7 @@ __device__ __forceinline__ void bwd_rows_load(float (&E)[34], __amdgpu_buffer_rs
 // at a padded row = 2 (mod 4): register y is image row Pb - 12 + y, the quads start at y = 2 (mod 4); y = 0, 1 and y = 62, 63 are halves
 // of quads shared with the neighbour blocks (8-byte accesses).
 typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
-using patch::u32x4;
+using blk::u32x4;
 // quad q of the block (q = -1: the half quad of y = 0, 1; 0..14: y = 2 + 4 q ..; 15: the half quad of y = 62, 63)
 template <int Q> __device__ __forceinline__ void quad_load(float (&a)[64], __amdgpu_buffer_rsrc_t rs, int vq0, int W16)
 {
@@ -535,7 +525,7 @@ template <int Q> __device__ __forceinline__ void quad_update(const float (&r)[64
         __builtin_amdgcn_raw_buffer_store_b64(v, rs, vq0 + 15 * W16, 0, 0);
     } else {
         const u32x4 v = {__float_as_uint(U(2 + 4 * Q)), __float_as_uint(U(3 + 4 * Q)), __float_as_uint(U(4 + 4 * Q)), __float_as_uint(U(5 + 4 * Q))};
-        __builtin_amdgcn_raw_buffer_store_b128(v, rs, vq0 + Q * W16, 0, 0);  // (no scalar offset: srx_patch.hpp's st4 note)
+        __builtin_amdgcn_raw_buffer_store_b128(v, rs, vq0 + Q * W16, 0, 0);  // (no scalar offset: srx_block.hpp's st4 note)
     }
 }
 template <int Q0, int Q1> __device__ __forceinline__ void quads_update(const float (&r)[64], const float (&hv)[64], __amdgpu_buffer_rsrc_t rs, int vq0, int W16,
@@ -1108,7 +1098,7 @@ static inline size_t items_tab_bytes(int B, int N)
 // the records of one shift table and the range of their row tap origins: rng = oyf_min, oyf_max, oyb_min, oyb_max
 static inline void make_frames(const double *sh, int N, BFrame *fr, int nfr, int (&rng)[4])
 {
-    const double kq = -6.0 * patch::ZD;
+    const double kq = -6.0 * blk::ZD;
     rng[0] = rng[2] = 1 << 20, rng[1] = rng[3] = -(1 << 20);
     for (int q = 0; q < nfr; q++) {
         BFrame &f = fr[q];
@@ -1159,7 +1149,7 @@ static int ibp_t(const float *lr, int B, int N, int h, int w, const double *sh, 
         return SRX_E_WORKSPACE;
     if (A.nwy > 65535 || B > 65535 || H4 > 65535)
         return SRX_E_UNSUPPORTED;
-    const double kq = -6.0 * patch::ZD;
+    const double kq = -6.0 * blk::ZD;
     fused::Kernel7<float> kc, kt;
     fused::make_kernel7<float>(k, kh, kw, false, kc);
     fused::make_kernel7<float>(k, kh, kw, true, kt);

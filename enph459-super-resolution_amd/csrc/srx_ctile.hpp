@@ -170,31 +170,6 @@ template <typename T> __global__ void k_ctile_kw(KwTab t, T *__restrict__ dst)
         dst[threadIdx.x] = (T)t.v[threadIdx.x];
 }
 
-// ---- lane shifts that pull a given value in at the end of the wave --------------------------------------------------------
-// up: lane i reads lane i - 1, lane 0 keeps `fill`;  dn: lane i reads lane i + 1, lane 63 keeps `fill`
-__device__ __forceinline__ float shift_up(float v, float fill)
-{
-    return __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(fill), __float_as_int(v), 0x138, 0xf, 0xf, false));
-}
-__device__ __forceinline__ float shift_dn(float v, float fill)
-{
-    return __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(fill), __float_as_int(v), 0x130, 0xf, 0xf, false));
-}
-__device__ __forceinline__ double shift_up(double v, double fill)
-{
-    const long long a = __double_as_longlong(v), o = __double_as_longlong(fill);
-    const unsigned lo = (unsigned)__builtin_amdgcn_update_dpp((int)(unsigned)o, (int)(unsigned)a, 0x138, 0xf, 0xf, false);
-    const unsigned hi = (unsigned)__builtin_amdgcn_update_dpp((int)(unsigned)(o >> 32), (int)(unsigned)(a >> 32), 0x138, 0xf, 0xf, false);
-    return __longlong_as_double((long long)((unsigned long long)hi << 32 | lo));
-}
-__device__ __forceinline__ double shift_dn(double v, double fill)
-{
-    const long long a = __double_as_longlong(v), o = __double_as_longlong(fill);
-    const unsigned lo = (unsigned)__builtin_amdgcn_update_dpp((int)(unsigned)o, (int)(unsigned)a, 0x130, 0xf, 0xf, false);
-    const unsigned hi = (unsigned)__builtin_amdgcn_update_dpp((int)(unsigned)(o >> 32), (int)(unsigned)(a >> 32), 0x130, 0xf, 0xf, false);
-    return __longlong_as_double((long long)((unsigned long long)hi << 32 | lo));
-}
-
 // 7-tap correlation down the columns, in registers, zero beyond the region's rows (those outputs are outside every dependency cone
 // that ends in a stored pixel)
 template <typename T, int NR> __device__ __forceinline__ void blur_rows(T (&a)[NR], const T *__restrict__ k)
@@ -251,8 +226,8 @@ __device__ __forceinline__ void blur_lanes(T (&a)[NR], int u, int set, T *lds, i
     for (int i = 0; i < NR; i++) {
         const T l0 = nl[i * sl], l1 = nl[i * sl + 1], l2 = nl[i * sl + 2], r0 = nr[i * sr], r1 = nr[i * sr + 1], r2 = nr[i * sr + 2];
         const T c = a[i];
-        const T s1 = shift_up(c, l2), s2 = shift_up(s1, l1), s3 = shift_up(s2, l0);
-        const T t1 = shift_dn(c, r0), t2 = shift_dn(t1, r1), t3 = shift_dn(t2, r2);
+        const T s1 = blk::shift_up(c, l2), s2 = blk::shift_up(s1, l1), s3 = blk::shift_up(s2, l0);
+        const T t1 = blk::shift_dn(c, r0), t2 = blk::shift_dn(t1, r1), t3 = blk::shift_dn(t2, r2);
         a[i] = k0 * s3 + k1 * s2 + k2 * s1 + k3 * c + k4 * t1 + k5 * t2 + k6 * t3;
         asm volatile("" : "+v"(a[i]));  // an opaque use right here: the row's arithmetic stays with its shifts
         if ((i & 3) == 3)
@@ -272,11 +247,11 @@ template <> __device__ __forceinline__ void load_pair<float>(__amdgpu_buffer_rsr
 }
 template <> __device__ __forceinline__ void load_pair<double>(__amdgpu_buffer_rsrc_t rs, int voff, int soff, double &x, double &y)
 {
-    const patch::u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(rs, voff, soff, 0);
+    const blk::u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(rs, voff, soff, 0);
     x = __longlong_as_double((long long)((unsigned long long)v.y << 32 | v.x)), y = __longlong_as_double((long long)((unsigned long long)v.w << 32 | v.z));
 }
 // (the whole offset in the vector register: a 128-bit store with a scalar offset is not covered by the compiler's store-data hazard
-// handling, srx_patch.hpp st4)
+// handling, srx_block.hpp st4)
 template <typename T> __device__ __forceinline__ void store_pair(__amdgpu_buffer_rsrc_t rs, int voff, T x, T y);
 template <> __device__ __forceinline__ void store_pair<float>(__amdgpu_buffer_rsrc_t rs, int voff, float x, float y)
 {
@@ -286,7 +261,7 @@ template <> __device__ __forceinline__ void store_pair<float>(__amdgpu_buffer_rs
 template <> __device__ __forceinline__ void store_pair<double>(__amdgpu_buffer_rsrc_t rs, int voff, double x, double y)
 {
     const unsigned long long a = (unsigned long long)__double_as_longlong(x), c = (unsigned long long)__double_as_longlong(y);
-    const patch::u32x4 v = {(unsigned)a, (unsigned)(a >> 32), (unsigned)c, (unsigned)(c >> 32)};
+    const blk::u32x4 v = {(unsigned)a, (unsigned)(a >> 32), (unsigned)c, (unsigned)(c >> 32)};
     __builtin_amdgcn_raw_buffer_store_b128(v, rs, voff, 0, 0);
 }
 

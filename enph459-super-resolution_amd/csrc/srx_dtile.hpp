@@ -26,17 +26,16 @@ namespace dtile {
 
 using patch::AxisC;
 using patch::AxisW;
-using patch::f8;
-using patch::FIX;
-using patch::ld4;
-using patch::ld_u2;
+using blk::f8;
+using blk::ld4;
+using blk::ld_u2;
 using patch::NN_PAD;
-using patch::RW;
-using patch::sload8;
-using patch::SLOT0;
-using patch::SLOT1;
-using patch::st4;
-using patch::u32x4;
+using blk::RW;
+using blk::sload8;
+using blk::SLOT0;
+using blk::SLOT1;
+using blk::st4;
+using blk::u32x4;
 using patch::YW;
 
 constexpr int RY = 256;    // window rows (4 block rows)
@@ -240,18 +239,7 @@ __device__ __forceinline__ void local_axes(const TileD &td, const DArgs &da, int
     exy = (td.flags & 1) ? da.y.ex : 0, nby = (td.flags & 1) ? da.y.nb : 0;
     exx = (td.flags & 2) ? da.x.ex : 0, nbx = (td.flags & 2) ? da.x.nb : 0;
 }
-// near-band pixel t of a window (k_ibp_patch's enumeration with the window's width): window-local natural coordinates, G strip offset
-__device__ __forceinline__ void near_coords(int t, int RX, int exy, int exx, int nby, int nbx, int &ngy, int &ngx, int &dst)
-{
-    const int WN = RX + exx, LN = exx + nbx, ntop = (exy + nby) * WN;
-    if (t < ntop) {
-        const int rr = t / WN, cc = t - rr * WN;
-        ngy = rr - exy, ngx = cc - exx, dst = rr * YW + cc;
-    } else {
-        const int q = t - ntop, rr = q / max(LN, 1), cc = q - rr * max(LN, 1);
-        ngy = nby + rr, ngx = cc - exx, dst = 3 * YW + rr * 3 + cc;
-    }
-}
+// (near-band pixel t of a window: patch::near_coords with the window's width -- window-local natural coordinates, G strip offset)
 __device__ __forceinline__ int near_count(int RX, int exy, int exx, int nby, int nbx)
 {
     return (exy + nby) * (RX + exx) + (RY - nby) * (exx + nbx);
@@ -273,7 +261,7 @@ __global__ void __launch_bounds__(256)
     if (t >= nn)
         return;
     int ngy, ngx, dst;
-    near_coords(t, RX, exy, exx, nby, nbx, ngy, ngx, dst);
+    patch::near_coords(t, RX, exy, exx, nby, nbx, ngy, ngx, dst);
     const int gy = td.oy + ngy, gx = td.ox + ngx;  // image (natural) coordinates
     const int ni = mosaic::near_index(gy + 13, gx + 13, da.W + 27, PBy, PBx), pk = ncu[ni], cnt = pk & 255;
     int cu = pk >> 8;
@@ -304,7 +292,7 @@ __global__ void __launch_bounds__(256)
     if (t >= near_count(RX, exy, exx, nby, nbx))
         return;
     int ngy, ngx, dst;
-    near_coords(t, RX, exy, exx, nby, nbx, ngy, ngx, dst);
+    patch::near_coords(t, RX, exy, exx, nby, nbx, ngy, ngx, dst);
     const int gy = td.oy + ngy, gx = td.ox + ngx, Wg = da.W + 27, Hg = da.H + 27;
     const int ni = mosaic::near_index(gy + 13, gx + 13, Wg, PBy, PBx);
     Mn[((size_t)b * ntabs + tab) * NN_PAD + t] = make_float2(Mg[((size_t)b * Hg + gy + 13) * Wg + gx + 13], Mu[(size_t)b * NB + ni]);
@@ -420,8 +408,8 @@ __device__ __forceinline__ void dtile_body(float *lds, const float *__restrict__
         for (int q = 0; q < 16; q++)
             ld4(rs_src, vcol, sql + q * W * 16, a[4 * q], a[4 * q + 1], a[4 * q + 2], a[4 * q + 3]);
         if (PSF == 0) {
-            patch::blur_block(a, s == 0, s == 3, Rown, Rup, Rdn, SLOT0, lane, sload8(awy));
-        } else {  // round 4: srx_patch.hpp's 7 x 7 form (blur2d_pass1 / blur2d_fix), here on a window: what lies beyond a window edge is zero for
+            blk::blur_block(a, s == 0, s == 3, Rown, Rup, Rdn, SLOT0, lane, sload8(awy));
+        } else {  // round 4: srx_block.hpp's 7 x 7 form (blur2d_pass1 / blur2d_fix), here on a window: what lies beyond a window edge is zero for
                   // the blur as it is for the separable one (inside the halo nobody owns)
             Rown[SLOT0 + lane] = a[0];
             Rown[SLOT0 + 64 + lane] = a[1];
@@ -435,12 +423,12 @@ __device__ __forceinline__ void dtile_body(float *lds, const float *__restrict__
                 hl[0] = Rup[SLOT0 + 192 + lane], hl[1] = Rup[SLOT0 + 256 + lane], hl[2] = Rup[SLOT0 + 320 + lane];
             if (s != 3)
                 hr[0] = Rdn[SLOT0 + lane], hr[1] = Rdn[SLOT0 + 64 + lane], hr[2] = Rdn[SLOT0 + 128 + lane];
-            patch::blur2d_pass1<PSF == 2 ? 2 : 3>(a, hl, hr, Rown, lane, tb.k2);
+            blk::blur2d_pass1<PSF == 2 ? 2 : 3>(a, hl, hr, Rown, lane, tb.k2);
             __syncthreads();
-            patch::blur2d_fix<PSF == 2 ? 2 : 3>(a, u == 0, u == NSX - 1, Rown, Rlf, Rrt, lane, [](int) {}, [](int, float v) { return v; });
+            blk::blur2d_fix<PSF == 2 ? 2 : 3>(a, u == 0, u == NSX - 1, Rown, Rlf, Rrt, lane, [](int) {}, [](int, float v) { return v; });
         }
         __builtin_amdgcn_sched_barrier(0);
-        patch::fwd_chain(a, s == 0, s == 3, Rown, Rup, Rdn, SLOT1, SLOT0, lane, sload8(awy + 16), yex);
+        blk::fwd_chain(a, s == 0, s == 3, Rown, Rup, Rdn, SLOT1, SLOT0, lane, sload8(awy + 16), yex);
         __builtin_amdgcn_sched_barrier(0);
         if (exy && s == 0)  // the Y row above the image rides in the window's last row (inside the halo: nobody owns it)
             rowbuf[64 * u + lane] = yex;
@@ -448,7 +436,7 @@ __device__ __forceinline__ void dtile_body(float *lds, const float *__restrict__
         if (exy && s == 3)
             a[63] = rowbuf[64 * u + lane];
         __builtin_amdgcn_sched_barrier(0);
-        patch::transpose64(a, r, Rown, lane);
+        blk::transpose64(a, r, Rown, lane);
         __builtin_amdgcn_sched_barrier(0);
     }
     float sq = 0.f;
@@ -460,10 +448,10 @@ __device__ __forceinline__ void dtile_body(float *lds, const float *__restrict__
         const bool rowown = !wrapped && gy >= td.y0 && gy < td.y1;
         const float crow = C01 ? (float)((rmask >> lane) & 1ull) : 0.f;
         if (PSF == 0)
-            patch::blur_block(r, u == 0, u == NSX - 1, Rown, Rlf, Rrt, SLOT0, lane, sload8(awx));
+            blk::blur_block(r, u == 0, u == NSX - 1, Rown, Rlf, Rrt, SLOT0, lane, sload8(awx));
         __builtin_amdgcn_sched_barrier(0);
         float yexx = 0.f;  // Y[gy, -1] (u == 0)
-        patch::fwd_chain(r, u == 0, u == NSX - 1, Rown, Rlf, Rrt, SLOT1, SLOT0, lane, sload8(awx + 16), yexx);
+        blk::fwd_chain(r, u == 0, u == NSX - 1, Rown, Rlf, Rrt, SLOT1, SLOT0, lane, sload8(awx + 16), yexx);
         __builtin_amdgcn_sched_barrier(0);
         // ---- near band (windows on the top / left image edge): descriptors, strips of Y, the listed sums, strips of G
         const __amdgpu_buffer_rsrc_t rsNe = fused::plane_rsrc(tb.nent, (size_t)da.ngrp * tb.ntabs * NN_PAD);
@@ -698,13 +686,13 @@ __device__ __forceinline__ void dtile_body(float *lds, const float *__restrict__
             const float gm1 = u == 0 ? gtop : Rlf[SLOT1 + 128 + lane];
             const float gp1 = u == NSX - 1 ? 0.f : Rrt[SLOT1 + lane], gp2 = u == NSX - 1 ? 0.f : Rrt[SLOT1 + 64 + lane];
             float hlo[3], hhi[3];  // (unused here: the adjoint 7 x 7 runs once, in stage C)
-            patch::bwd_chain_x<PSF == 0>(r, a, u == 0, u == NSX - 1, Rown, Rlf, Rrt, SLOT0 + 384, SLOT0, lane, sload8(awx + 16), sload8(awx + 8), gm1, gp1, gp2, gtop,
+            blk::bwd_chain_x<PSF == 0>(r, a, u == 0, u == NSX - 1, Rown, Rlf, Rrt, SLOT0 + 384, SLOT0, lane, sload8(awx + 16), sload8(awx + 8), gm1, gp1, gp2, gtop,
                                          [](int) {}, [](int, float v) { return v; }, hlo, hhi);
         }
         __builtin_amdgcn_sched_barrier(0);
         __syncthreads();  // every wave has read its neighbours' slots before the transposes overwrite them
         __builtin_amdgcn_sched_barrier(0);
-        patch::transpose64(a, r, Rown, lane);
+        blk::transpose64(a, r, Rown, lane);
         __builtin_amdgcn_sched_barrier(0);
     }
     {  // ================= stage C: column layout again, r[i] = row 64 s + i (row 63 of s == 3: the wrapped row -1) =================
@@ -747,14 +735,14 @@ __device__ __forceinline__ void dtile_body(float *lds, const float *__restrict__
                              return v;
                          };
         if (PSF == 0) {
-            patch::bwd_chain(r, a, s == 0, s == 3, Rown, Rup, Rdn, SLOT1 + 384, SLOT1, lane, sload8(awy + 16), sload8(awy + 8), gm1, gp1, gp2, gtop, mid, post);
+            blk::bwd_chain(r, a, s == 0, s == 3, Rown, Rup, Rdn, SLOT1 + 384, SLOT1, lane, sload8(awy + 16), sload8(awy + 8), gm1, gp1, gp2, gtop, mid, post);
         } else {
             float hl[3], hr[3];
-            patch::bwd_chain_x<false>(r, a, s == 0, s == 3, Rown, Rup, Rdn, SLOT1 + 384, SLOT1, lane, sload8(awy + 16), sload8(awy + 8), gm1, gp1, gp2, gtop, [](int) {},
+            blk::bwd_chain_x<false>(r, a, s == 0, s == 3, Rown, Rup, Rdn, SLOT1 + 384, SLOT1, lane, sload8(awy + 16), sload8(awy + 8), gm1, gp1, gp2, gtop, [](int) {},
                                       [](int, float v) { return v; }, hl, hr);
-            patch::blur2d_pass1<PSF == 2 ? 2 : 3>(a, hl, hr, Rown, lane, tb.k2 + 56);
+            blk::blur2d_pass1<PSF == 2 ? 2 : 3>(a, hl, hr, Rown, lane, tb.k2 + 56);
             __syncthreads();
-            patch::blur2d_fix<PSF == 2 ? 2 : 3>(a, u == 0, u == NSX - 1, Rown, Rlf, Rrt, lane, mid, post);
+            blk::blur2d_fix<PSF == 2 ? 2 : 3>(a, u == 0, u == NSX - 1, Rown, Rlf, Rrt, lane, mid, post);
         }
         __builtin_amdgcn_sched_barrier(0);
         // ---- store what this window owns: whole row quads (wave-uniform), the lane's column or nothing

@@ -23,27 +23,21 @@
 //
 // HBM traffic per iteration and HR pixel: read hr twice (the second read, for the update, hits L2 / MALL), read M and C,
 // write hr = the algorithmic 12 B + the re-read; no intermediate plane exists.
+//
+// The block primitives the stages are made of -- transpose64, chain64, fwd_chain, bwd_chain, blur_block, the 7 x 7 Horner blur, st4 /
+// ld4 -- live in srx_block.hpp (namespace blk), templated on the element type: every wave-block kernel family calls them there, and the
+// float64 strips of srx_stile.hpp instantiate the same source in double.  This file is the patch kernel, its tables, its eligibility,
+// its carve and its driver.
 #pragma once
+#include "srx_block.hpp"
 #include "srx_mosaic.hpp"
 
 namespace srx {
 namespace patch {
+using namespace blk;
 
 #ifndef SRX_PARK16
 #define SRX_PARK16 1
-#endif
-#ifndef SRX_ADDTID
-#define SRX_ADDTID 1
-#endif
-#ifndef SRX_M0_NOP
-#define SRX_M0_NOP "s_nop 0\n\t"  // the ISA asks for one wait state between a scalar write of M0 and an LDS add-TID instruction, and inside
-                                  // an asm block nobody inserts it.  Without it the first store of a block sometimes went out with the M0 of
-                                  // before (round 3: k_ibp_ztile's 7 x 7 form, one row of one wave wrong in 7 of 40 calls, always behind the
-                                  // tile that sums the previous iteration's MSE partials; tools/stress_determinism.py, tests/test_gpu_parity.py::
-                                  // test_frame_kernel_is_deterministic).  "" reproduces it.
-#endif
-#ifndef SRX_TRANSPOSE_DEF
-#define SRX_TRANSPOSE_DEF 1
 #endif
 #ifndef SRX_PATCH_DBG
 #define SRX_PATCH_DBG 0  // timing ablations of a development build only (results are wrong): 1 no M loads, 2 no hr re-read,
@@ -51,36 +45,11 @@ namespace patch {
                          // iteration): 8 -> 150, 2 -> 152, 8|2 -> 144, 8|2|1 -> 139, all -> 138: the memory operations are 14 % of the
                          // iteration; requesting the parked state or the near-band descriptors a chain earlier changes nothing.
 constexpr int PN = 256;        // patch edge (HR pixels)
-constexpr int TSD = 68;        // LDS row stride of a half-block transpose (a multiple of 4 words: 16-byte row reads; 17 quads: the 16
-                               // lanes the LDS serves together read 16 different quads of banks, conflict-free)
-constexpr int RW = 32 * TSD;   // LDS words of a wave's private region
-constexpr int SLOT0 = 0, SLOT1 = 1024;  // exchange slots inside the private region (<= 6 x 64 words each)
-constexpr int FIX = 16;        // samples over which a neighbour's carry is added
 constexpr int YW = 260;        // row pitch of the near-band strips
 constexpr int OFF_YT = 16 * RW, OFF_YL = OFF_YT + 4 * YW, OFF_GT = OFF_YL + 4 * YW, OFF_GL = OFF_GT + 3 * YW,
               OFF_ROW = OFF_GL + 3 * YW, OFF_PART = OFF_ROW + PN, LDS_WORDS = OFF_PART + 32;
 static_assert(LDS_WORDS * 4 <= 160 * 1024, "LDS budget");
 
-constexpr double ZD = -0.26794919243112270647;
-constexpr float PZ = (float)ZD;
-constexpr float K2 = (float)(1.0 / (1.0 - ZD));                 // steady state of the causal recursion: q = v' K2
-constexpr float K1 = (float)(1.0 / ((1.0 - ZD) * (1.0 - ZD)));
-constexpr float K3 = (float)(ZD / (1.0 - ZD * ZD));
-constexpr float K4 = (float)(1.0 / (1.0 - ZD * ZD));
-struct ZPow {
-    float v[FIX];
-    constexpr ZPow() : v()
-    {
-        double p = ZD;
-        for (int i = 0; i < FIX; i++) {
-            v[i] = (float)p;
-            p *= ZD;
-        }
-    }
-};
-__device__ constexpr ZPow ZP{};  // ZP.v[i] = z^(i+1)
-
-typedef float f8 __attribute__((ext_vector_type(8)));
 // Filter weights of one axis.  They live in device memory and are fetched with scalar loads right where a stage needs them
 // (sload8): as by-value kernel arguments the two sets would sit in ~50 scalar registers for the whole iteration loop.
 struct AxisW {
@@ -93,12 +62,6 @@ struct AxisC {
     int nb;       // -n_min: near-band samples inside the grid
     int E;        // padded Y index = rho + E
 };
-__device__ __forceinline__ f8 sload8(const float *p)
-{
-    f8 v;
-    asm volatile("s_load_dwordx8 %0, %1, 0x0\n\ts_waitcnt lgkmcnt(0)" : "=s"(v) : "s"(p) : "memory");
-    return v;
-}
 
 constexpr int NN_PAD = 2048;  // near-band pixels of a patch (<= 2 per thread)
 
@@ -194,10 +157,11 @@ __global__ void __launch_bounds__(256)
         atomicAnd(&m8[b], 0);
 }
 
-// near-band pixel t of the patch enumeration -> natural coordinates and offset in the G strips
-__device__ __forceinline__ void near_coords(int t, int exy, int exx, int nby, int nbx, int &ngy, int &ngx, int &dst)
+// near-band pixel t of the enumeration of a region RX columns wide (the patch: PN; a window of k_ibp_dtile: its own width) -> natural
+// coordinates and offset in the G strips
+__device__ __forceinline__ void near_coords(int t, int RX, int exy, int exx, int nby, int nbx, int &ngy, int &ngx, int &dst)
 {
-    const int WN = PN + exx, LN = exx + nbx, ntop = (exy + nby) * WN;
+    const int WN = RX + exx, LN = max(exx + nbx, 1), ntop = (exy + nby) * WN;  // (no left strip: no t reaches the second branch)
     if (t < ntop) {
         const int rr = t / WN, cc = t - rr * WN;
         ngy = rr - exy, ngx = cc - exx, dst = rr * YW + cc;
@@ -222,7 +186,7 @@ __global__ void __launch_bounds__(256)
     if (t >= nn)
         return;
     int ngy, ngx, dst;
-    near_coords(t, exy, exx, nby, nbx, ngy, ngx, dst);
+    near_coords(t, PN, exy, exx, nby, nbx, ngy, ngx, dst);
     const int ni = mosaic::near_index(ngy + 13, ngx + 13, PN + 27, PBy, PBx), pk = ncu[ni], cnt = pk & 255, cu = pk >> 8;
     const int own = strip_off(ngy, ngx, exy, exx, nby);
     nrec[t] = make_uint2((unsigned)cnt | (unsigned)cu << 8 | (unsigned)dst << 16, (unsigned)own);
@@ -245,7 +209,7 @@ __global__ void __launch_bounds__(256)
     if (t >= nn)
         return;
     int ngy, ngx, dst;
-    near_coords(t, exy, exx, nby, nbx, ngy, ngx, dst);
+    near_coords(t, PN, exy, exx, nby, nbx, ngy, ngx, dst);
     const int Wg = PN + 27, ni = mosaic::near_index(ngy + 13, ngx + 13, Wg, PBy, PBx);
     Mn[(size_t)b * NN_PAD + t] = make_float2(Mg[((size_t)b * Wg + ngy + 13) * Wg + ngx + 13], Mu[(size_t)b * NB + ni]);
 }
@@ -403,7 +367,7 @@ __global__ void __launch_bounds__(256)
     double var = 0.0;
     if (t < nn) {
         int ngy, ngx, dst;
-        near_coords(t, exy, exx, nby, nbx, ngy, ngx, dst);
+        near_coords(t, PN, exy, exx, nby, nbx, ngy, ngx, dst);
         const int p = ngy + 13, q = ngx + 13;
         const S *src = lr + (size_t)b * N * h * w;
         double M = 0.0, S1 = 0.0, S2 = 0.0;
@@ -433,470 +397,6 @@ __global__ void __launch_bounds__(256)
     }
 }
 
-// 16 bytes per lane through a buffer descriptor: the parked state travels as four rows per instruction (a CU issues a vector
-// memory instruction every ~9 cycles whatever its width -- 12 descriptor loads took a wave 1.7 K cycles to issue -- so the 64 + 64
-// one-word stores and loads that parked and re-read the state were a quarter of the iteration's critical path)
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-// The store takes its whole offset in the vector register and NO scalar offset.  A 128-bit store's data registers may not be
-// overwritten by the very next vector instruction; the compiler's hazard recogniser knows that rule but exempts a buffer store
-// whose soffset is a scalar register (GCNHazardRecognizer::createsVALUHazard) -- and on gfx950 the exemption does not hold when the
-// memory pipeline is busy: tools/microbench/store_data_war.hip (16 waves per workgroup, 1024 workgroups) sees dwords 2, 3 of lanes
-// 12..15 of a 16-lane row carry the overwriting values, with 0 wait states only.  k_ibp_dtile's first build stored rows 2, 3 of some
-// row quads from the wrong register pair exactly there (a register-allocator v_mov_b64 right behind the store).
-__device__ __forceinline__ void st4(__amdgpu_buffer_rsrc_t rs, int voff, int soff, float x, float y, float z, float w)
-{
-    u32x4 v = {__float_as_uint(x), __float_as_uint(y), __float_as_uint(z), __float_as_uint(w)};
-    __builtin_amdgcn_raw_buffer_store_b128(v, rs, voff + soff, 0, 0);
-}
-__device__ __forceinline__ void ld4(__amdgpu_buffer_rsrc_t rs, int voff, int soff, float &x, float &y, float &z, float &w)
-{
-    const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(rs, voff, soff, 0);
-    x = __uint_as_float(v.x), y = __uint_as_float(v.y), z = __uint_as_float(v.z), w = __uint_as_float(v.w);
-}
-
-// two consecutive words through a buffer descriptor (32-bit lane offset; out of range reads 0)
-__device__ __forceinline__ uint2 ld_u2(__amdgpu_buffer_rsrc_t rs, int byte_off)
-{
-    typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
-    const u32x2 v = __builtin_amdgcn_raw_buffer_load_b64(rs, byte_off, 0, 0);
-    return make_uint2(v.x, v.y);
-}
-
-// ---- wave-private 64 x 64 transpose through a 32-row LDS image ----------------------------------------------------------
-// in: a[i] = element (i, lane).  out: r[j] = element (lane, j).  (Rows / columns are abstract: the same routine goes back.)
-__device__ __forceinline__ void transpose64(const float (&a)[64], float (&r)[64], float *Tw, int lane)
-{
-    // Each half of the wave reads its rows in its own pass, so r[] is written under a lane predicate -- and a predicated write
-    // keeps the other lanes' previous contents: without a full definition the compiler must treat r[] as live from wherever it was
-    // last written, across the whole preceding stage and around the iteration loop (64 registers pinned beside the 64 of the
-    // working plane: ~150 spills per iteration).  An empty asm defines every element, placed where its life should start: after
-    // pass 0 has parked a[0..31] in LDS, not before (an up-front definition keeps 128 registers live through the first 32 stores).
-    // (SRX_TRANSPOSE_DEF 0: pass 0 reads unpredicated instead -- the upper half-wave re-reads the lower half's rows.  Same
-    // registers, but a third more LDS read traffic in a phase the LDS bounds: C2 162 instead of 156 us per iteration.)
-    // The rows are read 16 bytes at a time (ds_read_b128, 4 LDS cycles per wave-instruction for 1 KB): with the 66-word pitch before,
-    // rows were only 8-byte aligned and hipcc fused the adjacent 8-byte reads into ds_read2_b64, which moves its 1 KB in 8 cycles.  Same-box
-    // A/B on C2: 132.5-133.5 -> 128.3-130.1 us per iteration.  Reading with the WHOLE wave instead (the half-waves exchange quadrants by
-    // v_permlane32_swap first, half as many reads, none predicated) shortens the transposes further and gains nothing: the swaps cost a
-    // SIMD's four waves 25 cycles each, and the time reappears at the barriers around the transposes.
-    const unsigned m0v = __builtin_amdgcn_readfirstlane((unsigned)(uintptr_t)Tw);  // LDS byte address of the wave's region
-    (void)m0v;
-#pragma unroll
-    for (int h = 0; h < 2; h++) {
-#if SRX_ADDTID
-        // Tw[i * TSD + lane] = a[32 h + i] as ds_write_addtid_b32 (address = M0 + offset + 4 * lane, no address register): two LDS
-        // cycles per wave-instruction, where ds_write_b32 takes four (its address and data registers travel to the LDS at two cycles
-        // per dword) -- the transposes are bound by exactly that (C2: 154 -> 152 us per iteration).  M0 and the stores in one asm block:
-        // the compiler does not model M0 here.  M0 carries the full LDS byte address (the wave regions reach 139 KB; gfx950 honours more
-        // than the 16 bits older ISA documents name -- with the address masked to 16 bits waves 8..15 wrote into the wrong regions and
-        // tests/test_gpu_parity.py::test_patch_kernel_vs_oracle failed at once).
-        static_assert(TSD * 4 == 272, "offsets below");
-        asm volatile("s_mov_b32 m0, %16\n\t" SRX_M0_NOP
-                     "ds_write_addtid_b32 %0 offset:0\n\t"
-                     "ds_write_addtid_b32 %1 offset:272\n\t"
-                     "ds_write_addtid_b32 %2 offset:544\n\t"
-                     "ds_write_addtid_b32 %3 offset:816\n\t"
-                     "ds_write_addtid_b32 %4 offset:1088\n\t"
-                     "ds_write_addtid_b32 %5 offset:1360\n\t"
-                     "ds_write_addtid_b32 %6 offset:1632\n\t"
-                     "ds_write_addtid_b32 %7 offset:1904\n\t"
-                     "ds_write_addtid_b32 %8 offset:2176\n\t"
-                     "ds_write_addtid_b32 %9 offset:2448\n\t"
-                     "ds_write_addtid_b32 %10 offset:2720\n\t"
-                     "ds_write_addtid_b32 %11 offset:2992\n\t"
-                     "ds_write_addtid_b32 %12 offset:3264\n\t"
-                     "ds_write_addtid_b32 %13 offset:3536\n\t"
-                     "ds_write_addtid_b32 %14 offset:3808\n\t"
-                     "ds_write_addtid_b32 %15 offset:4080\n\t"
-                     :: "v"(a[32 * h + 0]), "v"(a[32 * h + 1]), "v"(a[32 * h + 2]), "v"(a[32 * h + 3]), "v"(a[32 * h + 4]), "v"(a[32 * h + 5]), "v"(a[32 * h + 6]), "v"(a[32 * h + 7]), "v"(a[32 * h + 8]), "v"(a[32 * h + 9]), "v"(a[32 * h + 10]), "v"(a[32 * h + 11]), "v"(a[32 * h + 12]), "v"(a[32 * h + 13]), "v"(a[32 * h + 14]), "v"(a[32 * h + 15]), "s"(m0v) : "memory", "m0");
-        asm volatile("s_mov_b32 m0, %16\n\t" SRX_M0_NOP
-                     "ds_write_addtid_b32 %0 offset:4352\n\t"
-                     "ds_write_addtid_b32 %1 offset:4624\n\t"
-                     "ds_write_addtid_b32 %2 offset:4896\n\t"
-                     "ds_write_addtid_b32 %3 offset:5168\n\t"
-                     "ds_write_addtid_b32 %4 offset:5440\n\t"
-                     "ds_write_addtid_b32 %5 offset:5712\n\t"
-                     "ds_write_addtid_b32 %6 offset:5984\n\t"
-                     "ds_write_addtid_b32 %7 offset:6256\n\t"
-                     "ds_write_addtid_b32 %8 offset:6528\n\t"
-                     "ds_write_addtid_b32 %9 offset:6800\n\t"
-                     "ds_write_addtid_b32 %10 offset:7072\n\t"
-                     "ds_write_addtid_b32 %11 offset:7344\n\t"
-                     "ds_write_addtid_b32 %12 offset:7616\n\t"
-                     "ds_write_addtid_b32 %13 offset:7888\n\t"
-                     "ds_write_addtid_b32 %14 offset:8160\n\t"
-                     "ds_write_addtid_b32 %15 offset:8432\n\t"
-                     :: "v"(a[32 * h + 16]), "v"(a[32 * h + 17]), "v"(a[32 * h + 18]), "v"(a[32 * h + 19]), "v"(a[32 * h + 20]), "v"(a[32 * h + 21]), "v"(a[32 * h + 22]), "v"(a[32 * h + 23]), "v"(a[32 * h + 24]), "v"(a[32 * h + 25]), "v"(a[32 * h + 26]), "v"(a[32 * h + 27]), "v"(a[32 * h + 28]), "v"(a[32 * h + 29]), "v"(a[32 * h + 30]), "v"(a[32 * h + 31]), "s"(m0v) : "memory", "m0");
-#else
-#pragma unroll
-        for (int i = 0; i < 32; i++)
-            Tw[i * TSD + lane] = a[32 * h + i];
-#endif
-        __builtin_amdgcn_wave_barrier();
-#if SRX_TRANSPOSE_DEF
-        if (h == 0) {
-#pragma unroll
-            for (int j = 0; j < 64; j++)
-                asm volatile("" : "=v"(r[j]));
-        }
-        if ((lane >> 5) == h) {
-#else
-        if (h == 0 || (lane >> 5) == h) {
-#endif
-            const float4 *row = reinterpret_cast<const float4 *>(Tw + (lane & 31) * TSD);
-#pragma unroll
-            for (int k = 0; k < 16; k++) {
-                const float4 v = row[k];
-                r[4 * k] = v.x, r[4 * k + 1] = v.y, r[4 * k + 2] = v.z, r[4 * k + 3] = v.w;
-            }
-        }
-        __builtin_amdgcn_wave_barrier();
-    }
-}
-
-// ---- the recursion a[i] <- z a[i -+ 1] + a[i] over the 64 samples of a lane, as NSUB independent sub-chains ---------------------------
-// One chain is 64 DEPENDENT fmas, and a dependent fma issues every ~11 cycles (tools/microbench/valu_issue.hip): a wave that runs its
-// chain alone -- the usual case, the waves of a SIMD leave the throughput-bound phases one after the other -- idles 9 of 11 cycles.
-// The recursion is linear, so the identity that joins the BLOCKS also cuts a chain inside a lane: sub-chain k > 0 starts from a zero
-// state, and the true state at its start -- the end value of sub-chain k - 1 -- is added afterwards as z^(i+1) * state over its first
-// FIX = 16 samples (|z|^17 = 2e-10).  Measured on one box (C2, tools/ab_bench.sh): one chain 138.3 us per iteration, two sub-chains
-// 132.8, four (16 steps, then 3 x 16 fix-up fmas whose end values are themselves fixed first) 141.8 -- with four waves per SIMD the
-// chains of several waves already overlap, and the fix-ups are real work.
-#ifndef SRX_CHAIN_NSUB
-#define SRX_CHAIN_NSUB 2
-#endif
-template <bool REV> __device__ __forceinline__ void chain64(float (&a)[64], float st0)
-{
-    constexpr int NSUB = SRX_CHAIN_NSUB, L = 64 / NSUB;
-    static_assert(NSUB == 1 || L >= FIX, "a fix-up may not reach into the next sub-chain's start");
-    const float z = PZ;
-    auto at = [&](int i) -> float & { return a[REV ? 63 - i : i]; };  // position along the direction of the recursion
-    float st[NSUB];
-#pragma unroll
-    for (int k = 0; k < NSUB; k++)
-        st[k] = k == 0 ? st0 : 0.f;
-#pragma unroll
-    for (int i = 0; i < L; i++) {
-#pragma unroll
-        for (int k = 0; k < NSUB; k++) {
-            st[k] = fmaf(z, st[k], at(k * L + i));
-            at(k * L + i) = st[k];
-        }
-    }
-    if (NSUB > 1) {
-        float e[NSUB];  // true end values of the sub-chains
-        e[0] = st[0];
-#pragma unroll
-        for (int k = 1; k < NSUB; k++)
-            e[k] = L == FIX ? fmaf(ZP.v[FIX - 1], e[k - 1], st[k]) : st[k];  // (longer sub-chains: the end is out of the fix-up's reach)
-#pragma unroll
-        for (int k = 1; k < NSUB; k++) {
-#pragma unroll
-            for (int i = 0; i < FIX; i++)
-                at(k * L + i) = fmaf(ZP.v[i], e[k - 1], at(k * L + i));
-        }
-    }
-}
-
-// ---- forward chain of one block, in place ------------------------------------------------------------------------------
-// a[] in: kq-scaled blurred samples b' of this block.  out: Y[rho], rho = the block's own 64 indices;
-// Y[rho] = sum_a wf[a] c[rho - 2 + a], c = P(pad12(b)).  yex (first block): Y[-1].
-// Rown / Rprev / Rnext: LDS regions of this wave and of the waves holding the previous / next block of the line.
-// Two workgroup barriers.  sa: 64-word slot, sb: 192-word slot.
-__device__ __forceinline__ void fwd_chain(float (&a)[64], bool first, bool last, float *Rown, const float *Rprev, const float *Rnext,
-                                          int sa, int sb, int lane, const f8 wfb, float &yex)
-{
-    const float z = PZ;
-    const float bfirst = a[0], blast = a[63];
-    chain64<false>(a, first ? bfirst * K2 : 0.f);  // inside the constant pad the causal state is the steady state
-    Rown[sa + lane] = a[63];
-    __syncthreads();
-    if (!first) {
-        const float carry = Rprev[sa + lane];
-#pragma unroll
-        for (int i = 0; i < FIX; i++)
-            a[i] = fmaf(ZP.v[i], carry, a[i]);
-    }
-    // coefficient of the first sample below the line: 12 constant pad samples, then SciPy's reflect end (z^24 away)
-    const float cb = last ? fmaf(a[63] - blast * K2, K3, blast * K1) : 0.f;
-    chain64<true>(a, cb);
-    float cm1 = 0.f, cm2 = 0.f;  // c[-1], c[-2] relative to the block
-    if (first) {                 // coefficients inside the top pad: c[i] = z c[i+1] + qs
-        const float qs = bfirst * K2;
-        cm1 = fmaf(z, a[0], qs);
-        cm2 = fmaf(z, cm1, qs);
-        const float cm3 = fmaf(z, cm2, qs);
-        yex = wfb[0] * cm3 + wfb[1] * cm2 + wfb[2] * cm1 + wfb[3] * a[0];
-    }
-    Rown[sb + lane] = a[0];
-    Rown[sb + 64 + lane] = a[62];
-    Rown[sb + 128 + lane] = a[63];
-    __syncthreads();
-    float hb = cb;
-    if (!last) {
-        hb = Rnext[sb + lane];
-#pragma unroll
-        for (int i = 0; i < FIX; i++)
-            a[63 - i] = fmaf(ZP.v[i], hb, a[63 - i]);
-    }
-    if (!first) {  // the previous block's last two coefficients, with the carry (this block's c[0]) they have not seen yet
-        cm2 = fmaf(ZP.v[1], a[0], Rprev[sb + 64 + lane]);
-        cm1 = fmaf(ZP.v[0], a[0], Rprev[sb + 128 + lane]);
-    }
-    float c2 = cm2, c1 = cm1;
-#pragma unroll
-    for (int i = 0; i < 64; i++) {
-        const float c0 = a[i], cn = i < 63 ? a[i + 1] : hb;
-        a[i] = wfb[0] * c2 + wfb[1] * c1 + wfb[2] * c0 + wfb[3] * cn;
-        c2 = c1, c1 = c0;
-    }
-}
-
-// ---- backward chain of one block ------------------------------------------------------------------------------------
-// a[] in: G samples of this block; gm1 / gp1 / gp2: G just before / after the block (halo exchange done by the caller);
-// gtop: G[-ex] of the line (first block).  out: corr = blur'( crop P( FIR_b G ) ).  Two workgroup barriers.
-// BLUR = false (a PSF that is not rank 1: the adjoint blur is blur2d's, once, in column layout): out = the coefficients themselves, and
-// hlo / hhi = the three coefficients before / after the block (zero outside the image) for that blur.
-template <bool BLUR, typename F, typename P>
-__device__ __forceinline__ void bwd_chain_x(float (&a)[64], float (&out)[64], bool first, bool last, float *Rown, const float *Rprev,
-                                            const float *Rnext, int s1, int s6, int lane, const f8 wfb, const f8 kt, float gm1, float gp1,
-                                            float gp2, float gtop, F mid, P post, float (&hlo)[3], float (&hhi)[3])
-{
-    const float z = PZ;
-    const float w0 = wfb[4], w1 = wfb[5], w2 = wfb[6], w3 = wfb[7];
-    const float vn = last ? w0 * a[63] : 0.f;  // v'[n]: the one pad sample below the line whose FIR window holds a real row
-    SRX_PSTAMP(15);
-    float st = 0.f;
-    if (first) {  // the pad: a constant run of G[-ex] (steady state), then the two samples whose window reaches rows 0, 1
-        st = (w0 + w1 + w2 + w3) * gtop * K2;
-        st = fmaf(z, st, (w0 + w1 + w2) * gtop + w3 * a[0]);
-        st = fmaf(z, st, (w0 + w1) * gtop + w2 * a[0] + w3 * a[1]);
-    }
-    // the FIR in place (independent fmas), then the recursion on its output
-    float gprev = gm1;
-#pragma unroll
-    for (int t = 0; t < 64; t++) {
-        const float g0 = a[t], g1 = t < 63 ? a[t + 1] : gp1, g2 = t < 62 ? a[t + 2] : (t == 62 ? gp1 : gp2);
-        a[t] = w0 * gprev + w1 * g0 + w2 * g1 + w3 * g2;
-        gprev = g0;
-    }
-    chain64<false>(a, st);
-    SRX_PSTAMP(16);
-    Rown[s1 + lane] = a[63];
-    __syncthreads();
-    SRX_PSTAMP(17);
-    if (!first) {
-        const float carry = Rprev[s1 + lane];
-#pragma unroll
-        for (int i = 0; i < FIX; i++)
-            a[i] = fmaf(ZP.v[i], carry, a[i]);
-    }
-    const float cb = last ? fmaf(z, a[63], vn) * K4 : 0.f;
-    chain64<true>(a, cb);
-    Rown[s6 + lane] = a[0];
-    Rown[s6 + 64 + lane] = a[1];
-    Rown[s6 + 128 + lane] = a[2];
-    Rown[s6 + 192 + lane] = a[61];
-    Rown[s6 + 256 + lane] = a[62];
-    Rown[s6 + 320 + lane] = a[63];
-    SRX_PSTAMP(18);
-    __syncthreads();
-    SRX_PSTAMP(19);
-    float e[70];  // the block's coefficients with three on either side (zero outside the image)
-    e[0] = e[1] = e[2] = e[67] = e[68] = e[69] = 0.f;
-    if (!last) {
-        const float cn = Rnext[s6 + lane];
-#pragma unroll
-        for (int i = 0; i < FIX; i++)
-            a[63 - i] = fmaf(ZP.v[i], cn, a[63 - i]);
-        e[67] = cn, e[68] = Rnext[s6 + 64 + lane], e[69] = Rnext[s6 + 128 + lane];
-    }
-    if (!first) {
-        e[0] = fmaf(ZP.v[2], a[0], Rprev[s6 + 192 + lane]);
-        e[1] = fmaf(ZP.v[1], a[0], Rprev[s6 + 256 + lane]);
-        e[2] = fmaf(ZP.v[0], a[0], Rprev[s6 + 320 + lane]);
-    }
-#pragma unroll
-    for (int i = 0; i < 64; i++)
-        e[3 + i] = a[i];
-    SRX_PSTAMP(20);
-    if (!BLUR) {
-        hlo[0] = e[0], hlo[1] = e[1], hlo[2] = e[2], hhi[0] = e[67], hhi[1] = e[68], hhi[2] = e[69];
-#pragma unroll
-        for (int i = 0; i < 64; i++)
-            out[i] = e[3 + i];
-        return;
-    }
-#pragma unroll
-    for (int q = 0; q < 4; q++) {
-        mid(q);  // caller's hook before every quarter of the blur (loads / stores to overlap with it)
-#pragma unroll
-        for (int i = 16 * q; i < 16 * q + 16; i++) {
-            float acc = kt[0] * e[i];
-#pragma unroll
-            for (int u = 1; u < 7; u++)
-                acc = fmaf(kt[u], e[i + u], acc);
-            out[i] = post(i, acc);  // caller's epilogue (identity, or the IBP update)
-        }
-        __builtin_amdgcn_sched_barrier(0);
-    }
-}
-
-template <typename F, typename P>
-__device__ __forceinline__ void bwd_chain(float (&a)[64], float (&out)[64], bool first, bool last, float *Rown, const float *Rprev,
-                                          const float *Rnext, int s1, int s6, int lane, const f8 wfb, const f8 kt, float gm1, float gp1,
-                                          float gp2, float gtop, F mid, P post)
-{
-    float hlo[3], hhi[3];
-    bwd_chain_x<true>(a, out, first, last, Rown, Rprev, Rnext, s1, s6, lane, wfb, kt, gm1, gp1, gp2, gtop, mid, post, hlo, hhi);
-}
-
-// blur (7-tap correlation) of a block with three samples from either neighbour block: halo exchange through the waves' own LDS
-// slots, one workgroup barrier.  a[] in: raw samples, out: sum_k kb[k] x[i - 3 + k] (zero outside the image).
-__device__ __forceinline__ void blur_block(float (&a)[64], bool first, bool last, float *Rown, const float *Rprev, const float *Rnext,
-                                           int s6, int lane, const f8 kb)
-{
-    Rown[s6 + lane] = a[0];
-    Rown[s6 + 64 + lane] = a[1];
-    Rown[s6 + 128 + lane] = a[2];
-    Rown[s6 + 192 + lane] = a[61];
-    Rown[s6 + 256 + lane] = a[62];
-    Rown[s6 + 320 + lane] = a[63];
-    __syncthreads();
-    float hl[3] = {0.f, 0.f, 0.f}, hr[3] = {0.f, 0.f, 0.f};
-    if (!first)
-        hl[0] = Rprev[s6 + 192 + lane], hl[1] = Rprev[s6 + 256 + lane], hl[2] = Rprev[s6 + 320 + lane];
-    if (!last)
-        hr[0] = Rnext[s6 + lane], hr[1] = Rnext[s6 + 64 + lane], hr[2] = Rnext[s6 + 128 + lane];
-    // In place, 8 outputs at a time: besides a[] only the 14-value window and the three old values the next group still needs
-    // are live, and a scheduling fence after every group keeps the compiler from interleaving more outputs than the registers hold
-    // (left alone it trades ~30 spilled registers per blur for instruction-level parallelism).
-    float c0 = hl[0], c1 = hl[1], c2 = hl[2];
-#pragma unroll
-    for (int j0 = 0; j0 < 64; j0 += 8) {
-        float w[14];
-        w[0] = c0, w[1] = c1, w[2] = c2;
-#pragma unroll
-        for (int j = 0; j < 8; j++)
-            w[3 + j] = a[j0 + j];
-#pragma unroll
-        for (int j = 0; j < 3; j++)
-            w[11 + j] = j0 + 8 + j < 64 ? a[j0 + 8 + j] : hr[j];
-        c0 = w[8], c1 = w[9], c2 = w[10];
-#pragma unroll
-        for (int j = 0; j < 8; j++) {
-            float acc = kb[0] * w[j];
-#pragma unroll
-            for (int k = 1; k < 7; k++)
-                acc = fmaf(kb[k], w[j + k], acc);
-            a[j0 + j] = acc;
-        }
-        __builtin_amdgcn_sched_barrier(0);
-    }
-}
-
-// ---- 7 x 7 correlation with a PSF that is not rank 1, on one block of the 4 x 4 grid, COLUMN layout (round 4) --------------------------
-// out[i][l] = sum_{r, c} K[r][c] in[i - 3 + r][l - 3 + c]: the r direction runs along the registers (three rows from the blocks above / below:
-// hl / hr), the c direction along the LANES -- every lane forms the seven column sums t_c = sum_r K[r][c] in[i - 3 + r] of its own column and
-// a Horner scheme of one-lane wave shifts combines them, out = t_3 + up(t_2 + up(t_1 + up(t_0))) + dn(t_4 + dn(t_5 + dn(t_6))) (k_ibp_ztile's
-// blur2d_block; two adjacent rows advance as one packed pair).  What k_ibp_ztile does not have is a neighbour in the lane direction: here the
-// waves left / right hold the next columns.  The shifts run with zero shifted in (pass 1), and by linearity what is missing at a wave's first /
-// last three lanes are the neighbour's OWN Horner partials at its last / first lane -- U1 = t_0, U2 = t_1 + up(U1), U3 = t_2 + up(U2) at lane 63,
-// D1 = t_6, D2, D3 at lane 0, none of which depends on a fill: lanes 63 and 0 publish them (one 16-byte LDS store per row with the other
-// lanes masked off; exec is set and restored inside the asm so that the loop stays one basic block), and behind a barrier every lane adds
-// the one it lacks (lane 0 <- U3, 1 <- U2, 2 <- U1 of the left wave; 63 <- D3, 62 <- D2, 61 <- D1 of the right one; a zero word elsewhere):
-// one LDS read and one add per row (pass 2, blur2d_fix, which also carries the caller's epilogue: the IBP update must see the complete sum).
-// RAD = 2: the PSF's outer ring is zero (the reference's measured PSF): 25 multiply-adds and four shifts per pixel instead of 49 and six.
-typedef float f2 __attribute__((ext_vector_type(2)));
-typedef float f4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ float lane_up(float v) { return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x138, 0xf, 0xf, true)); }
-__device__ __forceinline__ float lane_dn(float v) { return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x130, 0xf, 0xf, true)); }
-constexpr int SLOT_E = 1536;  // a wave's published partials: [64 rows][8 words] = U1 U2 U3 . D1 D2 D3 . (inside its private region, behind the exchange slots)
-constexpr int SLOT_D = 512;   // 256 words between the exchange slots: where the lanes that publish nothing store (distinct quads: no bank conflict)
-constexpr int SLOT_Z = 2048;  // eight zero words (what the lanes that lack nothing add; what a wave at the patch's edge reads for its missing neighbour)
-static_assert(SLOT_D >= SLOT0 + 448 && SLOT_D + 256 <= SLOT1 && SLOT_E >= SLOT1 + 448 && SLOT_E + 512 <= SLOT_Z && SLOT_Z + 8 <= RW, "slots inside the wave's region");
-
-#ifndef SRX_PATCH_B2D_NB
-#define SRX_PATCH_B2D_NB 4
-#endif
-template <int RAD>
-__device__ __forceinline__ void blur2d_pass1(float (&a)[64], const float (&hl)[3], const float (&hr)[3], float *Rown, int lane, const float *w56)
-{
-    static_assert(RAD == 2 || RAD == 3, "5 x 5 core or full 7 x 7");
-    constexpr int LO = 3 - RAD, HI = 3 + RAD;
-    f8 kw[7];  // kw[c][r]
-#pragma unroll
-    for (int c = 0; c < 7; c++)
-        kw[c] = sload8(w56 + 8 * c);
-    if (lane < 8)
-        Rown[SLOT_Z + lane] = 0.f;
-    // where this lane's 16 bytes of a row go: lane 63 -> U half, lane 0 -> D half of the row's slot; every other lane into its own quad of a
-    // dump area (the store is unpredicated: the loop stays one basic block)
-    f4 *edst = reinterpret_cast<f4 *>(__builtin_assume_aligned(lane == 63 ? Rown + SLOT_E : lane == 0 ? Rown + SLOT_E + 4 : Rown + SLOT_D + 4 * lane, 16));
-    const int estr = (lane == 63 || lane == 0) ? 2 : 0;  // in units of 16 bytes per row
-    constexpr int NB = SRX_PATCH_B2D_NB;
-    float c0 = hl[0], c1 = hl[1], c2 = hl[2];
-#pragma unroll
-    for (int j0 = 0; j0 < 64; j0 += NB) {
-        float w[NB + 6];
-        w[0] = c0, w[1] = c1, w[2] = c2;
-#pragma unroll
-        for (int j = 0; j < NB; j++)
-            w[3 + j] = a[j0 + j];
-#pragma unroll
-        for (int j = 0; j < 3; j++)
-            w[NB + 3 + j] = j0 + NB + j < 64 ? a[j0 + NB + j] : hr[j];
-        c0 = w[NB], c1 = w[NB + 1], c2 = w[NB + 2];
-        // (scalar multiply-adds, not k_ibp_ztile's packed pairs: with four waves per SIMD a v_pk_fma_f32 costs the SIMD what two v_fma_f32 do, and the
-        // pairs (w[m], w[m + 1]) of BOTH alignments tie the plane's registers into 64-bit tuples all the way back through the chains of stage C:
-        // 57 / 77 spilled registers and 0.32 GB of scratch traffic per C2 iteration in the packed form -- same time, 220 us.  The packed form's
-        // count-PLANE instantiations (103 spilled registers) also gave results that changed from call to call on two of four configurations of
-        // tools/dev/pt_check.py -- not a race (extra barriers changed nothing), no unwritten table (NaN poisoning left no NaN), never understood;
-        // this form has 1 - 2 spilled registers and passes all of them)
-#pragma unroll
-        for (int j = 0; j < NB; j++) {
-            float t[7];
-#pragma unroll
-            for (int c = LO; c <= HI; c++) {
-                t[c] = kw[c][LO] * w[j + LO];
-#pragma unroll
-                for (int r = LO + 1; r <= HI; r++)
-                    t[c] = fmaf(kw[c][r], w[j + r], t[c]);
-            }
-            float u1, u2, u3, d1, d2, d3;
-            if (RAD == 3) {
-                u1 = t[0], d1 = t[6];
-                u2 = t[1] + lane_up(u1), d2 = t[5] + lane_dn(d1);
-            } else {  // the missing first stage: U1 = D1 = 0
-                u1 = 0.f, d1 = 0.f;
-                u2 = t[1], d2 = t[5];
-            }
-            u3 = t[2] + lane_up(u2), d3 = t[4] + lane_dn(d2);
-            const float res = (t[3] + lane_up(u3)) + lane_dn(d3);
-            const f4 ev = lane == 0 ? (f4){d1, d2, d3, 0.f} : (f4){u1, u2, u3, 0.f};
-            edst[(j0 + j) * estr] = ev;
-            a[j0 + j] = res;
-            asm volatile("" : "+v"(a[j0 + j]));  // (as in k_ibp_ztile: the last adds of a pixel stay with its arithmetic)
-        }
-        __builtin_amdgcn_sched_barrier(0);
-    }
-}
-// pass 2: lfirst / llast: no wave before / after this one in the lane direction; Rlo / Rhi: the regions of those waves.  pre(q) runs before
-// quarter q of the rows (the parked state's loads), post(i, v) is the epilogue of row i.
-template <int RAD, typename PRE, typename POST>
-__device__ __forceinline__ void blur2d_fix(float (&a)[64], bool lfirst, bool llast, float *Rown, const float *Rlo, const float *Rhi, int lane, PRE pre, POST post)
-{
-    // word offset of the partial this lane lacks inside a row's slot of the neighbour: U3, U2, U1 for lanes 0, 1, 2; D1, D2, D3 for 61, 62, 63
-    const float *src = lane < 3 ? (lfirst ? Rown + SLOT_Z : Rlo + SLOT_E + 2 - lane) : lane >= 61 ? (llast ? Rown + SLOT_Z : Rhi + SLOT_E + 4 + lane - 61) : Rown + SLOT_Z;
-    const int str = (lane < 3 ? !lfirst : lane >= 61 ? !llast : false) ? 8 : 0;
-#pragma unroll
-    for (int q = 0; q < 4; q++) {
-        pre(q);
-#pragma unroll
-        for (int i = 16 * q; i < 16 * q + 16; i++)
-            a[i] = post(i, a[i] + src[i * str]);
-        __builtin_amdgcn_sched_barrier(0);
-    }
-}
 
 // =========================================================================================================================
 // All n_iter IBP iterations of one patch.  grid B, block 1024 (16 waves = 4 x 4 blocks of 64 x 64).

@@ -2,7 +2,8 @@
 // carves from the workspace, and the driver that prepares the call and runs the one chosen.  Included after every implementation header;
 // a new implementation is a header with shape_admits / eligible / iterate, a dims bound and a carve (its workspace layout as ONE function:
 // iterate runs it on the call's arena with the call's counts, tabs_bytes measures it on a counting arena with the shape-only bound of
-// those counts), a row here and a case in ibp()'s switch.
+// those counts), a row here and a case in ibp()'s switch.  A kernel on 64 x 64 register blocks builds on srx_block.hpp (namespace blk: transpose,
+// recursion, pad forms, blurs -- one source for float and double) and adds none of that arithmetic of its own.
 #pragma once
 #include "srx_mosaic.hpp"
 #include "srx_patch.hpp"

@@ -15,12 +15,12 @@
 //                           H-prefilter + FIR = Y, the near band, G = M - C Y, the MSE sum, H-FIR' + prefilter, H-blur'.
 //
 // Between the two ONE plane per patch crosses memory once each way (8 B per pixel and direction), row-major, in place: k_ibp_sv reads and
-// writes its columns of it as they are (lane = column), k_ibp_sh transposes its rows in and out (srx_patch.hpp's wave-private transpose64
+// writes its columns of it as they are (lane = column), k_ibp_sh transposes its rows in and out (srx_block.hpp's wave-private transpose64
 // on the low and the high words).  Per HR pixel and iteration: sv reads G' 8 + hr 8, writes hr 8 + Yv 8; sh reads Yv 8 + M 1 (bytes) or
 // 8, writes G' 8 = 49 B against the algorithmic 24 (SURVEY 8d in float64) -- where the tile kernels moved ~150.  Measured (C2, B = 1024):
 // both kernels run at the memory's pace (sv 2.15 GB in ~340 us, sh 1.14 GB in ~290), VALU time is a fifth of it.
-// The closed forms of SciPy's 12-sample pad, the carry fix-ups between blocks (z^(i+1) * carry over the first FIX samples; FIX = 28 in
-// float64: |z|^29 = 3e-17) and the near band are srx_patch.hpp's, in T.  Row -1 of Y / G (frames with n_k > 0) rides as plane row 0:
+// The closed forms of SciPy's 12-sample pad and the carry fix-ups between blocks (z^(i+1) * carry over the first FIX samples; FIX = 28 in
+// float64: |z|^29 = 3e-17) are srx_block.hpp's, the source k_ibp_patch instantiates in float; the near band is srx_patch.hpp's.  Row -1 of Y / G (frames with n_k > 0) rides as plane row 0:
 // the planes between the kernels hold row q = gy + ex (the last grid row is empty then, srx_patch.hpp's axis_ok).
 #pragma once
 #include "srx_patch.hpp"
@@ -30,30 +30,9 @@ namespace stile {
 
 using patch::NN_PAD;
 using patch::PN;
-using patch::RW;
+using blk::RW;
 using patch::YW;
 
-template <typename T> struct Cn;
-template <> struct Cn<double> {
-    static constexpr int FIX = 28;
-};
-template <> struct Cn<float> {
-    static constexpr int FIX = 16;
-};
-constexpr double ZD = patch::ZD;
-struct ZPowD {
-    double v[28];
-    constexpr ZPowD() : v()
-    {
-        double p = ZD;
-        for (int i = 0; i < 28; i++) {
-            v[i] = p;
-            p *= ZD;
-        }
-    }
-};
-__device__ constexpr ZPowD ZPD{};  // z^(i+1)
-template <typename T> __device__ __forceinline__ constexpr T zp(int i) { return (T)ZPD.v[i]; }
 template <typename T> __device__ __forceinline__ T clip255(T v) { return v < (T)0 ? (T)0 : (v > (T)255 ? (T)255 : v); }
 
 // exchange slots of a wave's private LDS region, in units of T (the region is RW floats = RW / 2 doubles)
@@ -69,203 +48,6 @@ template <typename T> struct AxW {  // filter weights of one axis (kernel argume
 template <typename T> struct T2 {
     T x, y;
 };
-
-// ---- 64 x 64 transpose of a block of T through the wave's region: the low and the high words as two float transposes ------------------
-__device__ __forceinline__ void transpose64(const double (&a)[64], double (&r)[64], float *Tw, int lane)
-{
-    float lo[64], t[64];
-    int hi[64];
-#pragma unroll
-    for (int i = 0; i < 64; i++)
-        lo[i] = __int_as_float(__double2loint(a[i])), hi[i] = __double2hiint(a[i]);
-    patch::transpose64(lo, t, Tw, lane);
-    int rl[64];
-#pragma unroll
-    for (int i = 0; i < 64; i++)
-        rl[i] = __float_as_int(t[i]), lo[i] = __int_as_float(hi[i]);
-    patch::transpose64(lo, t, Tw, lane);
-#pragma unroll
-    for (int i = 0; i < 64; i++)
-        r[i] = __hiloint2double(__float_as_int(t[i]), rl[i]);
-}
-__device__ __forceinline__ void transpose64(const float (&a)[64], float (&r)[64], float *Tw, int lane) { patch::transpose64(a, r, Tw, lane); }
-
-// a[i] <- z a[i -+ 1] + a[i] over the 64 samples of a lane, as two interleaved sub-chains (srx_patch.hpp's chain64)
-template <typename T, bool REV> __device__ __forceinline__ void chain64(T (&a)[64], T st0)
-{
-    constexpr int FIX = Cn<T>::FIX, L = 32;
-    static_assert(L >= FIX, "a fix-up may not reach into the next sub-chain's start");
-    const T z = (T)ZD;
-    auto at = [&](int i) -> T & { return a[REV ? 63 - i : i]; };
-    T s0 = st0, s1 = (T)0;
-#pragma unroll
-    for (int i = 0; i < L; i++) {
-        s0 = fma(z, s0, at(i));
-        at(i) = s0;
-        s1 = fma(z, s1, at(L + i));
-        at(L + i) = s1;
-    }
-#pragma unroll
-    for (int i = 0; i < FIX; i++)
-        at(L + i) = fma(zp<T>(i), s0, at(L + i));
-}
-
-// srx_patch.hpp's fwd_chain in T: a[] in = kq-scaled blurred samples of this block, out = Y on the block's own 64 indices; yex = Y[-1] (first)
-template <typename T>
-__device__ __forceinline__ void fwd_chain(T (&a)[64], bool first, bool last, T *Rown, const T *Rprev, const T *Rnext, int sa, int sb, int lane,
-                                          const T (&wf)[4], T &yex)
-{
-    constexpr int FIX = Cn<T>::FIX;
-    const T z = (T)ZD, K2 = (T)(1.0 / (1.0 - ZD)), K1 = (T)(1.0 / ((1.0 - ZD) * (1.0 - ZD))), K3 = (T)(ZD / (1.0 - ZD * ZD));
-    const T bfirst = a[0], blast = a[63];
-    chain64<T, false>(a, first ? bfirst * K2 : (T)0);
-    Rown[sa + lane] = a[63];
-    __syncthreads();
-    if (!first) {
-        const T carry = Rprev[sa + lane];
-#pragma unroll
-        for (int i = 0; i < FIX; i++)
-            a[i] = fma(zp<T>(i), carry, a[i]);
-    }
-    const T cb = last ? fma(a[63] - blast * K2, K3, blast * K1) : (T)0;
-    chain64<T, true>(a, cb);
-    T cm1 = 0, cm2 = 0;
-    if (first) {
-        const T qs = bfirst * K2;
-        cm1 = fma(z, a[0], qs);
-        cm2 = fma(z, cm1, qs);
-        const T cm3 = fma(z, cm2, qs);
-        yex = wf[0] * cm3 + wf[1] * cm2 + wf[2] * cm1 + wf[3] * a[0];
-    }
-    Rown[sb + lane] = a[0];
-    Rown[sb + 64 + lane] = a[62];
-    Rown[sb + 128 + lane] = a[63];
-    __syncthreads();
-    T hb = cb;
-    if (!last) {
-        hb = Rnext[sb + lane];
-#pragma unroll
-        for (int i = 0; i < FIX; i++)
-            a[63 - i] = fma(zp<T>(i), hb, a[63 - i]);
-    }
-    if (!first) {
-        cm2 = fma(zp<T>(1), a[0], Rprev[sb + 64 + lane]);
-        cm1 = fma(zp<T>(0), a[0], Rprev[sb + 128 + lane]);
-    }
-    T c2 = cm2, c1 = cm1;
-#pragma unroll
-    for (int i = 0; i < 64; i++) {
-        const T c0 = a[i], cn = i < 63 ? a[i + 1] : hb;
-        a[i] = wf[0] * c2 + wf[1] * c1 + wf[2] * c0 + wf[3] * cn;
-        c2 = c1, c1 = c0;
-    }
-}
-
-// 7-tap correlation in place, eight outputs at a time; hl / hr: the three samples before / after the block.  pre(j0) runs before the group
-// that starts at j0 (loads to overlap), post(i, acc) is the epilogue of output i.
-template <typename T, typename PRE, typename POST>
-__device__ __forceinline__ void blur_inplace(T (&a)[64], const T (&hl)[3], const T (&hr)[3], const T (&k)[7], PRE pre, POST post)
-{
-    T c0 = hl[0], c1 = hl[1], c2 = hl[2];
-#pragma unroll
-    for (int j0 = 0; j0 < 64; j0 += 8) {
-        pre(j0);
-        T w[14];
-        w[0] = c0, w[1] = c1, w[2] = c2;
-#pragma unroll
-        for (int j = 0; j < 8; j++)
-            w[3 + j] = a[j0 + j];
-#pragma unroll
-        for (int j = 0; j < 3; j++)
-            w[11 + j] = j0 + 8 + j < 64 ? a[j0 + 8 + j] : hr[j];
-        c0 = w[8], c1 = w[9], c2 = w[10];
-#pragma unroll
-        for (int j = 0; j < 8; j++) {
-            T acc = k[0] * w[j];
-#pragma unroll
-            for (int q = 1; q < 7; q++)
-                acc = fma(k[q], w[j + q], acc);
-            a[j0 + j] = post(j0 + j, acc);
-        }
-        __builtin_amdgcn_sched_barrier(0);
-    }
-}
-
-template <typename T>
-__device__ __forceinline__ void blur_block(T (&a)[64], bool first, bool last, T *Rown, const T *Rprev, const T *Rnext, int s6, int lane,
-                                           const T (&kb)[7])
-{
-    Rown[s6 + lane] = a[0];
-    Rown[s6 + 64 + lane] = a[1];
-    Rown[s6 + 128 + lane] = a[2];
-    Rown[s6 + 192 + lane] = a[61];
-    Rown[s6 + 256 + lane] = a[62];
-    Rown[s6 + 320 + lane] = a[63];
-    __syncthreads();
-    T hl[3] = {0, 0, 0}, hr[3] = {0, 0, 0};
-    if (!first)
-        hl[0] = Rprev[s6 + 192 + lane], hl[1] = Rprev[s6 + 256 + lane], hl[2] = Rprev[s6 + 320 + lane];
-    if (!last)
-        hr[0] = Rnext[s6 + lane], hr[1] = Rnext[s6 + 64 + lane], hr[2] = Rnext[s6 + 128 + lane];
-    blur_inplace(a, hl, hr, kb, [](int) {}, [](int, T v) { return v; });
-}
-
-// srx_patch.hpp's bwd_chain in T, in place: a[] in = G samples of this block (gm1 / gp1 / gp2: G just before / after it, gtop = G[-ex] of the
-// line), out = post(i, blur'(crop P(FIR' G))[i]).  Two workgroup barriers.
-template <typename T, typename PRE, typename POST>
-__device__ __forceinline__ void bwd_chain(T (&a)[64], bool first, bool last, T *Rown, const T *Rprev, const T *Rnext, int s1, int s6, int lane,
-                                          const T (&wb)[4], const T (&kt)[7], T gm1, T gp1, T gp2, T gtop, PRE pre, POST post)
-{
-    constexpr int FIX = Cn<T>::FIX;
-    const T z = (T)ZD, K2 = (T)(1.0 / (1.0 - ZD)), K4 = (T)(1.0 / (1.0 - ZD * ZD));
-    const T w0 = wb[0], w1 = wb[1], w2 = wb[2], w3 = wb[3];
-    const T vn = last ? w0 * a[63] : (T)0;
-    T st = 0;
-    if (first) {
-        st = (w0 + w1 + w2 + w3) * gtop * K2;
-        st = fma(z, st, (w0 + w1 + w2) * gtop + w3 * a[0]);
-        st = fma(z, st, (w0 + w1) * gtop + w2 * a[0] + w3 * a[1]);
-    }
-    T gprev = gm1;
-#pragma unroll
-    for (int t = 0; t < 64; t++) {
-        const T g0 = a[t], g1 = t < 63 ? a[t + 1] : gp1, g2 = t < 62 ? a[t + 2] : (t == 62 ? gp1 : gp2);
-        a[t] = w0 * gprev + w1 * g0 + w2 * g1 + w3 * g2;
-        gprev = g0;
-    }
-    chain64<T, false>(a, st);
-    Rown[s1 + lane] = a[63];
-    __syncthreads();
-    if (!first) {
-        const T carry = Rprev[s1 + lane];
-#pragma unroll
-        for (int i = 0; i < FIX; i++)
-            a[i] = fma(zp<T>(i), carry, a[i]);
-    }
-    const T cb = last ? fma(z, a[63], vn) * K4 : (T)0;
-    chain64<T, true>(a, cb);
-    Rown[s6 + lane] = a[0];
-    Rown[s6 + 64 + lane] = a[1];
-    Rown[s6 + 128 + lane] = a[2];
-    Rown[s6 + 192 + lane] = a[61];
-    Rown[s6 + 256 + lane] = a[62];
-    Rown[s6 + 320 + lane] = a[63];
-    __syncthreads();
-    T hl[3] = {0, 0, 0}, hr[3] = {0, 0, 0};  // coefficients outside the image are zero (the crop)
-    if (!last) {
-        const T cn = Rnext[s6 + lane];
-#pragma unroll
-        for (int i = 0; i < FIX; i++)
-            a[63 - i] = fma(zp<T>(i), cn, a[63 - i]);
-        hr[0] = cn, hr[1] = Rnext[s6 + 64 + lane], hr[2] = Rnext[s6 + 128 + lane];
-    }
-    if (!first) {  // the previous block's last three coefficients, with the carry (this block's c[0]) they have not seen yet
-        hl[0] = fma(zp<T>(2), a[0], Rprev[s6 + 192 + lane]);
-        hl[1] = fma(zp<T>(1), a[0], Rprev[s6 + 256 + lane]);
-        hl[2] = fma(zp<T>(0), a[0], Rprev[s6 + 320 + lane]);
-    }
-    blur_inplace(a, hl, hr, kt, pre, post);
-}
 
 // ---- eligibility: srx_patch.hpp's, for 8-byte elements -------------------------------------------------------------------------------
 static inline bool shape_admits(int elem_bytes, int H, int W) { return elem_bytes == 8 && H == PN && W == PN; }
@@ -322,7 +104,7 @@ __global__ void __launch_bounds__(256)
     if (t >= nn)
         return;
     int ngy, ngx, dst;
-    patch::near_coords(t, exy, exx, nby, nbx, ngy, ngx, dst);
+    patch::near_coords(t, PN, exy, exx, nby, nbx, ngy, ngx, dst);
     const int Wg = PN + 27, ni = mosaic::near_index(ngy + 13, ngx + 13, Wg, PBy, PBx);
     Mn[(size_t)b * NN_PAD + t] = T2<T>{Mg[((size_t)b * Wg + ngy + 13) * Wg + ngx + 13], Mu[(size_t)b * NB + ni]};
 }
@@ -385,14 +167,17 @@ __global__ void __launch_bounds__(256, 2)
         __syncthreads();
         const T gm1 = s == 0 ? gtop : Rup[S0 + 128 + lane];
         const T gp1 = s == 3 ? (T)0 : Rdn[S0 + lane], gp2 = s == 3 ? (T)0 : Rdn[S0 + 64 + lane];
+        // V-bwd: srx_block.hpp's backward chain -- its front half, then the blur' in place with the update as its epilogue
+        T hl[3], hr[3];
+        blk::bwd_front(a, s == 0, s == 3, Rown, Rup, Rdn, S1 + 384, S1, lane, aw.wb, gm1, gp1, gp2, gtop, hl, hr);
         T hv[2][8];  // the state's rows, a group ahead of the blur that consumes them
         auto load8 = [&](T(&d)[8], int j0) {
 #pragma unroll
             for (int j = 0; j < 8; j++)
                 d[j] = fused::buf_load<T>(rs_hr, colb, rowb + (j0 + j) * PN * EB);
         };
-        bwd_chain(
-            a, s == 0, s == 3, Rown, Rup, Rdn, S1 + 384, S1, lane, aw.wb, aw.kt, gm1, gp1, gp2, gtop,
+        blk::blur_inplace(
+            a, hl, hr, aw.kt,
             [&](int j0) {
                 if (j0 == 0)
                     load8(hv[0], 0);
@@ -406,9 +191,9 @@ __global__ void __launch_bounds__(256, 2)
         if (mode & 2)
             return;
     }
-    blur_block(a, s == 0, s == 3, Rown, Rup, Rdn, S0, lane, aw.kb);
+    blk::blur_block(a, s == 0, s == 3, Rown, Rup, Rdn, S0, lane, aw.kb);
     T yex = 0;
-    fwd_chain(a, s == 0, s == 3, Rown, Rup, Rdn, S1, S0, lane, aw.wf, yex);
+    blk::fwd_chain(a, s == 0, s == 3, Rown, Rup, Rdn, S1, S0, lane, aw.wf, yex);
     const __amdgpu_buffer_rsrc_t rs_y = fused::plane_rsrc(P + (size_t)b * PN * PN, (size_t)PN * PN);
 #pragma unroll
     for (int i = 0; i < 64; i++)
@@ -450,11 +235,11 @@ __device__ __forceinline__ void sh_body(float *lds, T *P, const STabs<T> &tb, co
 #pragma unroll
         for (int i = 0; i < 64; i++)
             a[i] = fused::buf_load<T>(rs_y, colb, (64 * s + i) * PN * EB);
-        transpose64(a, r, lds + u * RW, lane);
+        blk::transpose64(a, r, lds + u * RW, lane);
     }
-    blur_block(r, u == 0, u == 3, Rown, Rlf, Rrt, S0, lane, aw.kb);
+    blk::blur_block(r, u == 0, u == 3, Rown, Rlf, Rrt, S0, lane, aw.kb);
     T yexx = 0;  // Y[gy, -1] (u == 0)
-    fwd_chain(r, u == 0, u == 3, Rown, Rlf, Rrt, S1, S0, lane, aw.wf, yexx);
+    blk::fwd_chain(r, u == 0, u == 3, Rown, Rlf, Rrt, S1, S0, lane, aw.wf, yexx);
     // ---- requested here, consumed behind the strips' barrier: the byte mosaic of the G step and this thread's near-band descriptors.  This strip's
     // share of srx_patch.hpp's enumeration: the top rows (strip 0 only: at most 3 x 257 pixels, four per thread) and the left columns of its
     // own rows (at most 4 x 64, one per thread).  (As loads inside the near-band loop they were three dependent round trips per pixel and
@@ -464,7 +249,7 @@ __device__ __forceinline__ void sh_body(float *lds, T *P, const STabs<T> &tb, co
         const __amdgpu_buffer_rsrc_t rsM8 = fused::plane_rsrc(tb.Mt8 + (size_t)b * (PN / 4) * PN, (size_t)(PN / 4) * PN);
 #pragma unroll
         for (int g = 0; g < 4; g++) {
-            const patch::u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(rsM8, ((4 * u + g) * PN + gy) * 16, 0, 0);
+            const blk::u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(rsM8, ((4 * u + g) * PN + gy) * 16, 0, 0);
             m8w[4 * g] = v.x, m8w[4 * g + 1] = v.y, m8w[4 * g + 2] = v.z, m8w[4 * g + 3] = v.w;
         }
     }
@@ -602,12 +387,14 @@ __device__ __forceinline__ void sh_body(float *lds, T *P, const STabs<T> &tb, co
     const T gtop = exx ? gexx : r[0];
     const T gm1 = u == 0 ? gtop : Rlf[S1 + 128 + lane];
     const T gp1 = u == 3 ? (T)0 : Rrt[S1 + lane], gp2 = u == 3 ? (T)0 : Rrt[S1 + 64 + lane];
-    bwd_chain(r, u == 0, u == 3, Rown, Rlf, Rrt, S0 + 384, S0, lane, aw.wb, aw.kt, gm1, gp1, gp2, gtop, [](int) {}, [](int, T v) { return v; });
+    T hl[3], hr[3];
+    blk::bwd_front(r, u == 0, u == 3, Rown, Rlf, Rrt, S0 + 384, S0, lane, aw.wb, gm1, gp1, gp2, gtop, hl, hr);
+    blk::blur_inplace(r, hl, hr, aw.kt, [](int) {}, [](int, T v) { return v; });
     // back to the plane, over this strip's own rows, row-major (k_ibp_sv reads columns of it): the second transpose
     __syncthreads();  // the neighbours have read this wave's exchange slots, which the transpose runs over
     {
         T a[64];
-        transpose64(r, a, lds + u * RW, lane);
+        blk::transpose64(r, a, lds + u * RW, lane);
         const __amdgpu_buffer_rsrc_t rs_g = fused::plane_rsrc(P + (size_t)b * PN * PN, (size_t)PN * PN);
         const int colb = (64 * u + lane) * EB;
 #pragma unroll
@@ -630,7 +417,7 @@ __global__ void __launch_bounds__(256, 2)
 // ---- host --------------------------------------------------------------------------------------------------------------------------
 template <typename T> static inline void fill_axis(const mosaic::AxisPlan &pl, const T *cfwd, const T *cbwd, patch::AxisC &ax, AxW<T> &aw)
 {
-    const double kq = -6.0 * ZD;
+    const double kq = -6.0 * blk::ZD;
     double wv[4];
     fused::host_weights(1.0 - pl.delta, wv);
     for (int i = 0; i < 4; i++)

@@ -46,9 +46,11 @@
 namespace srx {
 namespace ztile {
 
-using patch::f8;
-using patch::sload8;
-using patch::TSD;
+using blk::f8;
+using blk::lane_dn;
+using blk::lane_up;
+using blk::sload8;
+using blk::TSD;
 typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
 
 
@@ -64,9 +66,9 @@ constexpr int SW = 4;             // strip pitch (rows of the top strip / column
 // that neither the exchange slots ([0, 384) and [1024, 1408)) nor anything else uses between the two transposes: row k of the top
 // strips in region k at 384 (Y) and 640 (G), the left strips in regions 0 and 1 at 1408 (RGY * 4 <= 704 words) -- which keeps a
 // one-block-high tile at 34.9 KB (the LDS would admit four tiles per CU; the register file admits three).
-constexpr int YT_OFF = 384, GT_OFF = 640, YL_OFF = 1408, GL_OFF = patch::RW + 1408;
-static_assert(SW <= 4 * NSY && 4 * RGY <= 704 && GT_OFF + RG <= patch::SLOT1 && YT_OFF + RG <= GT_OFF, "strip placement");
-constexpr int OFF_PART = 4 * NSY * patch::RW, LDS_WORDS = OFF_PART + 32;
+constexpr int YT_OFF = 384, GT_OFF = 640, YL_OFF = 1408, GL_OFF = blk::RW + 1408;
+static_assert(SW <= 4 * NSY && 4 * RGY <= 704 && GT_OFF + RG <= blk::SLOT1 && YT_OFF + RG <= GT_OFF, "strip placement");
+constexpr int OFF_PART = 4 * NSY * blk::RW, LDS_WORDS = OFF_PART + 32;
 static_assert(LDS_WORDS * 4 <= (NSY == 1 ? 40 : NSY == 2 ? 80 : 160) * 1024, "LDS budget");
 
 struct ZArgs {
@@ -292,8 +294,6 @@ __global__ void __launch_bounds__(256)
 // aligned pair; wave_shr:1 / wave_shl:1 move whole-wave, lane i reads lane i - 1 / i + 1.  tools/microbench/dpp_after_pk.hip: one wait
 // state between a packed producer and a DPP read is enough, the compiler leaves two.)
 typedef float f2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ float lane_up(float v) { return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x138, 0xf, 0xf, true)); }
-__device__ __forceinline__ float lane_dn(float v) { return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x130, 0xf, 0xf, true)); }
 
 // RAD: the PSF's support is (2 RAD + 1)^2 -- 3 for a full 7 x 7; 2 when its outer ring is zero, which is the reference's measured PSF
 // (load_measured_psf crops 5 x 5 around the pinhole peaks, mono_cal_target/run_sr.py:114-152; make_kernel7 embeds it): 25 multiply-adds
@@ -395,12 +395,12 @@ __global__ void __launch_bounds__(256 * NSY, SRX_ZTILE_WPE)
         xcd_block_2d(tx, ty);  // neighbouring tiles (12 shared rows of 64, 12 columns of 256) on one XCD's L2
     const int H = za.H, W = za.W, HP = za.HP, WP = za.WP;
     const int pr0 = ty * VTY, pc0 = tx * VT;  // padded coordinates of region (0, 0); natural = padded - 6
-    float *Rown = lds + wave * patch::RW;
-    const float *Rup = lds + (wave - 4) * patch::RW, *Rdn = lds + (wave + 4) * patch::RW;
-    const float *Rlf = lds + (wave - 1) * patch::RW, *Rrt = lds + (wave + 1) * patch::RW;
+    float *Rown = lds + wave * blk::RW;
+    const float *Rup = lds + (wave - 4) * blk::RW, *Rdn = lds + (wave + 4) * blk::RW;
+    const float *Rlf = lds + (wave - 1) * blk::RW, *Rrt = lds + (wave + 1) * blk::RW;
     float *Yl = lds + YL_OFF, *Gl = lds + GL_OFF;
-    auto Yt = [&](int row, int col) -> float & { return lds[row * patch::RW + YT_OFF + col]; };
-    auto Gt = [&](int row, int col) -> float & { return lds[row * patch::RW + GT_OFF + col]; };
+    auto Yt = [&](int row, int col) -> float & { return lds[row * blk::RW + YT_OFF + col]; };
+    auto Gt = [&](int row, int col) -> float & { return lds[row * blk::RW + GT_OFF + col]; };
     double *part = reinterpret_cast<double *>(lds + OFF_PART);
     const float *awy = tb.aw[0].kb, *awx = tb.aw[1].kb;
     const size_t splane = (size_t)(HP + 2) * WP, oplane = (size_t)HP * WP;
@@ -442,14 +442,14 @@ __global__ void __launch_bounds__(256 * NSY, SRX_ZTILE_WPE)
     // blur down the columns (three rows from the blocks above / below; zero at the region's edge: those outputs are outside
     // every dependency cone that ends in a stored pixel)
     SRX_PSTAMP(1);
-    auto vblur = [&](const f8 k) { patch::blur_block(a, s == 0, s == NSY - 1, Rown, Rup, Rdn, patch::SLOT0, lane, k); };
+    auto vblur = [&](const f8 k) { blk::blur_block(a, s == 0, s == NSY - 1, Rown, Rup, Rdn, blk::SLOT0, lane, k); };
     if (SEP) {
         vblur(sload8(awy));
         SRX_PSTAMP(2);
         __syncthreads();  // every wave has read its neighbours' slots before the transposes overwrite them
     }
     SRX_PSTAMP(3);
-    patch::transpose64(a, r, Rown, lane);
+    blk::transpose64(a, r, Rown, lane);
     SRX_PSTAMP(4);
     // ================= stage B: row layout.  r[j] = region (row 64 s + lane, column 64 u + j) =================
     const int rr = 64 * s + lane, gy = pr0 + rr - HALO;  // this lane's region / image row
@@ -473,9 +473,9 @@ __global__ void __launch_bounds__(256 * NSY, SRX_ZTILE_WPE)
         ldcm(cma, 0);
     }
     if (SEP)
-        patch::blur_block(r, u == 0, u == 3, Rown, Rlf, Rrt, patch::SLOT0, lane, sload8(awx));
+        blk::blur_block(r, u == 0, u == 3, Rown, Rlf, Rrt, blk::SLOT0, lane, sload8(awx));
     else
-        blur2d_block<RAD>(r, u == 0, u == 3, Rown, Rlf, Rrt, patch::SLOT0, lane, tb.k2);
+        blur2d_block<RAD>(r, u == 0, u == 3, Rown, Rlf, Rrt, blk::SLOT0, lane, tb.k2);
     SRX_PSTAMP(5);
     float sq = 0.f;
     // ---- near band (tiles on the top / left image edge): strips of b, the listed sums, strips of G
@@ -613,9 +613,9 @@ __global__ void __launch_bounds__(256 * NSY, SRX_ZTILE_WPE)
             part[wave] = ws;
     }
     if (SEP)
-        patch::blur_block(r, u == 0, u == 3, Rown, Rlf, Rrt, patch::SLOT1, lane, sload8(awx + 8));
+        blk::blur_block(r, u == 0, u == 3, Rown, Rlf, Rrt, blk::SLOT1, lane, sload8(awx + 8));
     else
-        blur2d_block<RAD>(r, u == 0, u == 3, Rown, Rlf, Rrt, patch::SLOT1, lane, tb.k2 + 56);
+        blur2d_block<RAD>(r, u == 0, u == 3, Rown, Rlf, Rrt, blk::SLOT1, lane, tb.k2 + 56);
     if (epart && tid == 0) {
         double t = 0.0;
 #pragma unroll
@@ -625,7 +625,7 @@ __global__ void __launch_bounds__(256 * NSY, SRX_ZTILE_WPE)
     }
     SRX_PSTAMP(8);
     __syncthreads();  // every wave has read its neighbours' slots before the transposes overwrite them
-    patch::transpose64(r, a, Rown, lane);
+    blk::transpose64(r, a, Rown, lane);
     SRX_PSTAMP(9);
     // ================= stage C: column layout again =================
     if (SEP)

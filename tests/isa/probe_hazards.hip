@@ -1,19 +1,19 @@
 // Probe for tests/test_isa_hazards.py: the two instruction sequences the lint looks for, compiled from the product's own
-// helpers (srx_patch.hpp).  Built twice by the test -- as shipped, and with -DSRX_M0_NOP="" -DSRX_PROBE_SOFFSET_STORE, the two
+// helpers (srx_block.hpp).  Built twice by the test -- as shipped, and with -DSRX_M0_NOP="" -DSRX_PROBE_SOFFSET_STORE, the two
 // forms round 3 found broken on gfx950 -- the lint must pass the first listing and flag the second.
-#include "srx_patch.hpp"
+#include "srx_patch.hpp"  // (the patch kernel rides along: the test lints it too)
 
 using namespace srx;
 
 extern "C" __global__ void __launch_bounds__(64) k_probe_transpose(const float *in, float *out)
 {
-    __shared__ float T[patch::RW];
+    __shared__ float T[blk::RW];
     const int lane = threadIdx.x;
     float a[64], r[64];
 #pragma unroll
     for (int i = 0; i < 64; i++)
         a[i] = in[i * 64 + lane];
-    patch::transpose64(a, r, T, lane);
+    blk::transpose64(a, r, T, lane);
 #pragma unroll
     for (int i = 0; i < 64; i++)
         out[i * 64 + lane] = r[i];
@@ -32,6 +32,6 @@ extern "C" __global__ void __launch_bounds__(64) k_probe_store(float *out, int s
     asm volatile("buffer_store_dwordx4 %0, %1, %2, %3 offen\n\tv_mov_b32 %0, 0" : "+v"(v) : "v"(lane * 16), "s"(rs), "s"(soff) : "memory");
     out[n / 4 - 1] = __uint_as_float(v.x);
 #else
-    patch::st4(rs, lane * 16, soff, x, y, z, w);
+    blk::st4(rs, lane * 16, soff, x, y, z, w);
 #endif
 }

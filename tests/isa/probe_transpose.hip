@@ -1,4 +1,4 @@
-// Probe for tests/test_gpu_transpose_probe.py: patch::transpose64 as the product's kernels use it -- one workgroup of 16 waves,
+// Probe for tests/test_gpu_transpose_probe.py: blk::transpose64 as the product's kernels use it -- one workgroup of 16 waves,
 // every wave with its own RW-word region of the LDS -- on blocks whose 16 x 4096 values are all distinct.  Each wave transposes its
 // 64 x 64 block and transposes it back; the host checks both images exactly (the routine only moves data).
 #include <hip/hip_runtime.h>
@@ -6,7 +6,7 @@
 #include <cstdio>
 #include <vector>
 
-#include "srx_patch.hpp"
+#include "srx_block.hpp"
 
 using namespace srx;
 
@@ -14,18 +14,18 @@ constexpr int NWAVE = 16, BLK = 64 * 64;
 
 extern "C" __global__ void __launch_bounds__(64 * NWAVE) k_probe_t64(const float *__restrict__ in, float *__restrict__ out_t, float *__restrict__ out_back)
 {
-    __shared__ __attribute__((aligned(16))) float lds[NWAVE * patch::RW];
+    __shared__ __attribute__((aligned(16))) float lds[NWAVE * blk::RW];
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int base = wave * BLK;  // < NWAVE * BLK: every access below stays inside the three NWAVE * BLK buffers
     float a[64], r[64];
 #pragma unroll
     for (int i = 0; i < 64; i++)
         a[i] = in[base + i * 64 + lane];
-    patch::transpose64(a, r, lds + wave * patch::RW, lane);
+    blk::transpose64(a, r, lds + wave * blk::RW, lane);
 #pragma unroll
     for (int i = 0; i < 64; i++)
         out_t[base + i * 64 + lane] = r[i];
-    patch::transpose64(r, a, lds + wave * patch::RW, lane);
+    blk::transpose64(r, a, lds + wave * blk::RW, lane);
 #pragma unroll
     for (int i = 0; i < 64; i++)
         out_back[base + i * 64 + lane] = a[i];

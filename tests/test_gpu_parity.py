@@ -393,7 +393,7 @@ def test_one_launch_kernel_float_frames():
 def test_frame_kernel_is_deterministic():
     """Repeated calls of the one-launch frame kernel give bit-identical results, in both PSF forms, on rough data (where a stale
     value is a large error).  Round 3 found the 7 x 7 form deviating in 7 of 40 calls: the first ds_write_addtid_b32 behind a
-    scalar write of M0 needs a wait state (srx_patch.hpp, SRX_M0_NOP); tools/stress_determinism.py is the long form of this test."""
+    scalar write of M0 needs a wait state (srx_block.hpp, SRX_M0_NOP); tools/stress_determinism.py is the long form of this test."""
     S.set_precision("f32")
     f, shifts = 2, synth.NOMINAL_5
     rng = np.random.default_rng(1)

@@ -1,4 +1,4 @@
-"""patch::transpose64 on its own, as the kernels call it: 16 waves of one workgroup, each with its private LDS region, each
+"""blk::transpose64 on its own, as the kernels call it: 16 waves of one workgroup, each with its private LDS region, each
 transposing a 64 x 64 block of distinct values and transposing it back (tests/isa/probe_transpose.hip).  The host compares both
 images exactly: the routine is pure data movement, whatever the width of its LDS reads and the lane exchange in front of them."""
 import os

@@ -1,4 +1,4 @@
-"""Static checks that go with patch::transpose64's wide LDS reads, on the shipped library's disassembly; no GPU needed.
+"""Static checks that go with blk::transpose64's wide LDS reads, on the shipped library's disassembly; no GPU needed.
 
 The transposes of k_ibp_patch read their LDS image sixteen bytes at a time: the rank-1 instantiations must hold no ds_read2_b64 (what
 hipcc makes of two adjacent 8-byte reads when the rows are only 8-byte aligned; it runs at the 4-byte rate) and exactly the ds_read_b128

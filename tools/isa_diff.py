@@ -1,0 +1,97 @@
+#!/usr/bin/env python3
+"""Compare the device code of two builds kernel by kernel: the check of a change that must not change a kernel.
+
+    hipcc <the Makefile's CXXFLAGS and INC> --cuda-device-only -S -o old.s csrc/srx_api.hip     # in the old tree
+    hipcc <the Makefile's CXXFLAGS and INC> --cuda-device-only -S -o new.s csrc/srx_api.hip     # in the new tree
+    python tools/isa_diff.py old.s new.s [-v]
+
+Per kernel symbol (the text from its label to its s_endpgm, comments and directives dropped, local labels renumbered) it says
+  identical   the same instructions with the same operands;
+  renamed     the same instructions in the same order, registers numbered differently;
+  reordered   the same number of instructions and the same multiset of opcodes, in another order;
+  CHANGED     anything else,
+and it compares the resource figures of the kernel descriptor (VGPRs, SGPRs, scratch, LDS).  Exit status 1 when a kernel is CHANGED,
+its figures differ, or a symbol exists on one side only.  -v lists every kernel that is not identical.
+"""
+import collections
+import re
+import shutil
+import subprocess
+import sys
+
+FIGURES = ("next_free_vgpr", "next_free_sgpr", "accum_offset", "private_segment_fixed_size", "group_segment_fixed_size")
+_REGISTER = re.compile(r"\b([vsa])(\d+|\[\d+:\d+\])")
+
+
+def kernels(text):
+    """{symbol: ([instruction lines], {figure: value})} of a `hipcc -S --cuda-device-only` listing"""
+    names = re.findall(r"^\s*\.amdhsa_kernel\s+(\S+)", text, re.M)
+    figs = {}
+    for m in re.finditer(r"^\s*\.amdhsa_kernel\s+(\S+)(.*?)^\s*\.end_amdhsa_kernel", text, re.M | re.S):
+        figs[m.group(1)] = {k: v for k, v in re.findall(r"\.amdhsa_(\w+)\s+(\S+)", m.group(2)) if k in FIGURES}
+    wanted, out, cur = set(names), {}, None
+    for raw in text.splitlines():
+        line = raw.split(";")[0].strip()
+        if cur is None:
+            if line.endswith(":") and line[:-1] in wanted:
+                cur = line[:-1]
+                out[cur] = []
+            continue
+        if not line or line.startswith("."):
+            continue
+        if line.endswith(":"):
+            continue
+        out[cur].append(re.sub(r"\.LBB\d+_", ".LBB_", line))
+        if line.startswith("s_endpgm"):
+            cur = None
+    return {n: (out.get(n, []), figs.get(n, {})) for n in names}
+
+
+def verdict(a, b):
+    if a == b:
+        return "identical"
+    if len(a) == len(b):
+        if [_REGISTER.sub(r"\1#", x) for x in a] == [_REGISTER.sub(r"\1#", x) for x in b]:
+            return "renamed"
+        if collections.Counter(x.split()[0] for x in a) == collections.Counter(x.split()[0] for x in b):
+            return "reordered"
+    return "CHANGED"
+
+
+def demangle(names):
+    try:
+        out = subprocess.run([shutil.which("llvm-cxxfilt") or shutil.which("c++filt") or "c++filt"], input="\n".join(names), capture_output=True, text=True, check=True).stdout.split("\n")
+        return dict(zip(names, (re.sub(r"\(.*", "", re.sub(r"^void ", "", o)) for o in out)))
+    except (OSError, subprocess.CalledProcessError):
+        return {n: n for n in names}
+
+
+def main(argv):
+    verbose = "-v" in argv
+    paths = [a for a in argv if a != "-v"]
+    if len(paths) != 2:
+        print(__doc__)
+        return 2
+    old, new = (kernels(open(p).read()) for p in paths)
+    only = sorted(set(old) ^ set(new))
+    both = [n for n in old if n in new]
+    pretty = demangle(both + only)
+    tally, lines, bad = collections.Counter(), [], bool(only)
+    for n in both:
+        (ia, fa), (ib, fb) = old[n], new[n]
+        v = verdict(ia, ib)
+        tally[v] += 1
+        figs = "figures equal" if fa == fb else "FIGURES " + " ".join(f"{k} {fa.get(k)}->{fb.get(k)}" for k in FIGURES if fa.get(k) != fb.get(k))
+        bad = bad or v == "CHANGED" or fa != fb
+        if v != "identical" or fa != fb:
+            lines.append(f"  {v:9s} {pretty[n]}: {len(ia)} -> {len(ib)} instructions, {figs}")
+    print(f"{len(old)} kernels in {paths[0]}, {len(new)} in {paths[1]}: " + ", ".join(f"{tally[k]} {k}" for k in ("identical", "renamed", "reordered", "CHANGED")))
+    for n in only:
+        print(f"  only in {paths[0] if n in old else paths[1]}: {pretty[n]}")
+    if verbose or bad:
+        print("\n".join(lines))
+    return 1 if bad else 0
+
+
+if __name__ == "__main__":
+    sys.exit(main(sys.argv[1:]))

@@ -7,7 +7,7 @@ instruction sits in an asm block:
       vector instruction that writes one of its data registers: GCNHazardRecognizer::createsVALUHazard exempts exactly this addressing
       form, and with many waves storing at once gfx950 does send the overwritten values (tools/microbench/store_data_war.hip).
   H2  a scalar write of M0 directly followed by an LDS add-TID access (ds_write_addtid_b32 / ds_read_addtid_b32): the ISA asks for one
-      wait state; inside an asm block nobody inserts it (srx_patch.hpp: SRX_M0_NOP).
+      wait state; inside an asm block nobody inserts it (srx_block.hpp: SRX_M0_NOP).
   H3  a VALU write of either operand of v_permlane16_swap / v_permlane32_swap fewer than two wait states before the swap reads it
       (every instruction in between is one wait state, s_nop N is N + 1).  The compiler's hazard recogniser pads the builtin;
       a swap written in inline asm has to carry its own padding (tools/microbench/lane_shift_cost.hip does).
