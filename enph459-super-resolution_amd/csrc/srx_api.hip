@@ -65,11 +65,11 @@ template <typename T> static int copy_items(const T *in, size_t stride, int B, s
 template <typename T>
 static int shift_sampled(const T *in, int B, int H, int W, double sy, double sx, int istep, int Ho, int Wo, T *out,
                          bool accumulate, T *pad, T *scr, AxisTap<T> *ty, AxisTap<T> *tx, bool taps_ready,
-                         hipStream_t st)
+                         hipStream_t st, unsigned flags)  // flags: of the ibp / saa call this runs in, 0 in a primitive entry point
 {
     const int Hp = H + 2 * SRX_NPAD, Wp = W + 2 * SRX_NPAD;
     SRX_TRY(pad_edge(in, B, H, W, pad, st));
-    SRX_TRY(fused::prefilter2d_fast(pad, scr, B, Hp, Wp, MODE_REFLECT, st));
+    SRX_TRY(fused::prefilter2d_fast(pad, scr, B, Hp, Wp, MODE_REFLECT, st, flags));
     if (!taps_ready) {
         SRX_TRY(build_taps(ty, Ho, Hp, TAP_SHIFT, istep, -sy, st));  // scipy negates the shift: cc = i + (-s)
         SRX_TRY(build_taps(tx, Wo, Wp, TAP_SHIFT, istep, -sx, st));
@@ -131,16 +131,16 @@ static int shift_cubic(const T *in, int B, int H, int W, double sy, double sx, T
     const auto [pad, scr, ty, tx] = carve_shift<T>(ar, shift_dims(B, H, W));
     if (!ar.ok)
         return SRX_E_WORKSPACE;
-    return shift_sampled(in, B, H, W, sy, sx, 1, H, W, out, false, pad, scr, ty, tx, false, st);
+    return shift_sampled(in, B, H, W, sy, sx, 1, H, W, out, false, pad, scr, ty, tx, false, st, 0);
 }
 
 // scipy.ndimage.zoom(order 3): in [B items, stride in_stride, h, w] -> out [B, Ho, Wo]
 template <typename T>
 static int zoom_into(const T *in, size_t in_stride, int B, int h, int w, int Ho, int Wo, T *out, T *coef, T *cscr,
-                     AxisTap<T> *ty, AxisTap<T> *tx, hipStream_t st)
+                     AxisTap<T> *ty, AxisTap<T> *tx, hipStream_t st, unsigned flags)  // flags: as shift_sampled's
 {
     SRX_TRY(copy_items(in, in_stride, B, (size_t)h * w, coef, st));
-    SRX_TRY(fused::prefilter2d_fast(coef, cscr, B, h, w, MODE_MIRROR, st));
+    SRX_TRY(fused::prefilter2d_fast(coef, cscr, B, h, w, MODE_MIRROR, st, flags));
     const double zy = Ho > 1 ? (double)(h - 1) / (double)(Ho - 1) : 1.0;
     const double zx = Wo > 1 ? (double)(w - 1) / (double)(Wo - 1) : 1.0;
     SRX_TRY(build_taps(ty, Ho, h, TAP_ZOOM, 1, zy, st));
@@ -179,7 +179,7 @@ static int zoom_cubic(const T *in, int B, int h, int w, int f, T *out, void *ws,
     const auto [coef, cscr, ty, tx] = carve_zoom<T>(ar, ZoomDims{(size_t)B, (size_t)h, (size_t)w, (size_t)h * f, (size_t)w * f});
     if (!ar.ok)
         return SRX_E_WORKSPACE;
-    return zoom_into(in, (size_t)h * w, B, h, w, h * f, w * f, out, coef, cscr, ty, tx, st);
+    return zoom_into(in, (size_t)h * w, B, h, w, h * f, w * f, out, coef, cscr, ty, tx, st, 0);
 }
 
 // forward_model = decimate(shift(blur(hr)))
@@ -202,7 +202,7 @@ static int forward_model(const T *hr, int B, int H, int W, const double *k, int 
     if (!ar.ok)
         return SRX_E_WORKSPACE;
     SRX_TRY(blur(hr, B, H, W, k, kh, kw, false, b, st));
-    return shift_sampled(b, B, H, W, sy * f, sx * f, f, sh, sw, out, false, pad, scr, ty, tx, false, st);
+    return shift_sampled(b, B, H, W, sy * f, sx * f, f, sh, sw, out, false, pad, scr, ty, tx, false, st, 0);
 }
 
 // back_project = blur_flipped(shift(zero_insert(err), -s f))
@@ -225,7 +225,7 @@ static int back_project(const T *err, int B, int eh, int ew, const double *k, in
         return SRX_E_WORKSPACE;
     hipLaunchKernelGGL(k_zero_insert<T>, dim3(cdiv(W, 64), cdiv(H, 4), B), dim3(64, 4), 0, st, err, eh, ew, f, H, W, up);
     SRX_CHECK_LAUNCH();
-    SRX_TRY(shift_sampled(up, B, H, W, -sy * f, -sx * f, 1, H, W, s2, false, pad, scr, ty, tx, false, st));
+    SRX_TRY(shift_sampled(up, B, H, W, -sy * f, -sx * f, 1, H, W, s2, false, pad, scr, ty, tx, false, st, 0));
     return blur(s2, B, H, W, k, kh, kw, true, out, st);
 }
 
@@ -246,20 +246,21 @@ template <typename T> static SaaComposedTabs<T> carve_saa_composed(Arena &ar, co
     return {ar.take<T>(d.B * d.h * d.w), ar.take<T>(d.B * d.h * d.w), ar.take<T>(d.B * d.H * d.W), ar.take<T>(Pp), ar.take<T>(Pp),
             ar.take<AxisTap<T>>(d.ty), ar.take<AxisTap<T>>(d.tx), ar.take<AxisTap<T>>(d.ty), ar.take<AxisTap<T>>(d.tx)};
 }
-static size_t saa_ws_composed(int eb, int B, int N, int h, int w, int f)
+static size_t saa_ws_composed(const SaaShape &s, int B)
 {
-    (void)N;
-    const size_t H = (size_t)h * f, W = (size_t)w * f, tl = tap_bound(eb, H > W ? H : W);
-    const SaaComposedDims d{(size_t)B, (size_t)h, (size_t)w, H, W, tl, tl};
-    return measured([&](Arena &m) { eb == 8 ? (void)carve_saa_composed<double>(m, d) : (void)carve_saa_composed<float>(m, d); });
+    const size_t H = (size_t)s.h * s.f, W = (size_t)s.w * s.f, tl = tap_bound(s.eb, H > W ? H : W);
+    const SaaComposedDims d{(size_t)B, (size_t)s.h, (size_t)s.w, H, W, tl, tl};
+    return measured([&](Arena &m) { s.eb == 8 ? (void)carve_saa_composed<double>(m, d) : (void)carve_saa_composed<float>(m, d); });
 }
 
-template <typename T>
-static int saa_composed(const T *lr, int B, int N, int h, int w, const double *sh, int f, T *out, void *ws, size_t wsb,
-                        hipStream_t st)
+template <typename T> static int saa_composed(const SaaCall<T> &c)
 {
-    const int H = h * f, W = w * f;
-    Arena ar(ws, wsb);
+    const int B = c.B, N = c.s.N, h = c.s.h, w = c.s.w, f = c.s.f, H = h * f, W = w * f;
+    const double *const sh = c.s.sh;
+    const T *const lr = c.lr;
+    T *const out = c.out;
+    const hipStream_t st = c.st;
+    Arena ar(c.ws, c.wsb);
     const auto [coef, cscr, up, pad, scr, zy, zx, ty, tx] =
         carve_saa_composed<T>(ar, SaaComposedDims{(size_t)B, (size_t)h, (size_t)w, (size_t)H, (size_t)W, (size_t)H, (size_t)W});
     if (!ar.ok)
@@ -268,9 +269,8 @@ static int saa_composed(const T *lr, int B, int N, int h, int w, const double *s
     if (fill_bytes(out, 0, n * sizeof(T), st) != hipSuccess)
         return SRX_E_HIP;
     for (int k = 0; k < N; k++) {
-        SRX_TRY(zoom_into(lr + (size_t)k * h * w, (size_t)N * h * w, B, h, w, H, W, up, coef, cscr, zy, zx, st));
-        SRX_TRY(shift_sampled(up, B, H, W, sh[2 * k] * f, sh[2 * k + 1] * f, 1, H, W, out, true, pad, scr, ty, tx,
-                              false, st));
+        SRX_TRY(zoom_into(lr + (size_t)k * h * w, (size_t)N * h * w, B, h, w, H, W, up, coef, cscr, zy, zx, st, c.s.flags));
+        SRX_TRY(shift_sampled(up, B, H, W, sh[2 * k] * f, sh[2 * k + 1] * f, 1, H, W, out, true, pad, scr, ty, tx, false, st, c.s.flags));
     }
     hipLaunchKernelGGL(k_div<T>, dim3(grid1d(n)), dim3(256), 0, st, out, (T)N, n);
     SRX_CHECK_LAUNCH();
@@ -304,25 +304,27 @@ template <typename T> static IbpComposedTabs<T> carve_ibp_composed(Arena &ar, co
     return t;
 }
 // the bound: the block partials of whole simulated frames (a call's residual covers min(sh, h) x min(sw, w) of them)
-static size_t ibp_ws_composed(int eb, int B, int N, int h, int w, int H, int W, int f)
+static size_t ibp_ws_composed(const IbpShape &s, int B)
 {
-    (void)h;
-    (void)w;
-    const int sh = cdiv(H, f), sw = cdiv(W, f);
-    const IbpComposedDims d{(size_t)B, (size_t)(N > 0 ? N : 0), (size_t)H, (size_t)W, (size_t)sh, (size_t)sw, tap_bound(eb, (size_t)(H > W ? H : W)),
+    const int H = s.H, W = s.W, sh = cdiv(H, s.f), sw = cdiv(W, s.f);
+    const IbpComposedDims d{(size_t)B, (size_t)(s.N > 0 ? s.N : 0), (size_t)H, (size_t)W, (size_t)sh, (size_t)sw, tap_bound(s.eb, (size_t)(H > W ? H : W)),
                             (size_t)cdiv(sw, 64) * cdiv(sh, 4)};
-    return measured([&](Arena &m) { eb == 8 ? (void)carve_ibp_composed<double>(m, d) : (void)carve_ibp_composed<float>(m, d); });
+    return measured([&](Arena &m) { s.eb == 8 ? (void)carve_ibp_composed<double>(m, d) : (void)carve_ibp_composed<float>(m, d); });
 }
 
-template <typename T>
-static int ibp_composed(const T *lr, int B, int N, int h, int w, const double *shf, const double *k, int kh, int kw,
-                        const T *hr_init, int H, int W, int f, int n_iter, double step, T *hr, double *errors, void *ws,
-                        size_t wsb, hipStream_t st)
+template <typename T> static int ibp_composed(const IbpCall<T> &c)
 {
+    const int B = c.B, N = c.s.N, h = c.s.h, w = c.s.w, H = c.s.H, W = c.s.W, f = c.s.f, kh = c.s.kh, kw = c.s.kw, n_iter = c.n_iter;
+    const double *const shf = c.s.sh, *const k = c.s.k, step = c.step;
+    const T *const lr = c.lr, *const hr_init = c.hr_init;
+    T *const hr = c.hr;
+    double *const errors = c.errors;
+    const hipStream_t st = c.st;
+    const unsigned flags = c.s.flags;
     const int sh = cdiv(H, f), sw = cdiv(W, f);
     const int mh = sh < h ? sh : h, mw = sw < w ? sw : w;
     const size_t P = (size_t)B * H * W;
-    Arena ar(ws, wsb);
+    Arena ar(c.ws, c.wsb);
     const int rblk = cdiv(mw, 64) * cdiv(mh, 4);
     const auto [b, up, s2, bp, corr, pad, scr, sim, err, taps, rpart] = carve_ibp_composed<T>(
         ar, IbpComposedDims{(size_t)B, (size_t)N, (size_t)H, (size_t)W, (size_t)sh, (size_t)sw, (size_t)(H > W ? H : W), (size_t)rblk});
@@ -346,8 +348,7 @@ static int ibp_composed(const T *lr, int B, int N, int h, int w, const double *s
         if (fill_bytes(corr, 0, P * sizeof(T), st) != hipSuccess)
             return SRX_E_HIP;
         for (int q = 0; q < N; q++) {
-            SRX_TRY(shift_sampled(b, B, H, W, 0, 0, f, sh, sw, sim, false, pad, scr, taps[4 * q], taps[4 * q + 1], true,
-                                  st));
+            SRX_TRY(shift_sampled(b, B, H, W, 0, 0, f, sh, sw, sim, false, pad, scr, taps[4 * q], taps[4 * q + 1], true, st, flags));
             hipLaunchKernelGGL(k_residual<T>, dim3(cdiv(mw, 64), cdiv(mh, 4), B), dim3(64, 4), 0, st,
                                lr + (size_t)q * h * w, (size_t)N * h * w, w, sim, (size_t)sh * sw, sw, mh, mw, err, errors ? rpart : nullptr);
             SRX_CHECK_LAUNCH();
@@ -358,8 +359,7 @@ static int ibp_composed(const T *lr, int B, int N, int h, int w, const double *s
             hipLaunchKernelGGL(k_zero_insert<T>, dim3(cdiv(W, 64), cdiv(H, 4), B), dim3(64, 4), 0, st, err, mh, mw, f, H,
                                W, up);
             SRX_CHECK_LAUNCH();
-            SRX_TRY(shift_sampled(up, B, H, W, 0, 0, 1, H, W, s2, false, pad, scr, taps[4 * q + 2], taps[4 * q + 3], true,
-                                  st));
+            SRX_TRY(shift_sampled(up, B, H, W, 0, 0, 1, H, W, s2, false, pad, scr, taps[4 * q + 2], taps[4 * q + 3], true, st, flags));
             SRX_TRY(blur(s2, B, H, W, k, kh, kw, true, bp, st));
             hipLaunchKernelGGL(k_add<T>, dim3(grid1d(P)), dim3(256), 0, st, corr, bp, P);
             SRX_CHECK_LAUNCH();
@@ -373,13 +373,6 @@ static int ibp_composed(const T *lr, int B, int N, int h, int w, const double *s
 // ---------------------------------------------------------------------------------------
 // dispatch
 // ---------------------------------------------------------------------------------------
-static bool basic_ibp_args_ok(const void *lr, int B, int N, int h, int w, const double *sh, const double *k, int kh,
-                              int kw, const void *hr_init, int H, int W, int f, int n_iter, void *hr)
-{
-    return lr && sh && k && hr_init && hr && B > 0 && N > 0 && h > 0 && w > 0 && H > 0 && W > 0 && f > 0 && kh > 0 &&
-           kw > 0 && n_iter >= 0;
-}
-
 #define SRX_MAX_BATCH_PER_LAUNCH 32768  // gridDim.z <= 65535; larger batches go through in chunks of this many items
 // The items of one chunk (shift_and_add's kernels take an (item, frame) pair per gridDim.z).  The workspace queries accept any B and N, so
 // these do: B <= 0 passes through, and a query that sizes a table or a staged copy for at least one item says so with std::max.
@@ -391,9 +384,48 @@ static inline int saa_chunk_items(int B, int N)
     return B;
 }
 
+// Argument and limit checks of an ibp call: of every srx_ibp entry point, the per-item form, a plan and srx_ibp_path_for.  present: the
+// call's device pointers are (only that counts).  Every invalid argument is answered before any limit.
+static int ibp_check(const IbpSpec &s, int B, int n_iter, bool present)
+{
+    if (!present || !s.sh || !s.k || B <= 0 || s.N <= 0 || s.h <= 0 || s.w <= 0 || s.H <= 0 || s.W <= 0 || s.f <= 0 || s.kh <= 0 || s.kw <= 0 || n_iter < 0)
+        return SRX_E_INVALID;
+    if (s.N > SRX_MAX_FRAMES || s.kh * s.kw > SRX_MAX_KERNEL_TAPS || !plane_fits((size_t)s.eb, s.N, s.h, s.w, s.H, s.W))
+        return SRX_E_UNSUPPORTED;
+    return SRX_OK;
+}
+// ... and of a shift_and_add call: every srx_saa entry point, the per-item form and srx_saa_path_for
+static int saa_check(const SaaSpec &s, int B, bool present)
+{
+    if (!present || !s.sh || B <= 0 || s.N <= 0 || s.h <= 0 || s.w <= 0 || s.f <= 0)
+        return SRX_E_INVALID;
+    if (s.N > SRX_MAX_FRAMES || (size_t)s.h * s.f >= ((size_t)1 << 30) || (size_t)s.w * s.f >= ((size_t)1 << 30) ||
+        !plane_fits((size_t)s.eb, s.N, s.h, s.w, s.h * s.f, s.w * s.f))
+        return SRX_E_UNSUPPORTED;
+    return SRX_OK;
+}
+
+// The shape-only workspace bounds (srx_ibp_workspace_bytes, srx_saa_workspace_bytes): the largest of the paths a call of this shape may
+// take.  Of the flags the two that name a path count and no other: no SRX_FLAG_DIAG_* switch changes a size.
+static size_t ibp_bound(const IbpShape &s, int B, unsigned flags)
+{
+    B = ibp_chunk_items(B);
+    const size_t a = ibp_ws_composed(s, B), b = std::max(fused::ibp_ws(s, B), mosaic::ibp_ws(s, B));
+    if (flags & SRX_FLAG_FUSED)
+        return b;
+    if (flags & SRX_FLAG_COMPOSED)
+        return a;
+    return a > b ? a : b;
+}
+static size_t saa_bound(const SaaShape &s, int B)
+{
+    B = saa_chunk_items(B, s.N);
+    return std::max(std::max(saa_ws_composed(s, B), fused::saa_ws(s, B)), mosaic::saa_ws(s, B));
+}
+
 // The route of one srx_ibp / srx_saa call (valid arguments within the library's limits), decided here and nowhere else: the call itself, its
-// per-item form, a plan, the exact workspace query and srx_*_path_for read it.  The batch size plays no part.  Precondition: runs under the entry point's CallFlags guard, like everything
-// below it -- the eligibility predicates and fused::make_kernel7 read the path-forcing flags through call_flags().  Pure host arithmetic.
+// per-item form, a plan, the exact workspace query and srx_*_path_for read it.  A function of the spec alone -- the shape, the two host
+// tables and the flags -- so the batch size plays no part and whoever holds a spec gets the route of that call.  Pure host arithmetic.
 enum Path { PATH_COMPOSED, PATH_FUSED, PATH_BTILE, PATH_MOSAIC };  // (shift_and_add has no PATH_BTILE)
 struct Route {
     int status;                    // an early answer (SRX_FLAG_FUSED on a call that cannot fuse), else SRX_OK
@@ -402,51 +434,50 @@ struct Route {
     const char *name;              // what srx_last_path() reports
 };
 
-static Route route_ibp(int eb, int N, int h, int w, int H, int W, int f, const double *sh, const double *k, int kh, int kw, unsigned flags)
+static Route route_ibp(const IbpSpec &s)
 {
-    const bool can_fuse = fused::ibp_eligible(N, h, w, sh, kh, kw, H, W, f);
-    if ((flags & SRX_FLAG_FUSED) && !can_fuse)
+    const bool can_fuse = fused::ibp_eligible(s);
+    if ((s.flags & SRX_FLAG_FUSED) && !can_fuse)
         return {SRX_E_UNSUPPORTED, PATH_COMPOSED, nullptr, "none"};
-    if (!can_fuse || (flags & SRX_FLAG_COMPOSED))
+    if (!can_fuse || (s.flags & SRX_FLAG_COMPOSED))
         return {SRX_OK, PATH_COMPOSED, nullptr, "composed"};
-    if (!(flags & SRX_FLAG_PER_FRAME) && mosaic::eligible(N, h, w, sh, kh, kw, H, W, f)) {
-        const mosaic::ImplRow &impl = mosaic::choose_impl(eb, N, H, W, sh, k, kh, kw, f);
+    if (!(s.flags & SRX_FLAG_PER_FRAME) && mosaic::eligible(s)) {
+        const mosaic::ImplRow &impl = mosaic::choose_impl(s);
         return {SRX_OK, PATH_MOSAIC, &impl, impl.name};
     }
-    if (btile::eligible(eb, N, h, w, sh, k, kh, kw, H, W, f))
+    if (btile::eligible(s))
         return {SRX_OK, PATH_BTILE, nullptr, "btile"};
     return {SRX_OK, PATH_FUSED, nullptr, "fused"};
 }
 
-static Route route_saa(int N, int h, int w, int f, const double *sh, unsigned flags)
+static Route route_saa(const SaaSpec &s)
 {
-    const bool can_fuse = fused::saa_eligible(N, h, w, sh, f);
-    if ((flags & SRX_FLAG_FUSED) && !can_fuse)
+    const bool can_fuse = fused::saa_eligible(s);
+    if ((s.flags & SRX_FLAG_FUSED) && !can_fuse)
         return {SRX_E_UNSUPPORTED, PATH_COMPOSED, nullptr, "none"};
-    if (!can_fuse || (flags & SRX_FLAG_COMPOSED))
+    if (!can_fuse || (s.flags & SRX_FLAG_COMPOSED))
         return {SRX_OK, PATH_COMPOSED, nullptr, "composed"};
-    if (!(flags & SRX_FLAG_PER_FRAME) && mosaic::saa_eligible(N, h, w, sh, f))
+    if (!(s.flags & SRX_FLAG_PER_FRAME) && mosaic::saa_eligible(s))
         return {SRX_OK, PATH_MOSAIC, nullptr, "mosaic"};
     return {SRX_OK, PATH_FUSED, nullptr, "fused"};
 }
 
 // What a call on route `r` must bring: exactly what a mosaic implementation carves (the shape-only bound covers it by construction,
 // tests/test_abi.py sweeps shapes for need <= bound), the shape-only bound on every other path.
-static size_t ibp_need(const Route &r, int eb, int B, int N, int h, int w, int H, int W, int f, unsigned flags)
+static size_t ibp_need(const Route &r, const IbpSpec &s, int B)
 {
-    B = ibp_chunk_items(B);
     if (r.status != SRX_OK || r.path != PATH_MOSAIC)
-        return srx_ibp_workspace_bytes(eb, B, N, h, w, H, W, f, flags);
-    return mosaic::ibp_ws_for(*r.impl, eb, B, N, H, W);
+        return ibp_bound(s, B, s.flags);
+    return mosaic::ibp_ws_for(*r.impl, s, ibp_chunk_items(B));
 }
 
 // The uint8 entry points (srx_ibp_u8lr_*, srx_saa_u8lr_*) off the mosaic family: the chunk's frames are converted to T at the front of the
 // workspace and the float driver runs on the rest.  (Those routes serve per-frame fractional shifts; the mosaic family reads the bytes itself.)
 template <typename T> static T *carve_u8_stage(Arena &ar, size_t n) { return ar.take<T>(n); }
-static inline size_t u8_stage_bytes(int eb, int Bc, int N, int h, int w)
+template <typename Shape> static inline size_t u8_stage_bytes(const Shape &s, int Bc)  // Shape: IbpShape or SaaShape
 {
-    const size_t n = (size_t)Bc * N * h * w;
-    return measured([&](Arena &m) { eb == 8 ? (void)carve_u8_stage<double>(m, n) : (void)carve_u8_stage<float>(m, n); });
+    const size_t n = (size_t)Bc * s.N * s.h * s.w;
+    return measured([&](Arena &m) { s.eb == 8 ? (void)carve_u8_stage<double>(m, n) : (void)carve_u8_stage<float>(m, n); });
 }
 
 template <typename T> static int u8_stage(const uint8_t *lr, size_t n, void *&ws, size_t &wsb, const T *&staged, hipStream_t st)
@@ -461,111 +492,93 @@ template <typename T> static int u8_stage(const uint8_t *lr, size_t n, void *&ws
     ws = (char *)ws + ar.off, wsb -= ar.off;
     return SRX_OK;
 }
+// the frames of a chunk in T and the workspace behind them: the caller's own, or the staged copy of its uint8 samples
+template <typename T, typename S> static int frames_in_t(const S *lr_, size_t n, void *&ws, size_t &wsb, const T *&lr, hipStream_t st)
+{
+    if constexpr (std::is_same<S, T>::value)
+        return lr = lr_, SRX_OK;
+    else
+        return u8_stage<T>(lr_, n, ws, wsb, lr, st);
+}
 
 // one chunk (at most SRX_MAX_BATCH_PER_LAUNCH items) of a call on the route its entry point decided
-template <typename T, typename S>
-static int ibp_run(const Route &r, const S *lr_, int B, int N, int h, int w, const double *sh, const double *k, int kh, int kw, const T *hr_init, int H,
-                   int W, int f, int n_iter, double step, T *hr, double *errors, void *ws, size_t wsb, hipStream_t st)
+template <typename T, typename S> static int ibp_run(const Route &r, const IbpCall<T, S> &c)
 {
     if (r.path == PATH_MOSAIC)
-        return mosaic::ibp<T, S>(*r.impl, lr_, B, N, h, w, sh, k, kh, kw, hr_init, H, W, f, n_iter, step, hr, errors, ws, wsb, st);
-    const T *lr;
-    if constexpr (std::is_same<S, T>::value)
-        lr = lr_;
-    else
-        SRX_TRY(u8_stage<T>(lr_, (size_t)B * N * h * w, ws, wsb, lr, st));
+        return mosaic::ibp<T, S>(*r.impl, c);
+    const T *lr = nullptr;
+    void *ws = c.ws;
+    size_t wsb = c.wsb;
+    SRX_TRY((frames_in_t<T, S>(c.lr, (size_t)c.B * c.s.N * c.s.h * c.s.w, ws, wsb, lr, c.st)));
+    const IbpCall<T> ct = c.on(lr, ws, wsb);
     switch (r.path) {
     case PATH_MOSAIC:  // (taken above)
         break;
     case PATH_BTILE:
         if constexpr (sizeof(T) == 4)
-            return btile::ibp(lr, B, N, h, w, sh, k, kh, kw, hr_init, H, W, n_iter, step, hr, errors, ws, wsb, st);
+            return btile::ibp(ct);
         return SRX_E_INVALID;  // (route_ibp gives float32 calls alone this path)
     case PATH_FUSED:
-        return fused::ibp<T>(lr, B, N, h, w, sh, k, kh, kw, hr_init, H, W, f, n_iter, step, hr, errors, ws, wsb, st);
+        return fused::ibp<T>(ct);
     case PATH_COMPOSED:
         break;
     }
-    return ibp_composed<T>(lr, B, N, h, w, sh, k, kh, kw, hr_init, H, W, f, n_iter, step, hr, errors, ws, wsb, st);
+    return ibp_composed<T>(ct);
 }
 
-template <typename T, typename S = T>
-static int ibp_dispatch(const S *lr, int B, int N, int h, int w, const double *sh, const double *k, int kh, int kw,
-                        const T *hr_init, int H, int W, int f, int n_iter, double step, T *hr, double *errors, void *ws,
-                        size_t wsb, hipStream_t st, unsigned flags)
+template <typename T, typename S> static int ibp_dispatch(const IbpCall<T, S> &c)
 {
-    if (!basic_ibp_args_ok(lr, B, N, h, w, sh, k, kh, kw, hr_init, H, W, f, n_iter, hr))
-        return SRX_E_INVALID;
-    if (N > SRX_MAX_FRAMES || kh * kw > SRX_MAX_KERNEL_TAPS || !plane_fits(sizeof(T), N, h, w, H, W))
-        return SRX_E_UNSUPPORTED;
-    const Route r = route_ibp((int)sizeof(T), N, h, w, H, W, f, sh, k, kh, kw, flags);  // once per call: the batch size plays no part
+    SRX_TRY(ibp_check(c.s, c.B, c.n_iter, c.lr && c.hr_init && c.hr));
+    const Route r = route_ibp(c.s);  // once per call: the batch size plays no part
     if (r.status != SRX_OK)
         return r.status;
     // a short or misaligned workspace is refused before anything is queued
-    size_t need = ibp_need(r, (int)sizeof(T), B, N, h, w, H, W, f, flags);
+    size_t need = ibp_need(r, c.s, c.B);
     if (!std::is_same<S, T>::value && r.path != PATH_MOSAIC)
-        need += u8_stage_bytes((int)sizeof(T), ibp_chunk_items(B), N, h, w);
-    if (ws_short(ws, wsb, need))
+        need += u8_stage_bytes(c.s, ibp_chunk_items(c.B));
+    if (ws_short(c.ws, c.wsb, need))
         return SRX_E_WORKSPACE;
     g_last_path = r.name;
     // batches beyond one launch's gridDim.z go through in chunks; the workspace is sized for one chunk and reused (stream order)
-    for (int b0 = 0; b0 < B; b0 += SRX_MAX_BATCH_PER_LAUNCH) {
-        const int bc = ibp_chunk_items(B - b0);
-        SRX_TRY((ibp_run<T, S>(r, lr + (size_t)b0 * N * h * w, bc, N, h, w, sh, k, kh, kw, hr_init + (size_t)b0 * H * W, H, W, f, n_iter, step,
-                           hr + (size_t)b0 * H * W, errors ? errors + (size_t)b0 * n_iter : nullptr, ws, wsb, st)));
-    }
-    return SRX_OK;
-}
-
-// argument and limit checks of every srx_saa entry point (and of srx_saa_path_for); lr / out: the device pointers, only their presence counts
-static int saa_check(size_t eb, const void *lr, int B, int N, int h, int w, const double *sh, int f, const void *out)
-{
-    if (!lr || !sh || !out || B <= 0 || N <= 0 || h <= 0 || w <= 0 || f <= 0)
-        return SRX_E_INVALID;
-    if (N > SRX_MAX_FRAMES || (size_t)h * f >= ((size_t)1 << 30) || (size_t)w * f >= ((size_t)1 << 30) || !plane_fits(eb, N, h, w, h * f, w * f))
-        return SRX_E_UNSUPPORTED;
+    for (int b0 = 0; b0 < c.B; b0 += SRX_MAX_BATCH_PER_LAUNCH)
+        SRX_TRY(ibp_run(r, c.chunk(b0, ibp_chunk_items(c.B - b0))));
     return SRX_OK;
 }
 
 // one chunk (at most saa_chunk_items items) of a call on the route its entry point decided
-template <typename T, typename S>
-static int saa_run(const Route &r, const S *lr_, int B, int N, int h, int w, const double *sh, int f, T *out, void *ws, size_t wsb, hipStream_t st)
+template <typename T, typename S> static int saa_run(const Route &r, const SaaCall<T, S> &c)
 {
     if (r.path == PATH_MOSAIC)
-        return mosaic::saa<T, S>(lr_, B, N, h, w, sh, f, out, ws, wsb, st);
-    const T *lr;
-    if constexpr (std::is_same<S, T>::value)
-        lr = lr_;
-    else
-        SRX_TRY(u8_stage<T>(lr_, (size_t)B * N * h * w, ws, wsb, lr, st));
-    if (r.path == PATH_FUSED)
-        return fused::saa<T>(lr, B, N, h, w, sh, f, out, ws, wsb, st);
-    return saa_composed<T>(lr, B, N, h, w, sh, f, out, ws, wsb, st);
+        return mosaic::saa<T, S>(c);
+    const T *lr = nullptr;
+    void *ws = c.ws;
+    size_t wsb = c.wsb;
+    SRX_TRY((frames_in_t<T, S>(c.lr, (size_t)c.B * c.s.N * c.s.h * c.s.w, ws, wsb, lr, c.st)));
+    const SaaCall<T> ct = c.on(lr, ws, wsb);
+    return r.path == PATH_FUSED ? fused::saa<T>(ct) : saa_composed<T>(ct);
 }
 
-template <typename T, typename S = T>
-static int saa_dispatch(const S *lr, int B, int N, int h, int w, const double *sh, int f, T *out, void *ws, size_t wsb,
-                        hipStream_t st, unsigned flags)
+template <typename T, typename S> static int saa_dispatch(const SaaCall<T, S> &c)
 {
-    SRX_TRY(saa_check(sizeof(T), lr, B, N, h, w, sh, f, out));
-    const Route r = route_saa(N, h, w, f, sh, flags);  // once per call: the batch size plays no part
+    SRX_TRY(saa_check(c.s, c.B, c.lr && c.out));
+    const Route r = route_saa(c.s);  // once per call: the batch size plays no part
     // Every refusal comes before anything is queued (the uint8 staging included).  These entry points answer a short workspace BEFORE
     // SRX_FLAG_FUSED on a table that cannot fuse, items::saa_dispatch_items the other way round: callers have met both orders, both stay.
-    constexpr bool u8 = !std::is_same<S, T>::value;
-    if (ws_short(ws, wsb, u8 ? srx_saa_u8lr_workspace_bytes((int)sizeof(T), B, N, h, w, f) : srx_saa_workspace_bytes((int)sizeof(T), B, N, h, w, f)))
+    const size_t stage = std::is_same<S, T>::value ? 0 : u8_stage_bytes(c.s, saa_chunk_items(c.B, c.s.N));  // (whatever the route: srx_saa_u8lr_workspace_bytes)
+    if (ws_short(c.ws, c.wsb, saa_bound(c.s, c.B) + stage))
         return SRX_E_WORKSPACE;
     if (r.status != SRX_OK)
         return r.status;
     g_last_path = r.name;
     // batches beyond one launch's gridDim.z go through in chunks; the workspace is sized for one chunk and reused (stream order)
-    for (int b0 = 0, bc; b0 < B; b0 += bc) {
-        bc = saa_chunk_items(B - b0, N);
-        SRX_TRY((saa_run<T, S>(r, lr + (size_t)b0 * N * h * w, bc, N, h, w, sh, f, out + (size_t)b0 * h * f * w * f, ws, wsb, st)));
+    for (int b0 = 0, bc; b0 < c.B; b0 += bc) {
+        bc = saa_chunk_items(c.B - b0, c.s.N);
+        SRX_TRY(saa_run(r, c.chunk(b0, bc)));
     }
     return SRX_OK;
 }
 
-#include "srx_items.hpp"  // one shift table per item: routing by runs on top of the dispatchers above
+#include "srx_items.hpp"  // one shift table per item: routing by runs on top of the route, the checks and the chunk drivers above
 
 // ---------------------------------------------------------------------------------------
 // plans: the per-call tables built ONCE, the iterations in several runs, rows of the state readable / replaceable in between
@@ -573,10 +586,10 @@ static int saa_dispatch(const S *lr, int B, int N, int h, int w, const double *s
 // small host record; the frames and the workspace must stay alive until the plan is destroyed.
 // ---------------------------------------------------------------------------------------
 struct srx_plan_s {
-    int eb, B, N, h, w, H, W, f, kh, kw, tr_lo, tr_hi;
-    double step;
-    unsigned flags;
+    IbpSpec s;            // the call every run makes; sh and k point at the copies below (a plan lives where it was made: never copied)
     double sh[2 * SRX_MAX_FRAMES], k[SRX_MAX_KERNEL_TAPS];
+    int B, tr_lo, tr_hi;
+    double step;
     const void *lr;
     bool z;               // k_ibp_ztile with hoisted tables (float32, integer HR shifts, frames of at least 128 x 128)
     ztile::State zs;
@@ -588,42 +601,50 @@ struct srx_plan_s {
 
 // a plan off the hoisted-table path keeps its state as a plain [B, H, W] plane at the head of the workspace
 template <typename T> static T *carve_plan_state(Arena &ar, size_t B, int H, int W) { return ar.take<T>(B * H * W); }
-
-template <typename T>
-static int plan_create(const T *lr, int B, int N, int h, int w, const double *sh, const double *k, int kh, int kw, const T *hr_init, int H, int W, int f,
-                       double step, int tr_lo, int tr_hi, void *ws, size_t wsb, hipStream_t st, unsigned flags, srx_plan_s **out)
+static size_t plan_bound(const IbpShape &s, int B, unsigned flags)
 {
-    if (!out || !basic_ibp_args_ok(lr, B, N, h, w, sh, k, kh, kw, hr_init, H, W, f, 0, ws) || tr_lo < 0 || tr_hi > H || tr_lo > tr_hi)
+    const size_t b1 = B > 0 ? B : 1;
+    return measured([&](Arena &m) { s.eb == 8 ? (void)carve_plan_state<double>(m, b1, s.H, s.W) : (void)carve_plan_state<float>(m, b1, s.H, s.W); }) +
+           ibp_bound(s, B, flags);
+}
+
+// c: the call the plan's runs make, less what a run brings (n_iter, errors) and with no hr: the state lives in the workspace
+template <typename T> static int plan_create(const IbpCall<T> &c, int tr_lo, int tr_hi, srx_plan_s **out)
+{
+    const IbpSpec &s = c.s;
+    const int B = c.B, checked = ibp_check(s, B, 0, c.lr && c.hr_init && c.ws);
+    if (!out || checked == SRX_E_INVALID || tr_lo < 0 || tr_hi > s.H || tr_lo > tr_hi)
         return SRX_E_INVALID;
-    if (N > SRX_MAX_FRAMES || kh * kw > SRX_MAX_KERNEL_TAPS || B > SRX_MAX_BATCH_PER_LAUNCH || !plane_fits(sizeof(T), N, h, w, H, W))
+    if (checked != SRX_OK || B > SRX_MAX_BATCH_PER_LAUNCH)
         return SRX_E_UNSUPPORTED;
-    if (ws_short(ws, wsb, srx_ibp_plan_workspace_bytes((int)sizeof(T), B, N, h, w, H, W, f, flags)))  // before anything is queued
+    if (ws_short(c.ws, c.wsb, plan_bound(s, B, s.flags)))  // before anything is queued
         return SRX_E_WORKSPACE;
     srx_plan_s *p = new srx_plan_s();
-    p->eb = (int)sizeof(T), p->B = B, p->N = N, p->h = h, p->w = w, p->H = H, p->W = W, p->f = f, p->kh = kh, p->kw = kw, p->tr_lo = tr_lo, p->tr_hi = tr_hi;
-    p->step = step, p->flags = flags, p->lr = lr, p->z = false, p->hr = nullptr, p->ws_rest = nullptr, p->wsb_rest = 0, p->path = "none";
-    std::memcpy(p->sh, sh, sizeof(double) * 2 * N);
-    std::memcpy(p->k, k, sizeof(double) * kh * kw);
-    Arena ar(ws, wsb);
+    std::memcpy(p->sh, s.sh, sizeof(double) * 2 * s.N);
+    std::memcpy(p->k, s.k, sizeof(double) * s.kh * s.kw);
+    p->s = s, p->s.sh = p->sh, p->s.k = p->k;
+    p->B = B, p->tr_lo = tr_lo, p->tr_hi = tr_hi, p->step = c.step, p->lr = c.lr;
+    p->z = false, p->hr = nullptr, p->ws_rest = nullptr, p->wsb_rest = 0, p->path = "none";
+    Arena ar(c.ws, c.wsb);
     int rc = SRX_OK;
-    const Route r = route_ibp((int)sizeof(T), N, h, w, H, W, f, sh, k, kh, kw, flags);
+    const Route r = route_ibp(s);
     const bool z = r.status == SRX_OK && r.path == PATH_MOSAIC && r.impl->id == mosaic::IMPL_ZTILE;
     if constexpr (sizeof(T) == 4) {  // (k_ibp_ztile is float32 only: ztile::eligible)
         if (z) {
-            mosaic::Common<float> c;
-            rc = mosaic::common_prep<float>(c, false, lr, B, N, h, w, sh, k, kh, kw, H, W, f, step, ar, st, tr_lo, tr_hi);
+            mosaic::Common<float> cm;
+            rc = mosaic::common_prep<float>(cm, false, c, ar, tr_lo, tr_hi);
             if (rc == SRX_OK)
-                rc = ztile::setup(p->zs, c, hr_init, tr_lo, tr_hi, ar, st);
+                rc = ztile::setup(p->zs, cm, c.hr_init, tr_lo, tr_hi, ar, c.st);
             p->z = true, p->path = "ztile";
         }
     }
     if (!z) {
-        T *hr = carve_plan_state<T>(ar, B, H, W);
+        T *hr = carve_plan_state<T>(ar, B, s.H, s.W);
         if (!ar.ok)
             rc = SRX_E_WORKSPACE;
-        else if (hipMemcpyAsync(hr, hr_init, (size_t)B * H * W * sizeof(T), hipMemcpyDeviceToDevice, st) != hipSuccess)
+        else if (hipMemcpyAsync(hr, c.hr_init, (size_t)B * s.H * s.W * sizeof(T), hipMemcpyDeviceToDevice, c.st) != hipSuccess)
             rc = SRX_E_HIP;
-        p->hr = hr, p->ws_rest = ar.ok ? (char *)ws + ar.off : nullptr, p->wsb_rest = ar.ok ? wsb - ar.off : 0, p->path = "call per run";
+        p->hr = hr, p->ws_rest = ar.ok ? (char *)c.ws + ar.off : nullptr, p->wsb_rest = ar.ok ? c.wsb - ar.off : 0, p->path = "call per run";
     }
     if (rc != SRX_OK) {
         delete p;
@@ -631,6 +652,13 @@ static int plan_create(const T *lr, int B, int N, int h, int w, const double *sh
     }
     *out = p;
     return SRX_OK;
+}
+
+// a run off the hoisted-table path: a whole srx_ibp call from the state plane onto itself
+template <typename T> static int plan_run(const srx_plan_s *p, int n_iter, double *errors, hipStream_t st)
+{
+    T *const hr = (T *)p->hr;
+    return ibp_dispatch(IbpCall<T>{p->s, (const T *)p->lr, p->B, hr, n_iter, p->step, hr, errors, p->ws_rest, p->wsb_rest, st});
 }
 
 template <typename T> __global__ void __launch_bounds__(256) k_rows_copy(const T *__restrict__ src, T *__restrict__ dst, int H, int W, int y0, int rows, int to_plane)
@@ -647,7 +675,7 @@ template <typename T> __global__ void __launch_bounds__(256) k_rows_copy(const T
 
 template <typename T> static int plan_rows(srx_plan_s *p, int y0, int y1, T *buf, bool set, hipStream_t st)
 {
-    if (!p || !buf || p->eb != (int)sizeof(T) || y0 < 0 || y1 > p->H || y0 >= y1)
+    if (!p || !buf || p->s.eb != (int)sizeof(T) || y0 < 0 || y1 > p->s.H || y0 >= y1)
         return SRX_E_INVALID;
     const int rows = y1 - y0;
     if (rows > 65535)
@@ -658,7 +686,7 @@ template <typename T> static int plan_rows(srx_plan_s *p, int y0, int y1, T *buf
         return SRX_E_INVALID;
     }
     T *hr = (T *)p->hr;
-    hipLaunchKernelGGL(k_rows_copy<T>, dim3(cdiv(p->W, 256), rows, p->B), dim3(256), 0, st, set ? (const T *)buf : (const T *)hr, set ? hr : buf, p->H, p->W, y0, rows,
+    hipLaunchKernelGGL(k_rows_copy<T>, dim3(cdiv(p->s.W, 256), rows, p->B), dim3(256), 0, st, set ? (const T *)buf : (const T *)hr, set ? hr : buf, p->s.H, p->s.W, y0, rows,
                        set ? 1 : 0);
     SRX_CHECK_LAUNCH();
     return SRX_OK;
@@ -669,24 +697,25 @@ template <typename T> static int plan_rows(srx_plan_s *p, int y0, int y1, T *buf
 // ---------------------------------------------------------------------------------------
 extern "C" {
 
-size_t srx_ibp_plan_workspace_bytes(int eb, int B, int N, int h, int w, int H, int W, int f, unsigned flags)
-{
-    const size_t b1 = B > 0 ? B : 1;
-    return measured([&](Arena &m) { eb == 8 ? (void)carve_plan_state<double>(m, b1, H, W) : (void)carve_plan_state<float>(m, b1, H, W); }) +
-           srx_ibp_workspace_bytes(eb, B, N, h, w, H, W, f, flags);
-}
+// The records of a call, from the arguments of its entry point under the names srx.h gives them.  An entry point builds its record and
+// hands it on; nothing else happens in it.
+#define SRX_IBP_SHAPE(EB) IbpShape{(EB), N, h, w, H, W, f}
+#define SRX_IBP_SPEC(EB) IbpSpec{SRX_IBP_SHAPE(EB), sh, k, kh, kw, flags}
+#define SRX_IBP_CALL(T, S, N_ITER, HR, ERRORS) IbpCall<T, S>{SRX_IBP_SPEC((int)sizeof(T)), lr, B, hr_init, (N_ITER), step, (HR), (ERRORS), ws, wsb, hs(s)}
+#define SRX_SAA_SHAPE(EB) SaaShape{(EB), N, h, w, f}
+#define SRX_SAA_CALL(T, S) SaaCall<T, S>{SaaSpec{SRX_SAA_SHAPE((int)sizeof(T)), sh, flags}, lr, B, out, ws, wsb, hs(s)}
+
+size_t srx_ibp_plan_workspace_bytes(int eb, int B, int N, int h, int w, int H, int W, int f, unsigned flags) { return plan_bound(SRX_IBP_SHAPE(eb), B, flags); }
 
 int srx_ibp_plan_create_f32(const float *lr, int B, int N, int h, int w, const double *sh, const double *k, int kh, int kw, const float *hr_init, int H,
                             int W, int f, double step, int tr_lo, int tr_hi, void *ws, size_t wsb, srx_stream_t s, unsigned flags, srx_plan_t **plan)
 {
-    CallFlags cf(flags);
-    return plan_create<float>(lr, B, N, h, w, sh, k, kh, kw, hr_init, H, W, f, step, tr_lo, tr_hi, ws, wsb, hs(s), flags, plan);
+    return plan_create(SRX_IBP_CALL(float, float, 0, nullptr, nullptr), tr_lo, tr_hi, plan);
 }
 int srx_ibp_plan_create_f64(const double *lr, int B, int N, int h, int w, const double *sh, const double *k, int kh, int kw, const double *hr_init, int H,
                             int W, int f, double step, int tr_lo, int tr_hi, void *ws, size_t wsb, srx_stream_t s, unsigned flags, srx_plan_t **plan)
 {
-    CallFlags cf(flags);
-    return plan_create<double>(lr, B, N, h, w, sh, k, kh, kw, hr_init, H, W, f, step, tr_lo, tr_hi, ws, wsb, hs(s), flags, plan);
+    return plan_create(SRX_IBP_CALL(double, double, 0, nullptr, nullptr), tr_lo, tr_hi, plan);
 }
 
 int srx_ibp_plan_run(srx_plan_t *p, int n_iter, double *errors, srx_stream_t s)
@@ -695,16 +724,11 @@ int srx_ibp_plan_run(srx_plan_t *p, int n_iter, double *errors, srx_stream_t s)
         return SRX_E_INVALID;
     if (n_iter == 0)
         return SRX_OK;
-    CallFlags cf(p->flags);
     if (p->z)
         return ztile::run(p->zs, n_iter, errors, hs(s));
-    if (errors && (p->tr_lo != 0 || p->tr_hi != p->H))
+    if (errors && (p->tr_lo != 0 || p->tr_hi != p->s.H))
         return SRX_E_UNSUPPORTED;  // a row range for the trace exists where the tables are hoisted (the float32 integer-shift frame kernel)
-    if (p->eb == 4)
-        return ibp_dispatch<float>((const float *)p->lr, p->B, p->N, p->h, p->w, p->sh, p->k, p->kh, p->kw, (const float *)p->hr, p->H, p->W, p->f, n_iter,
-                                   p->step, (float *)p->hr, errors, p->ws_rest, p->wsb_rest, hs(s), p->flags);
-    return ibp_dispatch<double>((const double *)p->lr, p->B, p->N, p->h, p->w, p->sh, p->k, p->kh, p->kw, (const double *)p->hr, p->H, p->W, p->f, n_iter,
-                                p->step, (double *)p->hr, errors, p->ws_rest, p->wsb_rest, hs(s), p->flags);
+    return p->s.eb == 4 ? plan_run<float>(p, n_iter, errors, hs(s)) : plan_run<double>(p, n_iter, errors, hs(s));
 }
 
 int srx_ibp_plan_get_rows_f32(srx_plan_t *p, int row_lo, int row_hi, float *dst, srx_stream_t s) { return plan_rows<float>(p, row_lo, row_hi, dst, false, hs(s)); }
@@ -794,33 +818,15 @@ size_t srx_zoom_workspace_bytes(int eb, int B, int h, int w, int f) { return zoo
 size_t srx_forward_workspace_bytes(int eb, int B, int H, int W) { return forward_ws(eb, B, H, W); }
 size_t srx_backproject_workspace_bytes(int eb, int B, int H, int W) { return backproject_ws(eb, B, H, W); }
 
-size_t srx_saa_workspace_bytes(int eb, int B, int N, int h, int w, int f)
-{
-    B = saa_chunk_items(B, N);
-    size_t a = saa_ws_composed(eb, B, N, h, w, f), b = fused::saa_ws(eb, B, N, h, w, f);
-    const size_t c = mosaic::saa_ws(eb, B, N, h, w, f);
-    a = a > b ? a : b;
-    return a > c ? a : c;
-}
+size_t srx_saa_workspace_bytes(int eb, int B, int N, int h, int w, int f) { return saa_bound(SRX_SAA_SHAPE(eb), B); }
 
 /* float figure + one staged copy (T) of a chunk's frames, whatever the route: the query has no shift table to tell the routes apart */
 size_t srx_saa_u8lr_workspace_bytes(int eb, int B, int N, int h, int w, int f)
 {
-    return srx_saa_workspace_bytes(eb, B, N, h, w, f) + u8_stage_bytes(eb, saa_chunk_items(B, N), N, h, w);
+    return saa_bound(SRX_SAA_SHAPE(eb), B) + u8_stage_bytes(SRX_SAA_SHAPE(eb), saa_chunk_items(B, N));
 }
 
-size_t srx_ibp_workspace_bytes(int eb, int B, int N, int h, int w, int H, int W, int f, unsigned flags)
-{
-    B = ibp_chunk_items(B);
-    size_t a = ibp_ws_composed(eb, B, N, h, w, H, W, f), b = fused::ibp_ws(eb, B, N, h, w, H, W, f);
-    const size_t c = mosaic::ibp_ws(eb, B, N, H, W);
-    b = b > c ? b : c;
-    if (flags & SRX_FLAG_FUSED)
-        return b;
-    if (flags & SRX_FLAG_COMPOSED)
-        return a;
-    return a > b ? a : b;
-}
+size_t srx_ibp_workspace_bytes(int eb, int B, int N, int h, int w, int H, int W, int f, unsigned flags) { return ibp_bound(SRX_IBP_SHAPE(eb), B, flags); }
 
 /* the same with the shift table and the PSF at hand: what THIS call will carve (a batch of 256 x 256 patches at a common fraction
  * needs no tile planes, a delta = 0 frame no patch tables ...), never more than srx_ibp_workspace_bytes */
@@ -828,64 +834,60 @@ size_t srx_ibp_workspace_bytes_for(int eb, int B, int N, int h, int w, int H, in
                                    int kw, unsigned flags)
 {
     if (!sh || !k || N <= 0 || N > SRX_MAX_FRAMES)
-        return srx_ibp_workspace_bytes(eb, B, N, h, w, H, W, f, flags);
-    CallFlags cf(flags);
-    return ibp_need(route_ibp(eb, N, h, w, H, W, f, sh, k, kh, kw, flags), eb, B, N, h, w, H, W, f, flags);
+        return ibp_bound(SRX_IBP_SHAPE(eb), B, flags);
+    const IbpSpec spec = SRX_IBP_SPEC(eb);
+    return ibp_need(route_ibp(spec), spec, B);
 }
 
 /* uint8 frames: the float figure on a mosaic-family route (the kernels read the bytes; nothing is staged), plus the staged chunk elsewhere */
 size_t srx_ibp_u8lr_workspace_bytes(int eb, int B, int N, int h, int w, int H, int W, int f, unsigned flags)
 {
-    return srx_ibp_workspace_bytes(eb, B, N, h, w, H, W, f, flags) +
-           u8_stage_bytes(eb, std::max(ibp_chunk_items(B), 1), N, h, w);
+    return ibp_bound(SRX_IBP_SHAPE(eb), B, flags) + u8_stage_bytes(SRX_IBP_SHAPE(eb), std::max(ibp_chunk_items(B), 1));
 }
 size_t srx_ibp_u8lr_workspace_bytes_for(int eb, int B, int N, int h, int w, int H, int W, int f, const double *sh, const double *k, int kh,
                                         int kw, unsigned flags)
 {
     if (!sh || !k || N <= 0 || N > SRX_MAX_FRAMES)
         return srx_ibp_u8lr_workspace_bytes(eb, B, N, h, w, H, W, f, flags);
-    CallFlags cf(flags);
-    const Route r = route_ibp(eb, N, h, w, H, W, f, sh, k, kh, kw, flags);
-    const size_t need = ibp_need(r, eb, B, N, h, w, H, W, f, flags);
+    const IbpSpec spec = SRX_IBP_SPEC(eb);
+    const Route r = route_ibp(spec);
+    const size_t need = ibp_need(r, spec, B);
     if (r.status == SRX_OK && r.path == PATH_MOSAIC)
         return need;
-    return need + u8_stage_bytes(eb, std::max(ibp_chunk_items(B), 1), N, h, w);
+    return need + u8_stage_bytes(spec, std::max(ibp_chunk_items(B), 1));
 }
 
-size_t srx_saa_items_workspace_bytes(int eb, int B, int N, int h, int w, int f) { return items::saa_ws_bound(eb, B, N, h, w, f); }
+size_t srx_saa_items_workspace_bytes(int eb, int B, int N, int h, int w, int f) { return items::saa_ws_bound(SRX_SAA_SHAPE(eb), B); }
 size_t srx_ibp_items_workspace_bytes(int eb, int B, int N, int h, int w, int H, int W, int f, unsigned flags)
 {
-    return items::ibp_ws_bound(eb, B, N, h, w, H, W, f, flags);
+    return items::ibp_ws_bound(SRX_IBP_SHAPE(eb), B, flags);
 }
 /* what THIS call carves: the largest run's need (a per-item "btile" run: its route's plus the tables of its items) */
 size_t srx_ibp_items_workspace_bytes_for(int eb, int B, int N, int h, int w, int H, int W, int f, const double *sh, const double *k, int kh,
                                          int kw, unsigned flags)
 {
     if (!sh || !k || N <= 0 || N > SRX_MAX_FRAMES || B <= 0)
-        return srx_ibp_items_workspace_bytes(eb, B, N, h, w, H, W, f, flags);
-    CallFlags cf(flags);
-    const items::Plan p = items::plan_ibp(eb, B, N, h, w, H, W, f, sh, k, kh, kw, flags);
-    return p.status == SRX_OK ? p.need : srx_ibp_items_workspace_bytes(eb, B, N, h, w, H, W, f, flags);
+        return items::ibp_ws_bound(SRX_IBP_SHAPE(eb), B, flags);
+    const items::Plan p = items::plan_ibp(SRX_IBP_SPEC(eb), B);
+    return p.status == SRX_OK ? p.need : items::ibp_ws_bound(SRX_IBP_SHAPE(eb), B, flags);
 }
 
+/* (true / 1 / 1 in the checks: the device pointers, the batch and the iterations that a query does not have) */
 const char *srx_ibp_path_for(int eb, int N, int h, int w, int H, int W, int f, const double *sh, const double *k, int kh, int kw, unsigned flags)
 {
-    int dummy = 0;  // (stands for the device pointers: only their presence is checked)
-    if ((eb != 4 && eb != 8) || !basic_ibp_args_ok(&dummy, 1, N, h, w, sh, k, kh, kw, &dummy, H, W, f, 1, &dummy) || N > SRX_MAX_FRAMES ||
-        kh * kw > SRX_MAX_KERNEL_TAPS || !plane_fits((size_t)eb, N, h, w, H, W))
+    const IbpSpec spec = SRX_IBP_SPEC(eb);
+    if ((eb != 4 && eb != 8) || ibp_check(spec, 1, 1, true) != SRX_OK)
         return "none";
-    CallFlags cf(flags);
-    const Route r = route_ibp(eb, N, h, w, H, W, f, sh, k, kh, kw, flags);
+    const Route r = route_ibp(spec);
     return r.status == SRX_OK ? r.name : "none";
 }
 
 const char *srx_saa_path_for(int eb, int N, int h, int w, int f, const double *sh, unsigned flags)
 {
-    int dummy = 0;  // (stands for the device pointers: only their presence is checked)
-    if ((eb != 4 && eb != 8) || saa_check((size_t)eb, &dummy, 1, N, h, w, sh, f, &dummy) != SRX_OK)
+    const SaaSpec spec{SRX_SAA_SHAPE(eb), sh, flags};
+    if ((eb != 4 && eb != 8) || saa_check(spec, 1, true) != SRX_OK)
         return "none";
-    CallFlags cf(flags);
-    const Route r = route_saa(N, h, w, f, sh, flags);
+    const Route r = route_saa(spec);
     return r.status == SRX_OK ? r.name : "none";
 }
 
@@ -1030,44 +1032,35 @@ int srx_psf_estimate_f64(const double *frames, int N, int H, int W, int halfwidt
     int srx_saa_##SFX(const T *lr, int B, int N, int h, int w, const double *sh, int f, T *out, void *ws, size_t wsb,   \
                       srx_stream_t s, unsigned flags)                                                                  \
     {                                                                                                                  \
-        CallFlags cf(flags);                                                                                           \
-        return saa_dispatch<T>(lr, B, N, h, w, sh, f, out, ws, wsb, hs(s), flags);                                     \
+        return saa_dispatch(SRX_SAA_CALL(T, T));                                                                       \
     }                                                                                                                  \
     int srx_ibp_##SFX(const T *lr, int B, int N, int h, int w, const double *sh, const double *k, int kh, int kw,       \
                       const T *hr_init, int H, int W, int f, int n_iter, double step, T *hr_out, double *errors,       \
                       void *ws, size_t wsb, srx_stream_t s, unsigned flags)                                            \
     {                                                                                                                  \
-        CallFlags cf(flags);                                                                                           \
-        return ibp_dispatch<T>(lr, B, N, h, w, sh, k, kh, kw, hr_init, H, W, f, n_iter, step, hr_out, errors, ws, wsb, \
-                               hs(s), flags);                                                                          \
+        return ibp_dispatch(SRX_IBP_CALL(T, T, n_iter, hr_out, errors));                                               \
     }                                                                                                                  \
     int srx_saa_items_##SFX(const T *lr, int B, int N, int h, int w, const double *sh, int f, T *out, void *ws,         \
                             size_t wsb, srx_stream_t s, unsigned flags)                                                \
     {                                                                                                                  \
-        CallFlags cf(flags);                                                                                           \
-        return items::saa_dispatch_items<T>(lr, B, N, h, w, sh, f, out, ws, wsb, hs(s), flags);                        \
+        return items::saa_dispatch_items(SRX_SAA_CALL(T, T));                                                          \
     }                                                                                                                  \
     int srx_ibp_items_##SFX(const T *lr, int B, int N, int h, int w, const double *sh, const double *k, int kh, int kw, \
                             const T *hr_init, int H, int W, int f, int n_iter, double step, T *hr_out, double *errors, \
                             void *ws, size_t wsb, srx_stream_t s, unsigned flags)                                      \
     {                                                                                                                  \
-        CallFlags cf(flags);                                                                                           \
-        return items::ibp_dispatch_items<T>(lr, B, N, h, w, sh, k, kh, kw, hr_init, H, W, f, n_iter, step, hr_out,     \
-                                            errors, ws, wsb, hs(s), flags);                                            \
+        return items::ibp_dispatch_items(SRX_IBP_CALL(T, T, n_iter, hr_out, errors));                                  \
     }                                                                                                                  \
     int srx_saa_u8lr_##SFX(const uint8_t *lr, int B, int N, int h, int w, const double *sh, int f, T *out, void *ws,    \
                            size_t wsb, srx_stream_t s, unsigned flags)                                                 \
     {                                                                                                                  \
-        CallFlags cf(flags);                                                                                           \
-        return saa_dispatch<T, uint8_t>(lr, B, N, h, w, sh, f, out, ws, wsb, hs(s), flags);                            \
+        return saa_dispatch(SRX_SAA_CALL(T, uint8_t));                                                                 \
     }                                                                                                                  \
     int srx_ibp_u8lr_##SFX(const uint8_t *lr, int B, int N, int h, int w, const double *sh, const double *k, int kh,   \
                            int kw, const T *hr_init, int H, int W, int f, int n_iter, double step, T *hr_out,          \
                            double *errors, void *ws, size_t wsb, srx_stream_t s, unsigned flags)                       \
     {                                                                                                                  \
-        CallFlags cf(flags);                                                                                           \
-        return ibp_dispatch<T, uint8_t>(lr, B, N, h, w, sh, k, kh, kw, hr_init, H, W, f, n_iter, step, hr_out, errors, \
-                                        ws, wsb, hs(s), flags);                                                        \
+        return ibp_dispatch(SRX_IBP_CALL(T, uint8_t, n_iter, hr_out, errors));                                         \
     }                                                                                                                  \
     int srx_decimate_##SFX(const T *in, int B, int H, int W, int f, int py, int px, T *out, srx_stream_t s)             \
     {                                                                                                                  \

@@ -449,17 +449,18 @@ __global__ void __launch_bounds__(NBY *NBX * 64, 2)
 }
 
 // ---- host ---------------------------------------------------------------------------------------------------------------
-static inline bool shape_admits(int elem_bytes, int H, int W) { return elem_bytes == 4 && H >= 32 && W >= 32; }
+static inline bool shape_admits(const IbpShape &s) { return s.eb == 4 && s.H >= 32 && s.W >= 32; }
 
-static inline bool eligible(int elem_bytes, int N, int H, int W, const double *sh, const double *k, int kh, int kw, int f)
+static inline bool eligible(const IbpSpec &s)
 {
-    if (!shape_admits(elem_bytes, H, W) || f < 2 || (size_t)(H + 32) * (W + 32) >= (1u << 28) || (call_flags() & SRX_FLAG_TILES))
+    const int f = s.f;
+    if (!shape_admits(s) || f < 2 || (size_t)(s.H + 32) * (s.W + 32) >= (1u << 28) || (s.flags & SRX_FLAG_TILES))
         return false;
     mosaic::AxisPlan py, px;
-    if (!mosaic::plan_axis(N, sh, 0, f, py) || !mosaic::plan_axis(N, sh, 1, f, px))
+    if (!mosaic::plan_axis(s.N, s.sh, 0, f, py) || !mosaic::plan_axis(s.N, s.sh, 1, f, px))
         return false;
     fused::Kernel7<float> kc;
-    fused::make_kernel7<float>(k, kh, kw, false, kc);
+    fused::make_kernel7<float>(s.k, s.kh, s.kw, false, kc, s.flags);
     return kc.separable != 0;
 }
 
@@ -480,10 +481,10 @@ static Carved carve(Arena &ar, const Dims &d)
     return {ar.take<float>(d.B * ((d.W + 3) / 4) * d.H * 4), ar.take<float>(d.B * Qn * Wg * 4), ar.take<float>(d.B * Qn * Wg * 8),
             ar.take<float>(d.B * (Hp + 4) * (Wp + 4)), ar.take<double>(d.B * ((size_t)windows_y((int)Hp) * windows_x((int)Wp) + d.nnear))};
 }
-static inline size_t tabs_bytes(int, int B, int, int H, int W)
+static inline size_t tabs_bytes(const IbpShape &s, int B)
 {
-    const size_t Hg = H + 2 * SRX_NPAD + 3, Wg = W + 2 * SRX_NPAD + 3;
-    return measured([&](Arena &m) { carve(m, Dims{(size_t)B, (size_t)H, (size_t)W, (size_t)cdiv((int)mosaic::near_bound(Hg, Wg), 256)}); });
+    const size_t Hg = s.H + 2 * SRX_NPAD + 3, Wg = s.W + 2 * SRX_NPAD + 3;
+    return measured([&](Arena &m) { carve(m, Dims{(size_t)B, (size_t)s.H, (size_t)s.W, (size_t)cdiv((int)mosaic::near_bound(Hg, Wg), 256)}); });
 }
 
 static int iterate(const mosaic::Common<float> &c, const float *hr_init, float *hr, int n_iter, double *errors, Arena &ar, hipStream_t st)

@@ -1047,16 +1047,16 @@ __global__ void __launch_bounds__(NBY *NBX * 64, SRX_BT_MINB)
 }
 
 // ---- host ---------------------------------------------------------------------------------------------------------------
-static inline bool eligible(int elem_bytes, int N, int h, int w, const double *sh, const double *k, int kh, int kw, int H, int W, int f)
+static inline bool eligible(const IbpSpec &s)
 {
-    if (elem_bytes != 4 || f != 2 || N > MAXF || H != 2 * h || W != 2 * w || H < 32 || W < 32 || (size_t)H * W >= (1u << 28) ||
-        (size_t)N * h * w >= (1u << 28))
+    if (s.eb != 4 || s.f != 2 || s.N > MAXF || s.H != 2 * s.h || s.W != 2 * s.w || s.H < 32 || s.W < 32 || (size_t)s.H * s.W >= (1u << 28) ||
+        (size_t)s.N * s.h * s.w >= (1u << 28))
         return false;
-    if (call_flags() & (SRX_FLAG_TILES | SRX_FLAG_DIAG_V1))
+    if (s.flags & (SRX_FLAG_TILES | SRX_FLAG_DIAG_V1))
         return false;
-    if (!fused::ibp_eligible(N, h, w, sh, kh, kw, H, W, f))
+    if (!fused::ibp_eligible(s))
         return false;
-    return kh <= 7 && kw <= 7;  // a rank-1 PSF as 7 + 7 taps, any other 7 x 7 along registers and lanes (blur2d_cross)
+    return s.kh <= 7 && s.kw <= 7;  // a rank-1 PSF as 7 + 7 taps, any other 7 x 7 along registers and lanes (blur2d_cross)
 }
 
 // one table per item: N records behind the header, item after item
@@ -1084,9 +1084,9 @@ static Carved carve(Arena &ar, const Dims &d)
     return {ar.take<float>(d.B * d.N * d.h * d.w), ar.take<double>(d.B * d.nwin), ar.take<float>(d.B * ((d.H + 3) / 4) * d.W * 4), carve_table(ar, d)};
 }
 // a call on one shared table ...
-static inline size_t ws_bytes(int B, int N, int h, int w, int H, int W)
+static inline size_t ws_bytes(const IbpShape &s, int B)
 {
-    return measured([&](Arena &m) { carve(m, Dims{(size_t)B, (size_t)N, (size_t)h, (size_t)w, (size_t)H, (size_t)W, windows(H, W), false}); });
+    return measured([&](Arena &m) { carve(m, Dims{(size_t)B, (size_t)s.N, (size_t)s.h, (size_t)s.w, (size_t)s.H, (size_t)s.W, windows(s.H, s.W), false}); });
 }
 // ... and what srx_items.hpp's queries add to it for a run with one table per item: those tables (more than the run carves, which
 // takes them in the place of the shared one)
@@ -1131,16 +1131,20 @@ static inline void make_frames(const double *sh, int N, BFrame *fr, int nfr, int
 // per_item: sh is [B][N][2], one table per item.  The host builds every item's records with make_frames (the weights an item gets are the
 // ones it gets alone by construction) and ceil(B * tab_stride(N) / PARAM_WORDS) launches of k_param_words carry them to the device; the
 // workspace holds items_tab_bytes(B, N) more.
-template <int NBY, int NBX>
-static int ibp_t(const float *lr, int B, int N, int h, int w, const double *sh, bool per_item, const double *k, int kh, int kw,
-                 const float *hr_init, int H, int W, int n_iter, double step, float *hr, double *errors, void *ws, size_t wsb, hipStream_t st)
+template <int NBY, int NBX> static int ibp_t(const IbpCall<float> &c, bool per_item)
 {
+    const int B = c.B, N = c.s.N, h = c.s.h, w = c.s.w, H = c.s.H, W = c.s.W, n_iter = c.n_iter;
+    const double *const sh = c.s.sh, step = c.step;
+    const float *const lr = c.lr, *const hr_init = c.hr_init;
+    float *const hr = c.hr;
+    double *const errors = c.errors;
+    const hipStream_t st = c.st;
     const int Hp = H + 2 * SRX_NPAD, Wp = W + 2 * SRX_NPAD;
     BArgs A;
     A.N = N, A.h = h, A.w = w, A.H = H, A.W = W;
     A.nwy = cdiv(Hp, Geo<NBY, NBX>::OWNY), A.nwx = cdiv(Wp, Geo<NBY, NBX>::OWNX);
     A.sn = (float)step / (float)N;
-    Arena ar(ws, wsb);
+    Arena ar(c.ws, c.wsb);
     const int H4 = (H + 3) / 4;
     const int frstride = per_item ? tab_stride(N) : 0;
     const auto [err, epart, S, frtab] =
@@ -1151,8 +1155,8 @@ static int ibp_t(const float *lr, int B, int N, int h, int w, const double *sh, 
         return SRX_E_UNSUPPORTED;
     const double kq = -6.0 * blk::ZD;
     fused::Kernel7<float> kc, kt;
-    fused::make_kernel7<float>(k, kh, kw, false, kc);
-    fused::make_kernel7<float>(k, kh, kw, true, kt);
+    fused::make_kernel7<float>(c.s.k, c.s.kh, c.s.kw, false, kc, c.s.flags);
+    fused::make_kernel7<float>(c.s.k, c.s.kh, c.s.kw, true, kt, c.s.flags);
     A.kby[7] = A.kbx[7] = A.kty[7] = A.ktx[7] = 0.f;
     for (int i = 0; i < 7; i++) {
         A.kby[i] = (float)(kq * (double)kc.cy[i]), A.kbx[i] = (float)(kq * (double)kc.cx[i]);
@@ -1230,18 +1234,10 @@ static int ibp_t(const float *lr, int B, int N, int h, int w, const double *sh, 
     return SRX_OK;
 }
 
-static int ibp(const float *lr, int B, int N, int h, int w, const double *sh, const double *k, int kh, int kw, const float *hr_init, int H,
-               int W, int n_iter, double step, float *hr, double *errors, void *ws, size_t wsb, hipStream_t st)
-{
-    return ibp_t<SRX_BT_NBY, SRX_BT_NBX>(lr, B, N, h, w, sh, false, k, kh, kw, hr_init, H, W, n_iter, step, hr, errors, ws, wsb, st);
-}
+static int ibp(const IbpCall<float> &c) { return ibp_t<SRX_BT_NBY, SRX_BT_NBX>(c, false); }
 
 // one table per item: sh is [B][N][2], every item routed to "btile" (srx_items.hpp)
-static int ibp_items(const float *lr, int B, int N, int h, int w, const double *sh, const double *k, int kh, int kw, const float *hr_init, int H,
-                     int W, int n_iter, double step, float *hr, double *errors, void *ws, size_t wsb, hipStream_t st)
-{
-    return ibp_t<SRX_BT_NBY, SRX_BT_NBX>(lr, B, N, h, w, sh, true, k, kh, kw, hr_init, H, W, n_iter, step, hr, errors, ws, wsb, st);
-}
+static int ibp_items(const IbpCall<float> &c) { return ibp_t<SRX_BT_NBY, SRX_BT_NBX>(c, true); }
 
 }  // namespace btile
 }  // namespace srx

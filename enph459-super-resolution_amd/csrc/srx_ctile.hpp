@@ -64,20 +64,21 @@ template <int NR> struct Lds {
                          LDS_T = OFF_ZERO + 4;
 };
 
-static inline bool shape_admits(int, int H, int W) { return H >= 128 && W >= 128; }
+static inline bool shape_admits(const IbpShape &s) { return s.H >= 128 && s.W >= 128; }
 
-static inline bool eligible(int elem_bytes, int N, int H, int W, const double *sh, const double *k, int kh, int kw, int f)
+static inline bool eligible(const IbpSpec &s)
 {
+    const int f = s.f;
     // float64 by default; float32 only on request (SRX_FLAG_DIAG_COLUMN_TILES: the A/B partner of k_ibp_ztile)
-    if (elem_bytes == 4 ? !(call_flags() & SRX_FLAG_DIAG_COLUMN_TILES) : elem_bytes != 8)
+    if (s.eb == 4 ? !(s.flags & SRX_FLAG_DIAG_COLUMN_TILES) : s.eb != 8)
         return false;
-    if (!shape_admits(elem_bytes, H, W) || f < 2 || (call_flags() & SRX_FLAG_TILES))
+    if (!shape_admits(s) || f < 2 || (s.flags & SRX_FLAG_TILES))
         return false;
     mosaic::AxisPlan py, px;
-    if (!mosaic::plan_axis(N, sh, 0, f, py) || !mosaic::plan_axis(N, sh, 1, f, px))
+    if (!mosaic::plan_axis(s.N, s.sh, 0, f, py) || !mosaic::plan_axis(s.N, s.sh, 1, f, px))
         return false;
     fused::Kernel7<double> kc;
-    fused::make_kernel7<double>(k, kh, kw, false, kc);
+    fused::make_kernel7<double>(s.k, s.kh, s.kw, false, kc, s.flags);
     return kc.separable && ztile::axis_ok(py, f) && ztile::axis_ok(px, f);
 }
 
@@ -521,10 +522,10 @@ template <typename T> static Carved<T> carve(Arena &ar, const ztile::Dims &d)
             ar.take<uint2>(d.B * (d.HP / 4) * d.WP), ar.take<int>(d.B), ar.take<T>(32), ar.take<unsigned>(d.NT), ar.take<uint4>(d.ngrp * d.NT),
             ar.take<T2<T>>(d.B * d.NT), ar.take<double>(d.B * d.ntiles), ar.take<double>(d.B * d.ntiles)};
 }
-static inline size_t tabs_bytes(int eb, int B, int N, int H, int W)
+static inline size_t tabs_bytes(const IbpShape &s, int B)
 {
-    const ztile::Dims d = ztile::dims_bound(B, N, H, W, rows_for(eb) - 2 * HALO);
-    return measured([&](Arena &m) { eb == 8 ? (void)carve<double>(m, d) : (void)carve<float>(m, d); });
+    const ztile::Dims d = ztile::dims_bound(B, s.N, s.H, s.W, rows_for(s.eb) - 2 * HALO);
+    return measured([&](Arena &m) { s.eb == 8 ? (void)carve<double>(m, d) : (void)carve<float>(m, d); });
 }
 
 template <typename T>

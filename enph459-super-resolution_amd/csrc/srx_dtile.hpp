@@ -124,7 +124,8 @@ struct Plan {
     AxisTiles ty, tx;
 };
 
-static inline bool plan(int H, int W, Plan &pl)
+// flags: the call's (SRX_FLAG_DIAG_WIDE_WINDOWS); eligible() and iterate() pass the same, the spec's and the prepared call's copy of it
+static inline bool plan(int H, int W, unsigned flags, Plan &pl)
 {
     // 4 x 3 waves (256 x 192 windows, 128 x 192 owned in the interior) unless the caller asks for the 16-wave shape.  Round 3 chose between
     // the two by a cost model of ONE frame (a round of 12-wave windows 37 us, of 16-wave windows 55 us on 3072 x 4096; eight frames 592
@@ -133,7 +134,7 @@ static inline bool plan(int H, int W, Plan &pl)
     // fixes; 72 / 246 before), the 12-wave one has 168 and is clean, and every width the wide shape takes the narrow one takes too.  The
     // plan depends on the shape only, so a batch gives every item the bits it gets alone.
     Plan p;
-    p.nsx = (call_flags() & SRX_FLAG_DIAG_WIDE_WINDOWS) ? 4 : 3;
+    p.nsx = (flags & SRX_FLAG_DIAG_WIDE_WINDOWS) ? 4 : 3;
     if (!plan_axis_tiles(H, RY, ALIGN_Y, p.ty) || !plan_axis_tiles(W, 64 * p.nsx, ALIGN_X, p.tx))
         return false;
     if ((long)p.ty.n * p.tx.n > MAX_TILES)
@@ -144,22 +145,23 @@ static inline bool plan(int H, int W, Plan &pl)
 
 // the superset of every shape plan() admits whatever the call flags say: what the shape-only workspace bound tests (256-row windows of
 // 192 (4 x 3 waves) or 256 columns, origins on row quads / 16-column groups)
-static inline bool shape_admits(int elem_bytes, int H, int W) { return elem_bytes == 4 && H >= RY && W >= 64 * 3 && H % ALIGN_Y == 0 && W % ALIGN_X == 0; }
+static inline bool shape_admits(const IbpShape &s) { return s.eb == 4 && s.H >= RY && s.W >= 64 * 3 && s.H % ALIGN_Y == 0 && s.W % ALIGN_X == 0; }
 
-static inline bool eligible(int elem_bytes, int N, int H, int W, const double *sh, const double *k, int kh, int kw, int f)
+static inline bool eligible(const IbpSpec &s)
 {
-    if (!shape_admits(elem_bytes, H, W) || f < 2 || (H == patch::PN && W == patch::PN && !(call_flags() & SRX_FLAG_DIAG_WIDE_WINDOWS)) || (call_flags() & SRX_FLAG_TILES))
+    const int f = s.f;
+    if (!shape_admits(s) || f < 2 || (s.H == patch::PN && s.W == patch::PN && !(s.flags & SRX_FLAG_DIAG_WIDE_WINDOWS)) || (s.flags & SRX_FLAG_TILES))
         return false;
     mosaic::AxisPlan py, px;
-    if (!mosaic::plan_axis(N, sh, 0, f, py) || !mosaic::plan_axis(N, sh, 1, f, px))
+    if (!mosaic::plan_axis(s.N, s.sh, 0, f, py) || !mosaic::plan_axis(s.N, s.sh, 1, f, px))
         return false;
     fused::Kernel7<float> kc;
-    fused::make_kernel7<float>(k, kh, kw, false, kc);
+    fused::make_kernel7<float>(s.k, s.kh, s.kw, false, kc, s.flags);
     // (round 4: a PSF that is not rank 1 on the 12-wave windows, srx_patch.hpp's 7 x 7 form -- when its outer ring is zero, as the reference's
     // measured PSF's is: 131 us per iteration on 3072 x 4096 at x4 against the tile kernels' 141; with full 7 x 7 support the windows take 164
     // (53 - 71 spilled registers under the 168-register cap) and the tile kernels keep the call)
     if (!kc.separable) {
-        bool ring0 = !(call_flags() & SRX_FLAG_DIAG_WIDE_WINDOWS);
+        bool ring0 = !(s.flags & SRX_FLAG_DIAG_WIDE_WINDOWS);
         for (int i = 0; i < 7; i++)
             for (int e : {i, 42 + i, 7 * i, 7 * i + 6})
                 ring0 = ring0 && kc.k[e] == 0.f;
@@ -169,7 +171,7 @@ static inline bool eligible(int elem_bytes, int N, int H, int W, const double *s
     if (!(patch::axis_ok(py, f) && patch::axis_ok(px, f)))
         return false;
     Plan pl;
-    if (!plan(H, W, pl))
+    if (!plan(s.H, s.W, s.flags, pl))
         return false;
     const int exy = py.nmax, nby = -py.nmin, exx = px.nmax, nbx = -px.nmin;
     return (exy + nby) * (256 + exx) + (RY - nby) * (exx + nbx) <= NN_PAD;  // the corner window's near band fits its lists
@@ -804,9 +806,9 @@ static Carved carve(Arena &ar, const Dims &d)
             ar.take<unsigned long long>(64 * 4), ar.take<int>(d.ntabs), ar.take<uint2>(d.ntabs * NN_PAD), ar.take<uint2>(d.ngrp * d.ntabs * NN_PAD),
             ar.take<float2>(d.B * d.ntabs * NN_PAD), ar.take<double>(d.B * d.ntiles), ar.take<double>(d.B * d.ntiles), ar.take<float>(112)};
 }
-static inline size_t tabs_bytes(int, int B, int N, int H, int W)
+static inline size_t tabs_bytes(const IbpShape &s, int B)
 {
-    return measured([&](Arena &m) { carve(m, Dims{(size_t)B, (size_t)H, (size_t)W, MAX_TABS, MAX_TILES, ((size_t)N + 3) / 4}); });
+    return measured([&](Arena &m) { carve(m, Dims{(size_t)B, (size_t)s.H, (size_t)s.W, MAX_TABS, MAX_TILES, ((size_t)s.N + 3) / 4}); });
 }
 
 // windows and 0/1 count masks, built on the device from the two axis plans (by-value arguments: no host buffer, no copy)
@@ -863,7 +865,7 @@ static int iterate(const mosaic::Common<float> &c, const float *hr_init, float *
     const double *Vtot = c.Vtot;
     const double scale = c.scale;
     Plan pl;
-    if (!plan(H, W, pl))
+    if (!plan(H, W, c.flags, pl))
         return SRX_E_UNSUPPORTED;
     const int ntiles = pl.ty.n * pl.tx.n, RX = 64 * pl.nsx, ngrp = NS / 4, ntabs = pl.tx.n + pl.ty.n - 1;
     const auto [s0, s1, Mt, Mt8, m8, Ct, aw, tiles, rowm, colm, nnt, nrec, nent, Mn, ep0, ep1, k2] =

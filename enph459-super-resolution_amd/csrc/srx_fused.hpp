@@ -21,6 +21,7 @@
 #include <cmath>
 #include <type_traits>
 
+#include "srx_call.hpp"
 #include "srx_prims.hpp"
 
 namespace srx {
@@ -68,8 +69,8 @@ template <typename T> static void make_tap(double dy, double dx, int bias, Frame
     }
 }
 
-// correlation weights of a kh x kw (odd, <= 7) convolution kernel embedded in 7x7
-template <typename T> static void make_kernel7(const double *k, int kh, int kw, bool flip, Kernel7<T> &out)
+// correlation weights of a kh x kw (odd, <= 7) convolution kernel embedded in 7x7; flags: the call's (SRX_FLAG_DIAG_NO_SEPARABLE is read here)
+template <typename T> static void make_kernel7(const double *k, int kh, int kw, bool flip, Kernel7<T> &out, unsigned flags)
 {
     for (int i = 0; i < 49; i++)
         out.k[i] = 0;
@@ -93,7 +94,7 @@ template <typename T> static void make_kernel7(const double *k, int kh, int kw, 
     for (int i = 0; i < 49; i++)
         if (std::fabs(c[i]) > amax)
             amax = std::fabs(c[i]), um = i / 7, vm = i % 7;
-    bool sep = amax > 0.0 && !(call_flags() & SRX_FLAG_DIAG_NO_SEPARABLE);
+    bool sep = amax > 0.0 && !(flags & SRX_FLAG_DIAG_NO_SEPARABLE);
     double dev = 0.0;
     for (int u = 0; u < 7 && sep; u++)
         for (int v = 0; v < 7; v++)
@@ -140,16 +141,13 @@ static inline bool shifts_ok(int N, const double *sh, int f)
     return true;
 }
 
-static inline bool ibp_eligible(int N, int h, int w, const double *sh, int kh, int kw, int H, int W, int f)
+static inline bool ibp_eligible(const IbpSpec &s)
 {
-    return N <= SRX_MAX_FRAMES && f >= 1 && f <= SRX_FUSED_MAX_FACTOR && H == h * f && W == w * f && (kh & 1) &&
-           (kw & 1) && kh <= 7 && kw <= 7 && H >= 8 && W >= 8 && shifts_ok(N, sh, f);
+    return s.N <= SRX_MAX_FRAMES && s.f >= 1 && s.f <= SRX_FUSED_MAX_FACTOR && s.H == s.h * s.f && s.W == s.w * s.f && (s.kh & 1) &&
+           (s.kw & 1) && s.kh <= 7 && s.kw <= 7 && s.H >= 8 && s.W >= 8 && shifts_ok(s.N, s.sh, s.f);
 }
 
-static inline bool saa_eligible(int N, int h, int w, const double *sh, int f)
-{
-    return N <= SRX_MAX_FRAMES && f >= 1 && h >= 2 && w >= 2 && shifts_ok(N, sh, f);
-}
+static inline bool saa_eligible(const SaaSpec &s) { return s.N <= SRX_MAX_FRAMES && s.f >= 1 && s.h >= 2 && s.w >= 2 && shifts_ok(s.N, s.sh, s.f); }
 
 // =========================================================================================
 // 7x7 correlation on an LDS tile: thread (tx, ty) of a (64, 4) block produces column tx, rows
@@ -1021,11 +1019,11 @@ __global__ void __launch_bounds__(256)
 }
 
 // spline_filter(order 3) of a [B, Hc, Wc] stack in place (through `scratch`): the tile kernel for float planes of at least
-// 64 x 64, the line kernels of srx_prims.hpp otherwise
-template <typename T> static int prefilter2d_fast(T *a, T *scratch, int B, int Hc, int Wc, int mode, hipStream_t st)
+// 64 x 64, the line kernels of srx_prims.hpp otherwise (or on request: flags, the call's, SRX_FLAG_DIAG_NO_PREFILTER_TILE; 0 outside a call)
+template <typename T> static int prefilter2d_fast(T *a, T *scratch, int B, int Hc, int Wc, int mode, hipStream_t st, unsigned flags)
 {
     if constexpr (sizeof(T) == 4) {  // (the double tile would not fit the LDS)
-        if (Hc >= 64 && Wc >= 64 && B <= 65535 && !(call_flags() & SRX_FLAG_DIAG_NO_PREFILTER_TILE)) {
+        if (Hc >= 64 && Wc >= 64 && B <= 65535 && !(flags & SRX_FLAG_DIAG_NO_PREFILTER_TILE)) {
             SRX_LAUNCH(KID_PREFILTER_TILE, k_prefilter_tile<T>, dim3(cdiv(Wc, 64), cdiv(Hc, 64), B), dim3(256), 0, st, a, scratch, Hc, Wc,
                        mode);
             if (hipMemcpyAsync(a, scratch, (size_t)B * Hc * Wc * sizeof(T), hipMemcpyDeviceToDevice, st) != hipSuccess)
@@ -1040,13 +1038,14 @@ template <typename T> static int prefilter2d_fast(T *a, T *scratch, int B, int H
 // is out of place by nature, so this saves prefilter2d_fast's two copies of the stack (in, and back from the scratch plane).
 // S = uint8_t (the camera's samples): the tile kernel reads the bytes itself, and the copy that the in-place forms start with becomes the
 // conversion -- no pass and no plane beyond those of the float call.
-template <typename T, typename S> static int prefilter2d_from(const S *src, T *dst, T *scratch, int B, int Hc, int Wc, int mode, hipStream_t st)
+template <typename T, typename S>
+static int prefilter2d_from(const S *src, T *dst, T *scratch, int B, int Hc, int Wc, int mode, hipStream_t st, unsigned flags)
 {
     constexpr bool u8 = !std::is_same<S, T>::value;
     static_assert(!u8 || std::is_same<S, uint8_t>::value, "LR samples: T or uint8_t");
     const size_t n = (size_t)B * Hc * Wc;
     if constexpr (sizeof(T) == 4) {
-        if (Hc >= 64 && Wc >= 64 && B <= 65535 && !(call_flags() & SRX_FLAG_DIAG_NO_PREFILTER_TILE)) {
+        if (Hc >= 64 && Wc >= 64 && B <= 65535 && !(flags & SRX_FLAG_DIAG_NO_PREFILTER_TILE)) {
             SRX_LAUNCH(KID_PREFILTER_TILE, (k_prefilter_tile<T, S>), dim3(cdiv(Wc, 64), cdiv(Hc, 64), B), dim3(256), 0, st, src, dst, Hc, Wc, mode);
             return SRX_OK;
         }
@@ -1057,7 +1056,7 @@ template <typename T, typename S> static int prefilter2d_from(const S *src, T *d
     } else if (hipMemcpyAsync(dst, src, n * sizeof(T), hipMemcpyDeviceToDevice, st) != hipSuccess) {
         return SRX_E_HIP;
     }
-    return prefilter2d_fast(dst, scratch, B, Hc, Wc, mode, st);
+    return prefilter2d_fast(dst, scratch, B, Hc, Wc, mode, st, flags);
 }
 
 // FWD: err[b,k,i,j] = lr[b,k,i,j] - (F_k P bpad)[f i, f j];  errors[b] += sum err^2 * scale.
@@ -1418,16 +1417,15 @@ template <typename T, typename Tap> static IbpTabs<T, Tap> carve_ibp(Arena &ar, 
             d.v2 ? ar.take<Tap>(d.tx) : nullptr, d.v2 ? ar.take<double>(d.B * cdiv((int)d.H, 16) * cdiv((int)d.W, 16)) : nullptr};
 }
 // the bound: v2, each tap table as (N + 8) (H + W + 48) entries of the widest form, two float64 lattice taps
-static inline size_t ibp_ws(int eb, int B, int N, int h, int w, int H, int W, int f)
+static inline size_t ibp_ws(const IbpShape &s, int B)
 {
-    (void)f;
-    const size_t nt = (size_t)(N + 8) * (H + W + 4 * SRX_NPAD);
-    const IbpDims d{(size_t)B, (size_t)N, (size_t)h, (size_t)w, (size_t)H, (size_t)W, nt, nt, true};
-    return measured([&](Arena &m) { eb == 8 ? (void)carve_ibp<double, LTap<double, 2>>(m, d) : (void)carve_ibp<float, LTap<double, 2>>(m, d); });
+    const size_t nt = (size_t)(s.N + 8) * (s.H + s.W + 4 * SRX_NPAD);
+    const IbpDims d{(size_t)B, (size_t)s.N, (size_t)s.h, (size_t)s.w, (size_t)s.H, (size_t)s.W, nt, nt, true};
+    return measured([&](Arena &m) { s.eb == 8 ? (void)carve_ibp<double, LTap<double, 2>>(m, d) : (void)carve_ibp<float, LTap<double, 2>>(m, d); });
 }
 
 // SRX_FLAG_DIAG_V1 selects the 8-launch iteration (stand-alone exact prefilter passes); default v2.
-static inline bool use_v1() { return (call_flags() & SRX_FLAG_DIAG_V1) != 0; }
+static inline bool use_v1(const IbpSpec &s) { return (s.flags & SRX_FLAG_DIAG_V1) != 0; }
 
 // v2 iteration loop: blur_pad -> fwd_tile -> bwd_tile, lattice-tap tables built once per call
 template <typename T, int F>
@@ -1477,13 +1475,16 @@ static int ibp_v2_loop(const T *lr, int B, int N, int h, int w, const FrameSet<T
     return SRX_OK;
 }
 
-template <typename T>
-static int ibp(const T *lr, int B, int N, int h, int w, const double *sh, const double *k, int kh, int kw,
-               const T *hr_init, int H, int W, int f, int n_iter, double step, T *hr, double *errors, void *ws,
-               size_t wsb, hipStream_t st)
+template <typename T> static int ibp(const IbpCall<T> &c)
 {
+    const int B = c.B, N = c.s.N, h = c.s.h, w = c.s.w, H = c.s.H, W = c.s.W, f = c.s.f, n_iter = c.n_iter;
+    const double *const sh = c.s.sh, step = c.step;
+    const T *const lr = c.lr, *const hr_init = c.hr_init;
+    T *const hr = c.hr;
+    double *const errors = c.errors;
+    const hipStream_t st = c.st;
     const int Hp = H + 2 * SRX_NPAD, Wp = W + 2 * SRX_NPAD;
-    Arena ar(ws, wsb);
+    Arena ar(c.ws, c.wsb);
     FrameSet<T> fwd, bwd;
     fwd.n = bwd.n = N;
     int omin_y = 1 << 30, omin_x = 1 << 30, omax_y = -(1 << 30), omax_x = -(1 << 30);
@@ -1496,8 +1497,8 @@ static int ibp(const T *lr, int B, int N, int h, int w, const double *sh, const 
     }
     const int th = f * 15 + (omax_y - omin_y) + 4, tw = f * 15 + (omax_x - omin_x) + 4;
     Kernel7<T> kc, kt;
-    make_kernel7<T>(k, kh, kw, false, kc);
-    make_kernel7<T>(k, kh, kw, true, kt);
+    make_kernel7<T>(c.s.k, c.s.kh, c.s.kw, false, kc, c.s.flags);
+    make_kernel7<T>(c.s.k, c.s.kh, c.s.kw, true, kt, c.s.flags);
     const size_t P = (size_t)B * H * W;
     if (errors && fill_bytes(errors, 0, (size_t)B * n_iter * sizeof(double), st) != hipSuccess)
         return SRX_E_HIP;
@@ -1505,7 +1506,7 @@ static int ibp(const T *lr, int B, int N, int h, int w, const double *sh, const 
         return SRX_E_HIP;
     const double scale = 1.0 / ((double)h * (double)w) / (double)N;
     const dim3 bgrid(cdiv(W, SRX_BT_W), cdiv(H, SRX_BT_H), B), bblk(64, 4);
-    if (f >= 2 && !use_v1()) {
+    if (f >= 2 && !use_v1(c.s)) {
         // ---- v2: blur_pad -> fwd_tile -> bwd_tile ----
 #define SRX_V2(FF)                                                                                                  \
     return ibp_v2_loop<T, FF>(lr, B, N, h, w, fwd, bwd, omin_y, omax_y, omin_x, omax_x, kc, kt, hr_init, H, W, n_iter, \
@@ -1524,13 +1525,13 @@ static int ibp(const T *lr, int B, int N, int h, int w, const double *sh, const 
     for (int it = 0; it < n_iter; it++) {
         const T *cur = it == 0 ? hr_init : hr;
         SRX_LAUNCH(KID_BLUR_PAD, (k_blur_pad<T, false>), bgrid, bblk, 0, st, cur, H, W, kc, pad);
-        SRX_TRY(prefilter2d_fast(pad, scr, B, Hp, Wp, MODE_REFLECT, st));
+        SRX_TRY(prefilter2d_fast(pad, scr, B, Hp, Wp, MODE_REFLECT, st, c.s.flags));
         SRX_LAUNCH(KID_FWD_RESIDUAL, k_fwd_residual<T>, dim3(cdiv(w, 16), cdiv(h, 16), B), dim3(16, 16),
                    (size_t)th * tw * sizeof(T), st, pad, Hp, Wp, lr, h, w, f, fwd, omin_y, omin_x, th, tw, err,
                    errors ? errors + it : nullptr, n_iter, scale);
         SRX_LAUNCH(KID_BACK_GATHER, k_back_gather<T>, dim3(cdiv(Wp, 64), cdiv(Hp, 4), B), dim3(64, 4), 0, st, err, h, w, f,
                    bwd, H, W, pad);
-        SRX_TRY(prefilter2d_fast(pad, scr, B, Hp, Wp, MODE_REFLECT, st));
+        SRX_TRY(prefilter2d_fast(pad, scr, B, Hp, Wp, MODE_REFLECT, st, c.s.flags));
         SRX_LAUNCH(KID_BLURT_UPDATE, (k_blurT_update<T, false>), bgrid, bblk, 0, st, pad, H, W, kt, (T)step, (T)N, cur, hr);
     }
     return SRX_OK;
@@ -1550,27 +1551,28 @@ template <typename T> static SaaTabs<T> carve_saa(Arena &ar, const SaaDims &d)
     return {ar.take<T>(d.B * d.N * d.h * d.w), ar.take<T>(d.B * d.N * d.h * d.w), ar.take<T>(d.B * H * W), ar.take<T>(d.B * Hp * Wp), ar.take<T>(d.B * Hp * Wp),
             ar.take<AxisTap<T>>(d.zy), ar.take<AxisTap<T>>(d.zx)};
 }
-static inline size_t saa_ws(int eb, int B, int N, int h, int w, int f)
+static inline size_t saa_ws(const SaaShape &s, int B)
 {
-    const size_t tl = tap_bound(eb, (size_t)(h > w ? h : w) * f);
-    const SaaDims d{(size_t)B, (size_t)N, (size_t)h, (size_t)w, (size_t)f, tl, tl};
-    return measured([&](Arena &m) { eb == 8 ? (void)carve_saa<double>(m, d) : (void)carve_saa<float>(m, d); });
+    const size_t tl = tap_bound(s.eb, (size_t)(s.h > s.w ? s.h : s.w) * s.f);
+    const SaaDims d{(size_t)B, (size_t)s.N, (size_t)s.h, (size_t)s.w, (size_t)s.f, tl, tl};
+    return measured([&](Arena &m) { s.eb == 8 ? (void)carve_saa<double>(m, d) : (void)carve_saa<float>(m, d); });
 }
 
 // The driver body of shift_and_add on this route.  fir(q, grid, block, up, pad) makes frame q's FIR launch: where its tap comes from is
 // all that differs between one table for the batch (saa below) and one per item (items::saa_fused_items).
-template <typename T, typename Fir>
-static int saa_with(Fir fir, const T *lr, int B, int N, int h, int w, int f, T *out, void *ws, size_t wsb, hipStream_t st)
+template <typename T, typename Fir> static int saa_with(Fir fir, const SaaCall<T> &c)
 {
+    const int B = c.B, N = c.s.N, h = c.s.h, w = c.s.w, f = c.s.f;
+    const hipStream_t st = c.st;
     if ((long)B * N > 65535)
         return SRX_E_UNSUPPORTED;
     const int H = h * f, W = w * f, Hp = H + 2 * SRX_NPAD, Wp = W + 2 * SRX_NPAD;
-    Arena ar(ws, wsb);
+    Arena ar(c.ws, c.wsb);
     const auto [coef, cscr, up, pad, scr, zy, zx] = carve_saa<T>(ar, SaaDims{(size_t)B, (size_t)N, (size_t)h, (size_t)w, (size_t)f, (size_t)H, (size_t)W});
     if (!ar.ok)
         return SRX_E_WORKSPACE;
     // spline coefficients of every LR frame at once: [B*N, h, w], 'mirror' ends (scipy.ndimage.zoom)
-    SRX_TRY(prefilter2d_from(lr, coef, cscr, B * N, h, w, MODE_MIRROR, st));
+    SRX_TRY(prefilter2d_from(c.lr, coef, cscr, B * N, h, w, MODE_MIRROR, st, c.s.flags));
     const double zy_ = H > 1 ? (double)(h - 1) / (double)(H - 1) : 1.0;
     const double zx_ = W > 1 ? (double)(w - 1) / (double)(W - 1) : 1.0;
     SRX_TRY(build_taps(zy, H, h, TAP_ZOOM, 1, zy_, st));
@@ -1579,16 +1581,16 @@ static int saa_with(Fir fir, const T *lr, int B, int N, int h, int w, int f, T *
         SRX_TRY(interp_strided(coef + (size_t)q * h * w, (size_t)N * h * w, B, h, w, zy, zx, H, W, up, st));
         SRX_TRY(fir(q, dim3(cdiv(Wp, 64), cdiv(Hp, 4), B), dim3(64, 4), up, pad));
     }
-    SRX_TRY(prefilter2d_fast(pad, scr, B, Hp, Wp, MODE_REFLECT, st));
-    SRX_LAUNCH(KID_CROP_DIV, k_crop_div<T>, dim3(cdiv(W, 64), cdiv(H, 4), B), dim3(64, 4), 0, st, pad, H, W, (T)N, out);
+    SRX_TRY(prefilter2d_fast(pad, scr, B, Hp, Wp, MODE_REFLECT, st, c.s.flags));
+    SRX_LAUNCH(KID_CROP_DIV, k_crop_div<T>, dim3(cdiv(W, 64), cdiv(H, 4), B), dim3(64, 4), 0, st, pad, H, W, (T)N, c.out);
     return SRX_OK;
 }
 
-template <typename T>
-static int saa(const T *lr, int B, int N, int h, int w, const double *sh, int f, T *out, void *ws, size_t wsb,
-               hipStream_t st)
+template <typename T> static int saa(const SaaCall<T> &c)
 {
-    const int H = h * f, W = w * f;
+    const int f = c.s.f, H = c.s.h * f, W = c.s.w * f;
+    const double *const sh = c.s.sh;
+    const hipStream_t st = c.st;
     auto fir = [&](int q, dim3 grd, dim3 blk, const T *up, T *pad) -> int {
         FrameTap<T> ft;
         make_tap<T>(-sh[2 * q] * f, -sh[2 * q + 1] * f, 0, ft);  // shift(+d): out[r] = in[r - d]
@@ -1598,7 +1600,7 @@ static int saa(const T *lr, int B, int N, int h, int w, const double *sh, int f,
             SRX_LAUNCH(KID_FIR_PAD, (k_fir_pad<T, true>), grd, blk, 0, st, up, H, W, ft, pad);
         return SRX_OK;
     };
-    return saa_with<T>(fir, lr, B, N, h, w, f, out, ws, wsb, st);
+    return saa_with<T>(fir, c);
 }
 
 }  // namespace fused

@@ -1,5 +1,7 @@
 // srx_items.hpp -- one shift table PER ITEM of a batch (srx_saa_items_*, srx_ibp_items_*).  Included from srx_api.hip behind the
-// dispatchers of the shared-table calls: everything here is routing on the host plus the two per-item forms of kernels that exist.
+// dispatchers of the shared-table calls, whose route_*, *_check, ibp_need and *_run it calls: everything here is routing on the host plus
+// the two per-item forms of kernels that exist.  In a spec or a call of this file sh is [B][N][2]; a table's route is the call's spec
+// with sh re-pointed at that table.
 //
 // Registration measures a table per item (srx_register_* returns [B, N, 2]); the shared-table calls made such a caller leave the batch.
 // Here the driver walks the batch in maximal RUNS of consecutive items:
@@ -106,55 +108,47 @@ template <typename RouteFn> static Plan plan_runs(const double *sh, int B, int N
 // ---------------------------------------------------------------------------------------
 // ibp
 // ---------------------------------------------------------------------------------------
-static Plan plan_ibp(int eb, int B, int N, int h, int w, int H, int W, int f, const double *sh, const double *k, int kh, int kw, unsigned flags)
+static Plan plan_ibp(const IbpSpec &s, int B)
 {
-    Plan p = plan_runs(sh, B, N, PATH_BTILE, SRX_MAX_BATCH_PER_LAUNCH,
-                       [&](const double *s) { return route_ibp(eb, N, h, w, H, W, f, s, k, kh, kw, flags); });
+    Plan p = plan_runs(s.sh, B, s.N, PATH_BTILE, SRX_MAX_BATCH_PER_LAUNCH, [&](const double *table) {
+        IbpSpec t = s;
+        t.sh = table;
+        return route_ibp(t);
+    });
     for (const Run &r : p.runs) {
-        size_t need = ibp_need(p.route[r.table], eb, r.n, N, h, w, H, W, f, flags);
+        size_t need = ibp_need(p.route[r.table], s, r.n);
         if (r.per_item)
-            need += btile::items_tab_bytes(r.n, N);
+            need += btile::items_tab_bytes(r.n, s.N);
         p.need = need > p.need ? need : p.need;
     }
     return p;
 }
 
-static size_t ibp_ws_bound(int eb, int B, int N, int h, int w, int H, int W, int f, unsigned flags)
+static size_t ibp_ws_bound(const IbpShape &s, int B, unsigned flags)
 {
-    return srx_ibp_workspace_bytes(eb, B, N, h, w, H, W, f, flags) + btile::items_tab_bytes(std::max(ibp_chunk_items(B), 1), N > 0 ? N : 1);
+    return ibp_bound(s, B, flags) + btile::items_tab_bytes(std::max(ibp_chunk_items(B), 1), s.N > 0 ? s.N : 1);
 }
 
-template <typename T>
-static int ibp_dispatch_items(const T *lr, int B, int N, int h, int w, const double *sh, const double *k, int kh, int kw, const T *hr_init, int H,
-                              int W, int f, int n_iter, double step, T *hr, double *errors, void *ws, size_t wsb, hipStream_t st, unsigned flags)
+template <typename T> static int ibp_dispatch_items(const IbpCall<T> &c)
 {
-    if (!basic_ibp_args_ok(lr, B, N, h, w, sh, k, kh, kw, hr_init, H, W, f, n_iter, hr))
-        return SRX_E_INVALID;
-    if (N > SRX_MAX_FRAMES || kh * kw > SRX_MAX_KERNEL_TAPS || !plane_fits(sizeof(T), N, h, w, H, W))
-        return SRX_E_UNSUPPORTED;
-    const Plan p = plan_ibp((int)sizeof(T), B, N, h, w, H, W, f, sh, k, kh, kw, flags);
+    SRX_TRY(ibp_check(c.s, c.B, c.n_iter, c.lr && c.hr_init && c.hr));
+    const Plan p = plan_ibp(c.s, c.B);
     if (p.status != SRX_OK)
         return p.status;
-    if (ws_short(ws, wsb, p.need))
+    if (ws_short(c.ws, c.wsb, p.need))
         return SRX_E_WORKSPACE;
     g_last_path = p.name;
-    const size_t fr = (size_t)N * h * w, P = (size_t)H * W;
     for (const Run &r : p.runs) {
-        const double *shr = sh + (size_t)r.b0 * 2 * N;
-        const Route &rt = p.route[r.table];
+        const double *shr = c.s.sh + (size_t)r.b0 * 2 * c.s.N;
         if (r.per_item) {
             if constexpr (sizeof(T) == 4)
-                SRX_TRY(btile::ibp_items(lr + r.b0 * fr, r.n, N, h, w, shr, k, kh, kw, hr_init + r.b0 * P, H, W, n_iter, step, hr + r.b0 * P,
-                                         errors ? errors + (size_t)r.b0 * n_iter : nullptr, ws, wsb, st));
+                SRX_TRY(btile::ibp_items(c.chunk(r.b0, r.n, shr)));
             else
                 return SRX_E_INVALID;  // (route_ibp gives float32 calls alone this path)
             continue;
         }
-        for (int b0 = r.b0; b0 < r.b0 + r.n; b0 += SRX_MAX_BATCH_PER_LAUNCH) {  // as ibp_dispatch
-            const int bc = ibp_chunk_items(r.b0 + r.n - b0);
-            SRX_TRY((ibp_run<T, T>(rt, lr + b0 * fr, bc, N, h, w, shr, k, kh, kw, hr_init + b0 * P, H, W, f, n_iter, step, hr + b0 * P,
-                                   errors ? errors + (size_t)b0 * n_iter : nullptr, ws, wsb, st)));
-        }
+        for (int b0 = r.b0; b0 < r.b0 + r.n; b0 += SRX_MAX_BATCH_PER_LAUNCH)  // as ibp_dispatch
+            SRX_TRY(ibp_run(p.route[r.table], c.chunk(b0, ibp_chunk_items(r.b0 + r.n - b0), shr)));
     }
     return SRX_OK;
 }
@@ -197,19 +191,20 @@ template <typename T> static inline size_t saa_tab_bytes(int B, int N)
     return measured([&](Arena &m) { carve_saa_tab<T>(m, B, N); });
 }
 
-static size_t saa_ws_bound(int eb, int B, int N, int h, int w, int f)
+static size_t saa_ws_bound(const SaaShape &s, int B)
 {
-    const int n = N > 0 ? N : 1, Bc = std::max(saa_chunk_items(B, n), 1);
-    return srx_saa_workspace_bytes(eb, B, N, h, w, f) + (eb == 4 ? saa_tab_bytes<float>(Bc, n) : saa_tab_bytes<double>(Bc, n));
+    const int n = s.N > 0 ? s.N : 1, Bc = std::max(saa_chunk_items(B, n), 1);
+    return saa_bound(s, B) + (s.eb == 4 ? saa_tab_bytes<float>(Bc, n) : saa_tab_bytes<double>(Bc, n));
 }
 
-// fused::saa with one table per item: sh [B][N][2]; tab: B * N taps of device memory.  The taps go up before the body runs; its own
+// fused::saa with one table per item: c.s.sh [B][N][2]; tab: B * N taps of device memory.  The taps go up before the body runs; its own
 // refusals cannot follow them, the dispatcher having held the workspace to the bound and the run to one chunk.
-template <typename T>
-static int saa_fused_items(const T *lr, int B, int N, int h, int w, const double *sh, int f, T *out, fused::FrameTap<T> *tab, void *ws, size_t wsb,
-                           hipStream_t st)
+template <typename T> static int saa_fused_items(const SaaCall<T> &c, fused::FrameTap<T> *tab)
 {
     using namespace fused;
+    const int B = c.B, N = c.s.N, f = c.s.f;
+    const double *const sh = c.s.sh;
+    const hipStream_t st = c.st;
     static_assert(sizeof(FrameTap<T>) % sizeof(int) == 0, "the taps travel as words");
     constexpr int TW = (int)(sizeof(FrameTap<T>) / sizeof(int));
     btile::ParamUpload words{st, reinterpret_cast<int *>(tab)};
@@ -222,7 +217,7 @@ static int saa_fused_items(const T *lr, int B, int N, int h, int w, const double
         SRX_TRY(words.put(ftw, TW));
     }
     SRX_TRY(words.finish());
-    const int H = h * f, W = w * f;
+    const int H = c.s.h * f, W = c.s.w * f;
     auto fir = [&](int q, dim3 grd, dim3 blk, const T *up, T *pad) -> int {
         if (q == 0)
             SRX_LAUNCH(KID_FIR_PAD, (k_fir_pad_items<T, false>), grd, blk, 0, st, up, H, W, tab, N, q, pad);
@@ -230,43 +225,43 @@ static int saa_fused_items(const T *lr, int B, int N, int h, int w, const double
             SRX_LAUNCH(KID_FIR_PAD, (k_fir_pad_items<T, true>), grd, blk, 0, st, up, H, W, tab, N, q, pad);
         return SRX_OK;
     };
-    return saa_with<T>(fir, lr, B, N, h, w, f, out, ws, wsb, st);
+    return saa_with<T>(fir, c);
 }
 
 // (what the call must bring is the shape-only bound: there is no exact query for shift_and_add)
-static Plan plan_saa(int eb, int B, int N, int h, int w, int f, const double *sh, unsigned flags)
+static Plan plan_saa(const SaaSpec &s, int B)
 {
-    Plan p = plan_runs(sh, B, N, PATH_FUSED, saa_chunk_items(B, N), [&](const double *s) { return route_saa(N, h, w, f, s, flags); });
-    p.need = saa_ws_bound(eb, B, N, h, w, f);
+    Plan p = plan_runs(s.sh, B, s.N, PATH_FUSED, saa_chunk_items(B, s.N), [&](const double *table) {
+        SaaSpec t = s;
+        t.sh = table;
+        return route_saa(t);
+    });
+    p.need = saa_ws_bound(s, B);
     return p;
 }
 
-template <typename T>
-static int saa_dispatch_items(const T *lr, int B, int N, int h, int w, const double *sh, int f, T *out, void *ws, size_t wsb, hipStream_t st,
-                              unsigned flags)
+template <typename T> static int saa_dispatch_items(const SaaCall<T> &c)
 {
-    SRX_TRY(saa_check(sizeof(T), lr, B, N, h, w, sh, f, out));
-    const Plan p = plan_saa((int)sizeof(T), B, N, h, w, f, sh, flags);
+    SRX_TRY(saa_check(c.s, c.B, c.lr && c.out));
+    const Plan p = plan_saa(c.s, c.B);
     if (p.status != SRX_OK)  // (before the workspace, unlike saa_dispatch: see there)
         return p.status;
-    if (ws_short(ws, wsb, p.need))
+    if (ws_short(c.ws, c.wsb, p.need))
         return SRX_E_WORKSPACE;
     g_last_path = p.name;
     // the head of the workspace holds the taps of one per-item run, every run's driver gets the rest
-    Arena ar(ws, wsb);
-    fused::FrameTap<T> *tab = carve_saa_tab<T>(ar, saa_chunk_items(B, N), N);
-    void *wsr = (char *)ws + ar.off;
-    const size_t wsrb = wsb - ar.off;
-    const size_t fr = (size_t)N * h * w, P = (size_t)h * f * w * f;
+    Arena ar(c.ws, c.wsb);
+    fused::FrameTap<T> *tab = carve_saa_tab<T>(ar, saa_chunk_items(c.B, c.s.N), c.s.N);
+    const SaaCall<T> rest = c.on(c.lr, (char *)c.ws + ar.off, c.wsb - ar.off);
     for (const Run &r : p.runs) {
-        const double *shr = sh + (size_t)r.b0 * 2 * N;
+        const double *shr = c.s.sh + (size_t)r.b0 * 2 * c.s.N;
         if (r.per_item) {
-            SRX_TRY(saa_fused_items<T>(lr + r.b0 * fr, r.n, N, h, w, shr, f, out + r.b0 * P, tab, wsr, wsrb, st));
+            SRX_TRY(saa_fused_items<T>(rest.chunk(r.b0, r.n, shr), tab));
             continue;
         }
         for (int b0 = r.b0, bc; b0 < r.b0 + r.n; b0 += bc) {  // as saa_dispatch
-            bc = saa_chunk_items(r.b0 + r.n - b0, N);
-            SRX_TRY((saa_run<T, T>(p.route[r.table], lr + b0 * fr, bc, N, h, w, shr, f, out + b0 * P, wsr, wsrb, st)));
+            bc = saa_chunk_items(r.b0 + r.n - b0, c.s.N);
+            SRX_TRY(saa_run(p.route[r.table], rest.chunk(b0, bc, shr)));
         }
     }
     return SRX_OK;

@@ -92,12 +92,12 @@ static inline bool plan_axis(int N, const double *sh, int axis, int f, AxisPlan 
     return true;
 }
 
-static inline bool eligible(int N, int h, int w, const double *sh, int kh, int kw, int H, int W, int f)
+static inline bool eligible(const IbpSpec &s)
 {
-    if (!fused::ibp_eligible(N, h, w, sh, kh, kw, H, W, f) || f < 2)
+    if (!fused::ibp_eligible(s) || s.f < 2)
         return false;
     AxisPlan a;
-    return plan_axis(N, sh, 0, f, a) && plan_axis(N, sh, 1, f, a) && H >= 32 && W >= 32;
+    return plan_axis(s.N, s.sh, 0, s.f, a) && plan_axis(s.N, s.sh, 1, s.f, a) && s.H >= 32 && s.W >= 32;
 }
 
 // ---------------------------------------------------------------------------------------
@@ -1221,6 +1221,7 @@ template <typename T> struct Common {
     const void *lr;  // T, or uint8_t when lr_u8 (the two kernels that read the frames have an instantiation for either)
     bool lr_u8;
     int B, N, h, w, H, W, f;
+    unsigned flags;      // the call's: the SRX_FLAG_DIAG_* switches the iterate() of an implementation reads
     double step, scale;  // scale: 1 / (samples of an item), the MSE trace's normalisation
     AxisPlan py, px;
     Kernel7<T> kc, kt;
@@ -1252,25 +1253,29 @@ template <typename T> static CommonTabs<T> carve_common(Arena &ar, const CommonD
     return {ar.take<T>(d.B * d.Hg * d.Wg), ar.take<T>(d.Hg * d.Wg), ar.take<T>(d.B * d.NB), ar.take<MTap>(d.N * d.ty), ar.take<MTap>(d.N * d.tx),
             ar.take<double>(d.B), ar.take<double>(d.B * cdiv((int)d.Wg, 64) * cdiv((int)d.Hg, 4)), ar.take<int>(d.NB), ar.take<int>(d.NB * d.NS)};
 }
-static inline size_t ws_common(int eb, int B, int N, int H, int W)
+static inline size_t ws_common(const IbpShape &s, int B)
 {
-    const size_t Hg = H + 2 * SRX_NPAD + 3, Wg = W + 2 * SRX_NPAD + 3, tl = Hg > Wg ? Hg : Wg;
-    const CommonDims d{(size_t)B, (size_t)N, Hg, Wg, tl, tl, near_bound(Hg, Wg), near_slots(N)};
-    return measured([&](Arena &m) { eb == 8 ? (void)carve_common<double>(m, d) : (void)carve_common<float>(m, d); });
+    const size_t Hg = s.H + 2 * SRX_NPAD + 3, Wg = s.W + 2 * SRX_NPAD + 3, tl = Hg > Wg ? Hg : Wg;
+    const CommonDims d{(size_t)B, (size_t)s.N, Hg, Wg, tl, tl, near_bound(Hg, Wg), near_slots(s.N)};
+    return measured([&](Arena &m) { s.eb == 8 ? (void)carve_common<double>(m, d) : (void)carve_common<float>(m, d); });
 }
 
 // own_build: the implementation reads the LR frames itself and wants no M / C / Mu planes (a batch of patches on a full phase grid,
-// srx_patch.hpp's k_patch_build -- the M plane of 1024 patches is 328 MB written here and read back once by k_patch_prep)
+// srx_patch.hpp's k_patch_build -- the M plane of 1024 patches is 328 MB written here and read back once by k_patch_prep).
+// Of `call` it reads the spec, the frames, the batch size, the step and the stream.
 template <typename T, typename S = T>
-static int common_prep(Common<T> &c, bool own_build, const S *lr, int B, int N, int h, int w, const double *sh, const double *k, int kh, int kw, int H,
-                       int W, int f, double step, Arena &ar, hipStream_t st, int tr_lo, int tr_hi)
+static int common_prep(Common<T> &c, bool own_build, const IbpCall<T, S> &call, Arena &ar, int tr_lo, int tr_hi)
 {
+    const IbpSpec &s = call.s;
+    const int B = call.B, N = s.N, h = s.h, w = s.w, H = s.H, W = s.W, f = s.f;
+    const S *const lr = call.lr;
+    const hipStream_t st = call.st;
     const int Hp = H + 2 * SRX_NPAD, Wp = W + 2 * SRX_NPAD, Hg = Hp + 3, Wg = Wp + 3;
     static_assert(std::is_same<S, T>::value || std::is_same<S, uint8_t>::value, "LR samples: T or uint8_t");
-    c.lr = lr, c.lr_u8 = !std::is_same<S, T>::value, c.B = B, c.N = N, c.h = h, c.w = w, c.H = H, c.W = W, c.f = f, c.step = step;
+    c.lr = lr, c.lr_u8 = !std::is_same<S, T>::value, c.B = B, c.N = N, c.h = h, c.w = w, c.H = H, c.W = W, c.f = f, c.flags = s.flags, c.step = call.step;
     c.scale = 1.0 / ((double)h * (double)w) / (double)N;
     AxisPlan &py = c.py, &px = c.px;
-    if (!plan_axis(N, sh, 0, f, py) || !plan_axis(N, sh, 1, f, px))
+    if (!plan_axis(N, s.sh, 0, f, py) || !plan_axis(N, s.sh, 1, f, px))
         return SRX_E_UNSUPPORTED;
     const int NB = py.PB * Wg + (Hg - py.PB) * px.PB;  // pixels of the near band
     const int NS = (int)near_slots(N);
@@ -1287,8 +1292,8 @@ static int common_prep(Common<T> &c, bool own_build, const S *lr, int B, int N, 
     MosaicArgs<T> &ma = c.ma;
     ma.Dy = py.D, ma.Dx = px.D, ma.PBy = py.PB, ma.PBx = px.PB, ma.RSy = py.RS, ma.RSx = px.RS;
     fused::axis_firs<T>(py.delta, px.delta, 1.0, ma.wfy, ma.wfx, ma.wby, ma.wbx);
-    fused::make_kernel7<T>(k, kh, kw, false, c.kc);
-    fused::make_kernel7<T>(k, kh, kw, true, c.kt);
+    fused::make_kernel7<T>(s.k, s.kh, s.kw, false, c.kc, s.flags);
+    fused::make_kernel7<T>(s.k, s.kh, s.kw, true, c.kt, s.flags);
     c.sep = c.kc.separable && c.kt.separable, c.zero = py.zero && px.zero;
     // ---- once per call: index maps, LR mosaic, count map, constant part of the MSE trace ----
     hipLaunchKernelGGL(k_build_mtaps, dim3(cdiv(Hg, 64), N), dim3(64), 0, st, tabY, Hg, H, f, dy);
@@ -1325,9 +1330,9 @@ template <typename T> static TileTabs<T> carve_tiles(Arena &ar, size_t B, int H,
     const int Hp = H + 2 * SRX_NPAD, Wp = W + 2 * SRX_NPAD, Hg = Hp + 3, Wg = Wp + 3;
     return {ar.take<T>(B * Hp * Wp), ar.take<T>(B * Hg * Wg), ar.take<double>(B * cdiv(Hg, 32) * cdiv(Wg, 32))};
 }
-static inline size_t tiles_bytes(int eb, int B, int, int H, int W)
+static inline size_t tiles_bytes(const IbpShape &s, int B)
 {
-    return measured([&](Arena &m) { eb == 8 ? (void)carve_tiles<double>(m, B, H, W) : (void)carve_tiles<float>(m, B, H, W); });
+    return measured([&](Arena &m) { s.eb == 8 ? (void)carve_tiles<double>(m, B, s.H, s.W) : (void)carve_tiles<float>(m, B, s.H, s.W); });
 }
 
 template <typename T>
@@ -1352,7 +1357,7 @@ static int iterate(const Common<T> &c, const T *hr_init, T *hr, int n_iter, doub
     const dim3 bgrid(cdiv(W, SRX_BT_W), cdiv(H, SRX_BT_H), B), bblk(64, 4);
     const dim3 fgrid(cdiv(Wg, TS), cdiv(Hg, c.zero ? FwdRows<T, true>::v : TS), B), wgrid(cdiv(W, TS), cdiv(H, TS), B);
     // delta = 0: blur and forward map in one kernel over image tiles (no blurred plane); SRX_NO_ZERO_FUSE keeps the two kernels
-    const bool zfuse = c.zero && !(call_flags() & SRX_FLAG_DIAG_NO_ZERO_FUSE);
+    const bool zfuse = c.zero && !(c.flags & SRX_FLAG_DIAG_NO_ZERO_FUSE);
     const int nblk = zfuse ? (int)(bgrid.x * bgrid.y) : (int)(fgrid.x * fgrid.y);  // MSE partial sums per item
     for (int it = 0; it < n_iter; it++) {
         const T *cur = it == 0 ? hr_init : hr;
@@ -1394,12 +1399,12 @@ static int iterate(const Common<T> &c, const T *hr_init, T *hr, int n_iter, doub
     return SRX_OK;
 }
 
-static inline bool saa_eligible(int N, int h, int w, const double *sh, int f)
+static inline bool saa_eligible(const SaaSpec &s)
 {
-    if (!fused::saa_eligible(N, h, w, sh, f) || f < 2 || f > 4 || h < 8 || w < 8)
+    if (!fused::saa_eligible(s) || s.f < 2 || s.f > 4 || s.h < 8 || s.w < 8)
         return false;
     AxisPlan a;
-    return plan_axis(N, sh, 0, f, a) && plan_axis(N, sh, 1, f, a);
+    return plan_axis(s.N, s.sh, 0, s.f, a) && plan_axis(s.N, s.sh, 1, s.f, a);
 }
 
 // the counts shift_and_add's layout depends on.  zy, zx: entries of the two zoom tap tables (H and W in a call); two_pass: the W plane
@@ -1419,28 +1424,31 @@ template <typename T> static SaaTabs<T> carve_saa(Arena &ar, const SaaDims &d)
             d.two_pass ? ar.take<T>(d.B * Hw * Ww) : nullptr};
 }
 // the bound: the two-pass form, and both tap tables at the longer side
-static inline size_t saa_ws(int eb, int B, int N, int h, int w, int f)
+static inline size_t saa_ws(const SaaShape &s, int B)
 {
-    const size_t tl = (size_t)(h > w ? h : w) * f;
-    const SaaDims d{(size_t)B, (size_t)N, (size_t)h, (size_t)w, (size_t)f, tap_bound(eb, tl), tap_bound(eb, tl), true};
-    return measured([&](Arena &m) { eb == 8 ? (void)carve_saa<double>(m, d) : (void)carve_saa<float>(m, d); });
+    const size_t tl = (size_t)(s.h > s.w ? s.h : s.w) * s.f;
+    const SaaDims d{(size_t)B, (size_t)s.N, (size_t)s.h, (size_t)s.w, (size_t)s.f, tap_bound(s.eb, tl), tap_bound(s.eb, tl), true};
+    return measured([&](Arena &m) { s.eb == 8 ? (void)carve_saa<double>(m, d) : (void)carve_saa<float>(m, d); });
 }
 
 // S: the type of the LR samples, T or uint8_t (srx_saa_u8lr_*).  The three prefilter forms are the only readers of the frames: the two
 // wave-per-frame kernels and the float32 tile kernel read bytes themselves; where the line kernels run (float64, or on request) the copy into
 // coef that the float call starts with is the conversion.  The workspace is the same for either sample type.
-template <typename T, typename S = T>
-static int saa(const S *lr, int B, int N, int h, int w, const double *sh, int f, T *out, void *ws, size_t wsb,
-               hipStream_t st)
+template <typename T, typename S = T> static int saa(const SaaCall<T, S> &c)
 {
+    const int B = c.B, N = c.s.N, h = c.s.h, w = c.s.w, f = c.s.f;
+    const double *const sh = c.s.sh;
+    const S *const lr = c.lr;
+    T *const out = c.out;
+    const hipStream_t st = c.st;
     if ((long)B * N > 65535)
         return SRX_E_UNSUPPORTED;
     const int H = h * f, W = w * f;
     AxisPlan py, px;
     if (!plan_axis(N, sh, 0, f, py) || !plan_axis(N, sh, 1, f, px))
         return SRX_E_UNSUPPORTED;
-    Arena ar(ws, wsb);
-    const bool two_pass = !(call_flags() & SRX_FLAG_DIAG_SAA_ONE_PASS);
+    Arena ar(c.ws, c.wsb);
+    const bool two_pass = !(c.s.flags & SRX_FLAG_DIAG_SAA_ONE_PASS);
     const int Hw = H + 2 * SRX_NPAD + 3, Ww = W + 2 * SRX_NPAD + 3;
     const auto [coef, cscr, zy, zx, Wpl] = carve_saa<T>(ar, SaaDims{(size_t)B, (size_t)N, (size_t)h, (size_t)w, (size_t)f, (size_t)H, (size_t)W, two_pass});
     if (!ar.ok)
@@ -1452,7 +1460,7 @@ static int saa(const S *lr, int B, int N, int h, int w, const double *sh, int f,
         SRX_LAUNCH(KID_PREFILTER_SMALL, (k_prefilter_small<T, S>), dim3(cdiv(B * N, 4)), dim3(256), 0, st, lr, coef, B * N, h, w,
                    (int)MODE_MIRROR);
     } else {
-        SRX_TRY(fused::prefilter2d_from(lr, coef, cscr, B * N, h, w, MODE_MIRROR, st));
+        SRX_TRY(fused::prefilter2d_from(lr, coef, cscr, B * N, h, w, MODE_MIRROR, st, c.s.flags));
     }
     SRX_TRY(build_taps(zy, H, h, TAP_ZOOM, 1, H > 1 ? (double)(h - 1) / (double)(H - 1) : 1.0, st));
     SRX_TRY(build_taps(zx, W, w, TAP_ZOOM, 1, W > 1 ? (double)(w - 1) / (double)(W - 1) : 1.0, st));

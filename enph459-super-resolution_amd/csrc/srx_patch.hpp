@@ -98,17 +98,18 @@ static inline bool axis_ok(const mosaic::AxisPlan &pl, int f)
 }
 
 // may a call of this shape EVER take the path: the shape-only workspace bound asks this, eligible() asks it first
-static inline bool shape_admits(int elem_bytes, int H, int W) { return elem_bytes == 4 && H == PN && W == PN; }
+static inline bool shape_admits(const IbpShape &s) { return s.eb == 4 && s.H == PN && s.W == PN; }
 
-static inline bool eligible(int elem_bytes, int N, int H, int W, const double *sh, const double *k, int kh, int kw, int f, bool rank1_only = false)
+static inline bool eligible(const IbpSpec &s, bool rank1_only = false)
 {
-    if (!shape_admits(elem_bytes, H, W) || f < 2)
+    const int f = s.f;
+    if (!shape_admits(s) || f < 2)
         return false;
     mosaic::AxisPlan py, px;
-    if (!mosaic::plan_axis(N, sh, 0, f, py) || !mosaic::plan_axis(N, sh, 1, f, px))
+    if (!mosaic::plan_axis(s.N, s.sh, 0, f, py) || !mosaic::plan_axis(s.N, s.sh, 1, f, px))
         return false;
     fused::Kernel7<float> kc;
-    fused::make_kernel7<float>(k, kh, kw, false, kc);
+    fused::make_kernel7<float>(s.k, s.kh, s.kw, false, kc, s.flags);
     // (round 4: a PSF that is not rank 1 runs the 7 x 7 form of the two blurs, blur2d_pass1 / blur2d_fix)
     if (!((kc.separable || !rank1_only) && axis_ok(py, f) && axis_ok(px, f)))
         return false;
@@ -925,10 +926,11 @@ static inline bool axis_map(const mosaic::AxisPlan &pl, int N, int f, AxisMap &a
     return true;
 }
 
-static inline bool builds_itself(const mosaic::AxisPlan &py, const mosaic::AxisPlan &px, int N, int f)
+// flags: the call's (SRX_FLAG_DIAG_NO_ZERO_FUSE)
+static inline bool builds_itself(const mosaic::AxisPlan &py, const mosaic::AxisPlan &px, int N, int f, unsigned flags)
 {
     unsigned long long ry[4], rx[4];
-    if ((call_flags() & SRX_FLAG_DIAG_NO_ZERO_FUSE) || !c01_masks(py, px, N, f, ry, rx) || PN / f > 255)
+    if ((flags & SRX_FLAG_DIAG_NO_ZERO_FUSE) || !c01_masks(py, px, N, f, ry, rx) || PN / f > 255)
         return false;  // (SRX_FLAG_DIAG_NO_ZERO_FUSE: the cross-check -- the tables through the batch's M / C / Mu planes, as round 3 built them)
     BuildMaps bm;
     int cy[SRX_MAX_FRAMES], cx[SRX_MAX_FRAMES], ny, nx;
@@ -957,9 +959,9 @@ static Carved carve(Arena &ar, const Dims &d)
     return {ar.take<BuildMaps>(1), ar.take<float>(d.B * PN * PN), ar.take<unsigned>(d.B * (PN / 4) * PN), ar.take<int>(d.B), ar.take<float>((size_t)PN * PN),
             ar.take<uint2>(NN_PAD), ar.take<uint2>(d.ngrp * NN_PAD), ar.take<float2>(d.B * NN_PAD), ar.take<AxisW>(2), ar.take<float>(112)};
 }
-static inline size_t tabs_bytes(int, int B, int N, int, int)
+static inline size_t tabs_bytes(const IbpShape &s, int B)
 {
-    return measured([&](Arena &m) { carve(m, Dims{(size_t)B, ((size_t)N + 3) / 4}); });
+    return measured([&](Arena &m) { carve(m, Dims{(size_t)B, ((size_t)s.N + 3) / 4}); });
 }
 
 // a PSF that is not rank 1: the 7 x 7 weights in column layout (lane-direction tap, then register-direction tap), the forward ones times
@@ -1015,7 +1017,7 @@ static int iterate(const mosaic::Common<float> &c, const float *hr_init, float *
         hipLaunchKernelGGL(k_patch_maps, dim3(1), dim3(256), 0, st, bm, maps);
         SRX_CHECK_LAUNCH();
         if (c.lr_u8) {  // byte frames: the byte plane of every patch and nothing else (m8 keeps its preset: no patch asks for the float plane)
-            if (!(call_flags() & SRX_FLAG_DIAG_U8_BYTE_LOADS) && c.w % 4 == 0 && nx * c.w <= PN)  // (the column classes' rows fill at most 64 words)
+            if (!(c.flags & SRX_FLAG_DIAG_U8_BYTE_LOADS) && c.w % 4 == 0 && nx * c.w <= PN)  // (the column classes' rows fill at most 64 words)
                 SRX_LAUNCH(KID_PATCH_BUILD, (k_patch_build<0, uint8_t, true>), dim3(PN / 16, B), dim3(256), 0, st, (const uint8_t *)c.lr, N, c.h, c.w, maps, m8, Mt, Mt8);
             else
                 SRX_LAUNCH(KID_PATCH_BUILD, (k_patch_build<0, uint8_t>), dim3(PN / 16, B), dim3(256), 0, st, (const uint8_t *)c.lr, N, c.h, c.w, maps, m8, Mt, Mt8);

@@ -22,26 +22,20 @@ enum Impl { IMPL_TILES = 0, IMPL_PATCH = 1, IMPL_ZTILE = 2, IMPL_DTILE = 3, IMPL
 struct ImplRow {
     Impl id;
     const char *name;                                // what srx_last_path() reports
-    bool (*shape_admits)(int eb, int H, int W);      // may a call of this shape EVER take it (the shape-only workspace bound's question);
+    bool (*shape_admits)(const IbpShape &);          // may a call of this shape EVER take it (the shape-only workspace bound's question);
                                                      // each header's eligible() asks its own first, so bound and dispatch cannot disagree
-    bool (*eligible)(int eb, int N, int H, int W, const double *sh, const double *k, int kh, int kw, int f);  // reads call_flags()
-    size_t (*tabs_bytes)(int eb, int B, int N, int H, int W);  // the implementation's carve, measured at its dims bound
+    bool (*eligible)(const IbpSpec &);               // does THIS call take it: its tables and its flags are in the spec
+    size_t (*tabs_bytes)(const IbpShape &, int B);   // the implementation's carve, measured at its dims bound
 };
 
 // (thin wrappers, not conditions of patch::eligible itself: stile::eligible calls that and must not inherit the flag exclusions -- a
 // float64 patch batch under SRX_FLAG_DIAG_WIDE_WINDOWS takes stile)
-static inline bool patch_row_eligible(int eb, int N, int H, int W, const double *sh, const double *k, int kh, int kw, int f)
-{
-    return !(call_flags() & (SRX_FLAG_TILES | SRX_FLAG_DIAG_WIDE_WINDOWS)) && patch::eligible(eb, N, H, W, sh, k, kh, kw, f);
-}
+static inline bool patch_row_eligible(const IbpSpec &s) { return !(s.flags & (SRX_FLAG_TILES | SRX_FLAG_DIAG_WIDE_WINDOWS)) && patch::eligible(s); }
 // a common fraction > 0: k_ibp_dtile's one launch per iteration on the frames it takes (75 us on 3072 x 4096 against the 86 of the
 // two-launch window kernels, whose G plane is a round trip through HBM), those kernels on every other shape (or on request)
-static inline bool dtile_row_eligible(int eb, int N, int H, int W, const double *sh, const double *k, int kh, int kw, int f)
-{
-    return !(call_flags() & SRX_FLAG_DIAG_TWO_LAUNCH) && dtile::eligible(eb, N, H, W, sh, k, kh, kw, f);
-}
-static inline bool tiles_shape_admits(int, int, int) { return true; }
-static inline bool tiles_eligible(int, int, int, int, const double *, const double *, int, int, int) { return true; }
+static inline bool dtile_row_eligible(const IbpSpec &s) { return !(s.flags & SRX_FLAG_DIAG_TWO_LAUNCH) && dtile::eligible(s); }
+static inline bool tiles_shape_admits(const IbpShape &) { return true; }
+static inline bool tiles_eligible(const IbpSpec &) { return true; }
 
 // in priority order; the last row takes every call the others leave
 static const ImplRow impl_table[] = {
@@ -54,37 +48,38 @@ static const ImplRow impl_table[] = {
     {IMPL_TILES, "mosaic", tiles_shape_admits, tiles_eligible, tiles_bytes},
 };
 
-static inline const ImplRow &choose_impl(int eb, int N, int H, int W, const double *sh, const double *k, int kh, int kw, int f)
+static inline const ImplRow &choose_impl(const IbpSpec &s)
 {
     const ImplRow *r = impl_table;
-    while (!r->eligible(eb, N, H, W, sh, k, kh, kw, f))
+    while (!r->eligible(s))
         r++;
     return *r;
 }
 
 // without the shift table and the PSF the implementation is not known: the largest of those the shape admits
-static inline size_t ibp_ws(int eb, int B, int N, int H, int W)
+static inline size_t ibp_ws(const IbpShape &s, int B)
 {
     size_t m = 0;
     for (const ImplRow &r : impl_table)
-        if (r.shape_admits(eb, H, W))
-            m = std::max(m, r.tabs_bytes(eb, B, N, H, W));
-    return ws_common(eb, B, N, H, W) + m;
+        if (r.shape_admits(s))
+            m = std::max(m, r.tabs_bytes(s, B));
+    return ws_common(s, B) + m;
 }
 
 // ... and with them: exactly what the call will carve
-static inline size_t ibp_ws_for(const ImplRow &impl, int eb, int B, int N, int H, int W)
-{
-    return ws_common(eb, B, N, H, W) + impl.tabs_bytes(eb, B, N, H, W);
-}
+static inline size_t ibp_ws_for(const ImplRow &impl, const IbpShape &s, int B) { return ws_common(s, B) + impl.tabs_bytes(s, B); }
 
 // S: the type of the LR samples, T or uint8_t (srx_ibp_u8lr_*).  Only the table building reads the frames (k_mosaic_build in common_prep,
 // the patch path's own build), so every implementation below is the same for either.
-template <typename T, typename S = T>
-static int ibp(const ImplRow &impl, const S *lr, int B, int N, int h, int w, const double *sh, const double *k, int kh, int kw, const T *hr_init, int H,
-               int W, int f, int n_iter, double step, T *hr, double *errors, void *ws, size_t wsb, hipStream_t st)
+template <typename T, typename S = T> static int ibp(const ImplRow &impl, const IbpCall<T, S> &call)
 {
-    if (n_iter == 0 && hr != hr_init && hipMemcpyAsync(hr, hr_init, (size_t)B * H * W * sizeof(T), hipMemcpyDeviceToDevice, st) != hipSuccess)
+    const IbpSpec &s = call.s;
+    const T *const hr_init = call.hr_init;
+    T *const hr = call.hr;
+    double *const errors = call.errors;
+    const int n_iter = call.n_iter;
+    const hipStream_t st = call.st;
+    if (n_iter == 0 && hr != hr_init && hipMemcpyAsync(hr, hr_init, (size_t)call.B * s.H * s.W * sizeof(T), hipMemcpyDeviceToDevice, st) != hipSuccess)
         return SRX_E_HIP;
     if (n_iter == 0)
         return SRX_OK;
@@ -92,11 +87,11 @@ static int ibp(const ImplRow &impl, const S *lr, int B, int N, int h, int w, con
     bool own_build = false;
     if (impl.id == IMPL_PATCH) {
         AxisPlan py, px;
-        own_build = plan_axis(N, sh, 0, f, py) && plan_axis(N, sh, 1, f, px) && patch::builds_itself(py, px, N, f);
+        own_build = plan_axis(s.N, s.sh, 0, s.f, py) && plan_axis(s.N, s.sh, 1, s.f, px) && patch::builds_itself(py, px, s.N, s.f, s.flags);
     }
-    Arena ar(ws, wsb);
+    Arena ar(call.ws, call.wsb);
     Common<T> c;
-    SRX_TRY((common_prep<T, S>(c, own_build, lr, B, N, h, w, sh, k, kh, kw, H, W, f, step, ar, st, 0, H)));
+    SRX_TRY((common_prep<T, S>(c, own_build, call, ar, 0, s.H)));
     switch (impl.id) {  // (the float32-only / float64-only drivers are not templates: eligible() admits them for their own type alone)
     case IMPL_STILE:  // float64 patches with a common fraction > 0: two launches per iteration on strips
         if constexpr (sizeof(T) == 8)

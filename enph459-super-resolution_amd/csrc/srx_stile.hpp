@@ -50,13 +50,15 @@ template <typename T> struct T2 {
 };
 
 // ---- eligibility: srx_patch.hpp's, for 8-byte elements -------------------------------------------------------------------------------
-static inline bool shape_admits(int elem_bytes, int H, int W) { return elem_bytes == 8 && H == PN && W == PN; }
+static inline bool shape_admits(const IbpShape &s) { return s.eb == 8 && s.H == PN && s.W == PN; }
 
-static inline bool eligible(int elem_bytes, int N, int H, int W, const double *sh, const double *k, int kh, int kw, int f)
+static inline bool eligible(const IbpSpec &s)
 {
-    if (!shape_admits(elem_bytes, H, W) || (call_flags() & SRX_FLAG_TILES))
+    if (!shape_admits(s) || (s.flags & SRX_FLAG_TILES))
         return false;
-    return patch::eligible(4, N, H, W, sh, k, kh, kw, f, true);  // rank-1 PSFs only (rank 1 is decided on the float64 weights there too)
+    IbpSpec s4 = s;  // the patch path's conditions, which are stated for its own 4-byte elements
+    s4.eb = 4;
+    return patch::eligible(s4, true);  // rank-1 PSFs only (rank 1 is decided on the float64 weights there too)
 }
 
 // ---- once per call: the patch path's operand planes in T ------------------------------------------------------------------------------
@@ -446,10 +448,10 @@ template <typename T> static Carved<T> carve(Arena &ar, const patch::Dims &d)
     return {ar.take<T>(d.B * PN * PN), ar.take<T>(d.B * PN * PN), ar.take<unsigned>(d.B * (PN / 4) * PN), ar.take<int>(d.B), ar.take<T>((size_t)PN * PN),
             ar.take<uint2>(NN_PAD), ar.take<uint2>(d.ngrp * NN_PAD), ar.take<T2<T>>(d.B * NN_PAD), ar.take<double>(d.B * 4)};
 }
-static inline size_t tabs_bytes(int eb, int B, int N, int, int)
+static inline size_t tabs_bytes(const IbpShape &s, int B)
 {
-    const patch::Dims d{(size_t)B, ((size_t)N + 3) / 4};
-    return measured([&](Arena &m) { eb == 8 ? (void)carve<double>(m, d) : (void)carve<float>(m, d); });
+    const patch::Dims d{(size_t)B, ((size_t)s.N + 3) / 4};
+    return measured([&](Arena &m) { s.eb == 8 ? (void)carve<double>(m, d) : (void)carve<float>(m, d); });
 }
 
 template <typename T>

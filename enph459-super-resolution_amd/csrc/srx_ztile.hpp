@@ -102,17 +102,18 @@ static inline bool axis_ok(const mosaic::AxisPlan &pl, int f)
     return pl.zero && nmax >= 0 && nmax <= 1 && nmin <= 0 && -nmin <= SW - 1 && -nmin <= f - 1;
 }
 
-static inline bool shape_admits(int elem_bytes, int H, int W) { return elem_bytes == 4 && H >= 128 && W >= 128; }
+static inline bool shape_admits(const IbpShape &s) { return s.eb == 4 && s.H >= 128 && s.W >= 128; }
 
-static inline bool eligible(int elem_bytes, int N, int H, int W, const double *sh, const double *k, int kh, int kw, int f)
+static inline bool eligible(const IbpSpec &s)
 {
-    if (!shape_admits(elem_bytes, H, W) || f < 2 || (call_flags() & SRX_FLAG_TILES))
+    const int f = s.f;
+    if (!shape_admits(s) || f < 2 || (s.flags & SRX_FLAG_TILES))
         return false;
     mosaic::AxisPlan py, px;
-    if (!mosaic::plan_axis(N, sh, 0, f, py) || !mosaic::plan_axis(N, sh, 1, f, px))
+    if (!mosaic::plan_axis(s.N, s.sh, 0, f, py) || !mosaic::plan_axis(s.N, s.sh, 1, f, px))
         return false;
     fused::Kernel7<float> kc;
-    fused::make_kernel7<float>(k, kh, kw, false, kc);
+    fused::make_kernel7<float>(s.k, s.kh, s.kw, false, kc, s.flags);
     // a PSF that is not rank 1 (the reference's --psf measured, mono_cal_target/run_sr.py:114-152) runs both 7 x 7 blurs in row
     // layout, rows = lanes: one block row per tile
     return (kc.separable || NSY == 1) && axis_ok(py, f) && axis_ok(px, f);
@@ -721,9 +722,9 @@ static Carved carve(Arena &ar, const Dims &d)
             ar.take<unsigned>(d.B * (d.WP / 2) * d.HP), ar.take<int>(d.B), ar.take<patch::AxisW>(2), ar.take<float>(112), ar.take<unsigned>(d.NT),
             ar.take<uint4>(d.ngrp * d.NT), ar.take<float2>(d.B * d.NT), ar.take<double>(d.B * d.ntiles), ar.take<double>(d.B * d.ntiles)};
 }
-static inline size_t tabs_bytes(int, int B, int N, int H, int W)
+static inline size_t tabs_bytes(const IbpShape &s, int B)
 {
-    return measured([&](Arena &m) { carve(m, dims_bound(B, N, H, W, VTY)); });
+    return measured([&](Arena &m) { carve(m, dims_bound(B, s.N, s.H, s.W, VTY)); });
 }
 
 // The state of a call between its launches: what iterate() keeps on its stack, and what a plan (srx_ibp_plan_*: the per-call tables built

@@ -95,6 +95,19 @@ def test_invalid_arguments_give_the_shared_calls_statuses(prec):
         got, want = _ibp(f"srx_ibp_items_{prec}", **kw), _ibp(f"srx_ibp_{prec}", **kw)
         assert got == want and got in (_lib.E_INVALID, _lib.E_UNSUPPORTED), (c, got, want)
     assert _ibp(f"srx_ibp_items_{prec}", 2, _lib_max_frames() + 1, bigp) == _lib.E_UNSUPPORTED
+    # the four places that check an ibp call -- the call, its per-item form, a plan and srx_ibp_path_for ("none" stands for a refusal
+    # there) -- answer one bad argument, and N = 33, alike: an invalid argument before a limit
+    k, kp = hd(synth.gaussian_psf())
+    for c, want in [(dict(sh=none_hd), _lib.E_INVALID), (dict(k=none_hd), _lib.E_INVALID), (dict(h=0), _lib.E_INVALID), (dict(f=0), _lib.E_INVALID),
+                    (dict(N=33, sh=bigp), _lib.E_UNSUPPORTED), (dict(N=33, sh=bigp, h=0), _lib.E_INVALID)]:
+        a = dict(B=2, N=4, sh=shp, k=kp, h=64, w=80, f=2)
+        a.update(c)
+        plan = ctypes.c_void_p()
+        got = [_ibp(f"srx_ibp_{prec}", **a), _ibp(f"srx_ibp_items_{prec}", **a),
+               getattr(lib(), f"srx_ibp_plan_create_{prec}")(FAKE, a["B"], a["N"], a["h"], a["w"], a["sh"], a["k"], 7, 7, FAKE, a["h"] * a["f"], a["w"] * a["f"],
+                                                            a["f"], 0.5, 0, a["h"] * a["f"], FAKE, 1 << 30, None, 0, ctypes.byref(plan))]
+        assert got == [want] * 3 and not plan.value, (c, got, want)
+        assert lib().srx_ibp_path_for(EB[prec], a["N"], a["h"], a["w"], a["h"] * a["f"], a["w"] * a["f"], a["f"], a["sh"], a["k"], 7, 7, 0) == b"none", c
     for c in [dict(lr=None), dict(out=None), dict(sh=none_hd), dict(B=0), dict(N=_lib_max_frames() + 1, sh=bigp)]:
         kw = dict(B=2, N=4, sh=shp)
         kw.update(c)

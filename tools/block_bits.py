@@ -6,6 +6,11 @@ once per build and compare the listings:
 
     SRX_LIB=old/libsrx.so python tools/block_bits.py > old.txt;  python tools/block_bits.py > new.txt;  diff old.txt new.txt
     python tools/block_bits.py --plan      # no GPU: the path the library would route every case to
+
+--flags prints a second list instead: one case per place below the entry points that reads a SRX_FLAG_DIAG_* switch of the call, each
+run with the flag off and with it on.  A run prints its path (asserted), the SHA-256 of its outputs and the launches per kernel id
+(srx_profile_get), so a flag that stops arriving where it is read changes the listing.  Compare the listings of two builds as above
+(--flags --plan: the routes, no GPU).
 """
 import hashlib
 import os
@@ -33,15 +38,89 @@ CASES += [("ztile", "ztile", "f32", 1, 2, 72, 140, synth.NOMINAL_5, "gauss", "u8
           ("btile", "btile", "f32", 1, 2, 32, 32, synth.MEASURED_4, "gauss", "u8"), ("atile", "atile", "f32", 1, 4, 40, 50, GRID16, "gauss", "u8")]
 
 
-def planned(prec, sh, psf, h, w, f):
+# (reader of the flag, call, path, precision, B, f, LR h, LR w, shifts, flags off, flag): the smallest shapes that reach each reader
+L = _lib
+FLAG_CASES = [("prefilter2d in shift_and_add", "saa", "fused", "f32", 2, 2, 64, 64, synth.NOMINAL_4, L.FLAG_PER_FRAME, L.FLAG_DIAG_NO_PREFILTER_TILE),
+              ("prefilter2d below the composed path", "ibp", "composed", "f32", 2, 2, 32, 32, synth.MEASURED_4, L.FLAG_COMPOSED, L.FLAG_DIAG_NO_PREFILTER_TILE),
+              ("use_v1", "ibp", "fused", "f64", 2, 2, 32, 32, synth.MEASURED_4, 0, L.FLAG_DIAG_V1),
+              ("make_kernel7", "ibp", "btile", "f32", 2, 2, 32, 32, synth.MEASURED_4, 0, L.FLAG_DIAG_NO_SEPARABLE),
+              ("mosaic::iterate zero fuse", "ibp", "mosaic", "f32", 2, 2, 72, 140, synth.NOMINAL_5, L.FLAG_TILES, L.FLAG_DIAG_NO_ZERO_FUSE),
+              ("patch::builds_itself", "ibp", "patch", "f32", 3, 4, 64, 64, GRID16, 0, L.FLAG_DIAG_NO_ZERO_FUSE),
+              ("patch::iterate byte loads", "ibp_u8", "patch", "f32", 3, 4, 64, 64, GRID16, 0, L.FLAG_DIAG_U8_BYTE_LOADS),
+              ("mosaic::saa", "saa", "mosaic", "f32", 2, 2, 64, 64, synth.NOMINAL_4, 0, L.FLAG_DIAG_SAA_ONE_PASS),
+              ("dtile::plan", "ibp", "dtile", "f32", 1, 4, 64, 80, GRID16, 0, L.FLAG_DIAG_WIDE_WINDOWS)]
+FLAGS_HEADER = """# one case per reader of a SRX_FLAG_DIAG_* switch below the entry points; every case with the flag off, then on
+# a case ends in 'off != on (what differs)' or in 'off == on'.  On the MI355X one case is indistinguishable by bits and launch counts:
+# 'patch::iterate byte loads', whose flag selects another instantiation of k_patch_build (same kernel id, same bits by design); the
+# kernel NAMES of a kernel trace of this run tell its two runs apart (k_patch_build<0, unsigned char, true> against <..., false>)
+# (SRX_FLAG_DIAG_V1's MSE trace is printed to 10 digits, not hashed: that iteration sums it with atomics, and two runs of one build differ
+# in its last bits)"""
+
+
+def planned(prec, sh, psf, h, w, f, flags=0, call="ibp"):
     sh = np.ascontiguousarray(np.asarray(sh, dtype=np.float64))
     k = np.ascontiguousarray(psf)
-    return _lib.load().srx_ibp_path_for(8 if prec == "f64" else 4, len(sh), h, w, h * f, w * f, f, sh.ctypes.data_as(_lib._HD),
-                                        k.ctypes.data_as(_lib._HD), k.shape[0], k.shape[1], 0).decode()
+    eb, shp = 8 if prec == "f64" else 4, sh.ctypes.data_as(_lib._HD)
+    if call == "saa":
+        return _lib.load().srx_saa_path_for(eb, len(sh), h, w, f, shp, flags).decode()
+    return _lib.load().srx_ibp_path_for(eb, len(sh), h, w, h * f, w * f, f, shp, k.ctypes.data_as(_lib._HD), k.shape[0], k.shape[1], flags).decode()
+
+
+def launches(lib):
+    """{kernel name: launches} since srx_profile_enable(1), the kernels that ran only"""
+    import ctypes
+    out = {}
+    for i in range(lib.srx_profile_kernel_count()):
+        ms, n = ctypes.c_double(), ctypes.c_long()
+        _lib.check(lib.srx_profile_get(i, ctypes.byref(ms), ctypes.byref(n)), "srx_profile_get")
+        if n.value:
+            out[lib.srx_profile_kernel_name(i).decode()] = n.value
+    return out
+
+
+def flag_cases(plan_only):
+    if not plan_only:
+        import torch
+        from sr_mi355x import api as S
+    lib, psf, bad = _lib.load(), PSFS["gauss"](), 0
+    print(FLAGS_HEADER)
+    for i, (name, call, want, prec, B, f, h, w, sh, base, flag) in enumerate(FLAG_CASES):
+        rng = np.random.default_rng(2000 + i)
+        lr = np.rint(rng.uniform(0, 255, (B, len(sh), h, w)))
+        hr0 = rng.uniform(0, 255, (B, h * f, w * f))
+        seen = []
+        for fl in (base, base | flag):
+            if plan_only:
+                got = planned(prec, sh, psf, h, w, f, fl, "saa" if call == "saa" else "ibp")
+                print(f"{name} flags={fl:#x}: {got}" + ("" if got == want else f"  (WANTED {want})"))
+                bad += got != want
+                continue
+            lib.srx_profile_enable(1)
+            if call == "saa":
+                outs = (S.shift_and_add_batched(lr, sh, f, precision=prec, flags=fl),)
+            elif call == "ibp_u8":
+                outs = S.ibp_u8_batched(lr.astype(np.uint8), sh, psf, hr0, f, 3, 0.5, precision=prec, flags=fl)
+            else:
+                outs = S.ibp_batched(lr, sh, psf, hr0, f, 3, 0.5, precision=prec, flags=fl)
+            torch.cuda.synchronize()
+            counts = launches(lib)
+            lib.srx_profile_enable(0)
+            assert S.last_path() == want, (name, fl, S.last_path())
+            digest = [hashlib.sha256(np.ascontiguousarray(t.cpu().numpy()).tobytes()).hexdigest() for t in outs]
+            if fl & L.FLAG_DIAG_V1:  # k_fwd_residual sums the trace with float64 atomics over an item's blocks: the last bits follow their order
+                digest[1] = "trace~" + ",".join(f"{v:.10g}" for v in outs[1].cpu().numpy().ravel())
+            seen.append((digest, counts))
+            print(f"{name} flags={fl:#x}: path={want} out={' '.join(digest)} launches={' '.join(f'{k}:{v}' for k, v in sorted(counts.items()))}", flush=True)
+        if not plan_only:
+            print(f"{name}: " + ("off == on" if seen[0] == seen[1] else "off != on (" + ", ".join(
+                w for w, d in (("bits", seen[0][0] != seen[1][0]), ("launches", seen[0][1] != seen[1][1])) if d) + ")"), flush=True)
+    return 1 if bad else 0
 
 
 def main(argv):
     plan_only = "--plan" in argv
+    if "--flags" in argv:
+        return flag_cases(plan_only)
     if not plan_only:
         import torch
         from sr_mi355x import api as S
