@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Randomised parity sweep: shift_and_add + ibp on random shapes / factors / frame sets / PSFs against the CPU oracle
+"""Randomised parity sweep: shift_and_add + ibp on random shapes / factors / frame sets / PSFs / steps against the CPU oracle
 (float64 tolerance 1e-8, float32 1e-3), every case through the auto-selected path and the composed path.
     python tools/fuzz_parity.py [n_cases] [seed]          (needs an MI355X; the oracle is only the checker)"""
 import os
@@ -72,8 +72,12 @@ def random_case(rng):
     return f, [(float(a), float(b)) for a, b in shifts], h, w, psf, n_iter, kind
 
 
+STEPS = (0.25, 0.3, 0.5, 1.0)
+
+
 def run(n_cases=100, seed=2026):
     rng = np.random.default_rng(seed)
+    step_rng = np.random.default_rng([seed, 1])  # a stream of its own: the shapes and frames of a given seed stay what they were
     O.set_threads(8)
     worst = {"f64": 0.0, "f32": 0.0}
     paths = {}
@@ -83,22 +87,23 @@ def run(n_cases=100, seed=2026):
         lr = np.clip(np.rint(rng.uniform(0, 255, (len(shifts), h, w))), 0, 255)
         if rng.uniform() < 0.25:  # a quarter of the cases with fractional samples: the float forms of the mosaic / operand planes
             lr = lr * 0.75 + 0.3
+        step = float(step_rng.choice(STEPS))  # after every other draw of the case
         saa_o = O.shift_and_add(list(lr), shifts, f)
-        hr_o, err_o = O.ibp(list(lr), shifts, psf, saa_o, f, n_iter, 0.5)
+        hr_o, err_o = O.ibp(list(lr), shifts, psf, saa_o, f, n_iter, step)
         for prec, tol in (("f64", 1e-8), ("f32", 1e-3)):
             S.set_precision(prec)
             for flags in (S.FLAG_AUTO, S.FLAG_COMPOSED):
                 saa = S.shift_and_add_batched(lr[None], shifts, f, flags=flags)[0].double().cpu().numpy()
                 p_saa = S.last_path()
                 import torch
-                hr, errs = S.ibp_batched(torch.from_numpy(lr)[None], shifts, psf, torch.from_numpy(saa_o)[None], f, n_iter, 0.5, flags=flags)
+                hr, errs = S.ibp_batched(torch.from_numpy(lr)[None], shifts, psf, torch.from_numpy(saa_o)[None], f, n_iter, step, flags=flags)
                 p_ibp = S.last_path()
                 d = max(float(np.abs(saa - saa_o).max()), float(np.abs(hr[0].double().cpu().numpy() - hr_o).max()))
                 e = float(np.max(np.abs(errs[0].cpu().numpy() - np.asarray(err_o)) / np.maximum(np.asarray(err_o), 1e-30)))
                 worst[prec] = max(worst[prec], d)
                 paths[(p_saa, p_ibp)] = paths.get((p_saa, p_ibp), 0) + 1
                 if not (d <= tol and e <= (1e-9 if prec == "f64" else 1e-4)):
-                    print(f"FAIL case {ci} {prec} flags={flags} kind={kind} f={f} N={len(shifts)} h={h} w={w} psf={psf.shape} it={n_iter} "
+                    print(f"FAIL case {ci} {prec} flags={flags} kind={kind} f={f} N={len(shifts)} h={h} w={w} psf={psf.shape} it={n_iter} step={step} "
                           f"paths={p_saa}/{p_ibp} max|d|={d:.3e} trace rel={e:.3e}\n  shifts={shifts}")
                     return 1
         if ci % 10 == 9:
