@@ -14,6 +14,7 @@
 #include "srx_metrics.hpp"
 #include "srx_psf.hpp"
 #include "srx_register.hpp"
+#include "srx_mean.hpp"
 
 using namespace srx;
 
@@ -901,6 +902,17 @@ int srx_decimate_u8(const uint8_t *in, int B, int H, int W, int f, int py, int p
     hipLaunchKernelGGL(k_decimate<uint8_t>, dim3(cdiv(w, 64), cdiv(h, 4), B), dim3(64, 4), 0, hs(s), in, H, W, f, py, px, h, w, out);
     SRX_CHECK_LAUNCH();
     return SRX_OK;
+}
+
+int srx_mean_u8(const uint8_t *in, int B, int R, int H, int W, int f, int py, int px, int out_elem_bytes, void *out, srx_stream_t s)
+{
+    if (!in || !out || B <= 0 || R <= 0 || H <= 0 || W <= 0 || f <= 0 || py < 0 || px < 0 || py >= H || px >= W ||
+        (out_elem_bytes != 4 && out_elem_bytes != 8))
+        return SRX_E_INVALID;
+    if (R > 65535 || B > 65535 || (size_t)R * H * W >= ((size_t)1 << 31))
+        return SRX_E_UNSUPPORTED;
+    return out_elem_bytes == 4 ? mean::mean_u8<float>(in, B, R, H, W, f, py, px, (float *)out, hs(s))
+                               : mean::mean_u8<double>(in, B, R, H, W, f, py, px, (double *)out, hs(s));
 }
 
 int srx_interleave4_u8(const uint8_t *frames, int B, int h, int w, uint8_t *out, srx_stream_t s)

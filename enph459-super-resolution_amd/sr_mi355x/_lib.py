@@ -76,6 +76,7 @@ _PLAIN = {
     "srx_ibp_items_workspace_bytes": (_Z, [_I, _I, _I, _I, _I, _I, _I, _I, _U]),
     "srx_ibp_items_workspace_bytes_for": (_Z, [_I, _I, _I, _I, _I, _I, _I, _I, _HD, _HD, _I, _I, _U]),
     "srx_decimate_u8": (_I, [_P, _I, _I, _I, _I, _I, _I, _P, _P]),
+    "srx_mean_u8": (_I, [_P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P]),
     "srx_ibp_path_for": (_c.c_char_p, [_I, _I, _I, _I, _I, _I, _I, _HD, _HD, _I, _I, _U]),
     "srx_saa_path_for": (_c.c_char_p, [_I, _I, _I, _I, _I, _HD, _U]),
     "srx_ibp_plan_workspace_bytes": (_Z, [_I, _I, _I, _I, _I, _I, _I, _I, _U]),

@@ -499,6 +499,21 @@ def mean_frames_batched(stacks):
     return _out(out, was_np)
 
 
+def mean_u8(stack_u8, f=1, py=0, px=0, precision=None):
+    """The mean over R uint8 frames of the samples at [py::f, px::f]: uint8 [B, R, H, W] -> device tensor [B, h, w] of the compute
+    precision (srx_mean_u8).  f=2 is the rep mean of the Bayer red planes (rgb_cal_target/run_sr.py:73-75, 107-108), f=1
+    np.mean(lr_frames, 0) (run_sr.py:274); the same bits as mean_frames_batched on decimate on u8_to_float, without the float frames."""
+    prec = precision or get_precision()
+    B, R, H, W = _shape4(stack_u8, "stack_u8")
+    x = _u8_dev(stack_u8, "stack_u8", 4)
+    f, py, px = int(f), int(py), int(px)
+    if f <= 0 or not (0 <= py < H and 0 <= px < W):
+        raise ValueError("mean_u8 needs f > 0, 0 <= py < H and 0 <= px < W")
+    out = torch.empty((B, -(-(H - py) // f), -(-(W - px) // f)), dtype=_TORCH_DT[prec], device=x.device)
+    _lib.check(_lib.load().srx_mean_u8(_p(x), B, R, H, W, f, py, px, _ELEM[prec], _p(out), _stream()), "srx_mean_u8")
+    return out
+
+
 def quantize_u8(img):
     """np.clip(img, 0, 255).astype(np.uint8): clamp, then truncate (run_sr.py:303)."""
     x, was_np = _to_dev(img, get_precision())

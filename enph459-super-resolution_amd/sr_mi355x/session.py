@@ -91,10 +91,14 @@ def _to_dev_frames(decoded, keep_u8):
     return [_to_dev_f(a) for a in decoded]
 
 
-def _frames_f64(lr):
-    """float64 view of a frame stack for the loaders' arithmetic (the frame mean): the stack itself, or the bytes converted (exact)"""
+def _frame_mean(lr):
+    """np.mean over the frames of [B, N, h, w] in LOADER_PRECISION -> [B, h, w]: float64 stacks through mean_frames_batched, uint8 stacks
+    (keep_u8 loaders) as bytes through mean_u8 (the same bits, no float copy of the frames)"""
     import torch
-    return api.u8_to_float(lr, precision=LOADER_PRECISION) if lr.dtype == torch.uint8 else lr
+    if lr.dtype == torch.uint8:
+        return api.mean_u8(lr, precision=LOADER_PRECISION)
+    with _loader_precision():
+        return api.mean_frames_batched(lr)
 
 
 def load_gray_dev(path, decoded=None):
@@ -122,8 +126,12 @@ def load_mono_cal_session(session_dir, keep_u8=False):
     return frames, shifts
 
 
-def load_rgb_cal_combo(combo_dir):
-    """rgb_cal_target/run_sr.py:78-113: red plane of every rep, mean over reps, shifts = metadata px / 2."""
+def load_rgb_cal_combo(combo_dir, keep_u8=False):
+    """rgb_cal_target/run_sr.py:78-113: red plane of every rep, mean over reps, shifts = metadata px / 2.
+    keep_u8, and every file 8-bit greyscale: the reps go up as bytes and mean_u8(f=2) forms each corner's frame from them -- the four
+    corners in one call when they have the same number of reps -- which is the same float64 frame, bit for bit.  A colour file (load_gray's
+    channel mean is not an integer) keeps the whole combo on the float64 path, as in load_corner_reps."""
+    import torch
     with open(os.path.join(combo_dir, "metadata.json")) as fp:
         meta = json.load(fp)
 
@@ -136,15 +144,32 @@ def load_rgb_cal_combo(combo_dir):
             return c["expected_dy_px"] / 2.0, c["expected_dx_px"] / 2.0
         raise KeyError(f"Cannot find shift for {label} in metadata")
 
-    frames, shifts = [], []
+    counts, paths, shifts = [], [], []
     for idx, label in enumerate(CORNER_ORDER):
         reps = sorted(f for f in os.listdir(combo_dir) if f.startswith(f"corner{idx}_rep") and f.endswith(".png"))
         if not reps:
             raise FileNotFoundError(f"No images for corner{idx} in {combo_dir}")
-        with _loader_precision():
-            reds = [api.extract_red(_to_dev_f(a)) for a in _decode_many([os.path.join(combo_dir, r) for r in reps])]
-            frames.append(api.mean_frames(reds))
+        counts.append(len(reps))
+        paths += [os.path.join(combo_dir, r) for r in reps]
         shifts.append(get_shift(label))
+    decoded = _decode_many(paths)
+    starts = np.concatenate([[0], np.cumsum(counts)])
+    corners = [decoded[starts[k]:starts[k + 1]] for k in range(len(counts))]
+    if keep_u8 and all(a.dtype == np.uint8 for a in decoded):
+        def reps_dev(groups):  # [len(groups), R, H, W] on the device, every file uploaded as its own bytes
+            dev = torch.empty((len(groups), len(groups[0])) + groups[0][0].shape, dtype=torch.uint8, device=api._device())
+            for k, files in enumerate(groups):
+                for r, a in enumerate(files):
+                    dev[k, r].copy_(torch.from_numpy(np.ascontiguousarray(a)))
+            return dev
+
+        if len(set(counts)) == 1:  # one B = 4 call
+            return list(api.mean_u8(reps_dev(corners), f=2, precision=LOADER_PRECISION)), shifts
+        return [api.mean_u8(reps_dev([c]), f=2, precision=LOADER_PRECISION)[0] for c in corners], shifts
+    frames = []
+    with _loader_precision():
+        for c in corners:
+            frames.append(api.mean_frames([api.extract_red(_to_dev_f(a)) for a in c]))
     return frames, shifts
 
 
@@ -182,8 +207,7 @@ def reconstruct(frames, shifts, psf_kernel, n_iter, factor=UPSAMPLE_FACTOR, step
     import torch
     lr64 = torch.stack(frames)  # float64, or uint8 frames (keep_u8 loaders): SAA and IBP then take the bytes themselves
     u8 = lr64.dtype == torch.uint8
-    with _loader_precision():
-        mean_lr = api.mean_frames(_frames_f64(lr64))  # float64; also what LR_(red_)mean.png is quantised from
+    mean_lr = _frame_mean(lr64[None])[0]  # float64; also what LR_(red_)mean.png is quantised from
     native = api.zoom_batched(mean_lr[None], factor)[0]
     if u8 and not row_bands:
         saa = api.shift_and_add_u8_batched(lr64[None], shifts, factor)
@@ -242,8 +266,7 @@ def reconstruct_batch(frame_sets, shifts, psf_kernel, n_iter, factor=UPSAMPLE_FA
     shifts = np.asarray(shifts, dtype=np.float64)
     if shifts.shape not in ((N, 2), (B, N, 2)):
         raise ValueError(f"shifts must be one table {(N, 2)} or one per frame set {(B, N, 2)}, not {shifts.shape}")
-    with _loader_precision():
-        mean_lr = api.mean_frames_batched(_frames_f64(lr64))
+    mean_lr = _frame_mean(lr64)
     native = api.zoom_batched(mean_lr, factor)
     if lr64.dtype == torch.uint8:
         saa = api.shift_and_add_u8_batched(lr64, shifts, factor)
@@ -440,7 +463,7 @@ def process_session(session_dir, psf_kernel, output_base, kind=None, n_iter=None
             frames, shifts = loaded or load_mono_cal_session(session_dir, keep_u8=keep_u8)
             lr_name, extra = "LR_mean.png", None
         else:
-            frames, shifts = loaded or load_rgb_cal_combo(session_dir)
+            frames, shifts = loaded or load_rgb_cal_combo(session_dir, keep_u8=keep_u8)
             lr_name = "LR_red_mean.png"
             extra = {"shifts.json": {"shifts_lr_yx": [list(s) for s in shifts], "corner_labels": CORNER_ORDER}}
         if register:
@@ -491,11 +514,12 @@ def process_session(session_dir, psf_kernel, output_base, kind=None, n_iter=None
 
 def load_session(session_dir, kind, keep_u8=False):
     """The host + upload half of process_session (what a Prefetcher runs ahead): decoded frames on the device.  keep_u8: as uint8 where
-    the kind's frames are the camera's samples (rgb_cal_target averages its reps: float64 either way)."""
+    the kind's frames are the camera's samples (rgb_cal_target averages its reps: float64 frames either way, formed from the bytes by
+    mean_u8 with keep_u8)."""
     if kind == "mono_cal_target":
         return load_mono_cal_session(session_dir, keep_u8=keep_u8)
     if kind == "rgb_cal_target":
-        return load_rgb_cal_combo(session_dir)
+        return load_rgb_cal_combo(session_dir, keep_u8=keep_u8)
     return load_corner_reps(session_dir, kind == "rgb_barcodes", keep_u8=keep_u8)
 
 

@@ -214,8 +214,8 @@ int srx_ibp_f64(const double *lr, int B, int N, int h, int w, const double *shif
  * align_up(min(B, 32768) N h w sizeof(T)) (256-byte granules) on the others; srx_ibp_u8lr_workspace_bytes (shape only) covers both.
  * srx_saa_u8lr_workspace_bytes = srx_saa_workspace_bytes + align_up(Bc N h w sizeof(T)), Bc = the items of one chunk (B, or
  * max(32768 / N, 1) when B N > 32768), on every route: the query has no shift table to tell them apart.
- * Registration reads the bytes as well (srx_register_u8_*, with srx_register_* below) and srx_psf_estimate_u8 the pinhole frames: every
- * stage that touches the camera's frames has a uint8 form. */
+ * Registration reads the bytes as well (srx_register_u8_*, with srx_register_* below), srx_psf_estimate_u8 the pinhole frames and srx_mean_u8
+ * (with the index maps below) the reps and frames that are averaged: every stage that touches the camera's frames has a uint8 form. */
 size_t srx_saa_u8lr_workspace_bytes(int elem_bytes, int B, int N, int h, int w, int factor);
 int srx_saa_u8lr_f32(const uint8_t *lr, int B, int N, int h, int w, const double *shifts_yx, int factor, float *out, void *ws,
                      size_t ws_bytes, srx_stream_t stream, unsigned flags);
@@ -319,6 +319,22 @@ int srx_u8_to_f32(const uint8_t *in, size_t n, float *out, srx_stream_t stream);
 int srx_u8_to_f64(const uint8_t *in, size_t n, double *out, srx_stream_t stream);
 int srx_quantize_u8_f32(const float *in, size_t n, uint8_t *out, srx_stream_t stream);
 int srx_quantize_u8_f64(const double *in, size_t n, uint8_t *out, srx_stream_t stream);
+
+/* ---- rep / frame mean on the camera's own samples: rgb_cal_target/run_sr.py:73-75 + 107-108 (f = 2, py = px = 0: the
+ * Bayer red plane of every rep, averaged), mono_cal_target/run_sr.py:274 (f = 1: np.mean(lr_frames, 0)) ----
+ * in uint8 [B, R, H, W] -> out T [B, h, w], h = ceil((H - py) / f), w = ceil((W - px) / f); T is float for out_elem_bytes 4 and double
+ * for 8.  out[b, i, j] = (T)sum_r in[b, r, py + i f, px + j f] / (T)R: exactly the bits of srx_mean_frames_T on srx_decimate_T on
+ * srx_u8_to_T of the frames.  Every partial sum of that chain is an integer of at most 255 R, exact in T (R <= 65535: below 2^24), so the
+ * order of the additions does not matter and the one division is the only rounding.
+ * No workspace, no allocation: one kernel launch on `stream`, no host synchronisation, capture-safe like the index maps above.
+ * `in` needs byte alignment only and `out` the alignment of T (frame r of a stack of odd H W starts on any byte, and so does a row of odd
+ * W): for f = 1 and f = 2 with H W a multiple of 16 every row peels a scalar head and tail around its own aligned 16-byte reads, and a
+ * lane stores 16 bytes at once only where it finds the address aligned; every other shape goes sample by sample.
+ * SRX_E_INVALID: a null pointer; B, R, H, W or f <= 0; py outside [0, H) or px outside [0, W); out_elem_bytes not 4 or 8.
+ * SRX_E_UNSUPPORTED: R > 65535 (the float sum would no longer be exact), B > 65535, one item's R H W of 2 GiB or more.  Both are
+ * decided on the host before any HIP call. */
+int srx_mean_u8(const uint8_t *in, int B, int R, int H, int W, int f, int py, int px, int out_elem_bytes /* 4, 8 */, void *out,
+                srx_stream_t stream);
 
 /* ---- 4-frame pixel interleave of the vendor live view (opt_materials/software/XPR_Software.py:196-205, 388-410) ----
  * frames uint8 [B, 4, h, w] -> out uint8 [B, 2h, 2w]: frame k zero-inserted at [::2, ::2], translated by the integer
