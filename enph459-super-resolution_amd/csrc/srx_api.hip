@@ -15,6 +15,7 @@
 #include "srx_psf.hpp"
 #include "srx_register.hpp"
 #include "srx_mean.hpp"
+#include "srx_png.hpp"
 
 using namespace srx;
 
@@ -913,6 +914,23 @@ int srx_mean_u8(const uint8_t *in, int B, int R, int H, int W, int f, int py, in
         return SRX_E_UNSUPPORTED;
     return out_elem_bytes == 4 ? mean::mean_u8<float>(in, B, R, H, W, f, py, px, (float *)out, hs(s))
                                : mean::mean_u8<double>(in, B, R, H, W, f, py, px, (double *)out, hs(s));
+}
+
+size_t srx_png_stream_bound(int H, int W) { return H > 0 && W > 0 ? png::stream_bound((size_t)H * ((size_t)W + 1)) : 0; }
+
+size_t srx_png_scratch_bytes(int B, int H, int W) { return png::scratch_bytes(B, H, W); }
+
+int srx_png_deflate_u8(const uint8_t *img, int B, int H, int W, void *streams, void *lengths, void *ws, size_t wsb, srx_stream_t s)
+{
+    return png::deflate(img, B, H, W, streams, lengths, ws, wsb, hs(s));
+}
+int srx_png_deflate_f32(const float *img, int B, int H, int W, void *streams, void *lengths, void *ws, size_t wsb, srx_stream_t s)
+{
+    return png::deflate(img, B, H, W, streams, lengths, ws, wsb, hs(s));
+}
+int srx_png_deflate_f64(const double *img, int B, int H, int W, void *streams, void *lengths, void *ws, size_t wsb, srx_stream_t s)
+{
+    return png::deflate(img, B, H, W, streams, lengths, ws, wsb, hs(s));
 }
 
 int srx_interleave4_u8(const uint8_t *frames, int B, int h, int w, uint8_t *out, srx_stream_t s)

@@ -491,14 +491,18 @@ template <typename T> __global__ void __launch_bounds__(256) k_u8_to(const uint8
         out[i] = (T)in[i];
 }
 
+// one sample of srx_quantize_u8_T (srx_png_deflate_T quantises with it as it reads)
+template <typename T> __device__ __forceinline__ uint8_t quantize_one(T v)
+{
+    v = v < (T)0 ? (T)0 : (v > (T)255 ? (T)255 : v);  // np.clip
+    return (uint8_t)v;                                // astype(uint8): truncation
+}
+
 template <typename T>
 __global__ void __launch_bounds__(256) k_quantize_u8(const T *__restrict__ in, size_t n, uint8_t *__restrict__ out)
 {
-    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) {
-        T v = in[i];
-        v = v < (T)0 ? (T)0 : (v > (T)255 ? (T)255 : v);  // np.clip
-        out[i] = (uint8_t)v;                              // astype(uint8): truncation
-    }
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256)
+        out[i] = quantize_one(in[i]);
 }
 
 // 4-frame pixel interleave of the vendor live view (opt_materials/software/XPR_Software.py:196-205, 388-410):

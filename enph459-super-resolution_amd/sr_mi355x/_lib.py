@@ -52,6 +52,7 @@ _TYPED = {
     "srx_register_{T}": (_I, [_P, _I, _I, _I, _I, _I, _HD, _I, _I, _I, _D, _P, _P, _P, _P, _Z, _P]),
     "srx_register_u8_{T}": (_I, [_P, _I, _I, _I, _I, _I, _HD, _I, _I, _I, _D, _P, _P, _P, _P, _Z, _P]),
     "srx_psf_estimate_{T}": (_I, [_P, _I, _I, _I, _I, _P, _P, _P, _Z, _P]),
+    "srx_png_deflate_{T}": (_I, [_P, _I, _I, _I, _P, _P, _P, _Z, _P]),
 }
 _PLAIN = {
     "srx_version": (_I, []),
@@ -90,6 +91,9 @@ _PLAIN = {
     "srx_register_workspace_bytes": (_Z, [_I, _I, _I, _I, _I, _I]),
     "srx_psf_estimate_workspace_bytes": (_Z, [_I, _I, _I, _I, _I]),
     "srx_psf_estimate_u8": (_I, [_P, _I, _I, _I, _I, _P, _P, _P, _Z, _P]),
+    "srx_png_stream_bound": (_Z, [_I, _I]),
+    "srx_png_scratch_bytes": (_Z, [_I, _I, _I]),
+    "srx_png_deflate_u8": (_I, [_P, _I, _I, _I, _P, _P, _P, _Z, _P]),
 }
 
 

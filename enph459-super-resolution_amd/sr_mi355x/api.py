@@ -522,6 +522,40 @@ def quantize_u8(img):
     return out.cpu().numpy() if was_np else out
 
 
+def png_deflate(images):
+    """The zlib streams of the 8-bit greyscale PNGs of `images` (srx_png_deflate_*): a [B, H, W] or [H, W] tensor / array, uint8 or float.
+    Float images are quantised as quantize_u8 does (the working precision's arithmetic) while they are read; no uint8 plane is made.
+    -> (streams uint8 [B, srx_png_stream_bound(H, W)], lengths int64 [B]) on the device, nothing synchronised: bytes [0, lengths[b]) of
+    row b inflate to the Up-filtered scanlines of image b, and session.png_container(W, H, those bytes) is the file."""
+    is_u8 = (images.dtype == torch.uint8) if isinstance(images, torch.Tensor) else (np.asarray(images).dtype == np.uint8)
+    if is_u8:
+        x = images if isinstance(images, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(images))
+        x, fn = x.to(device=_device()).contiguous(), _lib.load().srx_png_deflate_u8
+    else:
+        x, fn = _to_dev(images, get_precision())[0], _fn("srx_png_deflate", get_precision())
+    if x.dim() == 2:
+        x = x[None]
+    if x.dim() != 3:
+        raise ValueError("images must have the shape [B, H, W] or [H, W]")
+    B, H, W = (int(v) for v in x.shape)
+    lib = _lib.load()
+    streams = torch.empty((B, lib.srx_png_stream_bound(H, W)), dtype=torch.uint8, device=x.device)
+    lengths = torch.empty((B,), dtype=torch.int64, device=x.device)
+    ws, wsp, wsn = _ws(lib.srx_png_scratch_bytes(B, H, W))
+    _lib.check(fn(_p(x), B, H, W, _p(streams), _p(lengths), wsp, wsn, _stream()), "srx_png_deflate")
+    return streams, lengths
+
+
+def png_encode(images):
+    """-> a list of bytes, one complete PNG file per image of `images` (png_deflate's argument): the device's streams, downloaded and
+    wrapped by session.png_container.  A convenience: it synchronises."""
+    from . import session
+    streams, lengths = png_deflate(images)
+    H, W = (int(v) for v in images.shape[-2:])
+    host, n = streams.cpu().numpy(), lengths.cpu().tolist()
+    return [session.png_container(W, H, host[b, :n[b]].tobytes()) for b in range(len(n))]
+
+
 def u8_to_float(img_u8, precision=None):
     """uint8 frame -> float on the device (load_gray's cast, run_sr.py:73-75)."""
     prec = precision or get_precision()

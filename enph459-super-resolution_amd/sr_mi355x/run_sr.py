@@ -43,6 +43,9 @@ def main(argv=None):
                     help="keep the 8-bit frames as bytes on the device (every kind): shift_and_add and ibp read them through srx_saa_u8lr / "
                          "srx_ibp_u8lr, with --register registration through srx_register_u8, and the frame mean and rgb_cal_target's rep "
                          "mean of the red planes through srx_mean_u8; the files written are the same")
+    ap.add_argument("--png-on-device", action="store_true",
+                    help="compress the output PNGs on the device (srx_png_deflate: quantise, Up filter, run lengths and Huffman coding per "
+                         "32 KB chunk); the host only adds the container and its CRC-32.  Same pixels in every file, other bytes")
     args = ap.parse_args(argv)
     rank, world, local_rank = int(os.environ.get("RANK", "0")), int(os.environ.get("WORLD_SIZE", "1")), int(os.environ.get("LOCAL_RANK", "0"))
     dist = None
@@ -71,7 +74,7 @@ def main(argv=None):
     metrics_cb = session.write_metrics_device if (args.metrics and args.kind == "mono_cal_target") else None
     session.process_sessions(sessions, psf, args.output_dir, args.kind, rank=rank, world=world, on_images=metrics_cb,
                              row_bands=args.row_bands and world > 1, register=args.register,
-                             keep_u8=args.u8_frames)
+                             keep_u8=args.u8_frames, device_png=args.png_on_device)
     if dist is not None:
         dist.barrier()
     if rank == 0:

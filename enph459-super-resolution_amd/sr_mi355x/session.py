@@ -347,7 +347,6 @@ def write_png_u8(path, arr):
     1536 x 2048 plane -- the files-to-files rate of a session is exactly this work.  Here: the Up filter on the whole image as one
     numpy subtraction and one zlib pass with run-length matching only (Z_RLE: on Up-filtered reconstructions within 8 % of PIL's file
     size at level 1, in 0.4x its time -- measured on the reference's committed 3072 x 4096 SAA.png: 118 against 298 ms)."""
-    import struct
     import zlib
     a = np.ascontiguousarray(arr)
     if a.ndim != 2 or a.dtype != np.uint8:
@@ -361,12 +360,21 @@ def write_png_u8(path, arr):
     np.subtract(a[1:], a[:-1], out=raw[1:, 1:])  # modulo 256
     c = zlib.compressobj(PNG_COMPRESS_LEVEL, zlib.DEFLATED, 15, 9, zlib.Z_RLE)
     z = c.compress(raw) + c.flush()
+    with open(path, "wb") as fp:
+        fp.write(png_container(w, h, z))
+
+
+def png_container(w, h, zstream):
+    """The bytes of an 8-bit greyscale PNG file around the zlib stream of its scanlines: signature, IHDR, one IDAT, IEND.  The stream is
+    write_png_u8's own or the device's (api.png_deflate); the chunks' CRC-32 is host work either way (zlib.crc32 releases the GIL and
+    takes a few ms on the few MB of a 3072 x 4096 plane)."""
+    import struct
+    import zlib
 
     def chunk(tag, data):
-        return struct.pack(">I", len(data)) + tag + data + struct.pack(">I", zlib.crc32(tag + data) & 0xffffffff)
+        return struct.pack(">I", len(data)) + tag + data + struct.pack(">I", zlib.crc32(data, zlib.crc32(tag)) & 0xffffffff)
 
-    with open(path, "wb") as fp:
-        fp.write(b"\x89PNG\r\n\x1a\n" + chunk(b"IHDR", struct.pack(">IIBBBBB", w, h, 8, 0, 0, 0, 0)) + chunk(b"IDAT", z) + chunk(b"IEND", b""))
+    return b"\x89PNG\r\n\x1a\n" + chunk(b"IHDR", struct.pack(">IIBBBBB", w, h, 8, 0, 0, 0, 0)) + chunk(b"IDAT", bytes(zstream)) + chunk(b"IEND", b"")
 
 
 def _writer_pool():
@@ -385,11 +393,13 @@ def flush_writes():
         f.result()
 
 
-def _save_outputs(out_dir, images, errors, lr_name, extra=None):
+def _save_outputs(out_dir, images, errors, lr_name, extra=None, device_png=False):
     """Quantise on the device (clip + truncate, run_sr.py:303), queue the copies of the uint8 planes into pinned host buffers and hand
     the PNG encoding to worker threads, which wait for the copies' event -- the calling thread waits for nothing and goes on to queue the
     next item's device work.  `errors`: the MSE trace, a list or a device tensor (downloaded with the planes).  done.flag is written by
-    the last job of the directory, after every file of it exists."""
+    the last job of the directory, after every file of it exists.
+    device_png: the device compresses as well (api.png_deflate: same pixels in the files, other bytes); the jobs only wrap the streams
+    (png_container: the CRC-32) and write."""
     import torch
     os.makedirs(out_dir, exist_ok=True)
 
@@ -400,9 +410,21 @@ def _save_outputs(out_dir, images, errors, lr_name, extra=None):
         h.copy_(t, non_blocking=True)
         return h
 
-    planes = {f"{name}.png": to_host(api.quantize_u8(images[name])) for name in ("native_2x", "SAA", "SAA_IBP")}
-    with _loader_precision():
-        planes[lr_name] = to_host(api.quantize_u8(images["LR_mean"]))
+    hr_names = ("native_2x", "SAA", "SAA_IBP")
+    if device_png:
+        # the three HR planes as one [3, H, W] call on the float tensors (quantised as they are read), LR_mean as a second one in the
+        # loader's precision; what goes to the host is the slots and their lengths, and a job slices, wraps and writes
+        hr = torch.stack([images[name] for name in hr_names])
+        streams, lengths = api.png_deflate(hr)
+        with _loader_precision():
+            lr_streams, lr_lengths = api.png_deflate(images["LR_mean"])
+        hr_host, hr_len, lr_host, lr_len = to_host(streams), to_host(lengths), to_host(lr_streams), to_host(lr_lengths)
+        planes = {f"{name}.png": (hr_host, hr_len, k, tuple(hr.shape[1:])) for k, name in enumerate(hr_names)}
+        planes[lr_name] = (lr_host, lr_len, 0, tuple(images["LR_mean"].shape))
+    else:
+        planes = {f"{name}.png": to_host(api.quantize_u8(images[name])) for name in hr_names}
+        with _loader_precision():
+            planes[lr_name] = to_host(api.quantize_u8(images["LR_mean"]))
     err_host = to_host(errors) if isinstance(errors, torch.Tensor) else None
     ready = None
     if torch.cuda.is_available():
@@ -427,7 +449,12 @@ def _save_outputs(out_dir, images, errors, lr_name, extra=None):
     def job(fname, host):
         if ready is not None:
             ready.synchronize()
-        write_png_u8(os.path.join(out_dir, fname), host.numpy())
+        if device_png:
+            slots, lens, k, (h, w) = host
+            with open(os.path.join(out_dir, fname), "wb") as fp:
+                fp.write(png_container(w, h, slots[k, :int(lens[k])].numpy().tobytes()))
+        else:
+            write_png_u8(os.path.join(out_dir, fname), host.numpy())
         with lock:
             left[0] -= 1
             last = left[0] == 0
@@ -439,14 +466,15 @@ def _save_outputs(out_dir, images, errors, lr_name, extra=None):
 
 
 def process_session(session_dir, psf_kernel, output_base, kind=None, n_iter=None, verbose=True, batch_reps=True, loaded=None, flush=True,
-                    row_bands=False, on_images=None, register=False, keep_u8=False):
+                    row_bands=False, on_images=None, register=False, keep_u8=False, device_png=False):
     """Counterpart of process_session / process_combo.  Returns the list of output directories written
     (empty if everything was already done).  batch_reps: the reps of a barcode session that are still to do go through the
     library in one B = reps call (reconstruct_batch) instead of one call per rep (with register, every rep under its own table); `loaded`: frames already decoded by a
     Prefetcher (what load_corner_reps / load_mono_cal_session / load_rgb_cal_combo would return).  row_bands (the two cal_target
     kinds: one large image per session): all ranks work on this one session (reconstruct(row_bands=True)), rank 0 writes.
     register: reconstruct with shifts estimated from the frames (register_shifts) and write registration.json beside the PNGs.
-    keep_u8 (run_sr --u8-frames): the frames this call loads itself stay uint8 on the device; the files written are the same."""
+    keep_u8 (run_sr --u8-frames): the frames this call loads itself stay uint8 on the device; the files written are the same.
+    device_png (run_sr --png-on-device): the PNGs' streams are compressed on the device (_save_outputs): the same pixels in every file."""
     kind = kind or detect_kind(session_dir)
     if kind not in IBP_ITERATIONS:
         raise ValueError("kind must be one of " + ", ".join(IBP_ITERATIONS))
@@ -472,7 +500,7 @@ def process_session(session_dir, psf_kernel, output_base, kind=None, n_iter=None
         images, errors = reconstruct(frames, shifts, psf_kernel, n_iter, row_bands=row_bands)
         if images["SAA_IBP"] is None:  # row-band mode, not rank 0: the assembled image lives on rank 0
             return written
-        _save_outputs(out_dir, images, errors, lr_name, extra)
+        _save_outputs(out_dir, images, errors, lr_name, extra, device_png=device_png)
         if on_images:  # (the device tensors the PNGs were quantised from: metrics without reading the files back)
             on_images(out_dir, images)
         if flush:
@@ -504,7 +532,7 @@ def process_session(session_dir, psf_kernel, output_base, kind=None, n_iter=None
     else:
         results = [reconstruct(fr, shifts, psf_kernel, n_iter) for _, fr in todo]
     for (out_dir, _), (images, errors), extra in zip(todo, results, extras):
-        _save_outputs(out_dir, images, errors, "LR_red_mean.png" if red else "LR_mean.png", extra)
+        _save_outputs(out_dir, images, errors, "LR_red_mean.png" if red else "LR_mean.png", extra, device_png=device_png)
         say(f"    Output: {out_dir}")
         written.append(out_dir)
     if flush:
@@ -524,7 +552,7 @@ def load_session(session_dir, kind, keep_u8=False):
 
 
 def process_sessions(sessions, psf_kernel, output_base, kind, n_iter=None, verbose=True, rank=0, world=1, on_written=None, row_bands=False,
-                     on_images=None, register=False, keep_u8=False):
+                     on_images=None, register=False, keep_u8=False, device_png=False):
     """The reference's outer loop (mono_cal_target/run_sr.py:358-360, mono_barcodes/run_sr.py:301) over the sessions this
     rank owns (session i -> rank i mod world, parallel.map_sharded: independent items, no data-path collective), with the PNG
     decode and upload of session k + 1 overlapped with the device work of session k.  -> output directories written: by every
@@ -553,7 +581,7 @@ def process_sessions(sessions, psf_kernel, output_base, kind, n_iter=None, verbo
         count[0] += 1
         say(f"\n[rank {rank}: {count[0]}/{len(owned)}] {os.path.basename(sessions[i])}")
         out = process_session(sessions[i], psf_kernel, output_base, kind=kind, n_iter=n_iter, verbose=verbose, loaded=loaded,
-                              flush=on_written is not None, row_bands=row_bands, on_images=on_images, register=register)
+                              flush=on_written is not None, row_bands=row_bands, on_images=on_images, register=register, device_png=device_png)
         if on_written:
             for d in out:
                 on_written(d)

@@ -336,6 +336,35 @@ int srx_quantize_u8_f64(const double *in, size_t n, uint8_t *out, srx_stream_t s
 int srx_mean_u8(const uint8_t *in, int B, int R, int H, int W, int f, int py, int px, int out_elem_bytes /* 4, 8 */, void *out,
                 srx_stream_t stream);
 
+/* ---- the output PNGs' compressed stream, built on the device: the encoder half of cv2.imwrite / session.write_png_u8
+ * (mono_barcodes/run_sr.py:303-306) ----
+ * img T [B, H, W] -> streams uint8 [B][srx_png_stream_bound(H, W)], lengths int64 [B] (both DEVICE arrays, any byte address).  Bytes
+ * [0, lengths[b]) of slot b are a complete zlib stream (RFC 1950 / 1951) that inflates to the PNG scanlines of image b: H rows of 1 + W
+ * bytes, filter byte 2 (Up: the sample minus the one above it modulo 256, row 0 against zeros).  A host wraps it with the PNG signature,
+ * IHDR, one IDAT and IEND (session.png_container; the IDAT's CRC-32 stays on the host) and has the file.  The float forms quantise as they
+ * read, with srx_quantize_u8_T's arithmetic (clamp, then truncate: the same device function, so the same byte for every input); no uint8
+ * plane exists in between.
+ * Stream: 78 01; the H (W + 1) scanline bytes in chunks of SRX_PNG_CHUNK, each coded on its own and starting on a byte boundary --
+ * literals and distance-1 matches of 3..258 bytes (run lengths only, like Z_RLE; a run is cut where the 128-byte span of a lane ends), one
+ * dynamic-Huffman block with the chunk's own length-limited (15-bit, complete) literal/length code and one distance code, header in a
+ * fixed 1222-bit form, end-of-block, an empty stored block as byte alignment; a chunk that would not come out smaller than its n bytes + 5
+ * goes as one stored block, so a chunk never takes more than n + 5 bytes; then a final empty fixed block 03 00 and the Adler-32 of the
+ * scanlines, combined on the device from per-chunk sums in integers.
+ *   srx_png_stream_bound(H, W) = 2 + H (W + 1) + 5 ceil(H (W + 1) / SRX_PNG_CHUNK) + 6: bytes of one image's slot (0 for H or W <= 0).
+ *   srx_png_scratch_bytes(B, H, W): the workspace of a call, a multiple of 256 (0 for arguments no call accepts).
+ * Three kernel launches on `stream` whatever the samples hold; no allocation, no host synchronisation, no memset or copy node.  The bytes
+ * are the same run to run, and item b of a batch gets the bytes of a B = 1 call on its image.  The workspace may hold anything on entry
+ * (bits are ORed together in LDS only), inputs are never written, and nothing is written outside the slots (of which only
+ * [0, lengths[b]) is written), `lengths` and [0, ws_bytes).  `img` needs the alignment of its element only.
+ * SRX_E_INVALID: a null pointer; B, H or W <= 0.  SRX_E_UNSUPPORTED: H (W + 1) of 2 GiB or more, B > 65535.  SRX_E_WORKSPACE: the
+ * workspace is shorter than srx_png_scratch_bytes or not 256-byte aligned.  All decided on the host before any HIP call. */
+#define SRX_PNG_CHUNK 32768
+size_t srx_png_stream_bound(int H, int W);
+size_t srx_png_scratch_bytes(int B, int H, int W);
+int srx_png_deflate_u8(const uint8_t *img, int B, int H, int W, void *streams, void *lengths, void *ws, size_t ws_bytes, srx_stream_t stream);
+int srx_png_deflate_f32(const float *img, int B, int H, int W, void *streams, void *lengths, void *ws, size_t ws_bytes, srx_stream_t stream);
+int srx_png_deflate_f64(const double *img, int B, int H, int W, void *streams, void *lengths, void *ws, size_t ws_bytes, srx_stream_t stream);
+
 /* ---- 4-frame pixel interleave of the vendor live view (opt_materials/software/XPR_Software.py:196-205, 388-410) ----
  * frames uint8 [B, 4, h, w] -> out uint8 [B, 2h, 2w]: frame k zero-inserted at [::2, ::2], translated by the integer
  * (tx, ty) = (0,0), (0,+1), (-1,+1), (-1,0) HR pixels with cv2.BORDER_REFLECT_101, the four planes summed as uint8. */
