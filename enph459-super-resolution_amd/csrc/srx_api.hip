@@ -16,6 +16,7 @@
 #include "srx_register.hpp"
 #include "srx_mean.hpp"
 #include "srx_png.hpp"
+#include "srx_crc.hpp"
 
 using namespace srx;
 
@@ -931,6 +932,31 @@ int srx_png_deflate_f32(const float *img, int B, int H, int W, void *streams, vo
 int srx_png_deflate_f64(const double *img, int B, int H, int W, void *streams, void *lengths, void *ws, size_t wsb, srx_stream_t s)
 {
     return png::deflate(img, B, H, W, streams, lengths, ws, wsb, hs(s));
+}
+
+size_t srx_crc32_scratch_bytes(int B, size_t max_len) { return crc::scratch_bytes(B, max_len); }
+
+int srx_crc32(const void *data, int B, size_t stride, size_t max_len, const void *lengths, uint32_t seed, void *crc_out, void *ws, size_t wsb,
+              srx_stream_t s)
+{
+    return crc::crc32(data, B, stride, max_len, lengths, seed, crc_out, ws, wsb, hs(s));
+}
+
+size_t srx_png_file_bound(int H, int W) { return crc::file_bound(H, W); }
+
+size_t srx_png_file_scratch_bytes(int B, int H, int W) { return crc::file_scratch_bytes(B, H, W); }
+
+int srx_png_file_u8(const uint8_t *img, int B, int H, int W, void *files, void *lengths, void *ws, size_t wsb, srx_stream_t s)
+{
+    return crc::png_file(img, B, H, W, files, lengths, ws, wsb, hs(s));
+}
+int srx_png_file_f32(const float *img, int B, int H, int W, void *files, void *lengths, void *ws, size_t wsb, srx_stream_t s)
+{
+    return crc::png_file(img, B, H, W, files, lengths, ws, wsb, hs(s));
+}
+int srx_png_file_f64(const double *img, int B, int H, int W, void *files, void *lengths, void *ws, size_t wsb, srx_stream_t s)
+{
+    return crc::png_file(img, B, H, W, files, lengths, ws, wsb, hs(s));
 }
 
 int srx_interleave4_u8(const uint8_t *frames, int B, int h, int w, uint8_t *out, srx_stream_t s)

@@ -591,6 +591,22 @@ static inline size_t scratch_bytes(int B, int H, int W)
     return measured([&](Arena &m) { carve(m, (size_t)B, chunks_of((size_t)H * ((size_t)W + 1))); });
 }
 
+// the three launches: the streams at `streams + b * slot`, their lengths as int64 at `lengths + 8 b` (srx_png_file_* passes the slots of
+// its files, 41 bytes in, and eight bytes of its workspace)
+template <typename T>
+static int launch(const T *img, int B, int H, int W, const Plan &p, uint8_t *streams, size_t slot, uint8_t *lengths, hipStream_t st)
+{
+    const size_t chunks = chunks_of((size_t)H * ((size_t)W + 1));
+    const dim3 grid((unsigned)chunks, (unsigned)B);  // chunks <= 65536
+    hipLaunchKernelGGL(k_png_analyse<T>, grid, dim3(LANES), 0, st, img, H, W, (uint32_t)chunks, p);
+    SRX_CHECK_LAUNCH();
+    hipLaunchKernelGGL(k_png_offsets, dim3((unsigned)B), dim3(LANES), 0, st, H, W, (uint32_t)chunks, p, streams, slot, lengths);
+    SRX_CHECK_LAUNCH();
+    hipLaunchKernelGGL(k_png_emit<T>, grid, dim3(LANES), 0, st, img, H, W, (uint32_t)chunks, p, streams, slot);
+    SRX_CHECK_LAUNCH();
+    return SRX_OK;
+}
+
 // srx_png_deflate_*: the host checks, then the three launches
 template <typename T> static int deflate(const T *img, int B, int H, int W, void *streams_, void *lengths_, void *ws, size_t wsb, hipStream_t st)
 {
@@ -599,22 +615,15 @@ template <typename T> static int deflate(const T *img, int B, int H, int W, void
         return SRX_E_INVALID;
     if (unsupported(B, H, W))
         return SRX_E_UNSUPPORTED;
-    const size_t raw = (size_t)H * ((size_t)W + 1), chunks = chunks_of(raw);
+    const size_t raw = (size_t)H * ((size_t)W + 1);
     Arena ar(ws, wsb);
     ar.require(scratch_bytes(B, H, W));
     if (!ar.ok)
         return SRX_E_WORKSPACE;
-    const Plan p = carve(ar, (size_t)B, chunks);
+    const Plan p = carve(ar, (size_t)B, chunks_of(raw));
     if (!ar.ok)
         return SRX_E_WORKSPACE;
-    const dim3 grid((unsigned)chunks, (unsigned)B);  // chunks <= 65536
-    hipLaunchKernelGGL(k_png_analyse<T>, grid, dim3(LANES), 0, st, img, H, W, (uint32_t)chunks, p);
-    SRX_CHECK_LAUNCH();
-    hipLaunchKernelGGL(k_png_offsets, dim3((unsigned)B), dim3(LANES), 0, st, H, W, (uint32_t)chunks, p, streams, stream_bound(raw), lengths);
-    SRX_CHECK_LAUNCH();
-    hipLaunchKernelGGL(k_png_emit<T>, grid, dim3(LANES), 0, st, img, H, W, (uint32_t)chunks, p, streams, stream_bound(raw));
-    SRX_CHECK_LAUNCH();
-    return SRX_OK;
+    return launch(img, B, H, W, p, streams, stream_bound(raw), lengths, st);
 }
 
 }  // namespace png

@@ -53,6 +53,7 @@ _TYPED = {
     "srx_register_u8_{T}": (_I, [_P, _I, _I, _I, _I, _I, _HD, _I, _I, _I, _D, _P, _P, _P, _P, _Z, _P]),
     "srx_psf_estimate_{T}": (_I, [_P, _I, _I, _I, _I, _P, _P, _P, _Z, _P]),
     "srx_png_deflate_{T}": (_I, [_P, _I, _I, _I, _P, _P, _P, _Z, _P]),
+    "srx_png_file_{T}": (_I, [_P, _I, _I, _I, _P, _P, _P, _Z, _P]),
 }
 _PLAIN = {
     "srx_version": (_I, []),
@@ -94,6 +95,11 @@ _PLAIN = {
     "srx_png_stream_bound": (_Z, [_I, _I]),
     "srx_png_scratch_bytes": (_Z, [_I, _I, _I]),
     "srx_png_deflate_u8": (_I, [_P, _I, _I, _I, _P, _P, _P, _Z, _P]),
+    "srx_crc32_scratch_bytes": (_Z, [_I, _Z]),
+    "srx_crc32": (_I, [_P, _I, _Z, _Z, _P, _c.c_uint32, _P, _P, _Z, _P]),
+    "srx_png_file_bound": (_Z, [_I, _I]),
+    "srx_png_file_scratch_bytes": (_Z, [_I, _I, _I]),
+    "srx_png_file_u8": (_I, [_P, _I, _I, _I, _P, _P, _P, _Z, _P]),
 }
 
 

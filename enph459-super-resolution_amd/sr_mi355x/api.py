@@ -527,33 +527,80 @@ def png_deflate(images):
     Float images are quantised as quantize_u8 does (the working precision's arithmetic) while they are read; no uint8 plane is made.
     -> (streams uint8 [B, srx_png_stream_bound(H, W)], lengths int64 [B]) on the device, nothing synchronised: bytes [0, lengths[b]) of
     row b inflate to the Up-filtered scanlines of image b, and session.png_container(W, H, those bytes) is the file."""
-    is_u8 = (images.dtype == torch.uint8) if isinstance(images, torch.Tensor) else (np.asarray(images).dtype == np.uint8)
-    if is_u8:
-        x = images if isinstance(images, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(images))
-        x, fn = x.to(device=_device()).contiguous(), _lib.load().srx_png_deflate_u8
-    else:
-        x, fn = _to_dev(images, get_precision())[0], _fn("srx_png_deflate", get_precision())
-    if x.dim() == 2:
-        x = x[None]
-    if x.dim() != 3:
-        raise ValueError("images must have the shape [B, H, W] or [H, W]")
+    x, kind = _png_input(images)
     B, H, W = (int(v) for v in x.shape)
     lib = _lib.load()
     streams = torch.empty((B, lib.srx_png_stream_bound(H, W)), dtype=torch.uint8, device=x.device)
     lengths = torch.empty((B,), dtype=torch.int64, device=x.device)
     ws, wsp, wsn = _ws(lib.srx_png_scratch_bytes(B, H, W))
-    _lib.check(fn(_p(x), B, H, W, _p(streams), _p(lengths), wsp, wsn, _stream()), "srx_png_deflate")
+    _lib.check(getattr(lib, "srx_png_deflate_" + kind)(_p(x), B, H, W, _p(streams), _p(lengths), wsp, wsn, _stream()), "srx_png_deflate")
     return streams, lengths
 
 
+def _png_input(images):
+    """-> (device tensor [B, H, W], the entry points' suffix): uint8 stays bytes, anything else becomes the working precision"""
+    is_u8 = (images.dtype == torch.uint8) if isinstance(images, torch.Tensor) else (np.asarray(images).dtype == np.uint8)
+    if is_u8:
+        x = images if isinstance(images, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(images))
+        x, kind = x.to(device=_device()).contiguous(), "u8"
+    else:
+        x, kind = _to_dev(images, get_precision())[0], get_precision()
+    if x.dim() == 2:
+        x = x[None]
+    if x.dim() != 3:
+        raise ValueError("images must have the shape [B, H, W] or [H, W]")
+    return x, kind
+
+
+def png_file(images):
+    """The 8-bit greyscale PNG files of `images` (srx_png_file_*; png_deflate's argument), complete on the device: signature, IHDR, one IDAT
+    around png_deflate's stream with its CRC-32, IEND.
+    -> (files uint8 [B, srx_png_file_bound(H, W)], lengths int64 [B]) on the device, nothing synchronised: bytes [0, lengths[b]) of row b
+    are the file of image b, the bytes session.png_container(W, H, png_deflate's stream) would be."""
+    x, kind = _png_input(images)
+    B, H, W = (int(v) for v in x.shape)
+    lib = _lib.load()
+    files = torch.empty((B, lib.srx_png_file_bound(H, W)), dtype=torch.uint8, device=x.device)
+    lengths = torch.empty((B,), dtype=torch.int64, device=x.device)
+    ws, wsp, wsn = _ws(lib.srx_png_file_scratch_bytes(B, H, W))
+    _lib.check(getattr(lib, "srx_png_file_" + kind)(_p(x), B, H, W, _p(files), _p(lengths), wsp, wsn, _stream()), "srx_png_file")
+    return files, lengths
+
+
 def png_encode(images):
-    """-> a list of bytes, one complete PNG file per image of `images` (png_deflate's argument): the device's streams, downloaded and
-    wrapped by session.png_container.  A convenience: it synchronises."""
-    from . import session
-    streams, lengths = png_deflate(images)
-    H, W = (int(v) for v in images.shape[-2:])
-    host, n = streams.cpu().numpy(), lengths.cpu().tolist()
-    return [session.png_container(W, H, host[b, :n[b]].tobytes()) for b in range(len(n))]
+    """-> a list of bytes, one complete PNG file per image of `images` (png_deflate's argument): png_file's slots, downloaded and cut to
+    their lengths.  A convenience: it synchronises."""
+    files, lengths = png_file(images)
+    host, n = files.cpu().numpy(), lengths.cpu().tolist()
+    return [host[b, :n[b]].tobytes() for b in range(len(n))]
+
+
+def crc32(data, lengths=None, seed=0):
+    """zlib.crc32 of device buffers (srx_crc32): `data` a [B, n] or [n] uint8 tensor / array, item b its row's first min(lengths[b], n) bytes
+    (lengths: int64 [B] tensor / array, read on the device; None: whole rows), `seed` as in zlib.crc32(item, seed).
+    -> int64 device tensor [B], values in [0, 2^32); nothing is synchronised."""
+    x = data if isinstance(data, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(data))
+    if x.dtype != torch.uint8 or x.dim() not in (1, 2):
+        raise ValueError("data must be a uint8 tensor or array of the shape [B, n] or [n]")
+    x = x.to(device=_device()).contiguous()
+    if x.dim() == 1:
+        x = x[None]
+    B, n = (int(v) for v in x.shape)
+    seed = int(seed)
+    if B <= 0 or not 0 <= seed < (1 << 32):
+        raise ValueError("crc32 needs at least one item and a seed in [0, 2^32)")
+    if lengths is not None:
+        lengths = (lengths if isinstance(lengths, torch.Tensor) else torch.from_numpy(np.asarray(lengths, dtype=np.int64)))
+        lengths = lengths.to(device=x.device, dtype=torch.int64).contiguous()
+        if tuple(lengths.shape) != (B,):
+            raise ValueError("lengths must have the shape [B]")
+    if n == 0:  # no byte to read: every CRC is the seed
+        return torch.full((B,), seed, dtype=torch.int64, device=x.device)
+    lib = _lib.load()
+    out = torch.empty((B,), dtype=torch.int32, device=x.device)  # the uint32 values' bits
+    ws, wsp, wsn = _ws(lib.srx_crc32_scratch_bytes(B, n))
+    _lib.check(lib.srx_crc32(_p(x), B, n, n, None if lengths is None else _p(lengths), seed, _p(out), wsp, wsn, _stream()), "srx_crc32")
+    return out.to(torch.int64) & 0xFFFFFFFF
 
 
 def u8_to_float(img_u8, precision=None):

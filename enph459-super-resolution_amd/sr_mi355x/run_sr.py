@@ -44,8 +44,8 @@ def main(argv=None):
                          "srx_ibp_u8lr, with --register registration through srx_register_u8, and the frame mean and rgb_cal_target's rep "
                          "mean of the red planes through srx_mean_u8; the files written are the same")
     ap.add_argument("--png-on-device", action="store_true",
-                    help="compress the output PNGs on the device (srx_png_deflate: quantise, Up filter, run lengths and Huffman coding per "
-                         "32 KB chunk); the host only adds the container and its CRC-32.  Same pixels in every file, other bytes")
+                    help="build the output PNGs on the device (srx_png_file: quantise, Up filter, run lengths and Huffman coding per "
+                         "32 KB chunk, the container and its CRC-32); the host only writes the bytes.  Same pixels in every file, other bytes")
     args = ap.parse_args(argv)
     rank, world, local_rank = int(os.environ.get("RANK", "0")), int(os.environ.get("WORLD_SIZE", "1")), int(os.environ.get("LOCAL_RANK", "0"))
     dist = None

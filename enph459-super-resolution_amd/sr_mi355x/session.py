@@ -337,6 +337,7 @@ def _host_threads():
     return max(1, min(16, n))
 
 
+DEVICE_PNG_FILES = True  # device_png: whole files from the device (api.png_file); False: its streams, wrapped by png_container in the jobs
 PNG_COMPRESS_LEVEL = 1  # zlib level of the PNGs written (PIL's default is 6: ~4x the encode time for ~10 % smaller files; lossless either way)
 _writers, _pending = None, []
 
@@ -398,8 +399,9 @@ def _save_outputs(out_dir, images, errors, lr_name, extra=None, device_png=False
     the PNG encoding to worker threads, which wait for the copies' event -- the calling thread waits for nothing and goes on to queue the
     next item's device work.  `errors`: the MSE trace, a list or a device tensor (downloaded with the planes).  done.flag is written by
     the last job of the directory, after every file of it exists.
-    device_png: the device compresses as well (api.png_deflate: same pixels in the files, other bytes); the jobs only wrap the streams
-    (png_container: the CRC-32) and write."""
+    device_png: the device compresses as well (same pixels in the files, other bytes) and, with DEVICE_PNG_FILES, builds the container and
+    its CRC-32 around the stream (api.png_file): a job writes its slot's bytes as they are.  With DEVICE_PNG_FILES off the device makes the
+    streams only (api.png_deflate) and the jobs wrap them (png_container: the CRC-32 on the host) -- the same files byte for byte."""
     import torch
     os.makedirs(out_dir, exist_ok=True)
 
@@ -413,11 +415,13 @@ def _save_outputs(out_dir, images, errors, lr_name, extra=None, device_png=False
     hr_names = ("native_2x", "SAA", "SAA_IBP")
     if device_png:
         # the three HR planes as one [3, H, W] call on the float tensors (quantised as they are read), LR_mean as a second one in the
-        # loader's precision; what goes to the host is the slots and their lengths, and a job slices, wraps and writes
+        # loader's precision; what goes to the host is the slots and their lengths, and a job slices and writes
+        files = DEVICE_PNG_FILES
+        encode = api.png_file if files else api.png_deflate
         hr = torch.stack([images[name] for name in hr_names])
-        streams, lengths = api.png_deflate(hr)
+        streams, lengths = encode(hr)
         with _loader_precision():
-            lr_streams, lr_lengths = api.png_deflate(images["LR_mean"])
+            lr_streams, lr_lengths = encode(images["LR_mean"])
         hr_host, hr_len, lr_host, lr_len = to_host(streams), to_host(lengths), to_host(lr_streams), to_host(lr_lengths)
         planes = {f"{name}.png": (hr_host, hr_len, k, tuple(hr.shape[1:])) for k, name in enumerate(hr_names)}
         planes[lr_name] = (lr_host, lr_len, 0, tuple(images["LR_mean"].shape))
@@ -452,7 +456,10 @@ def _save_outputs(out_dir, images, errors, lr_name, extra=None, device_png=False
         if device_png:
             slots, lens, k, (h, w) = host
             with open(os.path.join(out_dir, fname), "wb") as fp:
-                fp.write(png_container(w, h, slots[k, :int(lens[k])].numpy().tobytes()))
+                if files:
+                    fp.write(memoryview(slots[k, :int(lens[k])].numpy()))
+                else:
+                    fp.write(png_container(w, h, slots[k, :int(lens[k])].numpy().tobytes()))
         else:
             write_png_u8(os.path.join(out_dir, fname), host.numpy())
         with lock:

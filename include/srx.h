@@ -341,7 +341,7 @@ int srx_mean_u8(const uint8_t *in, int B, int R, int H, int W, int f, int py, in
  * img T [B, H, W] -> streams uint8 [B][srx_png_stream_bound(H, W)], lengths int64 [B] (both DEVICE arrays, any byte address).  Bytes
  * [0, lengths[b]) of slot b are a complete zlib stream (RFC 1950 / 1951) that inflates to the PNG scanlines of image b: H rows of 1 + W
  * bytes, filter byte 2 (Up: the sample minus the one above it modulo 256, row 0 against zeros).  A host wraps it with the PNG signature,
- * IHDR, one IDAT and IEND (session.png_container; the IDAT's CRC-32 stays on the host) and has the file.  The float forms quantise as they
+ * IHDR, one IDAT and IEND (session.png_container) and has the file; srx_png_file_* below does that on the device.  The float forms quantise as they
  * read, with srx_quantize_u8_T's arithmetic (clamp, then truncate: the same device function, so the same byte for every input); no uint8
  * plane exists in between.
  * Stream: 78 01; the H (W + 1) scanline bytes in chunks of SRX_PNG_CHUNK, each coded on its own and starting on a byte boundary --
@@ -364,6 +364,49 @@ size_t srx_png_scratch_bytes(int B, int H, int W);
 int srx_png_deflate_u8(const uint8_t *img, int B, int H, int W, void *streams, void *lengths, void *ws, size_t ws_bytes, srx_stream_t stream);
 int srx_png_deflate_f32(const float *img, int B, int H, int W, void *streams, void *lengths, void *ws, size_t ws_bytes, srx_stream_t stream);
 int srx_png_deflate_f64(const double *img, int B, int H, int W, void *streams, void *lengths, void *ws, size_t ws_bytes, srx_stream_t stream);
+
+/* ---- CRC-32 of device buffers (zlib's and PNG's: reflected, P = 0xEDB88320, init and final xor 0xFFFFFFFF) ----
+ * Item b is bytes [0, min(lengths[b], max_len)) at data + b * stride; crc[b] = zlib.crc32(item, seed) (seed 0: a fresh CRC; a length of 0
+ * or less gives `seed`).  `data` may sit at any byte address and any stride >= max_len is allowed; `lengths` is a DEVICE int64 [B], 8-byte
+ * aligned and read on the device, or NULL for "every item is max_len long" (max_len only sizes the grid); `crc` is a DEVICE uint32 [B],
+ * 4-byte aligned.  No byte at or behind an item's length is read into its result.
+ * CRC-32 is linear over GF(2): a workgroup reduces one segment of SRX_CRC_SEGMENT bytes, each of its 256 lanes one span of SRX_CRC_SPAN
+ * bytes through a byte table in LDS, and combines the spans' remainders with multiplications by x^(8 bytes that follow) mod P; a second
+ * kernel combines the segments the same way and adds the seed's term.  Segments and spans are counted from the item's END (the first
+ * segment and its first span are the short ones), so an item of n bytes has ceil(n / SRX_CRC_SEGMENT) segments.
+ *   srx_crc32_scratch_bytes(B, max_len): the workspace of a call, a multiple of 256 (0 for arguments no call accepts).
+ * Two kernel launches on `stream`; no allocation, no host synchronisation, no memset or copy node; a fixed order, so the same bits run to
+ * run, and item b of a batch gets the value of a B = 1 call.  The workspace may hold anything on entry; only crc[0, B) and [0, ws_bytes)
+ * are written.
+ * SRX_E_INVALID: a null data or crc; B <= 0; max_len == 0; stride < max_len with B > 1; lengths not 8-byte or crc not 4-byte aligned.
+ * SRX_E_UNSUPPORTED: B > 65535, max_len of 2 GiB or more.  SRX_E_WORKSPACE: the workspace is shorter than srx_crc32_scratch_bytes or not
+ * 256-byte aligned.  All decided on the host before any HIP call, in this order. */
+#define SRX_CRC_SPAN 64
+#define SRX_CRC_SEGMENT 16384
+size_t srx_crc32_scratch_bytes(int B, size_t max_len);
+int srx_crc32(const void *data, int B, size_t stride, size_t max_len, const void *lengths, uint32_t seed, void *crc, void *ws, size_t ws_bytes,
+              srx_stream_t stream);
+
+/* ---- the output PNGs as complete files, built on the device: srx_png_deflate_*'s stream inside its container ----
+ * img T [B, H, W] -> files uint8 [B][srx_png_file_bound(H, W)], lengths int64 [B] (both DEVICE arrays, any byte address).  Bytes
+ * [0, lengths[b]) of slot b are the 8-bit greyscale PNG file of image b: the signature, IHDR with its CRC, one IDAT whose data is exactly
+ * the stream srx_png_deflate_* writes for the same image, the IDAT's CRC-32, IEND (what session.png_container builds around that stream on
+ * the host); lengths[b] is the stream's length + SRX_PNG_FILE_EXTRA.  A host writes the bytes to disk and has the file.
+ * The three launches of srx_png_deflate_* put the stream 41 bytes into the slot and its length into the workspace; srx_crc32's two kernels
+ * then reduce the stream under the seed crc32("IDAT") (the chunk's CRC covers its tag) and the second one stores the 41 bytes in front
+ * (IHDR and its CRC depend on W and H only: the host computes them and passes them as an argument), the 16 bytes behind and lengths[b].
+ *   srx_png_file_bound(H, W) = srx_png_stream_bound(H, W) + SRX_PNG_FILE_EXTRA: bytes of one image's slot (0 for H or W <= 0).
+ *   srx_png_file_scratch_bytes(B, H, W): the workspace of a call, a multiple of 256 and at least srx_png_scratch_bytes (0 for arguments
+ *   no call accepts).
+ * Five kernel launches on `stream`; otherwise the contract of srx_png_deflate_*: no allocation, no host synchronisation, the same bytes
+ * run to run and for item b of a batch as for a B = 1 call; the workspace may hold anything on entry; nothing is written outside
+ * [0, lengths[b]) of the slots, `lengths` and [0, ws_bytes); the same refusals in the same order. */
+#define SRX_PNG_FILE_EXTRA 57 /* 8 + 25 + 8 in front of the stream, 4 + 12 behind it */
+size_t srx_png_file_bound(int H, int W);
+size_t srx_png_file_scratch_bytes(int B, int H, int W);
+int srx_png_file_u8(const uint8_t *img, int B, int H, int W, void *files, void *lengths, void *ws, size_t ws_bytes, srx_stream_t stream);
+int srx_png_file_f32(const float *img, int B, int H, int W, void *files, void *lengths, void *ws, size_t ws_bytes, srx_stream_t stream);
+int srx_png_file_f64(const double *img, int B, int H, int W, void *files, void *lengths, void *ws, size_t ws_bytes, srx_stream_t stream);
 
 /* ---- 4-frame pixel interleave of the vendor live view (opt_materials/software/XPR_Software.py:196-205, 388-410) ----
  * frames uint8 [B, 4, h, w] -> out uint8 [B, 2h, 2w]: frame k zero-inserted at [::2, ::2], translated by the integer
