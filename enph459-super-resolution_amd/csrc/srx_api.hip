@@ -1019,6 +1019,24 @@ int srx_edge_dist_range(int H, int W, double m, double b, double norm, int rows_
 SRX_DEFINE_METRICS(f32, float)
 SRX_DEFINE_METRICS(f64, double)
 
+size_t srx_edge_sfr_scratch_bytes(int B, int H, int W) { return sfr::scratch_bytes(B, H, W); }
+
+int srx_edge_sfr_u8(const uint8_t *img, int B, int H, int W, size_t row_pitch, size_t item_pitch, int side, double sigma, void *summary, void *esf,
+                    void *mtf, void *status, void *ws, size_t wsb, srx_stream_t s)
+{
+    return sfr::edge_sfr(img, B, H, W, row_pitch, item_pitch, side, sigma, summary, esf, mtf, status, ws, wsb, hs(s));
+}
+int srx_edge_sfr_f32(const float *img, int B, int H, int W, size_t row_pitch, size_t item_pitch, int side, double sigma, void *summary, void *esf,
+                     void *mtf, void *status, void *ws, size_t wsb, srx_stream_t s)
+{
+    return sfr::edge_sfr(img, B, H, W, row_pitch, item_pitch, side, sigma, summary, esf, mtf, status, ws, wsb, hs(s));
+}
+int srx_edge_sfr_f64(const double *img, int B, int H, int W, size_t row_pitch, size_t item_pitch, int side, double sigma, void *summary, void *esf,
+                     void *mtf, void *status, void *ws, size_t wsb, srx_stream_t s)
+{
+    return sfr::edge_sfr(img, B, H, W, row_pitch, item_pitch, side, sigma, summary, esf, mtf, status, ws, wsb, hs(s));
+}
+
 size_t srx_register_workspace_bytes(int elem_bytes, int B, int N, int H, int W, int search)
 {
     return reg::workspace_bytes(elem_bytes, B, N, H, W, search);

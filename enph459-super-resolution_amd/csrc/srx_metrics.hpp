@@ -13,10 +13,13 @@
 //   SSIM             skimage structural_similarity (2-D; the vendor GUI's SSIM score, XPR_Software.py:1220-1256): the five windowed moments
 //                    held on chip in ONE pass over the two images (k_ssim), the mean of S as a float64 fixed-order reduction, the map optional;
 //                    its affine-fit form applies the fitted line inside the kernel.  The ECC score follows from the pair moments.
-// The percentile, the two line fits, the ESF interpolation, np.gradient / Hann / FFT of 72 samples, the 7-parameter Gaussian fit and the
-// 256^2 FFT of compute_mtf stay on the host (sr_mi355x/metrics.py): a few thousand operations each.
+// For these entry points the percentile, the two line fits, the ESF interpolation, np.gradient / Hann / FFT of 72 samples, the 7-parameter
+// Gaussian fit and the 256^2 FFT of compute_mtf stay on the host (sr_mi355x/metrics.py): a few thousand operations each.  srx_edge_sfr_*
+// (srx_sfr.hpp) is the slanted-edge chain whole, without a host step; the per-pixel filter arithmetic of k_correlate1d / k_sobel_mag lives
+// there, shared with it.
 #pragma once
 #include "srx_common.h"
+#include "srx_sfr.hpp"  // the per-pixel filter arithmetic (shared with srx_edge_sfr_* and its host model)
 
 namespace srx {
 namespace metrics {
@@ -166,29 +169,15 @@ __global__ void __launch_bounds__(256) k_spot_moments(const T *__restrict__ img,
 
 // ---- edge ROI: separable correlation with scipy.ndimage's 'reflect' boundary (d c b a | a b c d | d c b a), float64 -------------------
 // axis 0: along rows (y), axis 1: along columns (x).  taps [2 r + 1] by value (r <= 8).  grid (ceil(W / 64), ceil(H / 4)), block (64, 4)
-struct Taps17 {
-    double k[17];
-    int r;
-};
-__device__ __forceinline__ int reflect_idx(int i, int n)
-{
-    // numpy 'symmetric' / scipy 'reflect': ... 1 0 | 0 1 2 ... n-1 | n-1 n-2 ...
-    const int p = 2 * n;
-    i = ((i % p) + p) % p;
-    return i < n ? i : p - 1 - i;
-}
+using sfr::Taps17;
+using sfr::reflect_idx;
 __global__ void __launch_bounds__(256) k_correlate1d(const double *__restrict__ in, int H, int W, int axis, Taps17 t, double *__restrict__ out)
 {
 #pragma clang fp contract(off)  // (the host evaluates these expressions with separate multiplies and adds: same bits)
     const int x = blockIdx.x * 64 + threadIdx.x, y = blockIdx.y * 4 + threadIdx.y;
     if (x >= W || y >= H)
         return;
-    double s = 0.0;
-    for (int j = 0; j <= 2 * t.r; j++) {
-        const int yy = axis == 0 ? reflect_idx(y + j - t.r, H) : y, xx = axis == 1 ? reflect_idx(x + j - t.r, W) : x;
-        s += t.k[j] * in[(size_t)yy * W + xx];
-    }
-    out[(size_t)y * W + x] = s;
+    out[(size_t)y * W + x] = sfr::correlate_at(t, axis, y, x, H, W, [&](int yy, int xx) { return in[(size_t)yy * W + xx]; });
 }
 // mag = sqrt(gx^2 + gy^2), gx = sobel along axis 1 (derivative along x, smoothing along y), gy along axis 0; 'reflect' boundary
 __global__ void __launch_bounds__(256) k_sobel_mag(const double *__restrict__ in, int H, int W, double *__restrict__ mag)
@@ -197,13 +186,8 @@ __global__ void __launch_bounds__(256) k_sobel_mag(const double *__restrict__ in
     const int x = blockIdx.x * 64 + threadIdx.x, y = blockIdx.y * 4 + threadIdx.y;
     if (x >= W || y >= H)
         return;
-    auto at = [&](int yy, int xx) { return in[(size_t)reflect_idx(yy, H) * W + reflect_idx(xx, W)]; };
     // correlate [-1 0 1] along the derivative axis first, then [1 2 1] along the other (the order of metrics._sobel)
-    auto dx = [&](int yy) { return -1.0 * at(yy, x - 1) + 0.0 * at(yy, x) + 1.0 * at(yy, x + 1); };
-    auto dy = [&](int xx) { return -1.0 * at(y - 1, xx) + 0.0 * at(y, xx) + 1.0 * at(y + 1, xx); };
-    const double gx = 1.0 * dx(y - 1) + 2.0 * dx(y) + 1.0 * dx(y + 1);
-    const double gy = 1.0 * dy(x - 1) + 2.0 * dy(x) + 1.0 * dy(x + 1);
-    mag[(size_t)y * W + x] = sqrt(gx * gx + gy * gy);
+    mag[(size_t)y * W + x] = sfr::sobel_mag_at(y, x, H, W, [&](int yy, int xx) { return in[(size_t)yy * W + xx]; });
 }
 
 // every ROI pixel projected on the edge's normal: dist = (v - m u - b) / norm with (u, v) = (row, col) if rows_are_x else (col, row);
@@ -508,18 +492,8 @@ static int edge_magnitude(const double *roi, int H, int W, double sigma, double 
     if (!roi || !mag || H <= 0 || W <= 0 || !(sigma > 0.0))
         return SRX_E_INVALID;
     Taps17 t;
-    t.r = (int)(4.0 * sigma + 0.5);
-    if (t.r > 8)
+    if (!sfr::gaussian_taps(sigma, t))
         return SRX_E_UNSUPPORTED;
-    double sum = 0.0;
-    for (int j = 0; j <= 2 * t.r; j++) {
-        const double x = (double)(j - t.r);
-        t.k[j] = std::exp(-0.5 / (sigma * sigma) * x * x), sum += t.k[j];
-    }
-    for (int j = 0; j <= 2 * t.r; j++)
-        t.k[j] /= sum;
-    for (int j = 2 * t.r + 1; j < 17; j++)
-        t.k[j] = 0.0;
     Arena ar(ws, wsb);
     ar.require(workspace_bytes(1, H, W, 1));
     const auto [a, b] = carve_planes(ar, H, W);

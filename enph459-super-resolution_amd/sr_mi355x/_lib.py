@@ -54,6 +54,7 @@ _TYPED = {
     "srx_psf_estimate_{T}": (_I, [_P, _I, _I, _I, _I, _P, _P, _P, _Z, _P]),
     "srx_png_deflate_{T}": (_I, [_P, _I, _I, _I, _P, _P, _P, _Z, _P]),
     "srx_png_file_{T}": (_I, [_P, _I, _I, _I, _P, _P, _P, _Z, _P]),
+    "srx_edge_sfr_{T}": (_I, [_P, _I, _I, _I, _Z, _Z, _I, _D, _P, _P, _P, _P, _P, _Z, _P]),
 }
 _PLAIN = {
     "srx_version": (_I, []),
@@ -100,6 +101,8 @@ _PLAIN = {
     "srx_png_file_bound": (_Z, [_I, _I]),
     "srx_png_file_scratch_bytes": (_Z, [_I, _I, _I]),
     "srx_png_file_u8": (_I, [_P, _I, _I, _I, _P, _P, _P, _Z, _P]),
+    "srx_edge_sfr_scratch_bytes": (_Z, [_I, _I, _I]),
+    "srx_edge_sfr_u8": (_I, [_P, _I, _I, _I, _Z, _Z, _I, _D, _P, _P, _P, _P, _P, _Z, _P]),
 }
 
 

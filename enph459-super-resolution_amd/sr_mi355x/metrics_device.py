@@ -8,6 +8,9 @@ a frame or an ROI (the 12.6 MP PSNR reductions, the ROI's Gaussian + Sobel, the 
 sliding-window contrast); what stays on the host are the few-thousand-operation tails -- the 85th percentile and the two line fits of
 the edge pixels, the ESF interpolation, the 72-sample gradient / Hann / FFT (metrics.esf_to_mtf), the 7-parameter Gaussian fit and the
 256^2 FFT of compute_mtf.  There is no CPU fallback for the device parts: without libsrx.so / a GPU these functions raise.
+
+`edge_sfr` (srx_edge_sfr_*) is the slanted-edge chain whole -- percentile, fits, ESF, MTF50 / MTF10 -- for a batch of ROIs in one call
+without a host step; `cal_target_report(fused=True)` and `session.queue_metrics_device` are built on it.
 """
 import ctypes
 
@@ -40,6 +43,11 @@ def _ws(B, H, W, nbin):
 def pair_moments(ref, test, border=0):
     """[B, 7] float64 (host): n, sum t, sum r, sum t^2, sum t r, sum r^2, sum (r - t)^2 over ref / test [B, H, W] (or [H, W]) minus a
     `border`-pixel frame, one fused pass over the two device images."""
+    return pair_moments_device(ref, test, border).cpu().numpy()
+
+
+def pair_moments_device(ref, test, border=0):
+    """pair_moments without the copy back: the [B, 7] float64 device tensor, nothing synchronised"""
     r, prec = _dev(ref)
     t = test.to(device=r.device, dtype=r.dtype).contiguous() if isinstance(test, torch.Tensor) else _dev64(test).to(r.dtype)
     if r.dim() == 2:
@@ -50,23 +58,32 @@ def pair_moments(ref, test, border=0):
     out = torch.empty((B, 7), dtype=torch.float64, device=r.device)
     wt, wp, wn = _ws(B, H, W, 1)
     _lib.check(api._fn("srx_pair_moments", prec)(api._p(r), api._p(t), B, H, W, int(border), api._p(out), wp, wn, api._stream()), "srx_pair_moments")
-    return out.cpu().numpy()
+    return out
+
+
+def psnr_from_moments(row, peak=255.0):
+    """psnr's value from one row of pair_moments"""
+    return float("inf") if row[6] == 0.0 else float(10.0 * np.log10(peak * peak * row[0] / row[6]))
+
+
+def psnr_affine_from_moments(row, data_range=1.0):
+    """psnr_affine's value from one row of pair_moments (taken with its border)"""
+    n, st, sr, stt, strr, srr, _ = row
+    s_tt, s_tr, s_rr = stt - st * st / n, strr - st * sr / n, srr - sr * sr / n
+    mse = max((s_rr - (s_tr * s_tr / s_tt if s_tt > 0 else 0.0)) / n, 0.0) / (255.0 * 255.0)
+    return np.inf if mse == 0 else 10.0 * np.log10(data_range ** 2 / mse)
 
 
 def psnr(a, b, peak=255.0):
     """10 log10(peak^2 / MSE) of two device images, per item for a batch; float (or a list for a batch)."""
-    m = pair_moments(a, b)
-    v = [float("inf") if row[6] == 0.0 else float(10.0 * np.log10(peak * peak * row[0] / row[6])) for row in m]
+    v = [psnr_from_moments(row, peak) for row in pair_moments(a, b)]
     return v[0] if len(v) == 1 else v
 
 
 def psnr_affine(ref, test, border=10, data_range=1.0):
     """metrics.psnr_affine on device images: the least-squares line test -> a test + b from the five second-order moments, then
     MSE = (S_rr - S_tr^2 / S_tt) / n in centred moments, everything scaled to [0, 1] from 8-bit."""
-    n, st, sr, stt, strr, srr, _ = pair_moments(ref, test, border=border)[0]
-    s_tt, s_tr, s_rr = stt - st * st / n, strr - st * sr / n, srr - sr * sr / n
-    mse = max((s_rr - (s_tr * s_tr / s_tt if s_tt > 0 else 0.0)) / n, 0.0) / (255.0 * 255.0)
-    return np.inf if mse == 0 else 10.0 * np.log10(data_range ** 2 / mse)
+    return psnr_affine_from_moments(pair_moments(ref, test, border=border)[0], data_range)
 
 
 def _np_dtype(x):
@@ -246,12 +263,125 @@ def slanted_edge_esf(roi, side="left", verbose=False):
     return esf_x, esf_y, angle
 
 
-def cal_target_report(images, factor=2, side="left"):
-    """metrics.cal_target_report on DEVICE images ({title: CUDA tensor [1536 f, 2048 f] holding the values the PNG gets, i.e. already
-    clamped and truncated to 0..255}): MTF50 / MTF10 of the slanted edge in ROI 2, the mean local Michelson contrast of the bar
-    cross-section in ROI 1 -- the notebook's summary (analysis.ipynb cells 3-10) -- without reading the PNGs back."""
+EDGE_MAX_BINS, EDGE_SUMMARY = 80, 16  # SRX_EDGE_MAX_BINS, SRX_EDGE_SUMMARY (include/srx.h)
+EDGE_FIELDS = ("mtf50", "mtf10", "angle_deg", "m", "b", "rows_are_x", "threshold", "n_edge", "n_side", "nbin", "lo", "hi", "flipped", "m_c", "b_c")
+EDGE_STATUS = {1: "Too few edge pixels detected", 2: "Too few edge pixels on the chosen side", 3: "degenerate edge fit",
+               4: "too few non-empty ESF bins"}
+_EDGE_KINDS = {torch.uint8: "u8", torch.float32: "f32", torch.float64: "f64"}
+
+
+class EdgeSfr:
+    """The device outputs of one edge_sfr call: `summary` [B, 16], `esf` [B, 2, 80], `mtf` [B, 2, 40] (float64) and `status` [B] (int32), views
+    of ONE device block, so that result() is one copy.  Nothing has synchronised when the call returns."""
+
+    def __init__(self, block, B, one, keep):
+        self.block, self.B, self.one, self._keep, self._host = block, B, one, keep, None
+        self.summary, self.esf, self.mtf, self.status = self._views(block)
+
+    def _views(self, blk):
+        B, n, h = self.B, EDGE_SUMMARY, EDGE_MAX_BINS
+        return (blk[:B * n].view(B, n), blk[B * n:B * (n + 2 * h)].view(B, 2, h), blk[B * (n + 2 * h):B * (n + 3 * h)].view(B, 2, h // 2),
+                blk[B * (n + 3 * h):].view(torch.int32)[:B])
+
+    def start_copy(self):
+        """queue the copy into a pinned host buffer (non-blocking); result() then reads that buffer, so wait for an event recorded behind
+        this call first"""
+        self._host = torch.empty(self.block.shape, dtype=self.block.dtype, pin_memory=True)
+        self._host.copy_(self.block, non_blocking=True)
+        return self
+
+    def result(self):
+        """The one copy back (or the pinned buffer of start_copy) -> per item a dict: mtf50, mtf10 (cycles per ROI pixel, nan where the
+        curve never falls through), angle_deg, esf_x, esf_y, freq, mtf, status and the other summary fields; a list for a batch."""
+        summary, esf, mtf, status = (t.numpy() for t in self._views(self._host if self._host is not None else self.block.cpu()))
+        items = []
+        for b in range(self.B):
+            d = {k: float(v) for k, v in zip(EDGE_FIELDS, summary[b])}
+            st = int(status[b])
+            nbin = int(d["nbin"]) if st == 0 else 0
+            d.update(status=st, esf_x=esf[b, 0, :nbin].copy(), esf_y=esf[b, 1, :nbin].copy(), freq=mtf[b, 0, :nbin // 2].copy(),
+                     mtf=mtf[b, 1, :nbin // 2].copy())
+            items.append(d)
+        return items[0] if self.one else items
+
+
+def edge_sfr(images, side="left", sigma=1.5):
+    """The slanted-edge SFR of device ROIs in one call (srx_edge_sfr_*): metrics.slanted_edge_esf -> esf_to_mtf -> mtf_at_fraction with no
+    host step.  `images`: a CUDA tensor [H, W] or [B, H, W], uint8 / float32 / float64; it may be a ROI view of larger frames as long as
+    its columns are adjacent (the row and item strides are passed on, nothing is copied).  Returns an EdgeSfr; nothing synchronises
+    before its result()."""
+    if not isinstance(images, torch.Tensor) or not images.is_cuda or images.dtype not in _EDGE_KINDS or images.dim() not in (2, 3):
+        raise ValueError("edge_sfr takes a CUDA tensor [H, W] or [B, H, W] of uint8, float32 or float64")
+    if side not in ("left", "right"):
+        raise ValueError("side must be 'left' or 'right'")
+    one = images.dim() == 2
+    x = images[None] if one else images
+    B, H, W = (int(v) for v in x.shape)
+    if min(B, H, W) <= 0:
+        raise ValueError("edge_sfr: empty input")
+    item_pitch, row_pitch, col = (int(s) for s in x.stride())
+    if (W > 1 and col != 1) or (H > 1 and row_pitch < W) or (B > 1 and item_pitch < (H - 1) * max(row_pitch, W) + W):
+        raise ValueError("edge_sfr: columns must be adjacent, rows and items must not overlap (take a ROI as frames[:, r0:r1, c0:c1])")
+    row_pitch = max(row_pitch, W) if H > 1 else W
+    lib = _lib.load()
+    block = torch.empty(B * (EDGE_SUMMARY + 3 * EDGE_MAX_BINS) + (B + 1) // 2, dtype=torch.float64, device=x.device)
+    out = EdgeSfr(block, B, one, None)
+    ws = api._ws(lib.srx_edge_sfr_scratch_bytes(B, H, W))
+    out._keep = (x, ws[0])
+    _lib.check(getattr(lib, "srx_edge_sfr_" + _EDGE_KINDS[x.dtype])(api._p(x), B, H, W, row_pitch, max(item_pitch, 0), 0 if side == "left" else 1,
+                                                                     float(sigma), api._p(out.summary), api._p(out.esf), api._p(out.mtf),
+                                                                     api._p(out.status), ws[1], ws[2], api._stream()), "srx_edge_sfr")
+    return out
+
+
+def local_contrast_device(profile, window=16):
+    """local_contrast without the copy back: profile [B, n] on the device -> float64 device tensor [B, n]"""
+    p = _dev64(profile)
+    out = torch.empty_like(p)
+    _lib.check(_lib.load().srx_local_contrast_f64(api._p(p), p.shape[0], p.shape[1], int(window), api._p(out), api._stream()), "srx_local_contrast")
+    return out
+
+
+def _roi2(img, factor):
+    (r0, r1), (c0, c1) = metrics.ROI2_LR
+    return img[r0 * factor:r1 * factor, c0 * factor:c1 * factor]
+
+
+def _profile1(img, factor):
+    return img[metrics.ROI1_ROWS_LR[0] * factor:metrics.ROI1_ROWS_LR[1] * factor, metrics.ROI1_COL_LR * factor]
+
+
+def report_from_sfr(titles, sfr_items, contrast, factor=2):
+    """cal_target_report's dict from edge_sfr's items and the local-contrast rows of the profiles (host arrays): frequencies scaled to
+    cycles/mm here"""
     hr_pitch = metrics.SENSOR_PITCH_MM / factor
     out = {}
+    for title, it, ct in zip(titles, sfr_items, contrast):
+        if it["status"] != 0:
+            raise RuntimeError(f"{title}: {EDGE_STATUS.get(it['status'], 'edge_sfr status ' + str(it['status']))}")
+        out[title] = {"mtf50": it["mtf50"] / hr_pitch, "mtf10": it["mtf10"] / hr_pitch, "edge_angle_deg": it["angle_deg"],
+                      "mean_contrast": float(ct[8:-8].mean())}
+    return out
+
+
+def cal_target_report(images, factor=2, side="left", fused=False):
+    """metrics.cal_target_report on DEVICE images ({title: CUDA tensor [1536 f, 2048 f] holding the values the PNG gets, i.e. already
+    clamped and truncated to 0..255}): MTF50 / MTF10 of the slanted edge in ROI 2, the mean local Michelson contrast of the bar
+    cross-section in ROI 1 -- the notebook's summary (analysis.ipynb cells 3-10) -- without reading the PNGs back.
+    fused: the ROIs of all images go through ONE edge_sfr call and the profiles through one local-contrast call, with one copy back each
+    (the default runs slanted_edge_esf per image, with its four round trips); the same dict within rounding."""
+    hr_pitch = metrics.SENSOR_PITCH_MM / factor
+    out = {}
+    if fused:
+        for title, img in images.items():
+            if tuple(img.shape) != (1536 * factor, 2048 * factor):
+                raise ValueError(f"{title}: the notebook's ROIs are defined on the {1536 * factor} x {2048 * factor} cal-target frame")
+        imgs = [img if img.dtype in _EDGE_KINDS else img.to(torch.float64) for img in images.values()]
+        if len({i.dtype for i in imgs}) > 1:
+            imgs = [i.to(torch.float64) for i in imgs]
+        sfr = edge_sfr(torch.stack([_roi2(i.to(api._device()), factor) for i in imgs]), side=side)
+        ct = local_contrast_device(torch.stack([_profile1(i.to(api._device()), factor) for i in imgs]), window=16)
+        return report_from_sfr(list(images), sfr.result(), ct.cpu().numpy(), factor)
     for title, img in images.items():
         if tuple(img.shape) != (1536 * factor, 2048 * factor):
             raise ValueError(f"{title}: the notebook's ROIs are defined on the {1536 * factor} x {2048 * factor} cal-target frame")

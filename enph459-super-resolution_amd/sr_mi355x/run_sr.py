@@ -31,6 +31,9 @@ def main(argv=None):
     ap.add_argument("--metrics", action="store_true",
                     help="mono_cal_target only: also write metrics.json (slanted-edge MTF50/MTF10, bar contrast: the "
                          "summary of the reference's analysis.ipynb) next to the PNGs")
+    ap.add_argument("--metrics-on-device", action="store_true",
+                    help="with --metrics: the whole report is queued on the device (srx_edge_sfr: percentile, line fits, ESF, MTF50 / MTF10 "
+                         "of the three ROIs in one call) and metrics.json is written by a worker thread; the main thread waits for nothing")
     ap.add_argument("--row-bands", action="store_true",
                     help="several GPUs on ONE image: split every image's IBP loop into row bands (cal_target kinds; under torchrun)")
     ap.add_argument("--register", action="store_true",
@@ -47,6 +50,8 @@ def main(argv=None):
                     help="build the output PNGs on the device (srx_png_file: quantise, Up filter, run lengths and Huffman coding per "
                          "32 KB chunk, the container and its CRC-32); the host only writes the bytes.  Same pixels in every file, other bytes")
     args = ap.parse_args(argv)
+    if args.metrics_on_device and not args.metrics:
+        ap.error("--metrics-on-device needs --metrics")
     rank, world, local_rank = int(os.environ.get("RANK", "0")), int(os.environ.get("WORLD_SIZE", "1")), int(os.environ.get("LOCAL_RANK", "0"))
     dist = None
     if world > 1:  # one process per GPU: pick the device before anything touches it
@@ -70,8 +75,11 @@ def main(argv=None):
     sessions = session.discover_sessions(args.data_dir, args.kind)
     print(f"Found {len(sessions)} session(s):\n" + "\n".join(f"  {os.path.basename(s)}" for s in sessions))
     t0 = time.time()
-    # --metrics: from the device tensors the PNGs were quantised from (session.write_metrics_device), not from the files
-    metrics_cb = session.write_metrics_device if (args.metrics and args.kind == "mono_cal_target") else None
+    # --metrics: from the device tensors the PNGs were quantised from (session.write_metrics_device), not from the files;
+    # --metrics-on-device: the same report queued whole (session.queue_metrics_device)
+    metrics_cb = None
+    if args.metrics and args.kind == "mono_cal_target":
+        metrics_cb = session.queue_metrics_device if args.metrics_on_device else session.write_metrics_device
     session.process_sessions(sessions, psf, args.output_dir, args.kind, rank=rank, world=world, on_images=metrics_cb,
                              row_bands=args.row_bands and world > 1, register=args.register,
                              keep_u8=args.u8_frames, device_png=args.png_on_device)

@@ -626,6 +626,51 @@ def write_metrics_device(out_dir, images, factor=UPSAMPLE_FACTOR):
     return rep
 
 
+def queue_metrics_device(out_dir, images, factor=UPSAMPLE_FACTOR):
+    """write_metrics_device's metrics.json without a wait on the calling thread (process_session's on_images hook; run_sr
+    --metrics-on-device).  Everything is queued: the three ROIs go from the quantised BYTES through one srx_edge_sfr_u8 call
+    (metrics_device.edge_sfr: threshold, line fits, ESF, MTF50 / MTF10 on the device), the four PSNR reductions are two B = 2
+    pair-moment calls (borders 0 and 10), the three bar profiles one local-contrast call; the results are copied into pinned buffers
+    behind one event, and a job of the writer pool waits for it, finishes the few host operations (cycles/mm, the PSNR formulas, the
+    mean) and writes the file.  flush_writes() covers the job.  Same values as write_metrics_device within rounding.
+    Two things follow from the queue.  An item whose status is not 0 (too few edge pixels, ...) raises RuntimeError inside the job, so
+    the error surfaces at flush_writes(), not at this call.  And the job is separate from _save_outputs' PNG jobs, whose last one
+    writes done.flag: as with write_metrics_device, a run interrupted between the two leaves a directory that is marked done and has no
+    metrics.json, and a rerun skips it (session.write_metrics(out_dir) computes the report from the PNGs of such a directory)."""
+    import torch
+    from . import metrics_device as md
+    names = ("native_2x", "SAA", "SAA_IBP")
+    q = [api.quantize_u8(images[n]) for n in names]
+    for n, t in zip(names, q):
+        if tuple(t.shape) != (1536 * factor, 2048 * factor):
+            raise ValueError(f"{n}: the notebook's ROIs are defined on the {1536 * factor} x {2048 * factor} cal-target frame")
+    sfr = md.edge_sfr(torch.stack([md._roi2(t, factor) for t in q])).start_copy()
+    qf = api.u8_to_float(torch.stack(q + [q[2]]), precision="f32")  # native_2x, SAA | SAA_IBP twice: ref = qf[:2], test = qf[2:]
+    moments = torch.stack([md.pair_moments_device(qf[:2], qf[2:], border=0), md.pair_moments_device(qf[:2], qf[2:], border=10)])
+    contrast = md.local_contrast_device(torch.stack([md._profile1(t, factor) for t in q]), window=16)
+
+    def to_host(t):
+        h = torch.empty(t.shape, dtype=t.dtype, pin_memory=True)
+        h.copy_(t, non_blocking=True)
+        return h
+
+    mom_host, ct_host = to_host(moments), to_host(contrast)
+    ready = torch.cuda.Event()
+    ready.record()
+
+    def job():
+        ready.synchronize()
+        rep = md.report_from_sfr(names, sfr.result(), ct_host.numpy(), factor)
+        mom = mom_host.numpy()
+        rep["psnr_db"] = {f"SAA_IBP_vs_{n}": {"plain": md.psnr_from_moments(mom[0, k]), "affine_fit": float(md.psnr_affine_from_moments(mom[1, k]))}
+                          for k, n in enumerate(names[:2])}
+        with open(os.path.join(out_dir, "metrics.json"), "w") as fp:
+            json.dump(rep, fp, indent=2)
+        return rep
+
+    _pending.append(_writer_pool().submit(job))
+
+
 def write_metrics(out_dir, factor=UPSAMPLE_FACTOR):
     """metrics.json for one mono_cal_target output directory: the reference's notebook summary (analysis.ipynb cells
     3-10) computed from the uint8 PNGs just written, as the notebook does."""

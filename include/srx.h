@@ -459,6 +459,48 @@ int srx_ssim_f64(const double *ref, const double *test, int B, int H, int W, int
                  double data_range, double k1, double k2, const double *affine, double *mssim, double *map, void *ws, size_t ws_bytes,
                  srx_stream_t stream);
 
+/* ---- slanted-edge SFR of device ROIs in one call: metrics.slanted_edge_esf -> esf_to_mtf -> mtf_at_fraction (analysis.ipynb cells 6 - 10) ----
+ * img T [B] ROIs of H x W, read in place: `img` points at the first sample of item 0's ROI, rows are row_pitch ELEMENTS apart and items
+ * item_pitch elements (a ROI inside a [B, Hf, Wf] stack: row_pitch = Wf, item_pitch = Hf Wf); `img` needs the alignment of its element only.
+ * side 0 ("left": the edge pixels with a negative distance to the centre line) or 1; sigma: the Gaussian of the edge detector (1.5).
+ * Outputs, all DEVICE arrays; summary and status are required, esf and mtf may be NULL; every element of every output passed is written:
+ *   summary float64 [B][SRX_EDGE_SUMMARY] = {mtf50, mtf10 (cycles per ROI pixel; NaN where the curve never falls through), angle_deg, m, b,
+ *           rows_are_x, threshold, n_edge, n_side, nbin, lo, hi, flipped, m_c, b_c, 0}
+ *   esf     float64 [B][2][SRX_EDGE_MAX_BINS]: x, then y; 0 behind nbin
+ *   mtf     float64 [B][2][SRX_EDGE_MAX_BINS / 2]: frequency in cycles/px, then the MTF, DC included; 0 behind nbin / 2
+ *   status  int32 [B]: 0 ok; 1 fewer than 20 edge pixels; 2 fewer than 10 on the chosen side; 3 a degenerate fit (the u of the pixels have no
+ *           spread) or no pixel with a distance in (-8, 10); 4 nbin < 4 or fewer than 3 non-empty bins.  For a nonzero status the summary holds
+ *           NaN for what was not reached (slot 15 stays 0) and the item's esf / mtf are NaN throughout; nothing is left unwritten.
+ * Per item: the magnitude plane has the bits of srx_edge_magnitude_f64 on the ROI converted to double (the same device functions).  threshold =
+ * np.percentile(mag, 85) bit for bit: an exact radix selection on the bit patterns (8-bit digits, integer histograms in LDS, ties counted), the
+ * two order statistics around (n - 1) 0.85 combined as numpy's _lerp does.  That holds for FINITE samples: a NaN or Inf sample gives NaN
+ * magnitudes, whose bit patterns order above +Inf here, where np.percentile returns NaN for the whole plane; nothing faults (a NaN
+ * threshold leaves no edge pixel: status 1), but the value is then not numpy's.  Edge pixels: mag > threshold; rows_are_x = (row span >= column
+ * span).  The two np.polyfit lines (m_c, b_c through all edge pixels, m, b through those on the chosen side) are the closed form on EXACT integer
+ * sums n, su, sv, suu, suv: m = (n suv - su sv) / (n suu - su^2) with both differences exact (128-bit) and converted once, b = (sv - m su) / n.
+ * lo, hi: min / max of the distances (v - m u - b) / sqrt(1 + m^2) in (-8, 10) (srx_edge_dist_range's expression); bin edges lo + i / 4,
+ * ceil(((hi + 1/4) - lo) / (1/4)) of them as np.arange counts, nbin one less.  Bin sums in a fixed order: the rows in min(H, 256) groups of
+ * ceil(H / groups) consecutive rows, a group's pixels of a bin added in raster order, then the groups in index order.  ESF = sum / count, empty
+ * bins filled as np.interp fills them over the non-empty ones, reversed (x negated) if it falls; LSF = np.gradient's non-uniform second-order
+ * form, times np.hanning; a direct DFT for k < nbin / 2 (the twiddle index j k reduced mod nbin in integers), divided by its DC value if positive;
+ * freq[k] = k / (nbin mean(diff(x))); MTF50 / MTF10: the first downward crossing among k >= 1, interpolated as metrics.mtf_at_fraction does.
+ *   srx_edge_sfr_scratch_bytes(B, H, W): the workspace of a call, a multiple of 256 (0 for arguments no call accepts).
+ * Six kernel launches on `stream` whatever the samples hold; no allocation, no host synchronisation, no memset or copy node.  The bits are the
+ * same run to run, and item b of a batch gets the bits of a B = 1 call.  The workspace may hold anything on entry; only the outputs and
+ * [0, ws_bytes) are written; inputs are never written.
+ * SRX_E_INVALID: a null img / summary / status; B, H or W <= 0; row_pitch < W; item_pitch < (H - 1) row_pitch + W with B > 1; side not 0 / 1;
+ * sigma not > 0.  SRX_E_UNSUPPORTED: H W > 2^20, B > 65535, a Gaussian radius above 8 (as srx_edge_magnitude_f64).  SRX_E_WORKSPACE: the
+ * workspace is shorter than srx_edge_sfr_scratch_bytes or not 256-byte aligned.  All decided on the host before any HIP call, in this order. */
+#define SRX_EDGE_MAX_BINS 80 /* distances in (-8, 10) at 1/4 px give at most 72 bins */
+#define SRX_EDGE_SUMMARY 16
+size_t srx_edge_sfr_scratch_bytes(int B, int H, int W);
+int srx_edge_sfr_u8(const uint8_t *img, int B, int H, int W, size_t row_pitch, size_t item_pitch, int side, double sigma, void *summary, void *esf,
+                    void *mtf, void *status, void *ws, size_t ws_bytes, srx_stream_t stream);
+int srx_edge_sfr_f32(const float *img, int B, int H, int W, size_t row_pitch, size_t item_pitch, int side, double sigma, void *summary, void *esf,
+                     void *mtf, void *status, void *ws, size_t ws_bytes, srx_stream_t stream);
+int srx_edge_sfr_f64(const double *img, int B, int H, int W, size_t row_pitch, size_t item_pitch, int side, double sigma, void *summary, void *esf,
+                     void *mtf, void *status, void *ws, size_t ws_bytes, srx_stream_t stream);
+
 /* ---- sub-pixel frame registration (translation only), on DEVICE frames ----
  * frames [B, N, H, W] (the srx_saa layout); for every item b and frame k != ref: d = shifts[b][k] with frames[k] ~ ndi.shift(frames[ref], d),
  * LR pixels, (dy, dx): the sign convention of shifts_yx, so anchor + d (anchor = the reference frame's known shift) goes straight into
