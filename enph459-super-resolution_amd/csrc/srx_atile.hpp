@@ -44,9 +44,6 @@ using btile::XW;
 using btile::zero_outside;
 using blk::RW;
 
-#ifndef SRX_AT_DBG
-#define SRX_AT_DBG 0  // timing ablations of a development build (results are wrong): 1 no operand loads, 2 no G stores, 4 no G loads (backward)
-#endif
 struct AArgs {
     int H, W, Hg, Wg, nwx, nwy;  // (nwx, nwy: the FORWARD kernel's windows)
     int Dy, Dx, PBy, PBx;        // G[p', q'] pairs with Y[p' - Dy, q' - Dx]; p' < PBy or q' < PBx: near band
@@ -126,12 +123,6 @@ template <int OFF, int Y0, int Y1, bool CHK> struct FarQuads {
     static __device__ __forceinline__ bool on(int y, int y0, int y1) { return y >= 0 && y < 64 && (CHK ? (y >= y0 && y < y1) : (y >= Y0 && y < Y1)); }
     static __device__ __forceinline__ void load1(float (&m)[8], __amdgpu_buffer_rsrc_t rsMC, int voff)
     {
-        if (SRX_AT_DBG & 1) {
-#pragma unroll
-            for (int i = 0; i < 8; i++)
-                m[i] = (i & 1) ? 1.f : __int_as_float(voff & 0xff);
-            return;
-        }
         const u32x4 a = __builtin_amdgcn_raw_buffer_load_b128(rsMC, voff, 0, 0);
         const u32x4 b = __builtin_amdgcn_raw_buffer_load_b128(rsMC, voff + 16, 0, 0);
         m[0] = __uint_as_float(a.x), m[1] = __uint_as_float(a.y), m[2] = __uint_as_float(a.z), m[3] = __uint_as_float(a.w);
@@ -166,10 +157,7 @@ template <int OFF, int Y0, int Y1, bool CHK> struct FarQuads {
                 g[q] = (o && C > 0.f) ? fmaf(-C, c[(y >= 0 && y < 64) ? y : 0], M) : 0.f;
                 sq = fmaf(g[q] * g[q], mosaic::rcp_count(C), sq);
             }
-            if (SRX_AT_DBG & 2) {
-                if (g[0] + g[1] + g[2] + g[3] == 123.456f)
-                    fused::buf_store<float>(g[0], rsG, vg0, 0);
-            } else if (all) {
+            if (all) {
                 const u32x4 v = {__float_as_uint(g[0]), __float_as_uint(g[1]), __float_as_uint(g[2]), __float_as_uint(g[3])};
                 __builtin_amdgcn_raw_buffer_store_b128(v, rsG, vg0 + j * Wg16, 0, 0);
             } else {
@@ -386,7 +374,7 @@ __global__ void __launch_bounds__(NBY *NBX * 64, 2)
         }
 #pragma unroll
         for (int j = 0; j < 16; j++) {
-            const u32x4 t = (SRX_AT_DBG & 4) ? u32x4{(unsigned)j, 0x3f800000u, (unsigned)vq0 & 0xffu, 0u} : __builtin_amdgcn_raw_buffer_load_b128(rsG, vq0 + j * Wg16, 0, 0);
+            const u32x4 t = __builtin_amdgcn_raw_buffer_load_b128(rsG, vq0 + j * Wg16, 0, 0);
             g[2 + 4 * j] = __uint_as_float(t.x), g[3 + 4 * j] = __uint_as_float(t.y), g[4 + 4 * j] = __uint_as_float(t.z), g[5 + 4 * j] = __uint_as_float(t.w);
         }
         g[66] = fused::buf_load<float>(rsG, vq0 + 16 * Wg16, 0);

@@ -25,18 +25,12 @@
 namespace srx {
 namespace blk {
 
-#ifndef SRX_ADDTID
-#define SRX_ADDTID 1
-#endif
 #ifndef SRX_M0_NOP
 #define SRX_M0_NOP "s_nop 0\n\t"  // the ISA asks for one wait state between a scalar write of M0 and an LDS add-TID instruction, and inside
                                   // an asm block nobody inserts it.  Without it the first store of a block sometimes went out with the M0 of
                                   // before (round 3: k_ibp_ztile's 7 x 7 form, one row of one wave wrong in 7 of 40 calls, always behind the
                                   // tile that sums the previous iteration's MSE partials; tools/stress_determinism.py, tests/test_gpu_parity.py::
                                   // test_frame_kernel_is_deterministic).  "" reproduces it.
-#endif
-#ifndef SRX_TRANSPOSE_DEF
-#define SRX_TRANSPOSE_DEF 1
 #endif
 constexpr int TSD = 68;        // LDS row stride of a half-block transpose (a multiple of 4 words: 16-byte row reads; 17 quads: the 16
                                // lanes the LDS serves together read 16 different quads of banks, conflict-free)
@@ -113,18 +107,16 @@ __device__ __forceinline__ void transpose64(const float (&a)[64], float (&r)[64]
     // last written, across the whole preceding stage and around the iteration loop (64 registers pinned beside the 64 of the
     // working plane: ~150 spills per iteration).  An empty asm defines every element, placed where its life should start: after
     // pass 0 has parked a[0..31] in LDS, not before (an up-front definition keeps 128 registers live through the first 32 stores).
-    // (SRX_TRANSPOSE_DEF 0: pass 0 reads unpredicated instead -- the upper half-wave re-reads the lower half's rows.  Same
-    // registers, but a third more LDS read traffic in a phase the LDS bounds: C2 162 instead of 156 us per iteration.)
+    // (Reading pass 0 unpredicated instead -- the upper half-wave re-reads the lower half's rows -- takes the same registers,
+    // but a third more LDS read traffic in a phase the LDS bounds: measured C2 162 against 156 us per iteration.)
     // The rows are read 16 bytes at a time (ds_read_b128, 4 LDS cycles per wave-instruction for 1 KB): with the 66-word pitch before,
     // rows were only 8-byte aligned and hipcc fused the adjacent 8-byte reads into ds_read2_b64, which moves its 1 KB in 8 cycles.  Same-box
     // A/B on C2: 132.5-133.5 -> 128.3-130.1 us per iteration.  Reading with the WHOLE wave instead (the half-waves exchange quadrants by
     // v_permlane32_swap first, half as many reads, none predicated) shortens the transposes further and gains nothing: the swaps cost a
     // SIMD's four waves 25 cycles each, and the time reappears at the barriers around the transposes.
     const unsigned m0v = __builtin_amdgcn_readfirstlane((unsigned)(uintptr_t)Tw);  // LDS byte address of the wave's region
-    (void)m0v;
 #pragma unroll
     for (int h = 0; h < 2; h++) {
-#if SRX_ADDTID
         // Tw[i * TSD + lane] = a[32 h + i] as ds_write_addtid_b32 (address = M0 + offset + 4 * lane, no address register): two LDS
         // cycles per wave-instruction, where ds_write_b32 takes four (its address and data registers travel to the LDS at two cycles
         // per dword) -- the transposes are bound by exactly that (C2: 154 -> 152 us per iteration).  M0 and the stores in one asm block:
@@ -168,22 +160,13 @@ __device__ __forceinline__ void transpose64(const float (&a)[64], float (&r)[64]
                      "ds_write_addtid_b32 %14 offset:8160\n\t"
                      "ds_write_addtid_b32 %15 offset:8432\n\t"
                      :: "v"(a[32 * h + 16]), "v"(a[32 * h + 17]), "v"(a[32 * h + 18]), "v"(a[32 * h + 19]), "v"(a[32 * h + 20]), "v"(a[32 * h + 21]), "v"(a[32 * h + 22]), "v"(a[32 * h + 23]), "v"(a[32 * h + 24]), "v"(a[32 * h + 25]), "v"(a[32 * h + 26]), "v"(a[32 * h + 27]), "v"(a[32 * h + 28]), "v"(a[32 * h + 29]), "v"(a[32 * h + 30]), "v"(a[32 * h + 31]), "s"(m0v) : "memory", "m0");
-#else
-#pragma unroll
-        for (int i = 0; i < 32; i++)
-            Tw[i * TSD + lane] = a[32 * h + i];
-#endif
         __builtin_amdgcn_wave_barrier();
-#if SRX_TRANSPOSE_DEF
         if (h == 0) {
 #pragma unroll
             for (int j = 0; j < 64; j++)
                 asm volatile("" : "=v"(r[j]));
         }
         if ((lane >> 5) == h) {
-#else
-        if (h == 0 || (lane >> 5) == h) {
-#endif
             const float4 *row = reinterpret_cast<const float4 *>(Tw + (lane & 31) * TSD);
 #pragma unroll
             for (int k = 0; k < 16; k++) {
@@ -222,12 +205,10 @@ __device__ __forceinline__ void transpose64(const double (&a)[64], double (&r)[6
 // FIX = 16 samples (|z|^17 = 2e-10).  Measured on one box (C2, tools/ab_bench.sh): one chain 138.3 us per iteration, two sub-chains
 // 132.8, four (16 steps, then 3 x 16 fix-up fmas whose end values are themselves fixed first) 141.8 -- with four waves per SIMD the
 // chains of several waves already overlap, and the fix-ups are real work.
-#ifndef SRX_CHAIN_NSUB
-#define SRX_CHAIN_NSUB 2
-#endif
+constexpr int CHAIN_NSUB = 2;
 template <bool REV, typename T> __device__ __forceinline__ void chain64(T (&a)[64], T st0)
 {
-    constexpr int NSUB = SRX_CHAIN_NSUB, L = 64 / NSUB, FIX = Cn<T>::FIX;
+    constexpr int NSUB = CHAIN_NSUB, L = 64 / NSUB, FIX = Cn<T>::FIX;
     static_assert(NSUB == 1 || L >= FIX, "a fix-up may not reach into the next sub-chain's start");
     const T z = Cn<T>::Z;
     auto at = [&](int i) -> T & { return a[REV ? 63 - i : i]; };  // position along the direction of the recursion
@@ -514,9 +495,7 @@ constexpr int SLOT_D = 512;   // 256 words between the exchange slots: where the
 constexpr int SLOT_Z = 2048;  // eight zero words (what the lanes that lack nothing add; what a wave at the patch's edge reads for its missing neighbour)
 static_assert(SLOT_D >= SLOT0 + 448 && SLOT_D + 256 <= SLOT1 && SLOT_E >= SLOT1 + 448 && SLOT_E + 512 <= SLOT_Z && SLOT_Z + 8 <= RW, "slots inside the wave's region");
 
-#ifndef SRX_PATCH_B2D_NB
-#define SRX_PATCH_B2D_NB 4
-#endif
+constexpr int B2D_NB = 4;  // rows that blur2d_pass1 advances together
 template <int RAD>
 __device__ __forceinline__ void blur2d_pass1(float (&a)[64], const float (&hl)[3], const float (&hr)[3], float *Rown, int lane, const float *w56)
 {
@@ -532,7 +511,7 @@ __device__ __forceinline__ void blur2d_pass1(float (&a)[64], const float (&hl)[3
     // dump area (the store is unpredicated: the loop stays one basic block)
     f4 *edst = reinterpret_cast<f4 *>(__builtin_assume_aligned(lane == 63 ? Rown + SLOT_E : lane == 0 ? Rown + SLOT_E + 4 : Rown + SLOT_D + 4 * lane, 16));
     const int estr = (lane == 63 || lane == 0) ? 2 : 0;  // in units of 16 bytes per row
-    constexpr int NB = SRX_PATCH_B2D_NB;
+    constexpr int NB = B2D_NB;
     float c0 = hl[0], c1 = hl[1], c2 = hl[2];
 #pragma unroll
     for (int j0 = 0; j0 < 64; j0 += NB) {

@@ -39,21 +39,8 @@ constexpr float K2 = blk::Cn<float>::K2;
 #else
 #define SRX_PSTAMP2(PH) do { } while (0)
 #endif
-#ifndef SRX_BT_PREFETCH
-#define SRX_BT_PREFETCH 1  // the forward kernel's LR samples requested ahead of the H-FIR and the transpose
-#endif
-#ifndef SRX_BT_DBG
-#define SRX_BT_DBG 0  // timing ablations of a development build (results are wrong): 1 no residual stores, 2 no state stores, 4 no LR loads,
-#endif                // 8 no residual loads, 16 no state loads, 32 no transposes (registers copied)
-#ifndef SRX_BT_NBY
-#define SRX_BT_NBY 2  // window shape in 64 x 64 blocks = waves (ibp_t's comment has what other shapes measured)
-#endif
-#ifndef SRX_BT_NBX
-#define SRX_BT_NBX 2
-#endif
-#ifndef SRX_BT_MINB
-#define SRX_BT_MINB 2  // workgroups per CU the register allocation aims at
-#endif
+constexpr int BT_NBY = 2, BT_NBX = 2;  // window shape in 64 x 64 blocks = waves (ibp_t's comment has what other shapes measured)
+constexpr int BT_MINB = 2;             // workgroups per CU the register allocation aims at
 constexpr int HLO = 14, HHI = 18;  // halo before / after the owned span (forward kernel: 3 blur + 11 | 3 FIR reach + 11 + 3 + 1)
 constexpr int HHB = 14;            // ... after the owned span of the backward kernel (11 + 3): its windows own 100 x 100, a tenth fewer of them
 constexpr int MAXF = 16;           // frames per call
@@ -175,15 +162,9 @@ __device__ __forceinline__ void zero_outside(float (&a)[64], int c0, int hi)
 // outputs per instruction (v_pk_fma_f32).  These kernels run one or two waves per SIMD, where a wave issues an instruction every
 // ~5 cycles whatever it does (profiles/README.md): what counts is the number of instructions, and a packed fma is one.
 typedef float v2f __attribute__((ext_vector_type(2)));
-#ifndef SRX_BT_PK
-#define SRX_BT_PK 1
-#endif
 __device__ __forceinline__ void blur_block(float (&a)[64], bool first, bool last, float *Xown, const float *Xprev, const float *Xnext, int s6, int lane,
                                            const f8 kb)
 {
-#if !SRX_BT_PK
-    blk::blur_block(a, first, last, Xown, Xprev, Xnext, s6, lane, kb);
-#else
     Xown[s6 + lane] = a[0];
     Xown[s6 + 64 + lane] = a[1];
     Xown[s6 + 128 + lane] = a[2];
@@ -226,7 +207,6 @@ __device__ __forceinline__ void blur_block(float (&a)[64], bool first, bool last
             a[j0 + 2 * q] = acc[q].x, a[j0 + 2 * q + 1] = acc[q].y;
         __builtin_amdgcn_sched_barrier(0);
     }
-#endif
 }
 
 // ---- 7 x 7 correlation of a block in COLUMN layout (lane = column, registers = rows) for a PSF that is not rank 1 ------------------
@@ -410,16 +390,9 @@ __device__ __forceinline__ void hfir_up(float (&A)[64], const float (&g)[64], co
 
 __device__ __forceinline__ int asr1(int x) { return x >> 1; }  // floor(x / 2)
 
-__device__ __forceinline__ void transpose64(const float (&a)[64], float (&r)[64], float *Tw, int lane)
-{
-#if SRX_BT_DBG & 32
-#pragma unroll
-    for (int i = 0; i < 64; i++)
-        r[i] = a[i];
-#else
-    blk::transpose64(a, r, Tw, lane);
-#endif
-}
+// (a function of its own: with `using blk::transpose64` in its place the window kernels come out in another instruction order, k_ibp_bbwd
+// with 239 registers instead of 238)
+__device__ __forceinline__ void transpose64(const float (&a)[64], float (&r)[64], float *Tw, int lane) { blk::transpose64(a, r, Tw, lane); }
 
 constexpr int VOFF_OUT = (int)0x80000000;  // a lane offset that stays out of every descriptor's range when a row offset (< 2^30) is added
 
@@ -434,7 +407,7 @@ __device__ __forceinline__ void fwd_rows_load(float (&lv)[LVN], __amdgpu_buffer_
         int voff = vbase + i * w4;
         if (CHK)
             voff = (unsigned)(i - ilo) < nrow ? voff : VOFF_OUT;
-        lv[i - I0] = (SRX_BT_DBG & 4) ? __int_as_float(voff) : fused::buf_load<float>(rs_lr, voff, 0);
+        lv[i - I0] = fused::buf_load<float>(rs_lr, voff, 0);
     }
 }
 template <int I0, int I1, bool CHK, int LVN>
@@ -455,8 +428,7 @@ __device__ __forceinline__ void fwd_rows(const float (&t)[64], const float (&th)
             voff = ok ? voff : VOFF_OUT;
             e = ok ? e : 0.f;
         }
-        if (!(SRX_BT_DBG & 1))
-            fused::buf_store<float>(e, rs_er, voff, 0);  // out of the descriptor's range: dropped
+        fused::buf_store<float>(e, rs_er, voff, 0);  // out of the descriptor's range: dropped
         sq = fmaf(e, e, sq);
     }
 }
@@ -472,7 +444,7 @@ __device__ __forceinline__ void bwd_rows_load(float (&E)[34], __amdgpu_buffer_rs
         int voff = vrow0 + (CLAMP_LO ? max(row, 0) : row) * w4;
         if (CHECK_HI)
             voff = row < h ? voff : VOFF_OUT;
-        E[m] = (SRX_BT_DBG & 8) ? __int_as_float(voff & 0xffff) : fused::buf_load<float>(rs_er, voff, 0);
+        E[m] = fused::buf_load<float>(rs_er, voff, 0);
     }
 }
 
@@ -486,12 +458,7 @@ using blk::u32x4;
 // quad q of the block (q = -1: the half quad of y = 0, 1; 0..14: y = 2 + 4 q ..; 15: the half quad of y = 62, 63)
 template <int Q> __device__ __forceinline__ void quad_load(float (&a)[64], __amdgpu_buffer_rsrc_t rs, int vq0, int W16)
 {
-    if (SRX_BT_DBG & 16) {
-        if (Q >= 0 && Q < 15)
-            a[2 + 4 * Q] = a[3 + 4 * Q] = a[4 + 4 * Q] = a[5 + 4 * Q] = __int_as_float((vq0 + Q) & 0xffff);
-        else
-            a[Q < 0 ? 0 : 62] = a[Q < 0 ? 1 : 63] = 1.f;
-    } else if (Q == -1) {
+    if (Q == -1) {
         const u32x2 v = __builtin_amdgcn_raw_buffer_load_b64(rs, vq0 - W16 + 8, 0, 0);
         a[0] = __uint_as_float(v.x), a[1] = __uint_as_float(v.y);
     } else if (Q == 15) {
@@ -514,10 +481,7 @@ template <int Q> __device__ __forceinline__ void quad_update(const float (&r)[64
                                                             int ymax)
 {
     auto U = [&](int y) -> float { return y < ymax ? __builtin_amdgcn_fmed3f(fmaf(r[y], sn, hv[y]), 0.f, 255.f) : 0.f; };
-    if (SRX_BT_DBG & 2) {
-        if (U(2 + 4 * (Q < 0 ? 0 : (Q > 14 ? 14 : Q))) == 123.456f)
-            __builtin_amdgcn_raw_buffer_store_b32(1u, rs, vq0, 0, 0);
-    } else if (Q == -1) {
+    if (Q == -1) {
         const u32x2 v = {__float_as_uint(U(0)), __float_as_uint(U(1))};
         __builtin_amdgcn_raw_buffer_store_b64(v, rs, vq0 - W16 + 8, 0, 0);
     } else if (Q == 15) {
@@ -617,7 +581,7 @@ template <int NBY, int NBX> struct Geo {
 // forward: err[b, k, i, j] = lr - (F_k P pad B hr)[2 i, 2 j];  epart[b, window] = sum err^2 * scale.  grid (nwx, nwy, B)
 // =========================================================================================================================
 template <int NBY, int NBX, int PSF, bool ITEMS = false>  // PSF: 0 = rank 1 (7 + 7 taps); 2, 3 = the 2-D form with a support of 5 x 5 / 7 x 7
-__global__ void __launch_bounds__(NBY *NBX * 64, SRX_BT_MINB)
+__global__ void __launch_bounds__(NBY *NBX * 64, BT_MINB)
     k_ibp_bfwd(const float *__restrict__ S, const float *__restrict__ lr, float *__restrict__ err, BArgs A, const int *__restrict__ frtab,
                double *__restrict__ epart, double scale, int frstride)  // (frstride last: the other arguments lie where they lay)
 {
@@ -713,7 +677,6 @@ __global__ void __launch_bounds__(NBY *NBX * 64, SRX_BT_MINB)
         const bool interior = asr1(Pb - oyf_max) >= 0 && asr1(Pb + 1 - oyf_min) + 32 <= h;
         const int rowsel = !interior ? 0 : (s == 0 ? 1 : (s == NBY - 1 ? 2 : 3));
         float lv[32];  // (ONE array for every variant: two would both count as live across the exchange)
-#if SRX_BT_PREFETCH
         // interior blocks request their LR samples ahead of the H-FIR (the 32 checked rows of an edge block would spill)
         if (rowsel == 1)
             fwd_rows_load<IA0, 32, false>(lv, rs_lr, vbase, w4, ilo, nrow);
@@ -721,7 +684,6 @@ __global__ void __launch_bounds__(NBY *NBX * 64, SRX_BT_MINB)
             fwd_rows_load<0, IB1, false>(lv, rs_lr, vbase, w4, ilo, nrow);
         else if (NBY > 2 && rowsel == 3)
             fwd_rows_load<0, (NBY > 2 ? 32 : 0), false>(lv, rs_lr, vbase, w4, ilo, nrow);
-#endif
         float sv[64];
 #pragma unroll
         for (int half = 0; half < 2; half++) {
@@ -761,14 +723,6 @@ __global__ void __launch_bounds__(NBY *NBX * 64, SRX_BT_MINB)
         }
         if (rowsel == 0)
             fwd_rows_load<0, 32, true>(lv, rs_lr, vbase, w4, ilo, nrow);
-#if !SRX_BT_PREFETCH
-        else if (rowsel == 1)
-            fwd_rows_load<IA0, 32, false>(lv, rs_lr, vbase, w4, ilo, nrow);
-        else if (rowsel == 2)
-            fwd_rows_load<0, IB1, false>(lv, rs_lr, vbase, w4, ilo, nrow);
-        else if (NBY > 2 && rowsel == 3)
-            fwd_rows_load<0, (NBY > 2 ? 32 : 0), false>(lv, rs_lr, vbase, w4, ilo, nrow);
-#endif
         // the three rows past the block: the block below holds them
         float *ex = lds + L::OFF_EX + wave * 512 + (kp & 1) * 256;
         const float *exd = lds + L::OFF_EX + (wave + NBX) * 512 + (kp & 1) * 256;
@@ -810,7 +764,7 @@ __global__ void __launch_bounds__(NBY *NBX * 64, SRX_BT_MINB)
 // grid (nwx, nwy, B).  The window (0, 0) of an item also sums the forward kernel's per-window MSE partials.
 // =========================================================================================================================
 template <int NBY, int NBX, int PSF, bool ITEMS = false>
-__global__ void __launch_bounds__(NBY *NBX * 64, SRX_BT_MINB)
+__global__ void __launch_bounds__(NBY *NBX * 64, BT_MINB)
     k_ibp_bbwd(const float *__restrict__ err, float *__restrict__ S, BArgs A, const int *__restrict__ frtab, const double *__restrict__ epart,
                double *__restrict__ errors, int errors_stride, int frstride)
 {
@@ -904,7 +858,6 @@ __global__ void __launch_bounds__(NBY *NBX * 64, SRX_BT_MINB)
                         y2 = lane_ok ? __int_as_float(fk[14]) : 0.f, y3 = lane_ok ? __int_as_float(fk[15]) : 0.f;
             const float a0 = py ? y1 : y0, a1 = py ? y3 : y2;
             const float b0 = py ? y0 : 0.f, b1 = py ? y2 : y1, b2 = py ? 0.f : y3;
-#if SRX_BT_PK
             const v2f w0 = {a0, b0}, w1 = {a1, b1}, w2 = {0.f, b2};  // both rows of a pair from one residual row per instruction
 #pragma unroll
             for (int t = 0; t < 32; t++) {
@@ -913,13 +866,6 @@ __global__ void __launch_bounds__(NBY *NBX * 64, SRX_BT_MINB)
                 acc = __builtin_elementwise_fma(w0, (v2f){E[t], E[t]}, acc);
                 uu[2 * t] = acc.x, uu[2 * t + 1] = acc.y;
             }
-#else
-#pragma unroll
-            for (int t = 0; t < 32; t++) {
-                uu[2 * t] = fmaf(a0, E[t], a1 * E[t + 1]);
-                uu[2 * t + 1] = fmaf(b0, E[t], fmaf(b1, E[t + 1], b2 * E[t + 2]));
-            }
-#endif
             if (Pb < SRX_NPAD + 5) {  // top pad: the odd pad samples also hold LR row 0 (E[0]: ibase <= 0 here)
                 const float wq[4] = {y0, y1, y2, y3};
 #pragma unroll
@@ -1069,7 +1015,7 @@ struct Dims {
 };
 static inline size_t windows(int H, int W)
 {
-    return (size_t)cdiv(H + 2 * SRX_NPAD, Geo<SRX_BT_NBY, SRX_BT_NBX>::OWNY) * cdiv(W + 2 * SRX_NPAD, Geo<SRX_BT_NBY, SRX_BT_NBX>::OWNX);
+    return (size_t)cdiv(H + 2 * SRX_NPAD, Geo<BT_NBY, BT_NBX>::OWNY) * cdiv(W + 2 * SRX_NPAD, Geo<BT_NBY, BT_NBX>::OWNX);
 }
 struct Carved {
     float *err;
@@ -1125,9 +1071,9 @@ static inline void make_frames(const double *sh, int N, BFrame *fr, int nfr, int
 // against 2 x 4 (128 x 256, 96 x 224 owned, 1.52x recompute, ONE workgroup of eight waves per CU) on 1536 x 2048: one frame 48.3
 // against 44.4 us per iteration, eight frames 211 against 185 -- eight waves that meet at every barrier wait for their slowest,
 // two independent workgroups fill each other's waits (srx_ztile.hpp found the same).  Round 4, 2 x 3 and 3 x 2 waves (221 / 208 windows of
-// six waves: every window a compute unit of its own on one frame, tools/dev/bt_shape_ab.sh): one frame 2.087 / 2.16 against 2.06 ms per
+// six waves: every window a compute unit of its own on one frame): one frame 2.087 / 2.16 against 2.06 ms per
 // step, eight frames 11.5 / 12.1 against 9.6, measured PSF 2.46 / 2.49 against 2.42 -- the six waves' barriers cost more than the idle
-// compute units.  The shape is fixed (SRX_BT_NBY x SRX_BT_NBX), so a batch gives every item the bits it gets alone.
+// compute units.  The shape is fixed (BT_NBY x BT_NBX), so a batch gives every item the bits it gets alone.
 // per_item: sh is [B][N][2], one table per item.  The host builds every item's records with make_frames (the weights an item gets are the
 // ones it gets alone by construction) and ceil(B * tab_stride(N) / PARAM_WORDS) launches of k_param_words carry them to the device; the
 // workspace holds items_tab_bytes(B, N) more.
@@ -1234,10 +1180,10 @@ template <int NBY, int NBX> static int ibp_t(const IbpCall<float> &c, bool per_i
     return SRX_OK;
 }
 
-static int ibp(const IbpCall<float> &c) { return ibp_t<SRX_BT_NBY, SRX_BT_NBX>(c, false); }
+static int ibp(const IbpCall<float> &c) { return ibp_t<BT_NBY, BT_NBX>(c, false); }
 
 // one table per item: sh is [B][N][2], every item routed to "btile" (srx_items.hpp)
-static int ibp_items(const IbpCall<float> &c) { return ibp_t<SRX_BT_NBY, SRX_BT_NBX>(c, true); }
+static int ibp_items(const IbpCall<float> &c) { return ibp_t<BT_NBY, BT_NBX>(c, true); }
 
 }  // namespace btile
 }  // namespace srx

@@ -298,9 +298,7 @@ __device__ __forceinline__ void xcd_block_2d(int &bx, int &by)
     bx = (int)(id % gx);
     by = (int)(id / gx);
 }
-#ifndef SRX_XCD_FRAME
-#define SRX_XCD_FRAME 1  // the register-resident frame / window kernels (k_ibp_ztile, k_ibp_ctile, k_ibp_dtile) take their tiles in that order too
-#endif
+// (the register-resident frame / window kernels -- k_ibp_ztile, k_ibp_ctile, k_ibp_dtile -- take their tiles in that order too)
 
 // Diagnostic build only (-DSRX_STAMPS): s_memtime stamps at phase boundaries, thread 0 of every block, into a
 // buffer nothing else reads (tools/stamps.py reads it back).  No stamp executes in the normal build.

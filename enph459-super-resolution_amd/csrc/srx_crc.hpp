@@ -187,12 +187,9 @@ static_assert(LANES == 256 && (1 << ilog2(SPAN)) == SPAN && SPAN % 16 == 0, "the
 
 __device__ const Pow8 pow8_dev = make_pow8();
 
-// the segment in LDS: four bytes of padding behind every span (srx_png.hpp's Raw: 68 bytes = 17 banks from lane to lane).  A diagnostic
-// build with -DSRX_CRC_STAGE_PAD=0 puts the spans 64 bytes apart (measured: no difference beyond the rounds' spread).
-#ifndef SRX_CRC_STAGE_PAD
-#define SRX_CRC_STAGE_PAD 4
-#endif
-constexpr int PAD = SRX_CRC_STAGE_PAD, PITCH = SPAN + PAD;
+// the segment in LDS: four bytes of padding behind every span (srx_png.hpp's Raw: 68 bytes = 17 banks from lane to lane).  With the
+// spans 64 bytes apart instead: measured, no difference beyond the rounds' spread.
+constexpr int PAD = 4, PITCH = SPAN + PAD;
 static_assert(PAD >= 0 && PAD % 4 == 0, "the spans stay word aligned");
 constexpr int STAGE_BYTES = PITCH * LANES;
 __device__ __forceinline__ int padded(int v) { return v + (v / SPAN) * PAD; }

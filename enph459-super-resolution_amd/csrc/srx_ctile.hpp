@@ -24,17 +24,15 @@ namespace ctile {
 constexpr int RG = 256, HALO = 6, VT = RG - 2 * HALO, SW = 4;
 // Rows of a tile's region.  float32: 64 (52 owned).  float64: a region of 64 rows is 128 registers and the pre-update state cannot be
 // held beside it -- the first float64 form read it AGAIN behind the last blur (eight dependent batches of loads at the end of every
-// tile: 55 % of the wave-cycles waiting, 58 spilled registers, 1.63x the algorithmic traffic).  With SRX_CTILE_ROWS64 = 40 rows (28
+// tile: 55 % of the wave-cycles waiting, 58 spilled registers, 1.63x the algorithmic traffic).  With ROWS64 = 40 rows (28
 // owned) region and held state are 2 x 80 registers: 1.50x halo reads instead of 1.29x + the re-read, no second load phase, no spill.
 // mono_cal_target's shape, us per iteration on one box: 64 rows 115; 48 rows 106.6 (45 spilled); 44: 99.9; 40: 92.2; 36: 94.0; 32: 96.8.
-#ifndef SRX_CTILE_ROWS64
-#define SRX_CTILE_ROWS64 40
-#endif
+constexpr int ROWS64 = 40;
 template <typename T> struct Rows {
-    static constexpr int NR = sizeof(T) == 8 ? SRX_CTILE_ROWS64 : 64;
+    static constexpr int NR = sizeof(T) == 8 ? ROWS64 : 64;
 };
-static_assert(SRX_CTILE_ROWS64 % 4 == 0 && SRX_CTILE_ROWS64 > 2 * HALO && SRX_CTILE_ROWS64 <= 64, "row quads; something to own");
-static inline int rows_for(int eb) { return eb == 8 ? SRX_CTILE_ROWS64 : 64; }
+static_assert(ROWS64 % 4 == 0 && ROWS64 > 2 * HALO && ROWS64 <= 64, "row quads; something to own");
+static inline int rows_for(int eb) { return eb == 8 ? ROWS64 : 64; }
 
 struct CArgs {
     int H, W, tiles_x, tiles_y, HP, WP;
@@ -284,8 +282,7 @@ __global__ void __launch_bounds__(256, 2)
     const int tid = threadIdx.x, lane = tid & 63;
     const int u = __builtin_amdgcn_readfirstlane(tid >> 6);
     int tx = blockIdx.x, ty = blockIdx.y, b = blockIdx.z;
-    if (SRX_XCD_FRAME)
-        xcd_block_2d(tx, ty);
+    xcd_block_2d(tx, ty);
     const int H = ca.H, W = ca.W, HP = ca.HP, WP = ca.WP;
     const int pr0 = ty * VTY, pc0 = tx * VT;
     const bool top = ty == 0, left = tx == 0;
@@ -318,10 +315,8 @@ __global__ void __launch_bounds__(256, 2)
     // the packed operands of the G step: in float32 all sixteen row quads are in flight during the first two blurs; float64 has no
     // registers to spare (the region alone is 128) and fetches them four quads at a time inside the G step
     const int cmok = __builtin_amdgcn_readfirstlane(tb.cmok[b]);
-#ifndef SRX_CTILE_CMQ64
-#define SRX_CTILE_CMQ64 4
-#endif
-    constexpr int CMQ = sizeof(T) == 4 ? NR / 4 : (SRX_CTILE_CMQ64 == 0 ? NR / 4 : SRX_CTILE_CMQ64);
+    constexpr int CMQ64 = 4;
+    constexpr int CMQ = sizeof(T) == 4 ? NR / 4 : CMQ64;
     uint2 cm[CMQ];
     const size_t cplane = (size_t)(HP / 4) * WP;
     const __amdgpu_buffer_rsrc_t rsP = fused::plane_rsrc(tb.CM4 + (size_t)b * cplane, cplane);

@@ -338,7 +338,7 @@ __device__ __forceinline__ void dtile_body(float *lds, const float *__restrict__
     const int tid0 = threadIdx.x;
     const int wave = __builtin_amdgcn_readfirstlane(tid0 >> 6), s = wave / NSX, u = wave - s * NSX;
     const int b = blockIdx.y;
-    const unsigned wid = SRX_XCD_FRAME ? xcd_index(blockIdx.x, gridDim.x) : blockIdx.x;  // windows that share halos (32 of 256 / 192) on one XCD's L2
+    const unsigned wid = xcd_index(blockIdx.x, gridDim.x);  // windows that share halos (32 of 256 / 192) on one XCD's L2
     constexpr int m8 = M8 ? 1 : 0;
     TileD td;
     {

@@ -572,10 +572,7 @@ template <> struct TileCfg<float> { static constexpr int R = 11, T_HR = 64; };
 // float64 tiles: 64 since round 4 (32 before: with R = 23 a 32-wide tile filters (32 + 52)^2 samples for 32^2 outputs, 6.9x; 64: 3.3x with one
 // block of 100 KB per compute unit instead of two.  rgb_cal_target's shape in float64, us per iteration: k_fwd_tile 75 -> 55, k_bwd_tile
 // 181 -> 128; the x4 frame on the mosaic tile kernels 576 -> 473.  48 fails (k_bwd_mosaic halves its tile))
-#ifndef SRX_TILE64
-#define SRX_TILE64 64
-#endif
-template <> struct TileCfg<double> { static constexpr int R = 23, T_HR = SRX_TILE64; };
+template <> struct TileCfg<double> { static constexpr int R = 23, T_HR = 64; };
 
 // One line of the recursive cubic-spline prefilter on LDS, optionally fused with the 4-tap spline FIR:
 //   MODE 0: line <- P(line)                                      (n = n_in outputs)
@@ -587,9 +584,7 @@ template <> struct TileCfg<double> { static constexpr int R = 23, T_HR = SRX_TIL
 // The recursions run in a scaled form with ONE dependent fma per step and direction:
 //   causal      p[i] = v[i] + z p[i-1]        (c+ = 6 p);  the line stores q[i] = -6 z p[i] = -z c+[i]
 //   anticausal  c[i] = z c[i+1] + q[i]        (= z (c[i+1] - c+[i]), SciPy's form)
-#ifndef SRX_WALK_U
-#define SRX_WALK_U 8
-#endif
+constexpr int WALK_U = 8;  // steps of a walk unrolled together
 // boundary-condition flags of a walk (default 0 = SciPy 'reflect' at a true array end, what shift(mode='nearest') uses on its
 // pre-padded array): the line starts / ends at a true array end whose condition is 'mirror' (zoom's prefilter)
 #define SRX_BC_MIRROR_LO 1
@@ -605,7 +600,7 @@ template <typename T> struct WalkState {
 template <typename T, int S, int MODE>
 __device__ __forceinline__ void causal_run(T *__restrict__ line, int i0, int i1, WalkState<T> &st, T w0, T w1, T w2, T w3)
 {
-    constexpr int U = SRX_WALK_U, O = MODE == 1 ? 3 : 0;
+    constexpr int U = WALK_U, O = MODE == 1 ? 3 : 0;
     const T z = pole<T>(), kq = (T)-6 * z;
     int base = i0;
     for (; base + U <= i1; base += U) {
@@ -643,7 +638,7 @@ __device__ __forceinline__ void causal_run(T *__restrict__ line, int i0, int i1,
 template <typename T, int S, int MODE>
 __device__ __forceinline__ void anticausal_run(T *__restrict__ line, int ihi, int ilo, WalkState<T> &st, T w0, T w1, T w2, T w3)
 {
-    constexpr int U = SRX_WALK_U;
+    constexpr int U = WALK_U;
     const T z = pole<T>();
     int i = ihi;
     for (; i - (U - 1) >= ilo; i -= U) {

@@ -36,14 +36,10 @@ namespace srx {
 namespace patch {
 using namespace blk;
 
-#ifndef SRX_PARK16
-#define SRX_PARK16 1
-#endif
-#ifndef SRX_PATCH_DBG
-#define SRX_PATCH_DBG 0  // timing ablations of a development build only (results are wrong): 1 no M loads, 2 no hr re-read,
-#endif                   // 4 no near band, 8 no hr park store, 32 / 64 no far / near share of the MSE sum.  Measured (C2, 161 us per
-                         // iteration): 8 -> 150, 2 -> 152, 8|2 -> 144, 8|2|1 -> 139, all -> 138: the memory operations are 14 % of the
-                         // iteration; requesting the parked state or the near-band descriptors a chain earlier changes nothing.
+// What k_ibp_patch's memory operations cost, from timing ablations that computed wrong results (C2, 161 us per iteration): without
+// the hr park store 150, without the hr re-read 152, without both 144, without the M loads as well 139, without the near band and the
+// MSE sums too 138: the memory operations are 14 % of the iteration; requesting the parked state or the near-band descriptors a chain
+// earlier changes nothing.
 constexpr int PN = 256;        // patch edge (HR pixels)
 constexpr int YW = 260;        // row pitch of the near-band strips
 constexpr int OFF_YT = 16 * RW, OFF_YL = OFF_YT + 4 * YW, OFF_GT = OFF_YL + 4 * YW, OFF_GL = OFF_GT + 3 * YW,
@@ -465,13 +461,11 @@ __global__ void __launch_bounds__(1024)
         for (int i = 0; i < 64; i++)
             a[i] = fused::buf_load<float>(rs_in, l4 + (i & 3) * PN * 4, cb0 + (i >> 2) * PN * 16);
     }
-#if SRX_PARK16
     // The parked state has its own layout inside hr_out (wave, row quad, lane: 16 bytes per lane and instruction).  When the call is
     // in place (hr_in == hr_out) no wave may park before every wave has its initial state in registers.
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
     const int park0 = wave * 16384;  // byte offset of this wave's 64 x 64 block in the parking layout
-#endif
     for (int it = 0; it < n_iter; it++) {
         float r[64];
         // Everything derived from the lane index (LDS and global addresses, predicates) and from the block offsets is re-derived
@@ -491,18 +485,12 @@ __global__ void __launch_bounds__(1024)
         __builtin_amdgcn_sched_barrier(0);
         SRX_PSTAMP(0);
         // ================= stage A: column layout, lane = column 64 u + lane, a[i] = row 64 s + i =================
-        if (!(SRX_PATCH_DBG & 8)) {
-#if SRX_PARK16
+        {
             int pk = park0;
             asm volatile("" : "+s"(pk));
 #pragma unroll
             for (int q = 0; q < 16; q++)
                 st4(rs_out, l4 * 4, pk + q * 1024, a[4 * q], a[4 * q + 1], a[4 * q + 2], a[4 * q + 3]);
-#else
-#pragma unroll
-            for (int i = 0; i < 64; i++)
-                fused::buf_store<float>(a[i], rs_out, l4 + (i & 3) * PN * 4, cbl + (i >> 2) * PN * 16);
-#endif
         }
         if (PSF == 0) {
             blur_block(a, s == 0, s == 3, Rown, Rup, Rdn, SLOT0, lane, sload8(awy));
@@ -522,9 +510,6 @@ __global__ void __launch_bounds__(1024)
             blur2d_pass1<PSF == 2 ? 2 : 3>(a, hl, hr, Rown, lane, tb.k2);
             __syncthreads();
             blur2d_fix<PSF == 2 ? 2 : 3>(a, u == 0, u == 3, Rown, Rlf, Rrt, lane, [](int) {}, [](int, float v) { return v; });
-#ifdef SRX_PATCH_B2D_SYNC
-            __syncthreads();
-#endif
         }
         __builtin_amdgcn_sched_barrier(0);
         SRX_PSTAMP(1);
@@ -602,8 +587,7 @@ __global__ void __launch_bounds__(1024)
         if (m8) {
 #pragma unroll
             for (int q = 0; q < 4; q++) {
-                const u32x4 v = (SRX_PATCH_DBG & 1) ? u32x4{0x01020304u, 0x01020304u, 0x01020304u, 0x01020304u}
-                                                    : __builtin_amdgcn_raw_buffer_load_b128(rsM8, l4 * 4, m8l + q * PN * 16, 0);
+                const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(rsM8, l4 * 4, m8l + q * PN * 16, 0);
                 m8w[4 * q] = v.x, m8w[4 * q + 1] = v.y, m8w[4 * q + 2] = v.z, m8w[4 * q + 3] = v.w;
             }
         }
@@ -624,12 +608,12 @@ __global__ void __launch_bounds__(1024)
                 Gstrip[dst] = nm.x - ys;
                 if (cu > 0) {
                     const float gu = nm.y - (float)cu * Ystrip[nr.y];
-                    sq += (SRX_PATCH_DBG & 64) ? 0.f : gu * gu / (float)cu;
+                    sq += gu * gu / (float)cu;
                 }
             };
-            if (n0 && !(SRX_PATCH_DBG & 4))
+            if (n0)
                 near_px(nr0, ne0, nm0, tid);
-            if (n1 && !(SRX_PATCH_DBG & 4))
+            if (n1)
                 near_px(nr1, ne1, nm1, tid + 1024);
         }
         __syncthreads();
@@ -697,7 +681,7 @@ __global__ void __launch_bounds__(1024)
             }
             if (u == 0)  // the first nbx columns of the grid are near band: not part of the far-field sum
                 sqf -= (nbx > 0 ? gn[0] : 0.f) + (nbx > 1 ? gn[1] : 0.f) + (nbx > 2 ? gn[2] : 0.f);
-            sq += (rownear || (SRX_PATCH_DBG & 32)) ? 0.f : sqf;
+            sq += rownear ? 0.f : sqf;
             if (rownear) {
                 const float *src = Gt + (gy + exy) * YW + 64 * u + exx;
 #pragma unroll
@@ -772,21 +756,11 @@ __global__ void __launch_bounds__(1024)
             auto mid = [&](int q) {
                           // the parked state in 16-row batches, two in flight: batch q is consumed by quarter q of the blur
                           auto load16 = [&](float(&ld)[16], int bq) {
-#if SRX_PARK16
                               int pk = park0;
                               asm volatile("" : "+s"(pk));
 #pragma unroll
-                              for (int q = 0; q < 4; q++) {
-                                  if (SRX_PATCH_DBG & 2)
-                                      ld[4 * q] = ld[4 * q + 1] = ld[4 * q + 2] = ld[4 * q + 3] = 1.f;
-                                  else
-                                      ld4(rs_out, l4 * 4, pk + (4 * bq + q) * 1024, ld[4 * q], ld[4 * q + 1], ld[4 * q + 2], ld[4 * q + 3]);
-                              }
-#else
-#pragma unroll
-                              for (int i = 0; i < 16; i++)
-                                  ld[i] = (SRX_PATCH_DBG & 2) ? 1.f : fused::buf_load<float>(rs_out, l4 + (i & 3) * PN * 4, cbl + (4 * bq + (i >> 2)) * PN * 16);
-#endif
+                              for (int q = 0; q < 4; q++)
+                                  ld4(rs_out, l4 * 4, pk + (4 * bq + q) * 1024, ld[4 * q], ld[4 * q + 1], ld[4 * q + 2], ld[4 * q + 3]);
                           };
                           if (q == 0) {
                               SRX_PSTAMP(13);
@@ -810,9 +784,6 @@ __global__ void __launch_bounds__(1024)
                 blur2d_pass1<PSF == 2 ? 2 : 3>(a, hl, hr, Rown, lane, tb.k2 + 56);
                 __syncthreads();
                 blur2d_fix<PSF == 2 ? 2 : 3>(a, u == 0, u == 3, Rown, Rlf, Rrt, lane, mid, post);
-#ifdef SRX_PATCH_B2D_SYNC
-                __syncthreads();
-#endif
             }
         }
         __builtin_amdgcn_sched_barrier(0);
@@ -821,11 +792,9 @@ __global__ void __launch_bounds__(1024)
 #undef SRX_STAGE_LOCALS
     }
     {
-#if SRX_PARK16
         // the result goes out in image layout, over the parking layout: not before every wave has re-read its last parked rows
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
-#endif
         const int l4 = (tid0 & 63) * 4;
 #pragma unroll
         for (int i = 0; i < 64; i++)

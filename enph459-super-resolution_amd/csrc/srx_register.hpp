@@ -293,20 +293,18 @@ __global__ void __launch_bounds__(256) k_reg_coarse_u8(const uint8_t *__restrict
     }
 }
 
-// the coarse kernel of frames of type F.  SRX_REG_COARSE_PLAIN (a development build: profiles/README.md) runs uint8 frames through the
-// float kernel's structure with F = uint8_t in its loads and LDS planes instead: the ablation k_reg_coarse_u8 was measured against.
+// the coarse kernel of frames of type F.  uint8 frames through the float kernel's structure with F = uint8_t in its loads and LDS planes
+// instead is what k_reg_coarse_u8 was measured against (profiles/README.md).
 template <typename F>
 static inline void launch_coarse(const F *frames, const Geo &g, int search, const Plan &p, const Start &c0, double *part, hipStream_t st)
 {
     hipLaunchKernelGGL(k_reg_coarse<F>, dim3(p.cgx, p.cgy, g.nf()), dim3(256), 0, st, frames, g, search, p.crow, c0, part);
 }
-#ifndef SRX_REG_COARSE_PLAIN
 template <>
 inline void launch_coarse<uint8_t>(const uint8_t *frames, const Geo &g, int search, const Plan &p, const Start &c0, double *part, hipStream_t st)
 {
     hipLaunchKernelGGL(k_reg_coarse_u8, dim3(p.cgx, p.cgy, g.nf()), dim3(256), 0, st, frames, g, search, p.crow, c0, part);
 }
-#endif
 
 __device__ __forceinline__ double zm_ncc(double n, double st, double stt, double sr, double srr, double str)
 {

@@ -12,12 +12,12 @@
 // Tile shape (measured on one 3072 x 4096 frame / on eight): 256 threads = 4 waves side by side, 64 rows (NSY = 1), 34.9 KB of
 // LDS.  With the pre-update state re-read for the update: 152 registers, three tiles per CU, 245 MB of HBM traffic per iteration
 // (PMC; 5.1 TB/s -- the kernel was bound by its own traffic), 48.4 / 301 us.  With the state HELD in 64 more registers
-// (SRX_ZTILE_HOLD, the default): 216 registers, two tiles per CU, 180 MB, 43.9 / 268 us.  Taller tiles recompute less but run
+// (the shipped form): 216 registers, two tiles per CU, 180 MB, 43.9 / 268 us.  Taller tiles recompute less but run
 // slower: NSY = 2 (128 rows, 512 threads) 50 / 322 us, NSY = 4 (256 x 256, 1024 threads, one tile per CU) 64 / 446 us -- several
 // small independent workgroups per CU overlap one tile's memory phases with another's arithmetic, one lock-step workgroup
 // cannot.  Four tiles per CU (128 registers) spill 107 values: 61 / 452 us.  Round 4: the tiles are taken in XCD order (xcd_block_2d, frame by frame -- eight frames 257 us; re-numbered over the whole batch, one frame per XCD: 260 --: a tile's
 // vertical neighbours run on the same XCD, the 12 shared rows come from its L2): 160.7 -> 135.7 MB per iteration, 40.0 -> 39.4 us (the 7 x 7
-// form 46.5 -> 43.6); the re-reading form gains more from it (48.4 -> 42.2 / 263 us) and still loses to the held state (tools/dev/zhold_ab.sh).
+// form 46.5 -> 43.6); the re-reading form gains more from it (48.4 -> 42.2 / 263 us) and still loses to the held state.
 //
 // Near band (LR row / column 0 replicated into SciPy's pad: pixels g < -n_min, in the first rows / columns of the IMAGE): tiles
 // on the top / left image edge evaluate the per-pixel lists of k_build_near from two LDS strips of b, as k_ibp_patch does.
@@ -28,20 +28,6 @@
 // (41.4 -> 39.5 us per iteration on a 3072 x 4096 frame).
 #pragma once
 #include "srx_patch.hpp"
-#ifndef SRX_ZTILE_NSY
-#define SRX_ZTILE_NSY 1
-#endif
-#ifndef SRX_ZTILE_LOAD_EDGES_FIRST
-#define SRX_ZTILE_LOAD_EDGES_FIRST 1
-#endif
-#ifndef SRX_ZTILE_HOLD
-#define SRX_ZTILE_HOLD 1  // the pre-update state stays in 64 more registers (216 in all: two tiles per CU) instead of being read again
-                          // for the update: 245 -> 180 MB of HBM traffic per iteration of a 3072 x 4096 frame, 48.4 -> 43.9 us (eight
-                          // frames 301 -> 268 us).  0: re-read, 152 registers, three tiles per CU.
-#endif
-#ifndef SRX_ZTILE_WPE
-#define SRX_ZTILE_WPE (SRX_ZTILE_HOLD ? 2 : 3)  // waves per SIMD the kernel is compiled for = tiles per CU (4 waves per tile)
-#endif
 
 namespace srx {
 namespace ztile {
@@ -57,8 +43,9 @@ typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
 constexpr int RG = 256;           // region width (and the stride of the strips)
 constexpr int HALO = 6;           // 3 (blur) + 3 (adjoint blur)
 constexpr int VT = RG - 2 * HALO; // 244 valid columns per tile
-constexpr int NSY = SRX_ZTILE_NSY;  // block rows per tile: region height 64 NSY (1: see the header for what 2 and 4 measured)
+constexpr int NSY = 1;            // block rows per tile: region height 64 NSY (1: see the header for what 2 and 4 measured)
 constexpr int RGY = 64 * NSY, VTY = RGY - 2 * HALO;
+constexpr int WPE = 2;            // waves per SIMD the kernel is compiled for = tiles per CU (4 waves per tile): the held state below
 static_assert(HALO % 2 == 0 && VTY % 2 == 0, "row pairs: ownership boundaries and tile origins must be even");
 constexpr int SW = 4;             // strip pitch (rows of the top strip / columns of the left strip)
 // LDS: 16 wave regions of srx_patch.hpp (transpose image + exchange slots), then the near-band strips
@@ -382,7 +369,7 @@ __device__ __forceinline__ void blur2d_block(float (&a)[64], bool first, bool la
 // partial sums (or null); eprev: the previous iteration's, which one interior tile adds up into err_prev[item * err_stride].
 // =========================================================================================================================
 template <int PSF>  // 0: rank-1 PSF (7 + 7 taps), 3: full 7 x 7, 2: 7 x 7 whose outer ring is zero (5 x 5)
-__global__ void __launch_bounds__(256 * NSY, SRX_ZTILE_WPE)
+__global__ void __launch_bounds__(256 * NSY, WPE)
     k_ibp_ztile(const float *__restrict__ hr_src, float *__restrict__ hr_dst, ZTabs tb, ZArgs za, double *__restrict__ epart,
                 const double *__restrict__ eprev, const double *__restrict__ Vtot, double scale, double *__restrict__ err_prev, int err_stride)
 {
@@ -392,8 +379,7 @@ __global__ void __launch_bounds__(256 * NSY, SRX_ZTILE_WPE)
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), s = wave >> 2, u = wave & 3;
     int tx = blockIdx.x, ty = blockIdx.y, b = blockIdx.z;
-    if (SRX_XCD_FRAME)
-        xcd_block_2d(tx, ty);  // neighbouring tiles (12 shared rows of 64, 12 columns of 256) on one XCD's L2
+    xcd_block_2d(tx, ty);  // neighbouring tiles (12 shared rows of 64, 12 columns of 256) on one XCD's L2
     const int H = za.H, W = za.W, HP = za.HP, WP = za.WP;
     const int pr0 = ty * VTY, pc0 = tx * VT;  // padded coordinates of region (0, 0); natural = padded - 6
     float *Rown = lds + wave * blk::RW;
@@ -430,16 +416,16 @@ __global__ void __launch_bounds__(256 * NSY, SRX_ZTILE_WPE)
     // the six rows the halo exchange of the first blur sends first: its LDS stores and barrier then run under the other 58 loads
 #pragma unroll
     for (int k = 0; k < 32; k++) {
-        const int i = SRX_ZTILE_LOAD_EDGES_FIRST ? (k < 2 ? k : (k < 4 ? 28 + k : k - 2)) : k;  // pairs 0, 1, 30, 31 first
+        const int i = k < 2 ? k : (k < 4 ? 28 + k : k - 2);  // pairs 0, 1, 30, 31 first
         ld2(i, a[2 * i], a[2 * i + 1]);
     }
-    constexpr bool HOLD = SRX_ZTILE_HOLD;
-    float hold[HOLD ? 64 : 1];
-    if constexpr (HOLD) {
+    // The pre-update state stays in 64 more registers (216 in all: two tiles per CU) instead of being read again for the update
+    // (152 registers, three tiles per CU): 245 -> 180 MB of HBM traffic per iteration of a 3072 x 4096 frame, 48.4 -> 43.9 us (eight
+    // frames 301 -> 268 us).
+    float hold[64];
 #pragma unroll
-        for (int i = 0; i < 64; i++)
-            hold[i] = a[i];
-    }
+    for (int i = 0; i < 64; i++)
+        hold[i] = a[i];
     // blur down the columns (three rows from the blocks above / below; zero at the region's edge: those outputs are outside
     // every dependency cone that ends in a stored pixel)
     SRX_PSTAMP(1);
@@ -637,32 +623,10 @@ __global__ void __launch_bounds__(256 * NSY, SRX_ZTILE_WPE)
     const int trash = (HP >> 1) * WP * 8;  // the trash pair
     const int cc = 64 * u + lane;
     const int vst = (cc >= HALO && cc < RG - HALO && pc0 + cc - HALO < W) ? vc0 : 0x7ffffff0;
-    // loads and arithmetic first, every store at the very end: vmcnt counts loads and stores in one order, so a wait for a batch of
-    // loads behind a batch of stores would also wait for those stores to complete
-    if constexpr (HOLD) {
+    // the arithmetic first, every store at the very end
 #pragma unroll
-        for (int i = 0; i < 64; i++)
-            a[i] = __builtin_amdgcn_fmed3f(fmaf(a[i], za.sn, hold[i]), 0.f, 255.f);
-    } else {
-        float hv[16], hw[16];
-#pragma unroll
-        for (int k = 0; k < 8; k++)
-            ld2(k, hv[2 * k], hv[2 * k + 1]);
-#pragma unroll
-        for (int q = 0; q < 4; q++) {
-            float(&cur)[16] = (q & 1) ? hw : hv;
-            float(&nxt)[16] = (q & 1) ? hv : hw;
-            if (q < 3) {
-#pragma unroll
-                for (int k = 0; k < 8; k++)
-                    ld2(8 * (q + 1) + k, nxt[2 * k], nxt[2 * k + 1]);
-            }
-#pragma unroll
-            for (int i = 0; i < 16; i++)
-                a[16 * q + i] = __builtin_amdgcn_fmed3f(fmaf(a[16 * q + i], za.sn, cur[i]), 0.f, 255.f);
-            __builtin_amdgcn_sched_barrier(0);
-        }
-    }
+    for (int i = 0; i < 64; i++)
+        a[i] = __builtin_amdgcn_fmed3f(fmaf(a[i], za.sn, hold[i]), 0.f, 255.f);
     SRX_PSTAMP(11);
 #pragma unroll
     for (int k = 0; k < 32; k++) {

@@ -15,7 +15,8 @@ variant is max - min of its medians over the rounds.  (b) and (c) are compared b
 Also reported, counted from shapes: the bytes each form's conversion moves, the bytes the registration passes read from the frames, and
 the peak device memory of frames + converted copies + workspace.
 
---label NAME is stored in the JSON (the coarse-kernel ablation runs this tool on a library built with -DSRX_REG_COARSE_PLAIN through SRX_LIB).
+--label NAME is stored in the JSON (the coarse-kernel ablation ran this tool through SRX_LIB on a library built with -DSRX_REG_COARSE_PLAIN,
+a switch that was removed once the verdict was in: the commit before its removal builds it).
 --profile-run runs 20 calls of (b) and 20 of (c) on the mono_cal_target shape in f32 and exits: the workload for
 `rocprofv3 --kernel-trace --stats -- python tools/register_u8_time.py --profile-run` (nothing else traced).
 
