@@ -885,6 +885,15 @@ const char *srx_ibp_path_for(int eb, int N, int h, int w, int H, int W, int f, c
     return r.status == SRX_OK ? r.name : "none";
 }
 
+int srx_ibp_patch_gstep_for(int N, int f, const double *sh)
+{
+    mosaic::AxisPlan py, px;
+    if (!sh || N <= 0 || N > SRX_MAX_FRAMES || f < 2 || !mosaic::plan_axis(N, sh, 0, f, py) || !mosaic::plan_axis(N, sh, 1, f, px))
+        return -1;
+    unsigned long long ry[4], rx[4];
+    return patch::gstep_form(py, px, N, f, ry, rx);
+}
+
 const char *srx_saa_path_for(int eb, int N, int h, int w, int f, const double *sh, unsigned flags)
 {
     const SaaSpec spec{SRX_SAA_SHAPE(eb), sh, flags};

@@ -418,11 +418,17 @@ __global__ void k_patch_params(AxisWPair v, AxisW *dst)
     dst[1] = v.x;
 }
 
-template <bool C01, bool M8, int PSF = 0>  // PSF: 0 rank 1 (7 + 7 taps per blur), 3 full 7 x 7, 2 a 7 x 7 whose outer ring is zero
+// FORM: 0 rank 1 (7 + 7 taps per blur), 3 full 7 x 7, 2 a 7 x 7 whose outer ring is zero; 1 (with C01 and M8) rank 1 on a grid whose count
+// masks the host found all ones wherever the G step's result is used (gstep_form): the byte-mosaic G loop runs without the mask test.  A
+// template value like M8, for M8's reason: the allocator sees one G loop.
+template <bool C01, bool M8, int FORM = 0>
 __global__ void __launch_bounds__(1024)
     k_ibp_patch(const float *__restrict__ hr_in, float *__restrict__ hr_out, PatchTabs tb, PatchArgs pa, const double *__restrict__ Vtot,
                 double scale, double *__restrict__ errors, int n_iter)
 {
+    constexpr bool ALL1 = FORM == 1;
+    constexpr int PSF = ALL1 ? 0 : FORM;
+    static_assert(!ALL1 || (C01 && M8), "the all-ones G step is the byte mosaic's on a full phase grid");
     __shared__ __attribute__((aligned(16))) float lds[LDS_WORDS];
     const int tid0 = threadIdx.x;
     const int wave = __builtin_amdgcn_readfirstlane(tid0 >> 6), s = wave >> 2, u = wave & 3;
@@ -636,7 +642,14 @@ __global__ void __launch_bounds__(1024)
                 for (int j = 0; j < 64; j++) {
                     const float mv = (float)((m8w[j >> 2] >> (8 * (j & 3))) & 255u);
                     float g, w;
-                    if (C01) {
+                    if (C01 && ALL1 && j < 63) {
+                        // both masks are ones here (the flagship's 4 x 4 phases: every far-field pixel holds exactly one sample): what
+                        // fmaf(-1.f, r[j], mv) rounds to, without the scalar bit test and the select -- one of about five vector
+                        // instructions per element.  Same box, six interleaved runs each: 129.7 - 130.6 -> 127.9 - 128.6 us per iteration
+                        // (DESIGN.md section 6).
+                        g = mv - r[j];
+                        w = 1.f;
+                    } else if (C01) {  // (ALL1: the block's last column, which is the grid's empty last column when exx = 1)
                         const bool on = (cm >> j) & 1ull;  // wave-uniform; M = 0 where no frame contributes
                         g = on ? fmaf(-crow, r[j], mv) : 0.f;
                         w = 1.f;
@@ -866,6 +879,26 @@ static inline bool c01_masks(const mosaic::AxisPlan &py, const mosaic::AxisPlan 
     return true;
 }
 
+// Which G step a call on these plans takes: 0 the count plane, 1 the 0/1 masks of a full phase grid, tested per row and column, 2 the masks
+// known to be all ones (k_ibp_patch's FORM 1, the rank-1 kernel's byte-mosaic form).  It computes G = M - Y where the masks say
+// G = ry[gy] rx[gx] ? M - Y : 0, so every bit it no longer looks at must be set wherever that G is used:
+//   * columns 0 .. PN - 2, all of them (the squares of the first nbx columns are added to the far-field sum and subtracted again: they must
+//     be the same numbers); column PN - 1 -- the grid's empty last column when exx = 1 -- keeps its test in the kernel;
+//   * rows nby .. PN - 1 - exy: the rows before them and the wrapped row -1 take G from the near-band strips and add nothing to the sum.
+static inline int gstep_form(const mosaic::AxisPlan &py, const mosaic::AxisPlan &px, int N, int f, unsigned long long ry[4], unsigned long long rx[4])
+{
+    if (!c01_masks(py, px, N, f, ry, rx))
+        return 0;
+    const int nby = -py.nmin, exy = py.nmax > 0 ? 1 : 0;
+    for (int g = 0; g < PN - 1; g++)
+        if (!((rx[g >> 6] >> (g & 63)) & 1ull))
+            return 1;
+    for (int g = nby > 0 ? nby : 0; g < PN - exy; g++)
+        if (!((ry[g >> 6] >> (g & 63)) & 1ull))
+            return 1;
+    return 2;
+}
+
 // device memory of the patch path's tables, carved from the caller's workspace by mosaic::ibp
 // class tables of a full phase grid: which frames land on natural coordinate g along one axis (their class) and the LR index they bring
 static inline bool axis_map(const mosaic::AxisPlan &pl, int N, int f, AxisMap &am, int cls_of_frame[SRX_MAX_FRAMES], int &ncls)
@@ -968,7 +1001,8 @@ static int iterate(const mosaic::Common<float> &c, const float *hr_init, float *
     pa.ngrp = ngrp;
     if (pa.nn > NN_PAD)
         return SRX_E_UNSUPPORTED;
-    pa.c01 = c01_masks(py, px, N, f, pa.ry, pa.rx) ? 1 : 0;
+    const int gform = gstep_form(py, px, N, f, pa.ry, pa.rx);
+    pa.c01 = gform > 0 ? 1 : 0;
     if (fill_bytes(m8, 0xff, (size_t)B * sizeof(int), st) != hipSuccess)
         return SRX_E_HIP;
     const bool own = c.own_build;  // (common_prep built no M / C / Mu)
@@ -1026,7 +1060,10 @@ static int iterate(const mosaic::Common<float> &c, const float *hr_init, float *
         SRX_LAUNCH(KID_IBP_PATCH, (k_ibp_patch<C01_, false, PSF_>), dim3(B), dim3(1024), 0, st, hr_init, hr, tb, pa, c.Vtot, c.scale, errors, n_iter); \
     } while (0)
     if (pa.c01) {
-        if (psf == 0)
+        if (psf == 0 && gform == 2) {  // (the float-mosaic twin has no mask test to drop: the instantiation of the pair below)
+            SRX_LAUNCH(KID_IBP_PATCH, (k_ibp_patch<true, true, 1>), dim3(B), dim3(1024), 0, st, hr_init, hr, tb, pa, c.Vtot, c.scale, errors, n_iter);
+            SRX_LAUNCH(KID_IBP_PATCH, (k_ibp_patch<true, false, 0>), dim3(B), dim3(1024), 0, st, hr_init, hr, tb, pa, c.Vtot, c.scale, errors, n_iter);
+        } else if (psf == 0)
             SRX_PATCH_PAIR(true, 0);
         else if (psf == 2)
             SRX_PATCH_PAIR(true, 2);

@@ -82,6 +82,7 @@ _PLAIN = {
     "srx_mean_u8": (_I, [_P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P]),
     "srx_ibp_path_for": (_c.c_char_p, [_I, _I, _I, _I, _I, _I, _I, _HD, _HD, _I, _I, _U]),
     "srx_saa_path_for": (_c.c_char_p, [_I, _I, _I, _I, _I, _HD, _U]),
+    "srx_ibp_patch_gstep_for": (_I, [_I, _I, _HD]),
     "srx_ibp_plan_workspace_bytes": (_Z, [_I, _I, _I, _I, _I, _I, _I, _I, _U]),
     "srx_ibp_plan_run": (_I, [_P, _I, _P, _P]),
     "srx_ibp_plan_path": (_c.c_char_p, [_P]),

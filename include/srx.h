@@ -190,6 +190,11 @@ size_t srx_ibp_workspace_bytes_for(int elem_bytes, int B, int N, int h, int w, i
  * is decided from shapes, shifts, PSF and flags on the host, so this needs no device and queues nothing. */
 const char *srx_ibp_path_for(int elem_bytes, int N, int h, int w, int H, int W, int factor, const double *shifts_yx, const double *kernel,
                              int kh, int kw, unsigned flags);
+/* The form of the far-field residual step that the "patch" implementation takes on a table of shifts, decided on the host like the
+ * route: 2 a full phase grid whose 0/1 count masks are all ones where the step's result is used (no mask test), 1 a phase grid with empty
+ * rows or columns (masks tested), 0 a count plane (frames sharing a phase, or no product grid), -1 shifts without a common sub-pixel
+ * fraction per axis or arguments out of range.  Needs no device. */
+int srx_ibp_patch_gstep_for(int N, int factor, const double *shifts_yx);
 int srx_ibp_f32(const float *lr, int B, int N, int h, int w, const double *shifts_yx, const double *kernel, int kh,
                 int kw, const float *hr_init, int H, int W, int factor, int n_iter, double step, float *hr_out,
                 double *errors_out, void *ws, size_t ws_bytes, srx_stream_t stream, unsigned flags);
