@@ -11,7 +11,9 @@
 //     them and checks them against the oracle;
 //   * blur_inplace / blur_block: the 7-tap correlation along the registers with a three-sample halo from either neighbour;
 //   * bwd_chain_x / bwd_chain: bwd_front + k_ibp_patch's out-of-place blur' in quarters (the float64 strips end theirs with blur_inplace);
-//   * blur2d_pass1 / blur2d_fix: the 7 x 7 Horner blur in column layout; the DPP lane shifts; sload8, st4 / ld4 / ld_u2.
+//   * halo3_put / halo3_get and gnbr_put / gnbr_get: what a block publishes for its neighbours in front of a 7-tap blur (three samples
+//     either side) and in front of a backward chain (G just before, two samples behind), each as two halves around the caller's barrier;
+//   * blur2d_pass1 / blur2d_fix, together blur2d_cols: the 7 x 7 Horner blur in column layout; the DPP lane shifts; sload8, st4 / ld4 / ld_u2.
 //
 // The arithmetic is templated on the element type T: k_ibp_patch, k_ibp_dtile, k_ibp_ztile and the b / a kernels instantiate it in
 // float, the float64 strips of srx_stile.hpp in double -- the same source, so a fix reaches both.  What differs by T is stated here and
@@ -247,6 +249,46 @@ template <bool REV, typename T> __device__ __forceinline__ void add_carry(T (&a)
         a[REV ? 63 - i : i] = fma(zp<T>(i), carry, a[REV ? 63 - i : i]);
 }
 
+// ---- what the blocks of a line tell their neighbours, each in two halves with the workgroup barrier between them left to the caller ------
+// halo3: the three samples before / after a block (zero beyond the line's ends), for a 7-tap blur along the registers.  s6: a 384-word slot.
+template <typename T> struct Halo3 {
+    T lo[3], hi[3];
+};
+template <typename T> __device__ __forceinline__ void halo3_put(const T (&a)[64], T *Rown, int s6, int lane)
+{
+    Rown[s6 + lane] = a[0];
+    Rown[s6 + 64 + lane] = a[1];
+    Rown[s6 + 128 + lane] = a[2];
+    Rown[s6 + 192 + lane] = a[61];
+    Rown[s6 + 256 + lane] = a[62];
+    Rown[s6 + 320 + lane] = a[63];
+}
+template <typename T> __device__ __forceinline__ Halo3<T> halo3_get(bool first, bool last, const T *Rprev, const T *Rnext, int s6, int lane)
+{
+    Halo3<T> h = {{0, 0, 0}, {0, 0, 0}};
+    if (!first)
+        h.lo[0] = Rprev[s6 + 192 + lane], h.lo[1] = Rprev[s6 + 256 + lane], h.lo[2] = Rprev[s6 + 320 + lane];
+    if (!last)
+        h.hi[0] = Rnext[s6 + lane], h.hi[1] = Rnext[s6 + 64 + lane], h.hi[2] = Rnext[s6 + 128 + lane];
+    return h;
+}
+// gnbr: the G samples around a block that bwd_front's FIR reaches -- gm1 just before it (gtop, the line's G[-ex], in front of the first
+// block), gp1 / gp2 behind it (zero behind the last).  s3: a 192-word slot.  (By value into a const local: as three reference
+// out-parameters the same code cost k_ibp_patch 4 - 12 bytes of scratch and k_ibp_dtile a register.)
+template <typename T> struct GNbr {
+    T gm1, gp1, gp2;
+};
+template <typename T> __device__ __forceinline__ void gnbr_put(const T (&g)[64], T *Rown, int s3, int lane)
+{
+    Rown[s3 + lane] = g[0];
+    Rown[s3 + 64 + lane] = g[1];
+    Rown[s3 + 128 + lane] = g[63];
+}
+template <typename T> __device__ __forceinline__ GNbr<T> gnbr_get(bool first, bool last, const T *Rprev, const T *Rnext, int s3, int lane, T gtop)
+{
+    return {first ? gtop : Rprev[s3 + 128 + lane], last ? (T)0 : Rnext[s3 + lane], last ? (T)0 : Rnext[s3 + 64 + lane]};
+}
+
 // ---- forward chain of one block, in place ------------------------------------------------------------------------------
 // a[] in: kq-scaled blurred samples b' of this block.  out: Y[rho], rho = the block's own 64 indices;
 // Y[rho] = sum_a wf[a] c[rho - 2 + a], c = P(pad12(b)).  yex (first block): Y[-1].
@@ -332,12 +374,7 @@ __device__ __forceinline__ void bwd_front(T (&a)[64], bool first, bool last, T *
         add_carry<false>(a, Rprev[s1 + lane]);
     const T cb = last ? fma(z, a[63], vn) * K4 : (T)0;
     chain64<true>(a, cb);
-    Rown[s6 + lane] = a[0];
-    Rown[s6 + 64 + lane] = a[1];
-    Rown[s6 + 128 + lane] = a[2];
-    Rown[s6 + 192 + lane] = a[61];
-    Rown[s6 + 256 + lane] = a[62];
-    Rown[s6 + 320 + lane] = a[63];
+    halo3_put(a, Rown, s6, lane);  // (fetched below with the carry fix-ups, not by halo3_get)
     SRX_PSTAMP(18);
     __syncthreads();
     SRX_PSTAMP(19);
@@ -442,19 +479,10 @@ __device__ __forceinline__ void blur_inplace(T (&a)[64], const T (&hl)[3], const
 template <typename T, typename W>
 __device__ __forceinline__ void blur_block(T (&a)[64], bool first, bool last, T *Rown, const T *Rprev, const T *Rnext, int s6, int lane, const W &kb)
 {
-    Rown[s6 + lane] = a[0];
-    Rown[s6 + 64 + lane] = a[1];
-    Rown[s6 + 128 + lane] = a[2];
-    Rown[s6 + 192 + lane] = a[61];
-    Rown[s6 + 256 + lane] = a[62];
-    Rown[s6 + 320 + lane] = a[63];
+    halo3_put(a, Rown, s6, lane);
     __syncthreads();
-    T hl[3] = {0, 0, 0}, hr[3] = {0, 0, 0};
-    if (!first)
-        hl[0] = Rprev[s6 + 192 + lane], hl[1] = Rprev[s6 + 256 + lane], hl[2] = Rprev[s6 + 320 + lane];
-    if (!last)
-        hr[0] = Rnext[s6 + lane], hr[1] = Rnext[s6 + 64 + lane], hr[2] = Rnext[s6 + 128 + lane];
-    blur_inplace(a, hl, hr, kb, [](int) {}, [](int, T v) { return v; });
+    const Halo3<T> h = halo3_get(first, last, Rprev, Rnext, s6, lane);
+    blur_inplace(a, h.lo, h.hi, kb, [](int) {}, [](int, T v) { return v; });
 }
 
 // ---- one-lane wave shifts (DPP wave_shr:1 / wave_shl:1) ------------------------------------------------------------------------
@@ -574,6 +602,15 @@ __device__ __forceinline__ void blur2d_fix(float (&a)[64], bool lfirst, bool lla
             a[i] = post(i, a[i] + src[i * str]);
         __builtin_amdgcn_sched_barrier(0);
     }
+}
+// both passes on a block whose three rows above / below (hl / hr) the caller holds: one workgroup barrier
+template <int RAD, typename PRE, typename POST>
+__device__ __forceinline__ void blur2d_cols(float (&a)[64], const float (&hl)[3], const float (&hr)[3], bool lfirst, bool llast, float *Rown, const float *Rlo,
+                                            const float *Rhi, int lane, const float *w56, PRE pre, POST post)
+{
+    blur2d_pass1<RAD>(a, hl, hr, Rown, lane, w56);
+    __syncthreads();
+    blur2d_fix<RAD>(a, lfirst, llast, Rown, Rlo, Rhi, lane, pre, post);
 }
 
 }  // namespace blk

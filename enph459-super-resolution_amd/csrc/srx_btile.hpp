@@ -165,18 +165,10 @@ typedef float v2f __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ void blur_block(float (&a)[64], bool first, bool last, float *Xown, const float *Xprev, const float *Xnext, int s6, int lane,
                                            const f8 kb)
 {
-    Xown[s6 + lane] = a[0];
-    Xown[s6 + 64 + lane] = a[1];
-    Xown[s6 + 128 + lane] = a[2];
-    Xown[s6 + 192 + lane] = a[61];
-    Xown[s6 + 256 + lane] = a[62];
-    Xown[s6 + 320 + lane] = a[63];
+    blk::halo3_put(a, Xown, s6, lane);
     __syncthreads();
-    float hl[3] = {0.f, 0.f, 0.f}, hr[3] = {0.f, 0.f, 0.f};
-    if (!first)
-        hl[0] = Xprev[s6 + 192 + lane], hl[1] = Xprev[s6 + 256 + lane], hl[2] = Xprev[s6 + 320 + lane];
-    if (!last)
-        hr[0] = Xnext[s6 + lane], hr[1] = Xnext[s6 + 64 + lane], hr[2] = Xnext[s6 + 128 + lane];
+    const blk::Halo3<float> h = blk::halo3_get(first, last, Xprev, Xnext, s6, lane);
+    const float(&hl)[3] = h.lo, (&hr)[3] = h.hi;
     // In place, 16 outputs = 8 packed accumulators at a time, tap-major: eight independent instructions between two that depend on each
     // other (a dependent VALU instruction issues ~11 cycles behind its producer, and with one or two waves per SIMD nobody fills the gap:
     // four accumulators per group ran the blur at the latency of its 7-deep chains).
@@ -328,12 +320,7 @@ template <int RAD>
 __device__ __forceinline__ void blur2d_cross(float (&a)[64], bool sfirst, bool slast, bool ufirst, bool ulast, float *Xown, const float *Xup, const float *Xdn,
                                              const float *zero, int lane, const f8 (&kv)[7])
 {
-    Xown[SLOT_A + lane] = a[0];
-    Xown[SLOT_A + 64 + lane] = a[1];
-    Xown[SLOT_A + 128 + lane] = a[2];
-    Xown[SLOT_A + 192 + lane] = a[61];
-    Xown[SLOT_A + 256 + lane] = a[62];
-    Xown[SLOT_A + 320 + lane] = a[63];
+    blk::halo3_put(a, Xown, SLOT_A, lane);
     if (lane < RAD || lane > 63 - RAD) {  // row i: words 0..2 = columns 0, 1, 2; words 4..6 = columns 63, 62, 61 (the order a neighbour shifts them in)
         float *pub = Xown + SLOT_C + (lane < 3 ? lane : 67 - lane);
 #pragma unroll
@@ -341,11 +328,8 @@ __device__ __forceinline__ void blur2d_cross(float (&a)[64], bool sfirst, bool s
             pub[8 * i] = a[i];
     }
     __syncthreads();
-    float hl[3] = {0.f, 0.f, 0.f}, hr[3] = {0.f, 0.f, 0.f};  // rows -3, -2, -1 and 64, 65, 66
-    if (!sfirst)
-        hl[0] = Xup[SLOT_A + 192 + lane], hl[1] = Xup[SLOT_A + 256 + lane], hl[2] = Xup[SLOT_A + 320 + lane];
-    if (!slast)
-        hr[0] = Xdn[SLOT_A + lane], hr[1] = Xdn[SLOT_A + 64 + lane], hr[2] = Xdn[SLOT_A + 128 + lane];
+    const blk::Halo3<float> h = blk::halo3_get(sfirst, slast, Xup, Xdn, SLOT_A, lane);  // rows -3, -2, -1 and 64, 65, 66
+    const float(&hl)[3] = h.lo, (&hr)[3] = h.hi;
     // where this lane finds the columns a shift pulls in: lane 0 the left neighbour's 63, 62, 61, lane 63 the right neighbour's 0, 1, 2
     const bool l0 = lane == 0, l63 = lane == 63;
     const float *eM = l0 ? (ufirst ? zero : Xown - XW + SLOT_C + 4) : (l63 && !ulast ? Xown + XW + SLOT_C : zero);

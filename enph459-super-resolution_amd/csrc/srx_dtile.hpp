@@ -17,7 +17,8 @@
 //     units when ONE frame is all there is (3072 x 4096: 336 windows of 16 waves = 1.31 rounds of 256 CUs at 55 us per round, or 512 of
 //     12 waves = 2.00 rounds at 37 us).  plan() picks by modelled time of one frame.
 //   * Near band, count masks, byte mosaic: k_ibp_patch's, per window (only windows on the top / left image edge hold near-band
-//     pixels; the tables are built per such window).
+//     pixels; the tables are built per such window).  The near band's code is srx_patch.hpp's too (patch::near_count, near_put_y, near_px,
+//     near_get_g_left; whole rows of G come back eight columns at a time here), the exchanges around the chains srx_block.hpp's.
 #pragma once
 #include "srx_patch.hpp"
 
@@ -174,7 +175,7 @@ static inline bool eligible(const IbpSpec &s)
     if (!plan(s.H, s.W, s.flags, pl))
         return false;
     const int exy = py.nmax, nby = -py.nmin, exx = px.nmax, nbx = -px.nmin;
-    return (exy + nby) * (256 + exx) + (RY - nby) * (exx + nbx) <= NN_PAD;  // the corner window's near band fits its lists
+    return patch::near_count(RY, 256, exy, exx, nby, nbx) <= NN_PAD;  // the corner window's near band (at its widest, 4 x 4 waves) fits its lists
 }
 
 // ---- once per call ---------------------------------------------------------------------------------------------------------
@@ -241,11 +242,7 @@ __device__ __forceinline__ void local_axes(const TileD &td, const DArgs &da, int
     exy = (td.flags & 1) ? da.y.ex : 0, nby = (td.flags & 1) ? da.y.nb : 0;
     exx = (td.flags & 2) ? da.x.ex : 0, nbx = (td.flags & 2) ? da.x.nb : 0;
 }
-// (near-band pixel t of a window: patch::near_coords with the window's width -- window-local natural coordinates, G strip offset)
-__device__ __forceinline__ int near_count(int RX, int exy, int exx, int nby, int nbx)
-{
-    return (exy + nby) * (RX + exx) + (RY - nby) * (exx + nbx);
-}
+// (near-band pixel t of a window: patch::near_coords / near_count with the window's shape -- window-local natural coordinates, G strip offset)
 
 // per near-band window: the lists of k_build_near as strip offsets (k_patch_near_tab), the counted-sample count zeroed for pixels
 // whose (clamped) position another window owns.  grid (NN_PAD / 256, ntabs)
@@ -257,7 +254,7 @@ __global__ void __launch_bounds__(256)
     const TileD td = tiles[tab < da.tiles_x ? tab : (tab - da.tiles_x + 1) * da.tiles_x];  // top windows first, then the left ones (k_dtile_setup)
     int exy, nby, exx, nbx;
     local_axes(td, da, exy, nby, exx, nbx);
-    const int nn = near_count(RX, exy, exx, nby, nbx);
+    const int nn = patch::near_count(RY, RX, exy, exx, nby, nbx);
     if (t == 0)
         nn_out[tab] = nn;
     if (t >= nn)
@@ -291,7 +288,7 @@ __global__ void __launch_bounds__(256)
     const TileD td = tiles[tab < da.tiles_x ? tab : (tab - da.tiles_x + 1) * da.tiles_x];  // top windows first, then the left ones (k_dtile_setup)
     int exy, nby, exx, nbx;
     local_axes(td, da, exy, nby, exx, nbx);
-    if (t >= near_count(RX, exy, exx, nby, nbx))
+    if (t >= patch::near_count(RY, RX, exy, exx, nby, nbx))
         return;
     int ngy, ngx, dst;
     patch::near_coords(t, RX, exy, exx, nby, nbx, ngy, ngx, dst);
@@ -413,21 +410,10 @@ __device__ __forceinline__ void dtile_body(float *lds, const float *__restrict__
             blk::blur_block(a, s == 0, s == 3, Rown, Rup, Rdn, SLOT0, lane, sload8(awy));
         } else {  // round 4: srx_block.hpp's 7 x 7 form (blur2d_pass1 / blur2d_fix), here on a window: what lies beyond a window edge is zero for
                   // the blur as it is for the separable one (inside the halo nobody owns)
-            Rown[SLOT0 + lane] = a[0];
-            Rown[SLOT0 + 64 + lane] = a[1];
-            Rown[SLOT0 + 128 + lane] = a[2];
-            Rown[SLOT0 + 192 + lane] = a[61];
-            Rown[SLOT0 + 256 + lane] = a[62];
-            Rown[SLOT0 + 320 + lane] = a[63];
+            blk::halo3_put(a, Rown, SLOT0, lane);
             __syncthreads();
-            float hl[3] = {0.f, 0.f, 0.f}, hr[3] = {0.f, 0.f, 0.f};
-            if (s != 0)
-                hl[0] = Rup[SLOT0 + 192 + lane], hl[1] = Rup[SLOT0 + 256 + lane], hl[2] = Rup[SLOT0 + 320 + lane];
-            if (s != 3)
-                hr[0] = Rdn[SLOT0 + lane], hr[1] = Rdn[SLOT0 + 64 + lane], hr[2] = Rdn[SLOT0 + 128 + lane];
-            blk::blur2d_pass1<PSF == 2 ? 2 : 3>(a, hl, hr, Rown, lane, tb.k2);
-            __syncthreads();
-            blk::blur2d_fix<PSF == 2 ? 2 : 3>(a, u == 0, u == NSX - 1, Rown, Rlf, Rrt, lane, [](int) {}, [](int, float v) { return v; });
+            const blk::Halo3<float> h = blk::halo3_get(s == 0, s == 3, Rup, Rdn, SLOT0, lane);
+            blk::blur2d_cols<PSF == 2 ? 2 : 3>(a, h.lo, h.hi, u == 0, u == NSX - 1, Rown, Rlf, Rrt, lane, tb.k2, [](int) {}, [](int, float v) { return v; });
         }
         __builtin_amdgcn_sched_barrier(0);
         blk::fwd_chain(a, s == 0, s == 3, Rown, Rup, Rdn, SLOT1, SLOT0, lane, sload8(awy + 16), yex);
@@ -470,46 +456,14 @@ __device__ __forceinline__ void dtile_body(float *lds, const float *__restrict__
                 const uint2 m = ld_u2(rsMn, t8);
                 nm[i] = make_float2(__uint_as_float(m.x), __uint_as_float(m.y));
             }
-            {
-                const bool toprow = wrapped || (s == 0 && lane <= nby);  // (row nby is the first left-band row; its own Y sample lives in the top strip)
-                if (toprow) {
-                    float *dst = Yt + (gy + exy) * YW + 64 * u + exx;
-#pragma unroll
-                    for (int j = 0; j < 64; j++)
-                        dst[j] = r[j];
-                    if (u == 0 && exx)
-                        dst[-1] = yexx;
-                }
-                if (left && u == 0) {
-                    float *dst = Yl + (gy + exy) * 4 + exx;
-#pragma unroll
-                    for (int j = 0; j < 3; j++)
-                        if (j <= nbx)
-                            dst[j] = r[j];
-                    if (exx)
-                        dst[-1] = yexx;
-                }
-            }
+            // (the top strip takes row nby too: the first left-band row, whose own Y sample lives there)
+            patch::near_put_y(r, yexx, wrapped || (s == 0 && lane <= nby), left && u == 0, gy + exy, u, exx, nbx, Yt, Yl);
             __syncthreads();
 #pragma unroll
             for (int i = 0; i < NPT; i++) {
                 const int t = tid + i * NTHR;
-                if (t < nn) {
-                    const int cnt = nr[i].x & 255, cu = (nr[i].x >> 8) & 255, dst = nr[i].x >> 16;
-                    float ys = (cnt > 0 ? Ystrip[ne[i].x & 0xffff] : 0.f) + (cnt > 1 ? Ystrip[ne[i].x >> 16] : 0.f) +
-                               (cnt > 2 ? Ystrip[ne[i].y & 0xffff] : 0.f) + (cnt > 3 ? Ystrip[ne[i].y >> 16] : 0.f);
-                    for (int g = 1; 4 * g < cnt; g++) {
-                        const uint2 e = ld_u2(rsNe, ((g * tb.ntabs) * NN_PAD + tab0 + t) * 8);
-                        const int c = cnt - 4 * g;
-                        ys += (c > 0 ? Ystrip[e.x & 0xffff] : 0.f) + (c > 1 ? Ystrip[e.x >> 16] : 0.f) + (c > 2 ? Ystrip[e.y & 0xffff] : 0.f) +
-                              (c > 3 ? Ystrip[e.y >> 16] : 0.f);
-                    }
-                    Gstrip[dst] = nm[i].x - ys;
-                    if (cu > 0) {  // (zero where another window owns the pixel: k_dtile_near_tab)
-                        const float gu = nm[i].y - (float)cu * Ystrip[nr[i].y];
-                        sq += gu * gu / (float)cu;
-                    }
-                }
+                if (t < nn)  // (its counted-sample count is zero where another window owns the pixel: k_dtile_near_tab)
+                    patch::near_px(nr[i], ne[i], nm[i].x, nm[i].y, Ystrip, Gstrip, [&](int g) { return ld_u2(rsNe, ((g * tb.ntabs) * NN_PAD + tab0 + t) * 8); }, sq);
             }
             __syncthreads();
         }
@@ -655,15 +609,8 @@ __device__ __forceinline__ void dtile_body(float *lds, const float *__restrict__
                 if (u == 0 && exx && rownear)
                     gexx = src[-1];
             }
-            if (left && u == 0 && !rownear) {
-                const float *src = Gl + (gy - nby) * 3 + exx;
-#pragma unroll
-                for (int j = 0; j < 3; j++)
-                    if (j < nbx)
-                        r[j] = src[j];
-                if (exx)
-                    gexx = src[-1];
-            }
+            if (left && u == 0 && !rownear)
+                patch::near_get_g_left(r, gexx, Gl, gy - nby, exx, nbx);
         }
         if (epart) {
             const double ws = wave_sum((double)sq);
@@ -673,9 +620,7 @@ __device__ __forceinline__ void dtile_body(float *lds, const float *__restrict__
         __builtin_amdgcn_sched_barrier(0);
         // ---- H-bwd
         {
-            Rown[SLOT1 + lane] = r[0];
-            Rown[SLOT1 + 64 + lane] = r[1];
-            Rown[SLOT1 + 128 + lane] = r[63];
+            blk::gnbr_put(r, Rown, SLOT1, lane);
             __syncthreads();
             if (epart && tid == 0) {
                 double t = 0.0;
@@ -685,10 +630,9 @@ __device__ __forceinline__ void dtile_body(float *lds, const float *__restrict__
                 epart[(size_t)b * gridDim.x + wid] = t;
             }
             const float gtop = exx ? gexx : r[0];
-            const float gm1 = u == 0 ? gtop : Rlf[SLOT1 + 128 + lane];
-            const float gp1 = u == NSX - 1 ? 0.f : Rrt[SLOT1 + lane], gp2 = u == NSX - 1 ? 0.f : Rrt[SLOT1 + 64 + lane];
+            const blk::GNbr<float> nbr = blk::gnbr_get(u == 0, u == NSX - 1, Rlf, Rrt, SLOT1, lane, gtop);
             float hlo[3], hhi[3];  // (unused here: the adjoint 7 x 7 runs once, in stage C)
-            blk::bwd_chain_x<PSF == 0>(r, a, u == 0, u == NSX - 1, Rown, Rlf, Rrt, SLOT0 + 384, SLOT0, lane, sload8(awx + 16), sload8(awx + 8), gm1, gp1, gp2, gtop,
+            blk::bwd_chain_x<PSF == 0>(r, a, u == 0, u == NSX - 1, Rown, Rlf, Rrt, SLOT0 + 384, SLOT0, lane, sload8(awx + 16), sload8(awx + 8), nbr.gm1, nbr.gp1, nbr.gp2, gtop,
                                          [](int) {}, [](int, float v) { return v; }, hlo, hhi);
         }
         __builtin_amdgcn_sched_barrier(0);
@@ -704,13 +648,10 @@ __device__ __forceinline__ void dtile_body(float *lds, const float *__restrict__
             rowbuf[64 * u + lane] = r[63];
             r[63] = 0.f;
         }
-        Rown[SLOT0 + lane] = r[0];
-        Rown[SLOT0 + 64 + lane] = r[1];
-        Rown[SLOT0 + 128 + lane] = r[63];
+        blk::gnbr_put(r, Rown, SLOT0, lane);
         __syncthreads();
         const float gtop = exy ? rowbuf[64 * u + lane] : r[0];
-        const float gm1 = s == 0 ? gtop : Rup[SLOT0 + 128 + lane];
-        const float gp1 = s == 3 ? 0.f : Rdn[SLOT0 + lane], gp2 = s == 3 ? 0.f : Rdn[SLOT0 + 64 + lane];
+        const blk::GNbr<float> nbr = blk::gnbr_get(s == 0, s == 3, Rup, Rdn, SLOT0, lane, gtop);
         // The old state in 16-row batches, two in flight: batch q is consumed by quarter q of the blur.  Every batch's address passes
         // through an asm that also takes the last value the previous quarter produced (and clobbers memory): without that dependency
         // the loads -- pure reads -- are hoisted above the whole chain, all 64 rows at once, and the chain runs on spilled registers
@@ -737,14 +678,12 @@ __device__ __forceinline__ void dtile_body(float *lds, const float *__restrict__
                              return v;
                          };
         if (PSF == 0) {
-            blk::bwd_chain(r, a, s == 0, s == 3, Rown, Rup, Rdn, SLOT1 + 384, SLOT1, lane, sload8(awy + 16), sload8(awy + 8), gm1, gp1, gp2, gtop, mid, post);
+            blk::bwd_chain(r, a, s == 0, s == 3, Rown, Rup, Rdn, SLOT1 + 384, SLOT1, lane, sload8(awy + 16), sload8(awy + 8), nbr.gm1, nbr.gp1, nbr.gp2, gtop, mid, post);
         } else {
             float hl[3], hr[3];
-            blk::bwd_chain_x<false>(r, a, s == 0, s == 3, Rown, Rup, Rdn, SLOT1 + 384, SLOT1, lane, sload8(awy + 16), sload8(awy + 8), gm1, gp1, gp2, gtop, [](int) {},
-                                      [](int, float v) { return v; }, hl, hr);
-            blk::blur2d_pass1<PSF == 2 ? 2 : 3>(a, hl, hr, Rown, lane, tb.k2 + 56);
-            __syncthreads();
-            blk::blur2d_fix<PSF == 2 ? 2 : 3>(a, u == 0, u == NSX - 1, Rown, Rlf, Rrt, lane, mid, post);
+            blk::bwd_chain_x<false>(r, a, s == 0, s == 3, Rown, Rup, Rdn, SLOT1 + 384, SLOT1, lane, sload8(awy + 16), sload8(awy + 8), nbr.gm1, nbr.gp1, nbr.gp2, gtop,
+                                      [](int) {}, [](int, float v) { return v; }, hl, hr);
+            blk::blur2d_cols<PSF == 2 ? 2 : 3>(a, hl, hr, u == 0, u == NSX - 1, Rown, Rlf, Rrt, lane, tb.k2 + 56, mid, post);
         }
         __builtin_amdgcn_sched_barrier(0);
         // ---- store what this window owns: whole row quads (wave-uniform), the lane's column or nothing

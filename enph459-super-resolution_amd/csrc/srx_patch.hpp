@@ -27,7 +27,8 @@
 // The block primitives the stages are made of -- transpose64, chain64, fwd_chain, bwd_chain, blur_block, the 7 x 7 Horner blur, st4 /
 // ld4 -- live in srx_block.hpp (namespace blk), templated on the element type: every wave-block kernel family calls them there, and the
 // float64 strips of srx_stile.hpp instantiate the same source in double.  This file is the patch kernel, its tables, its eligibility,
-// its carve and its driver.
+// its carve and its driver -- and the near band of stage B for every kernel that runs it (near_count, near_coords, near_put_y, near_px,
+// near_get_g: k_ibp_patch here, the windows of srx_dtile.hpp, k_ibp_sh of srx_stile.hpp in double).
 #pragma once
 #include "srx_block.hpp"
 #include "srx_mosaic.hpp"
@@ -84,6 +85,101 @@ struct PatchTabs {
                                 // k2[t][c][r] = K[r][c], lane-direction tap c, register-direction tap r (rows padded to 8 words)
 };
 
+// ---- the near band, for every kernel that runs stage B (k_ibp_patch, k_ibp_dtile's windows, k_ibp_sh in T) ---------------------------
+// The near band of a region of RY rows x RX columns (the patch: PN x PN; a window: its own shape) is ONE enumeration: the top rows
+// -exy .. nby - 1 whole (columns -exx .. RX - 1), then the left columns -exx .. nbx - 1 of the rows below them.
+__host__ __device__ constexpr int near_top(int RX, int exy, int exx, int nby) { return (exy + nby) * (RX + exx); }
+__host__ __device__ constexpr int near_count(int RY, int RX, int exy, int exx, int nby, int nbx)
+{
+    return near_top(RX, exy, exx, nby) + (RY - nby) * (exx + nbx);
+}
+// pixel t of that enumeration -> natural coordinates and offset in the G strips
+__device__ __forceinline__ void near_coords(int t, int RX, int exy, int exx, int nby, int nbx, int &ngy, int &ngx, int &dst)
+{
+    const int WN = RX + exx, LN = max(exx + nbx, 1), ntop = near_top(RX, exy, exx, nby);  // (no left strip: no t reaches the second branch)
+    if (t < ntop) {
+        const int rr = t / WN, cc = t - rr * WN;
+        ngy = rr - exy, ngx = cc - exx, dst = rr * YW + cc;
+    } else {
+        const int q = t - ntop, rr = q / LN, cc = q - rr * LN;
+        ngy = nby + rr, ngx = cc - exx, dst = 3 * YW + rr * 3 + cc;
+    }
+}
+// offset of Y[ry, rx] in the strips: top strip rows ry <= nby, left strip otherwise (then rx <= nbx)
+__device__ __forceinline__ int strip_off(int ry, int rx, int exy, int exx, int nby)
+{
+    return ry <= nby ? (ry + exy) * YW + rx + exx : 4 * YW + (ry + exy) * 4 + rx + exx;
+}
+// In the kernel, row layout: lane = strip row q = gy + exy, r[j] = column 64 u + j, yexx = Y[gy, -1].
+// A lane's Y samples into the strips: its whole row (toprow: rows up to nby, the first left-band row included) and / or its first columns
+// (leftcol: the blocks of the region's first column)
+template <typename T> __device__ __forceinline__ void near_put_y(const T (&r)[64], T yexx, bool toprow, bool leftcol, int q, int u, int exx, int nbx, T *Yt, T *Yl)
+{
+    if (toprow) {
+        T *dst = Yt + q * YW + 64 * u + exx;
+#pragma unroll
+        for (int j = 0; j < 64; j++)
+            dst[j] = r[j];
+        if (u == 0 && exx)
+            dst[-1] = yexx;
+    }
+    if (leftcol) {
+        T *dst = Yl + q * 4 + exx;
+#pragma unroll
+        for (int j = 0; j < 3; j++)
+            if (j <= nbx)
+                dst[j] = r[j];
+        if (exx)
+            dst[-1] = yexx;
+    }
+}
+// the first c (at most four) of the Y samples a group of list entries names
+template <typename T> __device__ __forceinline__ T near_sum4(const T *Ys, uint2 e, int c)
+{
+    return (c > 0 ? Ys[e.x & 0xffff] : (T)0) + (c > 1 ? Ys[e.x >> 16] : (T)0) + (c > 2 ? Ys[e.y & 0xffff] : (T)0) + (c > 3 ? Ys[e.y >> 16] : (T)0);
+}
+// one near-band pixel: G = M - the sum of the listed Y samples, into the G strips; the counted samples' share of the MSE trace onto sq.
+// nr, ne: its records of k_patch_near_tab (ne: the first group of four entries); next(g): group g >= 1 -- more than four frames on a
+// pixel: the corner, or frames sharing a phase.  Ys / Gs: the strips (behind the barrier that follows near_put_y).
+template <typename T, typename NEXT> __device__ __forceinline__ void near_px(uint2 nr, uint2 ne, T M, T Mu, const T *Ys, T *Gs, NEXT next, T &sq)
+{
+    const int cnt = nr.x & 255, cu = (nr.x >> 8) & 255, dst = nr.x >> 16;
+    T ys = near_sum4(Ys, ne, cnt);
+    for (int g = 1; 4 * g < cnt; g++)
+        ys += near_sum4(Ys, next(g), cnt - 4 * g);
+    Gs[dst] = M - ys;
+    if (cu > 0) {
+        const T gu = Mu - (T)cu * Ys[nr.y];
+        sq += gu * gu / (T)cu;
+    }
+}
+// G of a lane's near-band pixels back from the strips (behind the barrier that follows near_px): the first nbx columns of a row below the
+// top band (row = gy - nby; a lane of the region's first column of blocks) ...
+template <typename T> __device__ __forceinline__ void near_get_g_left(T (&r)[64], T &gexx, const T *Gl, int row, int exx, int nbx)
+{
+    const T *src = Gl + row * 3 + exx;
+#pragma unroll
+    for (int j = 0; j < 3; j++)
+        if (j < nbx)
+            r[j] = src[j];
+    if (exx)
+        gexx = src[-1];
+}
+// ... or, rownear, the whole row (k_ibp_dtile reads its rows eight columns at a time and says why)
+template <typename T> __device__ __forceinline__ void near_get_g(T (&r)[64], T &gexx, bool rownear, int gy, int u, int exy, int exx, int nby, int nbx, const T *Gt, const T *Gl)
+{
+    if (rownear) {
+        const T *src = Gt + (gy + exy) * YW + 64 * u + exx;
+#pragma unroll
+        for (int j = 0; j < 64; j++)
+            r[j] = src[j];
+        if (u == 0 && exx)
+            gexx = src[-1];
+    } else if (u == 0) {
+        near_get_g_left(r, gexx, Gl, gy - nby, exx, nbx);
+    }
+}
+
 // ---- eligibility ----------------------------------------------------------------------------------------------------
 static inline bool axis_ok(const mosaic::AxisPlan &pl, int f)
 {
@@ -111,7 +207,7 @@ static inline bool eligible(const IbpSpec &s, bool rank1_only = false)
         return false;
     // the near band within the kernel's two-pixels-per-thread descriptor lists (iterate() computes the same count)
     const int exy = py.nmax, nby = -py.nmin, exx = px.nmax, nbx = -px.nmin;
-    return (exy + nby) * (PN + exx) + (PN - nby) * (exx + nbx) <= NN_PAD;
+    return near_count(PN, PN, exy, exx, nby, nbx) <= NN_PAD;
 }
 
 // ---- once per call: transposed far-field operands ---------------------------------------------------------------------
@@ -152,25 +248,6 @@ __global__ void __launch_bounds__(256)
     const bool bad = __syncthreads_or(b < B && !ok);
     if (bad && threadIdx.x == 0 && threadIdx.y == 0)
         atomicAnd(&m8[b], 0);
-}
-
-// near-band pixel t of the enumeration of a region RX columns wide (the patch: PN; a window of k_ibp_dtile: its own width) -> natural
-// coordinates and offset in the G strips
-__device__ __forceinline__ void near_coords(int t, int RX, int exy, int exx, int nby, int nbx, int &ngy, int &ngx, int &dst)
-{
-    const int WN = RX + exx, LN = max(exx + nbx, 1), ntop = (exy + nby) * WN;  // (no left strip: no t reaches the second branch)
-    if (t < ntop) {
-        const int rr = t / WN, cc = t - rr * WN;
-        ngy = rr - exy, ngx = cc - exx, dst = rr * YW + cc;
-    } else {
-        const int q = t - ntop, rr = q / LN, cc = q - rr * LN;
-        ngy = nby + rr, ngx = cc - exx, dst = 3 * YW + rr * 3 + cc;
-    }
-}
-// offset of Y[ry, rx] in the strips: top strip rows ry <= nby, left strip otherwise (then rx <= nbx)
-__device__ __forceinline__ int strip_off(int ry, int rx, int exy, int exx, int nby)
-{
-    return ry <= nby ? (ry + exy) * YW + rx + exx : 4 * YW + (ry + exy) * 4 + rx + exx;
 }
 
 // the per-pixel lists of k_build_near, re-expressed for the kernel: strip offsets instead of padded coordinates, grouped so
@@ -501,21 +578,10 @@ __global__ void __launch_bounds__(1024)
         if (PSF == 0) {
             blur_block(a, s == 0, s == 3, Rown, Rup, Rdn, SLOT0, lane, sload8(awy));
         } else {  // both directions of the PSF here (its weights carry kq^2: the H chain of stage B expects a scaled input too)
-            Rown[SLOT0 + lane] = a[0];
-            Rown[SLOT0 + 64 + lane] = a[1];
-            Rown[SLOT0 + 128 + lane] = a[2];
-            Rown[SLOT0 + 192 + lane] = a[61];
-            Rown[SLOT0 + 256 + lane] = a[62];
-            Rown[SLOT0 + 320 + lane] = a[63];
+            halo3_put(a, Rown, SLOT0, lane);
             __syncthreads();
-            float hl[3] = {0.f, 0.f, 0.f}, hr[3] = {0.f, 0.f, 0.f};
-            if (s != 0)
-                hl[0] = Rup[SLOT0 + 192 + lane], hl[1] = Rup[SLOT0 + 256 + lane], hl[2] = Rup[SLOT0 + 320 + lane];
-            if (s != 3)
-                hr[0] = Rdn[SLOT0 + lane], hr[1] = Rdn[SLOT0 + 64 + lane], hr[2] = Rdn[SLOT0 + 128 + lane];
-            blur2d_pass1<PSF == 2 ? 2 : 3>(a, hl, hr, Rown, lane, tb.k2);
-            __syncthreads();
-            blur2d_fix<PSF == 2 ? 2 : 3>(a, u == 0, u == 3, Rown, Rlf, Rrt, lane, [](int) {}, [](int, float v) { return v; });
+            const Halo3<float> h = halo3_get(s == 0, s == 3, Rup, Rdn, SLOT0, lane);
+            blur2d_cols<PSF == 2 ? 2 : 3>(a, h.lo, h.hi, u == 0, u == 3, Rown, Rlf, Rrt, lane, tb.k2, [](int) {}, [](int, float v) { return v; });
         }
         __builtin_amdgcn_sched_barrier(0);
         SRX_PSTAMP(1);
@@ -566,26 +632,7 @@ __global__ void __launch_bounds__(1024)
             nm0 = make_float2(__uint_as_float(m0.x), __uint_as_float(m0.y)), nm1 = make_float2(__uint_as_float(m1.x), __uint_as_float(m1.y));
         }
         // ---- near-band strips of Y
-        {
-            const bool toprow = wrapped || (s == 0 && lane <= nby);
-            if (toprow) {
-                float *dst = Yt + (gy + exy) * YW + 64 * u + exx;
-#pragma unroll
-                for (int j = 0; j < 64; j++)
-                    dst[j] = r[j];
-                if (u == 0 && exx)
-                    dst[-1] = yexx;
-            }
-            if (u == 0) {
-                float *dst = Yl + (gy + exy) * 4 + exx;
-#pragma unroll
-                for (int j = 0; j < 3; j++)
-                    if (j <= nbx)
-                        dst[j] = r[j];
-                if (exx)
-                    dst[-1] = yexx;
-            }
-        }
+        near_put_y(r, yexx, wrapped || (s == 0 && lane <= nby), u == 0, gy + exy, u, exx, nbx, Yt, Yl);
         __syncthreads();
         // the LR mosaic of the G step: in flight during the near-band phase
         const __amdgpu_buffer_rsrc_t rsM8 = fused::plane_rsrc(tb.Mt8 + (size_t)b * (PN / 4) * PN, (size_t)(PN / 4) * PN);
@@ -601,26 +648,15 @@ __global__ void __launch_bounds__(1024)
         SRX_PSTAMP(7);
         // ---- near band: G = M - sum of the listed Y samples; the counted samples' share of the MSE trace
         {
-            auto near_px = [&](uint2 nr, uint2 ne, float2 nm, int t) {
-                const int cnt = nr.x & 255, cu = (nr.x >> 8) & 255, dst = nr.x >> 16;
-                float ys = (cnt > 0 ? Ystrip[ne.x & 0xffff] : 0.f) + (cnt > 1 ? Ystrip[ne.x >> 16] : 0.f) +
-                           (cnt > 2 ? Ystrip[ne.y & 0xffff] : 0.f) + (cnt > 3 ? Ystrip[ne.y >> 16] : 0.f);
-                for (int g = 1; 4 * g < cnt; g++) {  // more than 4 frames on a pixel: the corner, or frames sharing a phase
-                    const uint2 e = ld_u2(rsNe, (g * NN_PAD + t) * 8);
-                    const int c = cnt - 4 * g;
-                    ys += (c > 0 ? Ystrip[e.x & 0xffff] : 0.f) + (c > 1 ? Ystrip[e.x >> 16] : 0.f) + (c > 2 ? Ystrip[e.y & 0xffff] : 0.f) +
-                          (c > 3 ? Ystrip[e.y >> 16] : 0.f);
-                }
-                Gstrip[dst] = nm.x - ys;
-                if (cu > 0) {
-                    const float gu = nm.y - (float)cu * Ystrip[nr.y];
-                    sq += gu * gu / (float)cu;
-                }
+            // (through one local lambda: with near_px called at both places directly the tail loop of either sat behind a branch and a wait of
+            // its own, and C2 lost 0.5 % -- 126.3 .. 127.4 -> 126.5 .. 128.1 us per iteration, six interleaved runs each)
+            auto px = [&](uint2 nr, uint2 ne, float2 nm, int t) {
+                near_px(nr, ne, nm.x, nm.y, Ystrip, Gstrip, [&](int g) { return ld_u2(rsNe, (g * NN_PAD + t) * 8); }, sq);
             };
             if (n0)
-                near_px(nr0, ne0, nm0, tid);
+                px(nr0, ne0, nm0, tid);
             if (n1)
-                near_px(nr1, ne1, nm1, tid + 1024);
+                px(nr1, ne1, nm1, tid + 1024);
         }
         __syncthreads();
         __builtin_amdgcn_sched_barrier(0);
@@ -695,22 +731,7 @@ __global__ void __launch_bounds__(1024)
             if (u == 0)  // the first nbx columns of the grid are near band: not part of the far-field sum
                 sqf -= (nbx > 0 ? gn[0] : 0.f) + (nbx > 1 ? gn[1] : 0.f) + (nbx > 2 ? gn[2] : 0.f);
             sq += rownear ? 0.f : sqf;
-            if (rownear) {
-                const float *src = Gt + (gy + exy) * YW + 64 * u + exx;
-#pragma unroll
-                for (int j = 0; j < 64; j++)
-                    r[j] = src[j];
-                if (u == 0 && exx)
-                    gexx = src[-1];
-            } else if (u == 0) {
-                const float *src = Gl + (gy - nby) * 3 + exx;
-#pragma unroll
-                for (int j = 0; j < 3; j++)
-                    if (j < nbx)
-                        r[j] = src[j];
-                if (exx)
-                    gexx = src[-1];
-            }
+            near_get_g(r, gexx, rownear, gy, u, exy, exx, nby, nbx, Gt, Gl);
         }
         // ---- MSE trace of this iteration (before the update): per-wave sums now, added up in a fixed order by thread 0 behind the
         // next barrier (no barrier of its own)
@@ -723,9 +744,7 @@ __global__ void __launch_bounds__(1024)
         SRX_PSTAMP(9);
         // ---- H-bwd
         {
-            Rown[SLOT1 + lane] = r[0];
-            Rown[SLOT1 + 64 + lane] = r[1];
-            Rown[SLOT1 + 128 + lane] = r[63];
+            gnbr_put(r, Rown, SLOT1, lane);
             __syncthreads();
             if (errors && tid == 0) {
                 double t = 0.0;
@@ -735,6 +754,7 @@ __global__ void __launch_bounds__(1024)
                 errors[(size_t)b * n_iter + it] = (t + Vtot[b]) * scale;
             }
             const float gtop = exx ? gexx : r[0];
+            // (written out: with gnbr_get here the count-plane float forms of the 7 x 7 PSF take 4 more bytes of scratch)
             const float gm1 = u == 0 ? gtop : Rlf[SLOT1 + 128 + lane];
             const float gp1 = u == 3 ? 0.f : Rrt[SLOT1 + lane], gp2 = u == 3 ? 0.f : Rrt[SLOT1 + 64 + lane];
             float hlo[3], hhi[3];  // (unused here: the adjoint 7 x 7 runs once, in stage C)
@@ -759,13 +779,10 @@ __global__ void __launch_bounds__(1024)
                 rowbuf[64 * u + lane] = r[63];
                 r[63] = 0.f;
             }
-            Rown[SLOT0 + lane] = r[0];
-            Rown[SLOT0 + 64 + lane] = r[1];
-            Rown[SLOT0 + 128 + lane] = r[63];
+            gnbr_put(r, Rown, SLOT0, lane);
             __syncthreads();
             const float gtop = exy ? rowbuf[64 * u + lane] : r[0];
-            const float gm1 = s == 0 ? gtop : Rup[SLOT0 + 128 + lane];
-            const float gp1 = s == 3 ? 0.f : Rdn[SLOT0 + lane], gp2 = s == 3 ? 0.f : Rdn[SLOT0 + 64 + lane];
+            const GNbr<float> nbr = gnbr_get(s == 0, s == 3, Rup, Rdn, SLOT0, lane, gtop);
             auto mid = [&](int q) {
                           // the parked state in 16-row batches, two in flight: batch q is consumed by quarter q of the blur
                           auto load16 = [&](float(&ld)[16], int bq) {
@@ -789,14 +806,12 @@ __global__ void __launch_bounds__(1024)
                           return __builtin_amdgcn_fmed3f(fmaf(corr, sn, ((i >> 4) & 1) ? hw[i & 15] : hv[i & 15]), 0.f, 255.f);
                       };
             if (PSF == 0) {
-                bwd_chain(r, a, s == 0, s == 3, Rown, Rup, Rdn, SLOT1 + 384, SLOT1, lane, sload8(awy + 16), sload8(awy + 8), gm1, gp1, gp2, gtop, mid, post);
+                bwd_chain(r, a, s == 0, s == 3, Rown, Rup, Rdn, SLOT1 + 384, SLOT1, lane, sload8(awy + 16), sload8(awy + 8), nbr.gm1, nbr.gp1, nbr.gp2, gtop, mid, post);
             } else {  // the coefficients, then the adjoint 7 x 7 of both directions; the update is the epilogue of its second pass
                 float hl[3], hr[3];
-                bwd_chain_x<false>(r, a, s == 0, s == 3, Rown, Rup, Rdn, SLOT1 + 384, SLOT1, lane, sload8(awy + 16), sload8(awy + 8), gm1, gp1, gp2, gtop, [](int) {},
-                                   [](int, float v) { return v; }, hl, hr);
-                blur2d_pass1<PSF == 2 ? 2 : 3>(a, hl, hr, Rown, lane, tb.k2 + 56);
-                __syncthreads();
-                blur2d_fix<PSF == 2 ? 2 : 3>(a, u == 0, u == 3, Rown, Rlf, Rrt, lane, mid, post);
+                bwd_chain_x<false>(r, a, s == 0, s == 3, Rown, Rup, Rdn, SLOT1 + 384, SLOT1, lane, sload8(awy + 16), sload8(awy + 8), nbr.gm1, nbr.gp1, nbr.gp2, gtop,
+                                   [](int) {}, [](int, float v) { return v; }, hl, hr);
+                blur2d_cols<PSF == 2 ? 2 : 3>(a, hl, hr, u == 0, u == 3, Rown, Rlf, Rrt, lane, tb.k2 + 56, mid, post);
             }
         }
         __builtin_amdgcn_sched_barrier(0);
@@ -830,6 +845,11 @@ static inline void fill_axis(const mosaic::AxisPlan &pl, const float *cfwd, cons
     for (int i = 0; i < 7; i++)
         aw.kb[i] = (float)(kq * (double)cfwd[i]), aw.kt[i] = cbwd[i];
     ax.ex = pl.nmax, ax.nb = -pl.nmin, ax.E = pl.E;
+}
+static inline void fill_near(PatchArgs &pa)  // (behind fill_axis of both axes)
+{
+    pa.ntop = near_top(PN, pa.y.ex, pa.x.ex, pa.y.nb);
+    pa.nn = near_count(PN, PN, pa.y.ex, pa.x.ex, pa.y.nb, pa.x.nb);
 }
 
 // Full phase grids (every frame its own (row class, column class), classes distinct modulo f): each far-field HR pixel
@@ -996,8 +1016,7 @@ static int iterate(const mosaic::Common<float> &c, const float *hr_init, float *
     fill_axis(py, c.kc.cy, c.kt.cy, pa.y, awp.y);
     fill_axis(px, c.kc.cx, c.kt.cx, pa.x, awp.x);
     pa.sn = (float)c.step / (float)N;
-    pa.ntop = (pa.y.ex + pa.y.nb) * (PN + pa.x.ex);
-    pa.nn = pa.ntop + (PN - pa.y.nb) * (pa.x.ex + pa.x.nb);
+    fill_near(pa);
     pa.ngrp = ngrp;
     if (pa.nn > NN_PAD)
         return SRX_E_UNSUPPORTED;

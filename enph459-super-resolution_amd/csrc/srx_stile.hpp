@@ -20,7 +20,8 @@
 // 8, writes G' 8 = 49 B against the algorithmic 24 (SURVEY 8d in float64) -- where the tile kernels moved ~150.  Measured (C2, B = 1024):
 // both kernels run at the memory's pace (sv 2.15 GB in ~340 us, sh 1.14 GB in ~290), VALU time is a fifth of it.
 // The closed forms of SciPy's 12-sample pad and the carry fix-ups between blocks (z^(i+1) * carry over the first FIX samples; FIX = 28 in
-// float64: |z|^29 = 3e-17) are srx_block.hpp's, the source k_ibp_patch instantiates in float; the near band is srx_patch.hpp's.  Row -1 of Y / G (frames with n_k > 0) rides as plane row 0:
+// float64: |z|^29 = 3e-17) are srx_block.hpp's, the source k_ibp_patch instantiates in float; the near band is srx_patch.hpp's, tables and
+// kernel code (patch::near_put_y, near_px, near_get_g in double).  Row -1 of Y / G (frames with n_k > 0) rides as plane row 0:
 // the planes between the kernels hold row q = gy + ex (the last grid row is empty then, srx_patch.hpp's axis_ok).
 #pragma once
 #include "srx_patch.hpp"
@@ -163,15 +164,12 @@ __global__ void __launch_bounds__(256, 2)
         for (int i = 0; i < 64; i++)
             a[i] = fused::buf_load<T>(rs_g, colb, rowb + (i + exy) * PN * EB);
         const T gtop = exy ? (s == 0 ? fused::buf_load<T>(rs_g, colb, 0) : (T)0) : a[0];
-        Rown[S0 + lane] = a[0];
-        Rown[S0 + 64 + lane] = a[1];
-        Rown[S0 + 128 + lane] = a[63];
+        blk::gnbr_put(a, Rown, S0, lane);
         __syncthreads();
-        const T gm1 = s == 0 ? gtop : Rup[S0 + 128 + lane];
-        const T gp1 = s == 3 ? (T)0 : Rdn[S0 + lane], gp2 = s == 3 ? (T)0 : Rdn[S0 + 64 + lane];
+        const blk::GNbr<T> nbr = blk::gnbr_get(s == 0, s == 3, Rup, Rdn, S0, lane, gtop);
         // V-bwd: srx_block.hpp's backward chain -- its front half, then the blur' in place with the update as its epilogue
         T hl[3], hr[3];
-        blk::bwd_front(a, s == 0, s == 3, Rown, Rup, Rdn, S1 + 384, S1, lane, aw.wb, gm1, gp1, gp2, gtop, hl, hr);
+        blk::bwd_front(a, s == 0, s == 3, Rown, Rup, Rdn, S1 + 384, S1, lane, aw.wb, nbr.gm1, nbr.gp1, nbr.gp2, gtop, hl, hr);
         T hv[2][8];  // the state's rows, a group ahead of the blur that consumes them
         auto load8 = [&](T(&d)[8], int j0) {
 #pragma unroll
@@ -261,7 +259,7 @@ __device__ __forceinline__ void sh_body(float *lds, T *P, const STabs<T> &tb, co
     uint2 nr[NQ], ne[NQ];
     T2<T> nm[NQ];
     {
-        const int WN = PN + exx, LN = exx + nbx, ntop = (exy + nby) * WN;
+        const int LN = exx + nbx, ntop = patch::near_top(PN, exy, exx, nby);
         const int gy_lo = max(nby, 64 * s - exy), gy_hi = min(PN - exy, 64 * s + 64 - exy);
 #pragma unroll
         for (int k = 0; k < NQ - 1; k++)
@@ -275,45 +273,14 @@ __device__ __forceinline__ void sh_body(float *lds, T *P, const STabs<T> &tb, co
         }
     }
     // ---- near-band strips of Y
-    if (s == 0 && q <= nby + exy) {
-        T *dst = Yt + q * YW + 64 * u + exx;
-#pragma unroll
-        for (int j = 0; j < 64; j++)
-            dst[j] = r[j];
-        if (u == 0 && exx)
-            dst[-1] = yexx;
-    }
-    if (u == 0) {
-        T *dst = Yl + q * 4 + exx;
-#pragma unroll
-        for (int j = 0; j < 3; j++)
-            if (j <= nbx)
-                dst[j] = r[j];
-        if (exx)
-            dst[-1] = yexx;
-    }
+    patch::near_put_y(r, yexx, s == 0 && q <= nby + exy, u == 0, q, u, exx, nbx, Yt, Yl);
     __syncthreads();
     // ---- near band: G = M - the listed Y samples; the counted samples' share of the MSE trace
     T sq = 0;
 #pragma unroll
-    for (int k = 0; k < NQ; k++) {
-        if (non[k]) {
-            const int cnt = nr[k].x & 255, cu = (nr[k].x >> 8) & 255, dst = nr[k].x >> 16;
-            T ys = (cnt > 0 ? strips[ne[k].x & 0xffff] : (T)0) + (cnt > 1 ? strips[ne[k].x >> 16] : (T)0) + (cnt > 2 ? strips[ne[k].y & 0xffff] : (T)0) +
-                   (cnt > 3 ? strips[ne[k].y >> 16] : (T)0);
-            for (int g = 1; 4 * g < cnt; g++) {  // more than four frames on a pixel: the corner, or frames sharing a phase
-                const uint2 e = tb.nent[(size_t)g * NN_PAD + nt[k]];
-                const int c = cnt - 4 * g;
-                ys += (c > 0 ? strips[e.x & 0xffff] : (T)0) + (c > 1 ? strips[e.x >> 16] : (T)0) + (c > 2 ? strips[e.y & 0xffff] : (T)0) +
-                      (c > 3 ? strips[e.y >> 16] : (T)0);
-            }
-            Gt[dst] = nm[k].x - ys;
-            if (cu > 0) {
-                const T gu = nm[k].y - (T)cu * strips[nr[k].y];
-                sq += gu * gu / (T)cu;
-            }
-        }
-    }
+    for (int k = 0; k < NQ; k++)
+        if (non[k])
+            patch::near_px(nr[k], ne[k], nm[k].x, nm[k].y, strips, Gt, [&](int g) { return tb.nent[(size_t)g * NN_PAD + nt[k]]; }, sq);
     __syncthreads();
     // ---- G = M - C Y on the grid; near-band pixels take their value from the strips
     T gexx = 0;  // G[gy, -1]
@@ -357,22 +324,7 @@ __device__ __forceinline__ void sh_body(float *lds, T *P, const STabs<T> &tb, co
         if (u == 0)
             sqf -= (nbx > 0 ? gn[0] : (T)0) + (nbx > 1 ? gn[1] : (T)0) + (nbx > 2 ? gn[2] : (T)0);
         sq += rownear ? (T)0 : sqf;
-        if (rownear) {
-            const T *src = Gt + q * YW + 64 * u + exx;
-#pragma unroll
-            for (int j = 0; j < 64; j++)
-                r[j] = src[j];
-            if (u == 0 && exx)
-                gexx = src[-1];
-        } else if (u == 0) {
-            const T *src = Gl + (gy - nby) * 3 + exx;
-#pragma unroll
-            for (int j = 0; j < 3; j++)
-                if (j < nbx)
-                    r[j] = src[j];
-            if (exx)
-                gexx = src[-1];
-        }
+        patch::near_get_g(r, gexx, rownear, gy, u, exy, exx, nby, nbx, Gt, Gl);
     }
     if (want_err) {
         const double ws = wave_sum((double)sq);
@@ -380,17 +332,14 @@ __device__ __forceinline__ void sh_body(float *lds, T *P, const STabs<T> &tb, co
             part[u] = ws;
     }
     // ---- H-bwd
-    Rown[S1 + lane] = r[0];
-    Rown[S1 + 64 + lane] = r[1];
-    Rown[S1 + 128 + lane] = r[63];
+    blk::gnbr_put(r, Rown, S1, lane);
     __syncthreads();
     if (want_err && tid == 0)
         epart[4 * b + s] = (part[0] + part[1]) + (part[2] + part[3]);
     const T gtop = exx ? gexx : r[0];
-    const T gm1 = u == 0 ? gtop : Rlf[S1 + 128 + lane];
-    const T gp1 = u == 3 ? (T)0 : Rrt[S1 + lane], gp2 = u == 3 ? (T)0 : Rrt[S1 + 64 + lane];
+    const blk::GNbr<T> nbr = blk::gnbr_get(u == 0, u == 3, Rlf, Rrt, S1, lane, gtop);
     T hl[3], hr[3];
-    blk::bwd_front(r, u == 0, u == 3, Rown, Rlf, Rrt, S0 + 384, S0, lane, aw.wb, gm1, gp1, gp2, gtop, hl, hr);
+    blk::bwd_front(r, u == 0, u == 3, Rown, Rlf, Rrt, S0 + 384, S0, lane, aw.wb, nbr.gm1, nbr.gp1, nbr.gp2, gtop, hl, hr);
     blk::blur_inplace(r, hl, hr, aw.kt, [](int) {}, [](int, T v) { return v; });
     // back to the plane, over this strip's own rows, row-major (k_ibp_sv reads columns of it): the second transpose
     __syncthreads();  // the neighbours have read this wave's exchange slots, which the transpose runs over
@@ -469,8 +418,7 @@ static int iterate(const mosaic::Common<T> &c, const T *hr_init, T *hr, int n_it
     fill_axis<T>(py, c.kc.cy, c.kt.cy, pa.y, awy);
     fill_axis<T>(px, c.kc.cx, c.kt.cx, pa.x, awx);
     pa.sn = 0.f;
-    pa.ntop = (pa.y.ex + pa.y.nb) * (PN + pa.x.ex);
-    pa.nn = pa.ntop + (PN - pa.y.nb) * (pa.x.ex + pa.x.nb);
+    patch::fill_near(pa);
     pa.ngrp = ngrp;
     if (pa.nn > NN_PAD)
         return SRX_E_UNSUPPORTED;

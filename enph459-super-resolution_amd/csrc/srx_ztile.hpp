@@ -292,22 +292,14 @@ __device__ __forceinline__ void blur2d_block(float (&a)[64], bool first, bool la
 {
     static_assert(RAD == 2 || RAD == 3, "5 x 5 core or full 7 x 7");
     constexpr int LO = 3 - RAD, HI = 3 + RAD;  // taps [LO, HI] of either axis
-    Rown[s6 + lane] = a[0];
-    Rown[s6 + 64 + lane] = a[1];
-    Rown[s6 + 128 + lane] = a[2];
-    Rown[s6 + 192 + lane] = a[61];
-    Rown[s6 + 256 + lane] = a[62];
-    Rown[s6 + 320 + lane] = a[63];
+    blk::halo3_put(a, Rown, s6, lane);
     f8 kw[7];  // kw[u][v]
 #pragma unroll
     for (int u = 0; u < 7; u++)
         kw[u] = sload8(w56 + 8 * u);
     __syncthreads();
-    float hl[3] = {0.f, 0.f, 0.f}, hr[3] = {0.f, 0.f, 0.f};
-    if (!first)
-        hl[0] = Rprev[s6 + 192 + lane], hl[1] = Rprev[s6 + 256 + lane], hl[2] = Rprev[s6 + 320 + lane];
-    if (!last)
-        hr[0] = Rnext[s6 + lane], hr[1] = Rnext[s6 + 64 + lane], hr[2] = Rnext[s6 + 128 + lane];
+    const blk::Halo3<float> h = blk::halo3_get(first, last, Rprev, Rnext, s6, lane);
+    const float(&hl)[3] = h.lo, (&hr)[3] = h.hi;
     // in place, NB outputs at a time (the window of NB + 6 inputs and the three old values the next group still needs are live)
     constexpr int NB = 4;
     float c0 = hl[0], c1 = hl[1], c2 = hl[2];

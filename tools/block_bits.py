@@ -36,6 +36,16 @@ CASES += [(f"stile {fn}", "stile", "f64", 3, 4, 64, 64, sh, "gauss", "u8") for f
 CASES += [(f"dtile {pn}", "dtile", "f32", 1, 4, 64, 48, GRID16, pn, "u8") for pn in ("gauss", "core5")]
 CASES += [("ztile", "ztile", "f32", 1, 2, 72, 140, synth.NOMINAL_5, "gauss", "u8"), ("ctile", "ctile", "f64", 1, 2, 72, 140, synth.NOMINAL_5, "gauss", "u8"),
           ("btile", "btile", "f32", 1, 2, 32, 32, synth.MEASURED_4, "gauss", "u8"), ("atile", "atile", "f32", 1, 4, 40, 50, GRID16, "gauss", "u8")]
+# (new cases go to the END: a case's seed is its index)
+# the float mosaic of the windows (M8 = false); then two frames per phase -- more than four frames on a near-band pixel, so the group tail of
+# patch::near_px runs on every route (the samples' sums pass 255: the float mosaic and a count plane) -- and the windows' count-plane
+# instantiation (k_ibp_dtile<false, 3, *>).  --plan prints the path only: it says that GRID12 and GRID16 * 2 stay on "dtile" at this shape.
+# That they run the count-plane instantiation follows from their count maps, which are no product of a row and a column mask
+# (patch::c01_masks: a phase missing from every row and column; two frames on one phase), so the driver launches <false, ...>
+CASES += [(f"dtile {pn} frac", "dtile", "f32", 1, 4, 64, 48, GRID16, pn, "frac") for pn in ("gauss", "core5")]
+CASES += [("patch grid16x2", "patch", "f32", 3, 4, 64, 64, GRID16 * 2, "gauss", "u8"), ("patch grid16x2 core5", "patch", "f32", 2, 4, 64, 64, GRID16 * 2, "core5", "u8"),
+          ("stile grid16x2", "stile", "f64", 3, 4, 64, 64, GRID16 * 2, "gauss", "u8"), ("dtile grid16x2", "dtile", "f32", 1, 4, 64, 48, GRID16 * 2, "gauss", "u8"),
+          ("dtile grid12", "dtile", "f32", 1, 4, 64, 48, GRID12, "gauss", "u8"), ("dtile grid12 frac core5", "dtile", "f32", 1, 4, 64, 48, GRID12, "core5", "frac")]
 
 
 # (reader of the flag, call, path, precision, B, f, LR h, LR w, shifts, flags off, flag): the smallest shapes that reach each reader

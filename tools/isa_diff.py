@@ -5,7 +5,8 @@
     hipcc <the Makefile's CXXFLAGS and INC> --cuda-device-only -S -o new.s csrc/srx_api.hip     # in the new tree
     python tools/isa_diff.py old.s new.s [-v]
 
-Per kernel symbol (the text from its label to its s_endpgm, comments and directives dropped, local labels renumbered) it says
+Per kernel symbol (the text from its label to its .Lfunc_end<n> label -- the whole function: a kernel with an early exit has an s_endpgm in
+front of its body -- comments and directives dropped, local labels renumbered) it says
   identical   the same instructions with the same operands;
   renamed     the same instructions in the same order, registers numbered differently;
   reordered   the same number of instructions and the same multiset of opcodes, in another order;
@@ -21,6 +22,7 @@ import sys
 
 FIGURES = ("next_free_vgpr", "next_free_sgpr", "accum_offset", "private_segment_fixed_size", "group_segment_fixed_size")
 _REGISTER = re.compile(r"\b([vsa])(\d+|\[\d+:\d+\])")
+_FUNC_END = re.compile(r"\.Lfunc_end\d+:")
 
 
 def kernels(text):
@@ -37,13 +39,12 @@ def kernels(text):
                 cur = line[:-1]
                 out[cur] = []
             continue
-        if not line or line.startswith("."):
+        if _FUNC_END.match(line):
+            cur = None
             continue
-        if line.endswith(":"):
+        if not line or line.startswith(".") or line.endswith(":"):
             continue
         out[cur].append(re.sub(r"\.LBB\d+_", ".LBB_", line))
-        if line.startswith("s_endpgm"):
-            cur = None
     return {n: (out.get(n, []), figs.get(n, {})) for n in names}
 
 
