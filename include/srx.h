@@ -429,10 +429,17 @@ int srx_interleave4_u8(const uint8_t *frames, int B, int h, int w, uint8_t *out,
  *                  ref / test [B, H, W]: PSNR = 10 log10(peak^2 n / out[6]); the affine-fit PSNR follows from the other five.
  *   local_contrast: (max - min) / (max + min + 1e-9) of profile[i - w/2 : i + w/2], 0 within w/2 of either end.  [B, n] -> [B, n]
  *   ring_sums    : ring k = pixels whose distance to (cy, cx) truncates to k: out = {sum[nbin], count[nbin]}   (radial_average)
+ *                  1 <= nbin <= 4096 (otherwise SRX_E_INVALID); the centre may lie off the image.
  *   spot_moments : out = {max, sum p, sum p y, sum p x} over the pixels with p > 0.1 max                       (subpixel_centre)
+ *                  H W <= 2^24 (otherwise SRX_E_INVALID).  The comparison is strict and in float64; no pixel above the threshold
+ *                  (a maximum <= 0): the three sums are 0.
  *   edge_magnitude: Sobel magnitude of the Gaussian(sigma)-smoothed ROI, scipy.ndimage 'reflect' boundaries; float64 [H, W] -> [H, W]
+ *                  sigma > 0 (otherwise SRX_E_INVALID); a radius int(4 sigma + 0.5) above 8 is SRX_E_UNSUPPORTED.
  *   edge_dist_range / edge_bins: every ROI pixel projected on the normal of the line v = m u + b ((u, v) = (row, col) if rows_are_x else
  *                  (col, row)): min / max of the distances in (-8, 10); sums and counts per 1/4-px bin [lo + i bw, lo + (i + 1) bw).
+ *                  edge_dist_range: out = {lo, hi}; when no pixel lies in (-8, 10) it stores {1e300, -1e300} (lo > hi: nothing to bin).
+ *                  H W <= 2^24 and norm > 0 (otherwise SRX_E_INVALID).  edge_bins: out = {sum[nbin], count[nbin]}, 1 <= nbin <= 128,
+ *                  norm > 0 and bw > 0 (otherwise SRX_E_INVALID); a pixel in (-8, 10) outside [lo, lo + nbin bw) is in no bin.
  *   ssim         : skimage structural_similarity (2-D) of the crop [border, size - border) of ref / test [B, H, W], in ONE pass over the two
  *                  images: window sums of x, y, x^2, y^2, x y by the separable correlation taps[2 radius + 1] (host float64; uniform or
  *                  Gaussian) with scipy's 'reflect' boundary, C1 = (k1 data_range)^2, C2 = (k2 data_range)^2, cov_norm = NP / (NP - 1) if
