@@ -17,6 +17,7 @@
 #include "srx_mean.hpp"
 #include "srx_png.hpp"
 #include "srx_crc.hpp"
+#include "srx_patches.hpp"
 
 using namespace srx;
 
@@ -924,6 +925,29 @@ int srx_mean_u8(const uint8_t *in, int B, int R, int H, int W, int f, int py, in
         return SRX_E_UNSUPPORTED;
     return out_elem_bytes == 4 ? mean::mean_u8<float>(in, B, R, H, W, f, py, px, (float *)out, hs(s))
                                : mean::mean_u8<double>(in, B, R, H, W, f, py, px, (double *)out, hs(s));
+}
+
+int srx_patches_count(int n, int L, int stride) { return patches::grid_count(n, L, stride); }
+
+int srx_patches_gather_u8(const uint8_t *frames, int B, int N, int h, int w, int ph, int pw, int sy, int sx, void *out, srx_stream_t s)
+{
+    return patches::gather<uint8_t>(frames, B, N, h, w, ph, pw, sy, sx, out, hs(s));
+}
+int srx_patches_gather_f32(const float *frames, int B, int N, int h, int w, int ph, int pw, int sy, int sx, void *out, srx_stream_t s)
+{
+    return patches::gather<float>(frames, B, N, h, w, ph, pw, sy, sx, out, hs(s));
+}
+int srx_patches_gather_f64(const double *frames, int B, int N, int h, int w, int ph, int pw, int sy, int sx, void *out, srx_stream_t s)
+{
+    return patches::gather<double>(frames, B, N, h, w, ph, pw, sy, sx, out, hs(s));
+}
+int srx_patches_blend_f32(const float *p, int B, int H, int W, int PH, int PW, int SY, int SX, int margin, void *out, srx_stream_t s)
+{
+    return patches::blend<float>(p, B, H, W, PH, PW, SY, SX, margin, out, hs(s));
+}
+int srx_patches_blend_f64(const double *p, int B, int H, int W, int PH, int PW, int SY, int SX, int margin, void *out, srx_stream_t s)
+{
+    return patches::blend<double>(p, B, H, W, PH, PW, SY, SX, margin, out, hs(s));
 }
 
 size_t srx_png_stream_bound(int H, int W) { return H > 0 && W > 0 ? png::stream_bound((size_t)H * ((size_t)W + 1)) : 0; }

@@ -13,7 +13,8 @@ _API = ("blur", "forward_model", "back_project", "shift_and_add", "ibp", "ndi_zo
         "FLAG_AUTO", "FLAG_COMPOSED", "FLAG_FUSED", "FLAG_PER_FRAME", "FLAG_TILES", "FLAG_DIAG_NO_ZERO_FUSE",
         "FLAG_DIAG_NO_SEPARABLE", "FLAG_DIAG_NO_PREFILTER_TILE", "FLAG_DIAG_V1", "FLAG_DIAG_WIDE_WINDOWS", "FLAG_DIAG_COLUMN_TILES", "FLAG_DIAG_TWO_LAUNCH", "FLAG_DIAG_SAA_ONE_PASS", "FLAG_DIAG_U8_BYTE_LOADS")
 
-__all__ = list(_API) + ["estimate_shifts", "estimate_psf"]
+_PATCHWISE = ("PatchGrid", "estimate_shift_field", "reconstruct_patchwise")
+__all__ = list(_API) + ["estimate_shifts", "estimate_psf"] + list(_PATCHWISE)
 
 
 def __getattr__(name):
@@ -23,6 +24,8 @@ def __getattr__(name):
         return importlib.import_module(".register", __name__).estimate_shifts
     if name == "estimate_psf":
         return importlib.import_module(".psf_device", __name__).estimate_psf
-    if name in ("api", "synth", "_lib", "session", "parallel", "rowband", "metrics", "register", "psf_device"):
+    if name in _PATCHWISE:  # (patchwise.gather / patchwise.blend stay in their module: the names are too plain for the package)
+        return getattr(importlib.import_module(".patchwise", __name__), name)
+    if name in ("api", "synth", "_lib", "session", "parallel", "rowband", "metrics", "register", "psf_device", "patchwise"):
         return importlib.import_module("." + name, __name__)
     raise AttributeError(name)

@@ -55,6 +55,8 @@ _TYPED = {
     "srx_png_deflate_{T}": (_I, [_P, _I, _I, _I, _P, _P, _P, _Z, _P]),
     "srx_png_file_{T}": (_I, [_P, _I, _I, _I, _P, _P, _P, _Z, _P]),
     "srx_edge_sfr_{T}": (_I, [_P, _I, _I, _I, _Z, _Z, _I, _D, _P, _P, _P, _P, _P, _Z, _P]),
+    "srx_patches_gather_{T}": (_I, [_P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P]),
+    "srx_patches_blend_{T}": (_I, [_P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P]),
 }
 _PLAIN = {
     "srx_version": (_I, []),
@@ -104,6 +106,8 @@ _PLAIN = {
     "srx_png_file_u8": (_I, [_P, _I, _I, _I, _P, _P, _P, _Z, _P]),
     "srx_edge_sfr_scratch_bytes": (_Z, [_I, _I, _I]),
     "srx_edge_sfr_u8": (_I, [_P, _I, _I, _I, _Z, _Z, _I, _D, _P, _P, _P, _P, _P, _Z, _P]),
+    "srx_patches_count": (_I, [_I, _I, _I]),
+    "srx_patches_gather_u8": (_I, [_P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P]),
 }
 
 

@@ -49,9 +49,17 @@ def main(argv=None):
     ap.add_argument("--png-on-device", action="store_true",
                     help="build the output PNGs on the device (srx_png_file: quantise, Up filter, run lengths and Huffman coding per "
                          "32 KB chunk, the container and its CRC-32); the host only writes the bytes.  Same pixels in every file, other bytes")
+    ap.add_argument("--patchwise", choices=["global", "local"], default=None,
+                    help="cal_target kinds: reconstruct in overlapping 256 x 256 HR patches that are blended back (sr_mi355x/patchwise.py).  "
+                         "local: every patch under the shifts registered on it, the shift field written as shift_field.json next to the "
+                         "PNGs; global: every patch under the session's one table (the baseline of local)")
     args = ap.parse_args(argv)
     if args.metrics_on_device and not args.metrics:
         ap.error("--metrics-on-device needs --metrics")
+    if args.patchwise and args.row_bands:
+        ap.error("--patchwise and --row-bands exclude each other")
+    if args.patchwise and args.kind not in ("mono_cal_target", "rgb_cal_target"):
+        ap.error("--patchwise is for the cal_target kinds (one large image per session)")
     rank, world, local_rank = int(os.environ.get("RANK", "0")), int(os.environ.get("WORLD_SIZE", "1")), int(os.environ.get("LOCAL_RANK", "0"))
     dist = None
     if world > 1:  # one process per GPU: pick the device before anything touches it
@@ -82,7 +90,7 @@ def main(argv=None):
         metrics_cb = session.queue_metrics_device if args.metrics_on_device else session.write_metrics_device
     session.process_sessions(sessions, psf, args.output_dir, args.kind, rank=rank, world=world, on_images=metrics_cb,
                              row_bands=args.row_bands and world > 1, register=args.register,
-                             keep_u8=args.u8_frames, device_png=args.png_on_device)
+                             keep_u8=args.u8_frames, device_png=args.png_on_device, patchwise=args.patchwise)
     if dist is not None:
         dist.barrier()
     if rank == 0:

@@ -199,12 +199,28 @@ def load_corner_reps(session_dir, red, keep_u8=False):
     return all_reps, list(CORNER_SHIFTS)
 
 
-def reconstruct(frames, shifts, psf_kernel, n_iter, factor=UPSAMPLE_FACTOR, step=IBP_STEP_SIZE, row_bands=False):
+def reconstruct(frames, shifts, psf_kernel, n_iter, factor=UPSAMPLE_FACTOR, step=IBP_STEP_SIZE, row_bands=False, patchwise=None,
+                patch_opts=None):
     """Native-2x, SAA and SAA+IBP of one frame set, all on the device (run_sr.py:274-292).
     -> dict of float device tensors + the MSE trace.
     row_bands: every rank of the process group calls this with the same frames; the IBP loop runs on row bands of the ONE image
-    (rowband.ibp_row_bands: halo rows exchanged point to point), and only rank 0 gets "SAA_IBP" (None elsewhere)."""
+    (rowband.ibp_row_bands: halo rows exchanged point to point), and only rank 0 gets "SAA_IBP" (None elsewhere).
+    patchwise: None (the whole frame under the one table, as the reference), "global" (cut into overlapping patches, every patch
+    under the one table, blended back) or "local" (every patch under the shifts registered on it): patchwise.reconstruct_patchwise
+    with PatchGrid(h, w, factor, **patch_opts).  The dict then also holds "shift_field" (shift_field.json's content; "local" only)."""
     import torch
+    if patchwise is not None:
+        from . import patchwise as pw
+        if patchwise not in ("global", "local"):
+            raise ValueError("patchwise must be None, 'global' or 'local'")
+        if row_bands:
+            raise ValueError("patchwise and row_bands exclude each other")
+        h, w = (int(v) for v in frames[0].shape)
+        grid = pw.PatchGrid(h, w, factor, **(patch_opts or {}))
+        images, errs, field = pw.reconstruct_patchwise(frames, shifts, psf_kernel, n_iter, factor, step, grid=grid, local=patchwise == "local")
+        if field is not None:
+            images["shift_field"] = pw.field_json(grid, shifts, field)
+        return images, errs
     lr64 = torch.stack(frames)  # float64, or uint8 frames (keep_u8 loaders): SAA and IBP then take the bytes themselves
     u8 = lr64.dtype == torch.uint8
     mean_lr = _frame_mean(lr64[None])[0]  # float64; also what LR_(red_)mean.png is quantised from
@@ -473,7 +489,7 @@ def _save_outputs(out_dir, images, errors, lr_name, extra=None, device_png=False
 
 
 def process_session(session_dir, psf_kernel, output_base, kind=None, n_iter=None, verbose=True, batch_reps=True, loaded=None, flush=True,
-                    row_bands=False, on_images=None, register=False, keep_u8=False, device_png=False):
+                    row_bands=False, on_images=None, register=False, keep_u8=False, device_png=False, patchwise=None, patch_opts=None):
     """Counterpart of process_session / process_combo.  Returns the list of output directories written
     (empty if everything was already done).  batch_reps: the reps of a barcode session that are still to do go through the
     library in one B = reps call (reconstruct_batch) instead of one call per rep (with register, every rep under its own table); `loaded`: frames already decoded by a
@@ -481,10 +497,14 @@ def process_session(session_dir, psf_kernel, output_base, kind=None, n_iter=None
     kinds: one large image per session): all ranks work on this one session (reconstruct(row_bands=True)), rank 0 writes.
     register: reconstruct with shifts estimated from the frames (register_shifts) and write registration.json beside the PNGs.
     keep_u8 (run_sr --u8-frames): the frames this call loads itself stay uint8 on the device; the files written are the same.
-    device_png (run_sr --png-on-device): the PNGs' streams are compressed on the device (_save_outputs): the same pixels in every file."""
+    device_png (run_sr --png-on-device): the PNGs' streams are compressed on the device (_save_outputs): the same pixels in every file.
+    patchwise (run_sr --patchwise; the two cal_target kinds): "global" or "local", reconstruct's argument, with patch_opts the keywords
+    of patchwise.PatchGrid; "local" writes shift_field.json (the grid, the patch centres, estimated / used / score / status) beside the PNGs."""
     kind = kind or detect_kind(session_dir)
     if kind not in IBP_ITERATIONS:
         raise ValueError("kind must be one of " + ", ".join(IBP_ITERATIONS))
+    if patchwise is not None and (kind not in ("mono_cal_target", "rgb_cal_target") or row_bands):
+        raise ValueError("patchwise is for the one-image-per-session kinds, and not together with row_bands")
     n_iter = IBP_ITERATIONS[kind] if n_iter is None else n_iter
     name = os.path.basename(os.path.normpath(session_dir))
     say = print if verbose else (lambda *a, **k: None)
@@ -504,7 +524,9 @@ def process_session(session_dir, psf_kernel, output_base, kind=None, n_iter=None
         if register:
             shifts, reg = register_shifts([frames], shifts)[0]
             extra = dict(extra or {}, **{"registration.json": reg})
-        images, errors = reconstruct(frames, shifts, psf_kernel, n_iter, row_bands=row_bands)
+        images, errors = reconstruct(frames, shifts, psf_kernel, n_iter, row_bands=row_bands, patchwise=patchwise, patch_opts=patch_opts)
+        if "shift_field" in images:
+            extra = dict(extra or {}, **{"shift_field.json": images.pop("shift_field")})
         if images["SAA_IBP"] is None:  # row-band mode, not rank 0: the assembled image lives on rank 0
             return written
         _save_outputs(out_dir, images, errors, lr_name, extra, device_png=device_png)
@@ -559,7 +581,7 @@ def load_session(session_dir, kind, keep_u8=False):
 
 
 def process_sessions(sessions, psf_kernel, output_base, kind, n_iter=None, verbose=True, rank=0, world=1, on_written=None, row_bands=False,
-                     on_images=None, register=False, keep_u8=False, device_png=False):
+                     on_images=None, register=False, keep_u8=False, device_png=False, patchwise=None, patch_opts=None):
     """The reference's outer loop (mono_cal_target/run_sr.py:358-360, mono_barcodes/run_sr.py:301) over the sessions this
     rank owns (session i -> rank i mod world, parallel.map_sharded: independent items, no data-path collective), with the PNG
     decode and upload of session k + 1 overlapped with the device work of session k.  -> output directories written: by every
@@ -570,6 +592,8 @@ def process_sessions(sessions, psf_kernel, output_base, kind, n_iter=None, verbo
     from . import parallel
     if row_bands and kind not in ("mono_cal_target", "rgb_cal_target"):
         raise ValueError("row_bands is for the one-image-per-session kinds (the barcode kinds batch their reps instead)")
+    if patchwise is not None and (kind not in ("mono_cal_target", "rgb_cal_target") or row_bands):
+        raise ValueError("patchwise is for the one-image-per-session kinds, and not together with row_bands")
     owned = list(range(len(sessions))) if row_bands else parallel.shard_indices(len(sessions), rank, world)
     say = print if verbose else (lambda *a, **k: None)
 
@@ -588,7 +612,8 @@ def process_sessions(sessions, psf_kernel, output_base, kind, n_iter=None, verbo
         count[0] += 1
         say(f"\n[rank {rank}: {count[0]}/{len(owned)}] {os.path.basename(sessions[i])}")
         out = process_session(sessions[i], psf_kernel, output_base, kind=kind, n_iter=n_iter, verbose=verbose, loaded=loaded,
-                              flush=on_written is not None, row_bands=row_bands, on_images=on_images, register=register, device_png=device_png)
+                              flush=on_written is not None, row_bands=row_bands, on_images=on_images, register=register, device_png=device_png,
+                              patchwise=patchwise, patch_opts=patch_opts)
         if on_written:
             for d in out:
                 on_written(d)

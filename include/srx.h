@@ -341,6 +341,36 @@ int srx_quantize_u8_f64(const double *in, size_t n, uint8_t *out, srx_stream_t s
 int srx_mean_u8(const uint8_t *in, int B, int R, int H, int W, int f, int py, int px, int out_elem_bytes /* 4, 8 */, void *out,
                 srx_stream_t stream);
 
+/* ---- a frame as a batch of overlapping patches, and the patches blended back into a frame ----
+ * No reference counterpart (it reconstructs a session under ONE shift table): these two index maps lead from a frame stack to the batched
+ * per-item entry points (srx_register_* with B = patches, srx_saa_items_* / srx_ibp_items_* with one table per patch) and back, so that a
+ * reconstruction can follow a shift that varies over the field (sr_mi355x/patchwise.py).
+ * Grid rule, per axis of n samples, patch length L, stride s: count = ceil((n - L) / s) + 1 patches, origin(i) = min(i s, n - L) -- the
+ * last patch is pulled inward, never padded, so every patch holds L real samples.  Patch p = iy count_x + ix; batch item b of the frames
+ * owns items [b P, (b + 1) P), P = count_y count_x.
+ *   srx_patches_count(n, L, s): the count of one axis, on the host (0 for arguments no call accepts: n, L or s <= 0, L > n, s > L, 2 s < L).
+ *   gather: frames T [B, N, h, w] -> patches T [B P, N, ph, pw] (the srx_ibp_items layout); T = uint8 keeps the bytes, so srx_register_u8_*
+ *           and the u8lr calls take them.  A pure index map, bit-exact.
+ *   blend : HR patches T [B P, PH, PW] -> out T [B, H, W].  Per axis, with R = L - s - 2 margin, patch i at origin o_i weighs the
+ *           coordinate x inside it by w_i(x) = clamp(min(dl, dr), 0, R), dl = x - o_i + 1 - margin if o_i > 0 else R, dr = o_i + L - x -
+ *           margin if o_i + L < n else R: nothing over the outer `margin` samples of a patch (where its reconstruction feels the patch's
+ *           own border), a ramp of R steps, R inside; no ramp and no margin at an edge of the image.  out = sum (T)(wy_i wx_j) v_ij /
+ *           (T)(Sy Sx), Sy = sum_i wy_i, Sx = sum_j wx_j: the integer product converted once, each term rounded once, the terms added in
+ *           ascending (i, j) by plain additions (nothing fused), one division -- numpy reproduces the bits (tests/patchwise_cases.py).
+ *           A term of weight 0 is not read.  With 2 s >= L at most 3 patches per axis cover a sample and the weight sum is positive.
+ * One kernel launch each on `stream`; no workspace, no allocation, no host synchronisation, capture-safe.  Inputs are never written and
+ * nothing is written outside the output.  Caller pointers need the alignment of their element only (a uint8 row of odd w starts on any
+ * byte): a row, or a lane's 16 bytes of one, goes as 16-byte vectors only where the kernel finds source and destination aligned itself.
+ * SRX_E_INVALID: a null pointer; B, N, h or w <= 0; L <= 0 or L > n; s <= 0 or s > L (either axis); blend: margin < 0 or R < 1.
+ * SRX_E_UNSUPPORTED: 2 s < L; one item's frames (gather) or one plane (blend) of 2 GiB or more; B P > 2^31 - 1.  All decided on the
+ * host before any HIP call, in this order. */
+int srx_patches_count(int n, int L, int stride);
+int srx_patches_gather_u8(const uint8_t *frames, int B, int N, int h, int w, int ph, int pw, int sy, int sx, void *patches, srx_stream_t stream);
+int srx_patches_gather_f32(const float *frames, int B, int N, int h, int w, int ph, int pw, int sy, int sx, void *patches, srx_stream_t stream);
+int srx_patches_gather_f64(const double *frames, int B, int N, int h, int w, int ph, int pw, int sy, int sx, void *patches, srx_stream_t stream);
+int srx_patches_blend_f32(const float *patches, int B, int H, int W, int PH, int PW, int SY, int SX, int margin, void *out, srx_stream_t stream);
+int srx_patches_blend_f64(const double *patches, int B, int H, int W, int PH, int PW, int SY, int SX, int margin, void *out, srx_stream_t stream);
+
 /* ---- the output PNGs' compressed stream, built on the device: the encoder half of cv2.imwrite / session.write_png_u8
  * (mono_barcodes/run_sr.py:303-306) ----
  * img T [B, H, W] -> streams uint8 [B][srx_png_stream_bound(H, W)], lengths int64 [B] (both DEVICE arrays, any byte address).  Bytes
