@@ -556,7 +556,12 @@ int srx_edge_sfr_f64(const double *img, int B, int H, int W, size_t row_pitch, s
  *            a batch item bit-identical to the same item alone).
  *   score  : [B, N] float64 device or NULL: zero-mean NCC of t(i + d) against the crop at the returned d (0 if either is constant; 1 at ref).
  *   status : [B, N] int device or NULL: 0 ok; 1 singular normal matrix (flat or one-directional content: the coarse shift is kept, never
- *            NaN); 2 coarse argmax on the search boundary; 3 not converged after n_iter steps.
+ *            NaN); 2 coarse argmax on the search boundary; 3 not converged after n_iter steps.  Where several apply the smallest code is
+ *            returned: 1 over 2 over 3.
+ * Held by tests/test_gpu_register_edges.py: n_iter = 0 returns the coarse integer shift and never status 3; tol = 0 never converges, so
+ * with n_iter > 0 it always ends in status 3 unless 1 or 2 applies; c0_k rounds half to even (std::rint: 0.5 -> 0, 1.5 -> 2, 2.5 -> 2,
+ * -3.5 -> -4); |init[k] - init[ref]| <= 1e6 is accepted on both axes -- so far out every sample is the frame's clamped corner, the
+ * window is constant, the score is exactly 0 at every offset and the tie rule alone decides.
  * SRX_E_INVALID: a null frames / shifts, B or size <= 0, N < 2, ref outside [0, N), search outside [0, 4], border < 0, n_iter < 0, tol < 0
  * or NaN, |init[k] - init[ref]| > 1e6.  SRX_E_UNSUPPORTED: a crop smaller than 16 x 16, N > SRX_MAX_FRAMES, B (N - 1) > 65535.
  * Workspace: srx_register_workspace_bytes(sizeof(T), B, N, H, W, search) (0 for arguments no call accepts) covers every border. */
