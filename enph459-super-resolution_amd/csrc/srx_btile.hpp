@@ -511,46 +511,30 @@ __global__ void __launch_bounds__(256) k_btile_copy_out(const float *__restrict_
         if (4 * q + c < H)
             dst[(size_t)(4 * q + c) * W] = v[c];
 }
-// the frame table where the lanes can index it (by-value kernel arguments indexed per lane become a scalar-load loop over the lanes)
-__global__ void k_btile_params(BArgs A, int *__restrict__ dst)
-{
-    const int *src = reinterpret_cast<const int *>(&A.fr[0]);
-    for (int i = threadIdx.x; i < MAXF * 20; i += blockDim.x)
-        dst[i] = src[i];
-}
-// the tables of a call with one per item: the host's records by value, PARAM_WORDS at a time (a launch's arguments are limited to 4 KiB)
-constexpr int PARAM_WORDS = 960;
-struct ParamWords {
-    int n;
-    int w[PARAM_WORDS];
-};
-__global__ void k_param_words(ParamWords P, int *__restrict__ dst)
-{
-    for (int i = threadIdx.x; i < P.n; i += blockDim.x)
-        dst[i] = P.w[i];
-}
-// host side: words put() one after the other land at dst, a launch every PARAM_WORDS of them and one more at finish() for the rest
+// The tables of a call with one per item, too long for one upload_record: words put() one after the other land at dst, a launch of
+// k_put_words every PARAM_WORDS of them and one more at finish() for the rest.  (The call's one frame table, BArgs::fr, goes up whole.)
 struct ParamUpload {
     hipStream_t st;
     int *dst;
-    ParamWords pw = {};  // (what lies past n travels too)
+    Words<PARAM_WORDS> pw = {};  // (what lies past n travels too)
+    int n = 0;
     int flush()
     {
-        hipLaunchKernelGGL(k_param_words, dim3(1), dim3(256), 0, st, pw, dst);
+        hipLaunchKernelGGL(k_put_words<PARAM_WORDS>, dim3(1), dim3(256), 0, st, pw, n, dst);
         SRX_CHECK_LAUNCH();
-        dst += pw.n, pw.n = 0;
+        dst += n, n = 0;
         return SRX_OK;
     }
-    int put(const int *src, int n)
+    int put(const int *src, int count)
     {
-        for (int i = 0; i < n; i++) {
-            pw.w[pw.n++] = src[i];
-            if (pw.n == PARAM_WORDS)
+        for (int i = 0; i < count; i++) {
+            pw.w[n++] = src[i];
+            if (n == PARAM_WORDS)
                 SRX_TRY(flush());
         }
         return SRX_OK;
     }
-    int finish() { return pw.n ? flush() : SRX_OK; }
+    int finish() { return n ? flush() : SRX_OK; }
 };
 
 // window geometry shared by the two kernels
@@ -1059,7 +1043,7 @@ static inline void make_frames(const double *sh, int N, BFrame *fr, int nfr, int
 // step, eight frames 11.5 / 12.1 against 9.6, measured PSF 2.46 / 2.49 against 2.42 -- the six waves' barriers cost more than the idle
 // compute units.  The shape is fixed (BT_NBY x BT_NBX), so a batch gives every item the bits it gets alone.
 // per_item: sh is [B][N][2], one table per item.  The host builds every item's records with make_frames (the weights an item gets are the
-// ones it gets alone by construction) and ceil(B * tab_stride(N) / PARAM_WORDS) launches of k_param_words carry them to the device; the
+// ones it gets alone by construction) and ceil(B * tab_stride(N) / PARAM_WORDS) launches of k_put_words carry them to the device; the
 // workspace holds items_tab_bytes(B, N) more.
 template <int NBY, int NBX> static int ibp_t(const IbpCall<float> &c, bool per_item)
 {
@@ -1118,8 +1102,7 @@ template <int NBY, int NBX> static int ibp_t(const IbpCall<float> &c, bool per_i
     if (n_iter == 0)
         return SRX_OK;
     if (!per_item) {
-        hipLaunchKernelGGL(k_btile_params, dim3(1), dim3(64), 0, st, A, frtab);
-        SRX_CHECK_LAUNCH();
+        SRX_TRY(upload_record(st, frtab, A.fr));
     } else {
         ParamUpload up{st, frtab};
         for (int b = 0; b < B; b++) {

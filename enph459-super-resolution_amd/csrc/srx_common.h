@@ -4,9 +4,11 @@
 #include <stddef.h>
 #include <stdint.h>
 #include <stdlib.h>
+#include <string.h>
 
 #include <atomic>
 #include <mutex>
+#include <type_traits>
 #include <vector>
 
 #include "srx.h"
@@ -258,6 +260,52 @@ static inline hipError_t fill_bytes(void *p, int byte, size_t bytes, hipStream_t
     hipLaunchKernelGGL(k_fill_words, dim3((unsigned)(blocks < 4096 ? (blocks ? blocks : 1) : 4096)), dim3(256), 0, st, (unsigned *)p, nwords, v);
     return hipGetLastError();
 }
+
+// ---- a small host record where lanes can index it ---------------------------------------------------------------------------------
+// A by-value kernel argument indexed per lane compiles to a scalar-load loop over the lanes, so a table the lanes of a hot kernel index
+// (blur weights, frame records, axis maps) lives in device memory.  It gets there as the argument of this kernel, which pays that loop
+// once per call: no host buffer to keep alive, no copy node in a captured graph.  A launch's arguments are limited to 4 KiB:
+// PARAM_WORDS words and the rest of the signature.  grid 1, block 256.
+constexpr int PARAM_WORDS = 960;
+template <int NW> struct Words {
+    int w[NW];
+};
+template <int NW> __global__ void __launch_bounds__(256) k_put_words(Words<NW> v, int n, int *__restrict__ dst)
+{
+    for (int i = threadIdx.x; i < n; i += 256)
+        dst[i] = v.w[i];
+}
+// the bytes of `rec` to dst, one launch
+template <typename R> static int upload_record(hipStream_t st, void *dst, const R &rec)
+{
+    static_assert(std::is_trivially_copyable<R>::value && sizeof(R) % 4 == 0, "the record travels as words");
+    static_assert(sizeof(R) <= 4 * PARAM_WORDS, "the record travels as one launch's arguments");
+    constexpr int NW = (int)(sizeof(R) / 4);
+    Words<NW> v;
+    memcpy(&v, &rec, sizeof(R));
+    hipLaunchKernelGGL(k_put_words<NW>, dim3(1), dim3(256), 0, st, v, NW, (int *)dst);
+    return hipGetLastError() == hipSuccess ? SRX_OK : SRX_E_HIP;
+}
+
+// ---- the two planes and the two sets of MSE partials of an iteration loop that ping-pongs -----------------------------------------
+// Iteration `it` reads plane (it & 1 ? s1 : s0) and writes the other; it leaves its tiles' partial sums in one of ep0 / ep1 and adds up the
+// ones its predecessor left in the other (the closing trace kernel adds up the last).  The PLANES go by the global iteration count `it`,
+// the PARTIALS by the run-local one, j: a plan's later runs (ztile::run) go on from the state at it != 0 while their trace starts at j = 0
+// with no predecessor; a whole call (ctile, dtile) has it == j.  `want`: the call asked for the trace.
+template <typename T> struct PingPong {
+    T *s0, *s1;
+    double *ep0, *ep1;
+    int it;
+    const T *src() const { return (it & 1) ? s1 : s0; }
+    T *dst() const { return (it & 1) ? s0 : s1; }
+    T *cur() const { return (it & 1) ? s1 : s0; }  // the state as it stands: what the next iteration reads
+    void advance() { it++; }
+    double *ep(int j, bool want) const { return want ? ((j & 1) ? ep1 : ep0) : nullptr; }
+    const double *eprev(int j, bool want) const { return j > 0 ? ep(j - 1, want) : nullptr; }
+    const double *last_ep(int n) const { return ep(n - 1, true); }  // of a run of n iterations
+    // where iteration j puts its predecessor's trace in errors[item][n] (item stride n; nothing reads it at j = 0)
+    static double *err_prev(double *errors, int j) { return errors ? errors + j - 1 : nullptr; }
+};
 
 // ---- device helpers -------------------------------------------------------------------
 template <typename T> __device__ __forceinline__ T wave_sum(T v)

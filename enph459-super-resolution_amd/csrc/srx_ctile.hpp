@@ -39,6 +39,11 @@ struct CArgs {
     int exy, exx, nby, nbx, Ey, Ex;
     int WT, LN, TOPN, ngrp;
     double sn;
+    // the frame geometry is srx_ztile.hpp's (frame_geometry); sn: step / N in the kernel's precision
+    static CArgs from_frame(const ztile::ZArgs &za, double sn)
+    {
+        return {za.H, za.W, za.tiles_x, za.tiles_y, za.HP, za.WP, za.exy, za.exx, za.nby, za.nbx, za.Ey, za.Ex, za.WT, za.LN, za.TOPN, za.ngrp, sn};
+    }
 };
 
 template <typename T> struct T2 {
@@ -126,48 +131,7 @@ __global__ void __launch_bounds__(256)
         atomicAnd(&cmok[b], 0);
 }
 
-template <typename T> __device__ __forceinline__ size_t state_off(int b, int row, int col, int HP, int WP)
-{
-    return (size_t)b * (HP + 2) * WP + ((size_t)(row >> 1) * WP + col) * 2 + (row & 1);
-}
-template <typename T>
-__global__ void __launch_bounds__(256) k_ctile_copy_in(const T *__restrict__ src, int H, int W, int HP, int WP, T *__restrict__ dst)
-{
-    const int x = blockIdx.x * 256 + threadIdx.x, y = blockIdx.y, b = blockIdx.z;
-    if (x < W)
-        dst[state_off<T>(b, y + HALO, x + HALO, HP, WP)] = src[((size_t)b * H + y) * W + x];
-}
-template <typename T>
-__global__ void __launch_bounds__(256) k_ctile_copy_out(const T *__restrict__ src, int H, int W, int HP, int WP, T *__restrict__ dst)
-{
-    const int x = blockIdx.x * 256 + threadIdx.x, y = blockIdx.y, b = blockIdx.z;
-    if (x < W)
-        dst[((size_t)b * H + y) * W + x] = src[state_off<T>(b, y + HALO, x + HALO, HP, WP)];
-}
-
-template <typename T>
-__global__ void __launch_bounds__(256)
-    k_ctile_near_m(const T *__restrict__ Mg, const T *__restrict__ Mu, int NB, int PBy, int PBx, ztile::ZArgs za, int NT, T2<T> *__restrict__ Mn)
-{
-    const int t = blockIdx.x * 256 + threadIdx.x, b = blockIdx.y;
-    if (t >= NT)
-        return;
-    int gy, gx;
-    ztile::near_coords(t, za, gy, gx);
-    const int Wg = za.W + 27, Hg = za.H + 27, ni = mosaic::near_index(gy + 13, gx + 13, Wg, PBy, PBx);
-    T2<T> v;
-    v.x = Mg[((size_t)b * Hg + gy + 13) * Wg + gx + 13], v.y = Mu[(size_t)b * NB + ni];
-    Mn[(size_t)b * NT + t] = v;
-}
-
-struct KwTab {
-    double v[32];
-};
-template <typename T> __global__ void k_ctile_kw(KwTab t, T *__restrict__ dst)
-{
-    if (threadIdx.x < 32)
-        dst[threadIdx.x] = (T)t.v[threadIdx.x];
-}
+// (the padded state planes, their copy-in / copy-out and the near band's (M, Mu) pairs are srx_ztile.hpp's, in this kernel's sample type)
 
 // 7-tap correlation down the columns, in registers, zero beyond the region's rows (those outputs are outside every dependency cone
 // that ends in a stored pixel)
@@ -534,55 +498,46 @@ static int iterate(const mosaic::Common<T> &c, const T *hr_init, T *hr, int n_it
     ztile::frame_geometry(za, H, W, VTY, py, px, NS);
     const int HP = za.HP, WP = za.WP;
     za.sn = (float)step / (float)N;
-    CArgs ca;
-    ca.H = H, ca.W = W, ca.tiles_x = za.tiles_x, ca.tiles_y = za.tiles_y, ca.HP = HP, ca.WP = WP;
-    ca.exy = za.exy, ca.exx = za.exx, ca.nby = za.nby, ca.nbx = za.nbx, ca.Ey = za.Ey, ca.Ex = za.Ex;
-    ca.WT = za.WT, ca.LN = za.LN, ca.TOPN = za.TOPN, ca.ngrp = za.ngrp;
-    ca.sn = sizeof(T) == 4 ? (double)((float)step / (float)N) : step / (double)N;
+    const CArgs ca = CArgs::from_frame(za, sizeof(T) == 4 ? (double)((float)step / (float)N) : step / (double)N);
     const ztile::Dims d = ztile::dims_of(B, za);
     const int NT = (int)d.NT, ntiles = (int)d.ntiles;
     const Carved<T> t = carve<T>(ar, d);
     if (!ar.ok)
         return SRX_E_WORKSPACE;
-    T *const s0 = t.s0, *const s1 = t.s1;
-    double *const ep0 = t.ep0, *const ep1 = t.ep1;
-    KwTab kv;
+    PingPong<T> pp = {t.s0, t.s1, t.ep0, t.ep1, 0};
+    T kv[32];
     for (int i = 0; i < 8; i++) {
-        kv.v[i] = i < 7 ? (double)c.kc.cy[i] : 0.0, kv.v[8 + i] = i < 7 ? (double)c.kc.cx[i] : 0.0;
-        kv.v[16 + i] = i < 7 ? (double)c.kt.cy[i] : 0.0, kv.v[24 + i] = i < 7 ? (double)c.kt.cx[i] : 0.0;
+        kv[i] = i < 7 ? c.kc.cy[i] : (T)0, kv[8 + i] = i < 7 ? c.kc.cx[i] : (T)0;
+        kv[16 + i] = i < 7 ? c.kt.cy[i] : (T)0, kv[24 + i] = i < 7 ? c.kt.cx[i] : (T)0;
     }
-    hipLaunchKernelGGL(k_ctile_kw<T>, dim3(1), dim3(64), 0, st, kv, t.kw);
-    SRX_CHECK_LAUNCH();
+    SRX_TRY(upload_record(st, t.kw, kv));
     hipLaunchKernelGGL(k_ctile_prep<T>, dim3(cdiv(WP, 256), HP / 2, B + 1), dim3(256), 0, st, c.Mg, c.Cg, B, H, W, HP, WP, za.nby, za.nbx, t.Mp, t.Cp);
     SRX_CHECK_LAUNCH();
     if (fill_bytes(t.cmok, 0xff, (size_t)B * sizeof(int), st) != hipSuccess)
         return SRX_E_HIP;
     hipLaunchKernelGGL(k_ctile_pack<T>, dim3(cdiv(WP, 256), HP / 4, B), dim3(256), 0, st, t.Mp, t.Cp, HP, WP, t.CM4, t.cmok);
     SRX_CHECK_LAUNCH();
-    hipLaunchKernelGGL(ztile::k_ztile_zero_border<T>, dim3(HP / 2 + 1, B), dim3(256), 0, st, s0, s1, H, W, HP, WP);  // (only what the image does not cover)
+    hipLaunchKernelGGL(ztile::k_ztile_zero_border<T>, dim3(HP / 2 + 1, B), dim3(256), 0, st, pp.s0, pp.s1, H, W, HP, WP);  // (only what the image does not cover)
     SRX_CHECK_LAUNCH();
-    hipLaunchKernelGGL(k_ctile_copy_in<T>, dim3(cdiv(W, 256), H, B), dim3(256), 0, st, hr_init, H, W, HP, WP, s0);
+    hipLaunchKernelGGL(ztile::k_ztile_copy_in<T>, dim3(cdiv(W, 256), H, B), dim3(256), 0, st, hr_init, H, W, HP, WP, pp.s0, 0);
     SRX_CHECK_LAUNCH();
     if (NT > 0) {
         hipLaunchKernelGGL(ztile::k_ztile_near_tab, dim3(cdiv(NT, 256)), dim3(256), 0, st, c.ncu, c.nyx, NS, py.PB, px.PB, za, NT, t.nrec, t.nent);
         SRX_CHECK_LAUNCH();
-        hipLaunchKernelGGL(k_ctile_near_m<T>, dim3(cdiv(NT, 256), B), dim3(256), 0, st, c.Mg, c.Mu, c.NB, py.PB, px.PB, za, NT, t.Mn);
+        hipLaunchKernelGGL((ztile::k_ztile_near_m<T, T2<T>>), dim3(cdiv(NT, 256), B), dim3(256), 0, st, c.Mg, c.Mu, c.NB, py.PB, px.PB, za, NT, t.Mn);
         SRX_CHECK_LAUNCH();
     }
     CTabs<T> tb{t.Mp, t.Cp, t.CM4, t.cmok, t.kw, t.nrec, t.nent, t.Mn};
     const dim3 grid(za.tiles_x, za.tiles_y, B);
-    for (int it = 0; it < n_iter; it++) {
-        const T *src = (it & 1) ? s1 : s0;
-        T *dst = (it & 1) ? s0 : s1;
-        double *ep = errors ? ((it & 1) ? ep1 : ep0) : nullptr;
-        const double *eprev = errors && it > 0 ? ((it & 1) ? ep0 : ep1) : nullptr;
-        SRX_LAUNCH(KID_IBP_CTILE, k_ibp_ctile<T>, grid, dim3(256), 0, st, src, dst, tb, ca, ep, eprev, Vtot, scale, errors ? errors + it - 1 : nullptr, n_iter);
-    }
-    if (errors) {
-        hipLaunchKernelGGL(ztile::k_ztile_trace, dim3(B), dim3(256), 0, st, ((n_iter - 1) & 1) ? ep1 : ep0, ntiles, Vtot, scale, errors + n_iter - 1, n_iter);
+    const bool want = errors != nullptr;
+    for (int j = 0; j < n_iter; j++, pp.advance())
+        SRX_LAUNCH(KID_IBP_CTILE, k_ibp_ctile<T>, grid, dim3(256), 0, st, pp.src(), pp.dst(), tb, ca, pp.ep(j, want), pp.eprev(j, want), Vtot, scale,
+                   pp.err_prev(errors, j), n_iter);
+    if (want) {
+        hipLaunchKernelGGL(ztile::k_ztile_trace, dim3(B), dim3(256), 0, st, pp.last_ep(n_iter), ntiles, Vtot, scale, errors + n_iter - 1, n_iter);
         SRX_CHECK_LAUNCH();
     }
-    hipLaunchKernelGGL(k_ctile_copy_out<T>, dim3(cdiv(W, 256), H, B), dim3(256), 0, st, (n_iter & 1) ? s1 : s0, H, W, HP, WP, hr);
+    hipLaunchKernelGGL(ztile::k_ztile_copy_out<T>, dim3(cdiv(W, 256), H, B), dim3(256), 0, st, pp.cur(), H, W, HP, WP, hr, 0);
     SRX_CHECK_LAUNCH();
     return SRX_OK;
 }

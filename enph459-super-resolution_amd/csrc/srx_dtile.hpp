@@ -789,14 +789,6 @@ __global__ void __launch_bounds__(256)
     }
 }
 
-template <int NSX, bool C01, int PSF = 0>
-static int launch_iter(dim3 grid, hipStream_t st, const float *src, float *dst, const DTabs &tb, const DArgs &da, double *ep, const double *eprev,
-                       const double *Vtot, double scale, double *err_prev, int stride)
-{
-    SRX_LAUNCH(KID_IBP_DTILE, (k_ibp_dtile<C01, NSX, PSF>), grid, dim3(256 * NSX), 0, st, src, dst, tb, da, ep, eprev, Vtot, scale, err_prev, stride);
-    return SRX_OK;
-}
-
 static int iterate(const mosaic::Common<float> &c, const float *hr_init, float *hr, int n_iter, double *errors, Arena &ar, hipStream_t st)
 {
     const int B = c.B, N = c.N, f = c.f, H = c.H, W = c.W, NS = c.NS;
@@ -813,7 +805,7 @@ static int iterate(const mosaic::Common<float> &c, const float *hr_init, float *
         return SRX_E_WORKSPACE;
     const int psf = fused::psf_form(c.kc, c.kt);
     if (psf != 0) {
-        if (pl.nsx != 3)
+        if (pl.nsx != 3 || psf == 3)  // (eligible() keeps full 7 x 7 support on the tile kernels)
             return SRX_E_UNSUPPORTED;
         SRX_TRY(patch::upload_k2(c.kc, c.kt, k2, st));
     }
@@ -832,8 +824,7 @@ static int iterate(const mosaic::Common<float> &c, const float *hr_init, float *
     hipLaunchKernelGGL(k_dtile_setup, dim3(cdiv(std::max(ntiles, 64 * (pl.ty.n + pl.tx.n) * 4), 256)), dim3(256), 0, st, pl.ty, pl.tx, fy, fx, N, f, H, W,
                        pl.nsx, tiles, rowm, colm);
     SRX_CHECK_LAUNCH();
-    hipLaunchKernelGGL(patch::k_patch_params, dim3(1), dim3(1), 0, st, awp, aw);
-    SRX_CHECK_LAUNCH();
+    SRX_TRY(upload_record(st, aw, awp));
     // ---- operand planes, near-band tables, state
     if (fill_bytes(m8, 0xff, (size_t)B * sizeof(int), st) != hipSuccess)
         return SRX_E_HIP;
@@ -847,35 +838,22 @@ static int iterate(const mosaic::Common<float> &c, const float *hr_init, float *
     SRX_CHECK_LAUNCH();
     DTabs tb{Mt, Mt8, m8, Ct, aw, tiles, rowm, colm, nnt, nrec, nent, Mn, ntabs, k2};
     const dim3 grid(ntiles, B);
-    for (int it = 0; it < n_iter; it++) {
-        const float *src = (it & 1) ? s1 : s0;
-        float *dst = (it & 1) ? s0 : s1;
-        double *e = errors ? ((it & 1) ? ep1 : ep0) : nullptr;
-        const double *eprev = errors && it > 0 ? ((it & 1) ? ep0 : ep1) : nullptr;
-        double *eo = errors ? errors + it - 1 : nullptr;
-        int rc;
+    const bool c01 = da.c01 != 0, want = errors != nullptr;
+    const auto kern = pl.nsx == 4 ? (c01 ? k_ibp_dtile<true, 4> : k_ibp_dtile<false, 4>)
+                      : psf == 2  ? (c01 ? k_ibp_dtile<true, 3, 2> : k_ibp_dtile<false, 3, 2>)
+                                  : (c01 ? k_ibp_dtile<true, 3> : k_ibp_dtile<false, 3>);
+    PingPong<float> pp = {s0, s1, ep0, ep1, 0};
+    for (int j = 0; j < n_iter; j++, pp.advance())
+        SRX_LAUNCH(KID_IBP_DTILE, kern, grid, dim3(256 * pl.nsx), 0, st, pp.src(), pp.dst(), tb, da, pp.ep(j, want), pp.eprev(j, want), Vtot, scale,
+                   pp.err_prev(errors, j), n_iter);
+    if (want) {
         if (pl.nsx == 4)
-            rc = da.c01 ? launch_iter<4, true>(grid, st, src, dst, tb, da, e, eprev, Vtot, scale, eo, n_iter)
-                        : launch_iter<4, false>(grid, st, src, dst, tb, da, e, eprev, Vtot, scale, eo, n_iter);
-        else if (psf == 2)
-            rc = da.c01 ? launch_iter<3, true, 2>(grid, st, src, dst, tb, da, e, eprev, Vtot, scale, eo, n_iter)
-                        : launch_iter<3, false, 2>(grid, st, src, dst, tb, da, e, eprev, Vtot, scale, eo, n_iter);
-        else if (psf == 3)
-            rc = SRX_E_UNSUPPORTED;  // (eligible() keeps full 7 x 7 support on the tile kernels)
+            hipLaunchKernelGGL(k_dtile_trace<1024>, dim3(B), dim3(1024), 0, st, pp.last_ep(n_iter), ntiles, Vtot, scale, errors + n_iter - 1, n_iter);
         else
-            rc = da.c01 ? launch_iter<3, true>(grid, st, src, dst, tb, da, e, eprev, Vtot, scale, eo, n_iter)
-                        : launch_iter<3, false>(grid, st, src, dst, tb, da, e, eprev, Vtot, scale, eo, n_iter);
-        SRX_TRY(rc);
-    }
-    if (errors) {
-        const double *last = ((n_iter - 1) & 1) ? ep1 : ep0;
-        if (pl.nsx == 4)
-            hipLaunchKernelGGL(k_dtile_trace<1024>, dim3(B), dim3(1024), 0, st, last, ntiles, Vtot, scale, errors + n_iter - 1, n_iter);
-        else
-            hipLaunchKernelGGL(k_dtile_trace<768>, dim3(B), dim3(768), 0, st, last, ntiles, Vtot, scale, errors + n_iter - 1, n_iter);
+            hipLaunchKernelGGL(k_dtile_trace<768>, dim3(B), dim3(768), 0, st, pp.last_ep(n_iter), ntiles, Vtot, scale, errors + n_iter - 1, n_iter);
         SRX_CHECK_LAUNCH();
     }
-    hipLaunchKernelGGL(k_dtile_copy_out, dim3(cdiv(W, 256), H / 4, B), dim3(256), 0, st, (n_iter & 1) ? s1 : s0, H, W, hr);
+    hipLaunchKernelGGL(k_dtile_copy_out, dim3(cdiv(W, 256), H / 4, B), dim3(256), 0, st, pp.cur(), H, W, hr);
     SRX_CHECK_LAUNCH();
     return SRX_OK;
 }

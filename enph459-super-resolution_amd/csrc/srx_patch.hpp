@@ -305,13 +305,6 @@ struct BuildMaps {
     signed char frame[4][4];  // frame of (row class, column class)
     int nby, nbx;
 };
-__global__ void k_patch_maps(BuildMaps v, BuildMaps *dst)  // (a lane-indexed by-value argument compiles to a scalar-load loop over the lanes)
-{
-    const int *s = reinterpret_cast<const int *>(&v);
-    int *d = reinterpret_cast<int *>(dst);
-    for (int i = threadIdx.x; i < (int)(sizeof(BuildMaps) / 4); i += blockDim.x)
-        d[i] = s[i];
-}
 // grid (PN / 16 bands, B), block 256: wave w takes rows w, w + 4, ... of the band, lane = column quad.
 // PASS 0 writes the BYTE plane of every patch and clears m8[b] (preset non-zero) when a sample it placed is not an integer in [0, 255];
 // PASS 1 writes the float plane of the patches so marked and returns at once for the others.  (Round 4's first form decided with a pass of
@@ -478,22 +471,9 @@ __global__ void __launch_bounds__(256)
 // the parking place of the pre-update state, re-read for the update -- the register file holds the state OR the working
 // plane, not both), reads the LR mosaic (bytes when the patch's samples are uint8) and the near-band descriptors.
 // =========================================================================================================================
-struct AxisWPair {
+struct AxisWPair {  // PatchTabs::aw as the host fills it
     AxisW y, x;
 };
-struct K2Pair {
-    float v[112];
-};
-__global__ void k_patch_k2(K2Pair t, float *__restrict__ dst)
-{
-    if (threadIdx.x < 112)
-        dst[threadIdx.x] = t.v[threadIdx.x];
-}
-__global__ void k_patch_params(AxisWPair v, AxisW *dst)
-{
-    dst[0] = v.y;
-    dst[1] = v.x;
-}
 
 // FORM: 0 rank 1 (7 + 7 taps per blur), 3 full 7 x 7, 2 a 7 x 7 whose outer ring is zero; 1 (with C01 and M8) rank 1 on a grid whose count
 // masks the host found all ones wherever the G step's result is used (gstep_form): the byte-mosaic G loop runs without the mask test.  A
@@ -991,15 +971,13 @@ static inline size_t tabs_bytes(const IbpShape &s, int B)
 static int upload_k2(const fused::Kernel7<float> &kc, const fused::Kernel7<float> &kt, float *k2, hipStream_t st)
 {
     const double kq = -6.0 * ZD;
-    K2Pair kv;
+    float kv[112];
     for (int c = 0; c < 7; c++)
         for (int r = 0; r < 8; r++) {
-            kv.v[8 * c + r] = r < 7 ? (float)(kq * kq * (double)kc.k[7 * r + c]) : 0.f;
-            kv.v[56 + 8 * c + r] = r < 7 ? kt.k[7 * r + c] : 0.f;
+            kv[8 * c + r] = r < 7 ? (float)(kq * kq * (double)kc.k[7 * r + c]) : 0.f;
+            kv[56 + 8 * c + r] = r < 7 ? kt.k[7 * r + c] : 0.f;
         }
-    hipLaunchKernelGGL(k_patch_k2, dim3(1), dim3(128), 0, st, kv, k2);
-    SRX_CHECK_LAUNCH();
-    return SRX_OK;
+    return upload_record(st, k2, kv);
 }
 
 // the iteration loop; the per-call tables (M, C, Mu, near lists, Vtot) are srx_mosaic.hpp's common_prep()'s
@@ -1036,8 +1014,7 @@ static int iterate(const mosaic::Common<float> &c, const float *hr_init, float *
         for (int q = 0; q < N; q++)
             bm.frame[cy[q]][cx[q]] = (signed char)q;
         bm.nby = pa.y.nb, bm.nbx = pa.x.nb;
-        hipLaunchKernelGGL(k_patch_maps, dim3(1), dim3(256), 0, st, bm, maps);
-        SRX_CHECK_LAUNCH();
+        SRX_TRY(upload_record(st, maps, bm));
         if (c.lr_u8) {  // byte frames: the byte plane of every patch and nothing else (m8 keeps its preset: no patch asks for the float plane)
             if (!(c.flags & SRX_FLAG_DIAG_U8_BYTE_LOADS) && c.w % 4 == 0 && nx * c.w <= PN)  // (the column classes' rows fill at most 64 words)
                 SRX_LAUNCH(KID_PATCH_BUILD, (k_patch_build<0, uint8_t, true>), dim3(PN / 16, B), dim3(256), 0, st, (const uint8_t *)c.lr, N, c.h, c.w, maps, m8, Mt, Mt8);
@@ -1066,8 +1043,7 @@ static int iterate(const mosaic::Common<float> &c, const float *hr_init, float *
                                pa.x.nb, pa.nn, Mn);
         SRX_CHECK_LAUNCH();
     }
-    hipLaunchKernelGGL(k_patch_params, dim3(1), dim3(1), 0, st, awp, aw);
-    SRX_CHECK_LAUNCH();
+    SRX_TRY(upload_record(st, aw, awp));
     const int psf = fused::psf_form(c.kc, c.kt);
     if (psf != 0)
         SRX_TRY(upload_k2(c.kc, c.kt, k2, st));

@@ -150,20 +150,22 @@ __global__ void __launch_bounds__(256)
         atomicAnd(&cmok[b], 0);
 }
 
-// state planes: [B][HP / 2 + 1][WP][2] (row pairs interleaved), image at (6, 6).  copy-in (the border was zeroed by a memset) and
-// copy-out.  grid (ceil(W/256), H, B)
-__device__ __forceinline__ size_t state_off(int b, int row, int col, int HP, int WP)
+// state planes: [B][HP / 2 + 1][WP][2] (row pairs interleaved), image at (6, 6), in samples of T (k_ibp_ztile: float; k_ibp_ctile: float
+// or double).  copy-in (the border was zeroed by k_ztile_zero_border) and copy-out.  grid (ceil(W/256), rows, B)
+__device__ __forceinline__ size_t state_off(int b, int row, int col, int HP, int WP)  // (in samples: the same for every T)
 {
     return (size_t)b * (HP + 2) * WP + ((size_t)(row >> 1) * WP + col) * 2 + (row & 1);
 }
 // (image rows [y0, y0 + rows) of the plane <-> a packed [B][rows][W] buffer: the whole image, or the halo rows of a row band)
-__global__ void __launch_bounds__(256) k_ztile_copy_in(const float *__restrict__ src, int rows, int W, int HP, int WP, float *__restrict__ dst, int y0)
+template <typename T>
+__global__ void __launch_bounds__(256) k_ztile_copy_in(const T *__restrict__ src, int rows, int W, int HP, int WP, T *__restrict__ dst, int y0)
 {
     const int x = blockIdx.x * 256 + threadIdx.x, y = blockIdx.y, b = blockIdx.z;
     if (x < W)
         dst[state_off(b, y0 + y + HALO, x + HALO, HP, WP)] = src[((size_t)b * rows + y) * W + x];
 }
-__global__ void __launch_bounds__(256) k_ztile_copy_out(const float *__restrict__ src, int rows, int W, int HP, int WP, float *__restrict__ dst, int y0)
+template <typename T>
+__global__ void __launch_bounds__(256) k_ztile_copy_out(const T *__restrict__ src, int rows, int W, int HP, int WP, T *__restrict__ dst, int y0)
 {
     const int x = blockIdx.x * 256 + threadIdx.x, y = blockIdx.y, b = blockIdx.z;
     if (x < W)
@@ -236,25 +238,21 @@ __global__ void __launch_bounds__(256)
     }
 }
 
+// P: the pair of T the iteration kernel reads Mn as (float2; ctile::T2<T>)
+template <typename T, typename P>
 __global__ void __launch_bounds__(256)
-    k_ztile_near_m(const float *__restrict__ Mg, const float *__restrict__ Mu, int NB, int PBy, int PBx, ZArgs za, int NT, float2 *__restrict__ Mn)
+    k_ztile_near_m(const T *__restrict__ Mg, const T *__restrict__ Mu, int NB, int PBy, int PBx, ZArgs za, int NT, P *__restrict__ Mn)
 {
-    const int T = blockIdx.x * 256 + threadIdx.x, b = blockIdx.y;
-    if (T >= NT)
+    static_assert(sizeof(P) == 2 * sizeof(T), "a pair of samples");
+    const int t = blockIdx.x * 256 + threadIdx.x, b = blockIdx.y;
+    if (t >= NT)
         return;
     int gy, gx;
-    near_coords(T, za, gy, gx);
+    near_coords(t, za, gy, gx);
     const int Wg = za.W + 27, Hg = za.H + 27, ni = mosaic::near_index(gy + 13, gx + 13, Wg, PBy, PBx);
-    Mn[(size_t)b * NT + T] = make_float2(Mg[((size_t)b * Hg + gy + 13) * Wg + gx + 13], Mu[(size_t)b * NB + ni]);
-}
-
-struct K2Tab {
-    float v[112];
-};
-__global__ void k_ztile_k2(K2Tab t, float *__restrict__ dst)
-{
-    if (threadIdx.x < 112)
-        dst[threadIdx.x] = t.v[threadIdx.x];
+    P v;
+    v.x = Mg[((size_t)b * Hg + gy + 13) * Wg + gx + 13], v.y = Mu[(size_t)b * NB + ni];
+    Mn[(size_t)b * NT + t] = v;
 }
 
 // MSE trace: sum of the tiles' partial sums of one iteration, fixed order.  grid B, block 256
@@ -688,14 +686,12 @@ static inline size_t tabs_bytes(const IbpShape &s, int B)
 struct State {
     ZArgs za;
     ZTabs tb;
-    float *s0, *s1;      // the two padded state planes; iteration `it` reads (it & 1 ? s1 : s0)
-    double *ep0, *ep1;   // per-tile MSE partials, alternating
+    PingPong<float> pp;  // the two padded state planes, the per-tile MSE partials, the iterations run so far
     const double *Vtot;
     double scale;
-    int B, ntiles, it;
+    int B, ntiles;
     bool sep;
     int psf;  // k_ibp_ztile's PSF form: 0 rank 1, 2 the 5 x 5 core of a 7 x 7, 3 full 7 x 7
-    float *cur() const { return (it & 1) ? s1 : s0; }
 };
 
 static int setup(State &zs, const mosaic::Common<float> &c, const float *hr_init, int tr_lo, int tr_hi, Arena &ar, hipStream_t st)
@@ -717,16 +713,14 @@ static int setup(State &zs, const mosaic::Common<float> &c, const float *hr_init
         awp.y.kb[i] = i < 7 ? c.kc.cy[i] : 0.f, awp.y.kt[i] = i < 7 ? c.kt.cy[i] : 0.f, awp.y.wfb[i] = 0.f;
         awp.x.kb[i] = i < 7 ? c.kc.cx[i] : 0.f, awp.x.kt[i] = i < 7 ? c.kt.cx[i] : 0.f, awp.x.wfb[i] = 0.f;
     }
-    hipLaunchKernelGGL(patch::k_patch_params, dim3(1), dim3(1), 0, st, awp, t.aw);
-    SRX_CHECK_LAUNCH();
+    SRX_TRY(upload_record(st, t.aw, awp));
     zs.psf = fused::psf_form(c.kc, c.kt);
     if (!c.sep) {
-        K2Tab kv;
+        float kv[112];
         for (int u = 0; u < 7; u++)
             for (int v = 0; v < 8; v++)
-                kv.v[8 * u + v] = v < 7 ? c.kc.k[7 * u + v] : 0.f, kv.v[56 + 8 * u + v] = v < 7 ? c.kt.k[7 * u + v] : 0.f;
-        hipLaunchKernelGGL(k_ztile_k2, dim3(1), dim3(128), 0, st, kv, t.k2);
-        SRX_CHECK_LAUNCH();
+                kv[8 * u + v] = v < 7 ? c.kc.k[7 * u + v] : 0.f, kv[56 + 8 * u + v] = v < 7 ? c.kt.k[7 * u + v] : 0.f;
+        SRX_TRY(upload_record(st, t.k2, kv));
     }
     hipLaunchKernelGGL(k_ztile_prep, dim3(cdiv(WP, 32), cdiv(HP, 32), B + 1), dim3(32, 8), 0, st, c.Mg, c.Cg, B, H, W, HP, WP, za.nby, za.nbx, t.Mt, t.Ct);
     SRX_CHECK_LAUNCH();
@@ -737,16 +731,17 @@ static int setup(State &zs, const mosaic::Common<float> &c, const float *hr_init
     // padded state planes: zero borders (and trash rows) once, then the image
     hipLaunchKernelGGL(k_ztile_zero_border<float>, dim3(HP / 2 + 1, B), dim3(256), 0, st, t.s0, t.s1, H, W, HP, WP);
     SRX_CHECK_LAUNCH();
-    hipLaunchKernelGGL(k_ztile_copy_in, dim3(cdiv(W, 256), H, B), dim3(256), 0, st, hr_init, H, W, HP, WP, t.s0, 0);
+    hipLaunchKernelGGL(k_ztile_copy_in<float>, dim3(cdiv(W, 256), H, B), dim3(256), 0, st, hr_init, H, W, HP, WP, t.s0, 0);
     SRX_CHECK_LAUNCH();
     if (NT > 0) {
         hipLaunchKernelGGL(k_ztile_near_tab, dim3(cdiv(NT, 256)), dim3(256), 0, st, c.ncu, c.nyx, NS, py.PB, px.PB, za, NT, t.nrec, t.nent);
         SRX_CHECK_LAUNCH();
-        hipLaunchKernelGGL(k_ztile_near_m, dim3(cdiv(NT, 256), B), dim3(256), 0, st, c.Mg, c.Mu, c.NB, py.PB, px.PB, za, NT, t.Mn);
+        hipLaunchKernelGGL((k_ztile_near_m<float, float2>), dim3(cdiv(NT, 256), B), dim3(256), 0, st, c.Mg, c.Mu, c.NB, py.PB, px.PB, za, NT, t.Mn);
         SRX_CHECK_LAUNCH();
     }
     zs.tb = ZTabs{t.Mt, t.Ct, t.CM, t.cmok, t.aw, t.k2, t.nrec, t.nent, t.Mn};
-    zs.s0 = t.s0, zs.s1 = t.s1, zs.ep0 = t.ep0, zs.ep1 = t.ep1, zs.Vtot = c.Vtot, zs.scale = c.scale, zs.B = B, zs.ntiles = ntiles, zs.it = 0, zs.sep = c.sep;
+    zs.pp = {t.s0, t.s1, t.ep0, t.ep1, 0};
+    zs.Vtot = c.Vtot, zs.scale = c.scale, zs.B = B, zs.ntiles = ntiles, zs.sep = c.sep;
     return SRX_OK;
 }
 
@@ -754,25 +749,16 @@ static int setup(State &zs, const mosaic::Common<float> &c, const float *hr_init
 static int run(State &zs, int n, double *errors, hipStream_t st)
 {
     const ZArgs &za = zs.za;
+    PingPong<float> &pp = zs.pp;
+    const bool want = errors != nullptr;
+    const auto kern = zs.psf == 0 ? k_ibp_ztile<0> : zs.psf == 2 ? k_ibp_ztile<2> : k_ibp_ztile<3>;
     // ping-pong between the two padded planes (a tile reads its neighbours' pixels of the previous iteration)
     const dim3 grid(za.tiles_x, za.tiles_y, zs.B);
-    for (int j = 0; j < n; j++, zs.it++) {
-        const float *src = (zs.it & 1) ? zs.s1 : zs.s0;
-        float *dst = (zs.it & 1) ? zs.s0 : zs.s1;
-        double *ep = errors ? ((j & 1) ? zs.ep1 : zs.ep0) : nullptr;
-        const double *eprev = errors && j > 0 ? ((j & 1) ? zs.ep0 : zs.ep1) : nullptr;  // the partial sums iteration j - 1 left
-        if (zs.psf == 0)
-            SRX_LAUNCH(KID_IBP_ZTILE, k_ibp_ztile<0>, grid, dim3(256 * NSY), 0, st, src, dst, zs.tb, za, ep, eprev, zs.Vtot, zs.scale,
-                       errors ? errors + j - 1 : nullptr, n);
-        else if (zs.psf == 2)
-            SRX_LAUNCH(KID_IBP_ZTILE, k_ibp_ztile<2>, grid, dim3(256 * NSY), 0, st, src, dst, zs.tb, za, ep, eprev, zs.Vtot, zs.scale,
-                       errors ? errors + j - 1 : nullptr, n);
-        else
-            SRX_LAUNCH(KID_IBP_ZTILE, k_ibp_ztile<3>, grid, dim3(256 * NSY), 0, st, src, dst, zs.tb, za, ep, eprev, zs.Vtot, zs.scale,
-                       errors ? errors + j - 1 : nullptr, n);
-    }
-    if (errors && n > 0) {
-        hipLaunchKernelGGL(k_ztile_trace, dim3(zs.B), dim3(256), 0, st, ((n - 1) & 1) ? zs.ep1 : zs.ep0, zs.ntiles, zs.Vtot, zs.scale, errors + n - 1, n);
+    for (int j = 0; j < n; j++, pp.advance())
+        SRX_LAUNCH(KID_IBP_ZTILE, kern, grid, dim3(256 * NSY), 0, st, pp.src(), pp.dst(), zs.tb, za, pp.ep(j, want), pp.eprev(j, want), zs.Vtot, zs.scale,
+                   pp.err_prev(errors, j), n);
+    if (want && n > 0) {
+        hipLaunchKernelGGL(k_ztile_trace, dim3(zs.B), dim3(256), 0, st, pp.last_ep(n), zs.ntiles, zs.Vtot, zs.scale, errors + n - 1, n);
         SRX_CHECK_LAUNCH();
     }
     return SRX_OK;
@@ -781,13 +767,13 @@ static int run(State &zs, int n, double *errors, hipStream_t st)
 // image rows [y0, y0 + rows) of the current state -> / <- a packed [B][rows][W] buffer
 static int rows_out(const State &zs, int y0, int rows, float *dst, hipStream_t st)
 {
-    hipLaunchKernelGGL(k_ztile_copy_out, dim3(cdiv(zs.za.W, 256), rows, zs.B), dim3(256), 0, st, zs.cur(), rows, zs.za.W, zs.za.HP, zs.za.WP, dst, y0);
+    hipLaunchKernelGGL(k_ztile_copy_out<float>, dim3(cdiv(zs.za.W, 256), rows, zs.B), dim3(256), 0, st, zs.pp.cur(), rows, zs.za.W, zs.za.HP, zs.za.WP, dst, y0);
     SRX_CHECK_LAUNCH();
     return SRX_OK;
 }
 static int rows_in(const State &zs, int y0, int rows, const float *src, hipStream_t st)
 {
-    hipLaunchKernelGGL(k_ztile_copy_in, dim3(cdiv(zs.za.W, 256), rows, zs.B), dim3(256), 0, st, src, rows, zs.za.W, zs.za.HP, zs.za.WP, zs.cur(), y0);
+    hipLaunchKernelGGL(k_ztile_copy_in<float>, dim3(cdiv(zs.za.W, 256), rows, zs.B), dim3(256), 0, st, src, rows, zs.za.W, zs.za.HP, zs.za.WP, zs.pp.cur(), y0);
     SRX_CHECK_LAUNCH();
     return SRX_OK;
 }

@@ -115,6 +115,29 @@ def test_btile_per_item(psf_name):
     np.testing.assert_allclose(e[2].cpu().numpy(), err_o, rtol=ERR_RTOL["f32"])
 
 
+def test_btile_per_item_tables_longer_than_one_upload():
+    """An item's table is 4 + 20 N words and one parameter launch carries 960: with N = 4 (84 words) eleven items fit (924) and twelve do
+    not (1008), so B = 12 is the smallest batch whose tables go up in two launches, item 11's record split between them.  The smallest
+    frame "btile" takes (32 x 32 HR); the per-item contract as above."""
+    prec, f, h, w, n_iter, B, N = "f32", 2, 16, 16, 2, 12, 4
+    words = 4 + 20 * N
+    assert (B - 1) * words <= 960 < B * words
+    psf = synth.gaussian_psf()
+    tables = np.stack([jitter(M4, 40 + b) for b in range(B)])
+    for t in tables:
+        assert path_for(prec, t, psf, h, w, f) == "btile"
+    lr = frames(B, N, h, w, prec, seed=6)
+    hr0 = start_image(lr, tables, f, prec)
+    ref_hr, ref_e, names = one_by_one(lr, tables, psf, hr0, f, n_iter, prec)
+    assert names == ["btile"] * B
+    hr, e = S.ibp_batched(lr, tables, psf, hr0, f, n_iter, 0.5, precision=prec)
+    assert S.last_path() == "btile"
+    for b in range(B):
+        assert torch.equal(hr[b], ref_hr[b]), f"item {b}: max |d| = {float((hr[b] - ref_hr[b]).abs().max())}"
+        assert torch.equal(e[b], ref_e[b]), (b, e[b], ref_e[b])
+    assert not torch.equal(hr[10], hr[11])
+
+
 # ---- 2. mixed routes --------------------------------------------------------------------------------------------------------------
 def test_mixed_routes():
     prec, f, h, w, n_iter = "f32", 2, 64, 80, 3
