@@ -587,8 +587,7 @@ template <> struct TileCfg<double> { static constexpr int R = 23, T_HR = 64; };
 constexpr int WALK_U = 8;  // steps of a walk unrolled together
 // boundary-condition flags of a walk (default 0 = SciPy 'reflect' at a true array end, what shift(mode='nearest') uses on its
 // pre-padded array): the line starts / ends at a true array end whose condition is 'mirror' (zoom's prefilter)
-#define SRX_BC_MIRROR_LO 1
-#define SRX_BC_MIRROR_HI 2
+constexpr int BC_MIRROR_LO = 1, BC_MIRROR_HI = 2;
 template <typename T> struct WalkState {
     T prev;        // causal state p[i-1] = c+[i-1] / 6
     T g0, g1, g2;  // MODE 1: the three newest FIR inputs
@@ -685,7 +684,7 @@ __device__ __forceinline__ void causal_begin(const T *__restrict__ line, int n, 
         if (MODE == 1)
             v0 = w0 * line[0] + w1 * line[S] + w2 * line[2 * S] + w3 * line[3 * S];
         st.prev = v0 / ((T)1 - z);
-    } else if (MODE == 0 && (bc & SRX_BC_MIRROR_LO)) {
+    } else if (MODE == 0 && (bc & BC_MIRROR_LO)) {
         // 'mirror' start (whole-sample symmetric, scipy.ndimage.zoom's prefilter): c+[0] = sum_i z^i 6 v[i], so the state
         // before sample 0 is sum_{i>=1} z^(i-1) v[i]  (lines of >= 64 samples: the far-end terms z^n vanish)
         T zi = 1, acc = 0;
@@ -722,7 +721,7 @@ template <typename T, int S, int MODE>
 __device__ __forceinline__ T anticausal_end(const T *__restrict__ line, int n, T p_last, int bc)
 {
     const T z = pole<T>();
-    if (MODE == 0 && (bc & SRX_BC_MIRROR_HI) && n >= 2)
+    if (MODE == 0 && (bc & BC_MIRROR_HI) && n >= 2)
         return ((T)6 * p_last - line[(n - 2) * S]) * (z / (z * z - (T)1));  // (z c+[n-2] + c+[n-1]) z / (z^2 - 1)
     return p_last * ((T)6 * z / (z - (T)1));
 }
@@ -743,75 +742,89 @@ __device__ __forceinline__ void walk_line(T *__restrict__ line, int n_in, bool e
     anticausal_run<T, S, MODE>(line, n - 2, need_lo, st, w0, w1, w2, w3);
 }
 
-// The same pass over `nlines` (<= 128) lines with TWO threads per line (256-thread block, barriers inside): thread
-// (line, seg) owns outputs [0, mid) or [mid, n).  The second half starts its causal recursion R samples early and
-// the first half its anticausal recursion R samples late, both from values pre-loaded into registers before the
-// other half may overwrite them -- the same |z|^R start-up error the tile edges already have.  Halves the serial
-// chain, which is what bounds this phase (2 of a block's 4 waves used to walk, 2 idled at the barrier).
-template <typename T, int S, int MODE, int R>
-__device__ __forceinline__ void walk_pass_2seg(T *__restrict__ base, int line_pitch, int nlines, int n_in, bool edge,
-                                               const T *__restrict__ w, int tid, int need_lo = 0, int bc = 0)
+constexpr int WALK_NT = 256;  // the block size walk_pass assumes
+
+// Whether a pass may give NSEG (2 or 4) threads to a line (block-uniform); if not, walk_pass halves NSEG.
+//   2: the cut needs R <= mid <= n - R with mid a multiple of 8 (and 8 outputs before it for MODE 1's register tail)
+//   4: the cuts need lo_1 >= R, hi_2 + R <= n and quarters of at least 8 outputs: all hold for n - need_lo >= 4 (R + 8);
+//      a wave per quarter serves 64 lines
+template <int R, int NSEG> __device__ __forceinline__ bool walk_splits(int nlines, int n, int need_lo)
 {
-    constexpr int O = MODE == 1 ? 3 : 0;
-    const T z = pole<T>(), kq = (T)-6 * z;
+    if (NSEG == 2)
+        return ((R + 7) & ~7) <= ((n - R) & ~7);
+    return nlines <= 64 && n - need_lo >= 4 * (R + 8);
+}
+
+// The outputs [lo, hi) of segment `seg` of NSEG, cut at multiples of 8.  Outputs below need_lo (block-uniform) are read by nobody:
+// the first segment's anticausal recursion stops there.
+//   2: the cut balances the two halves' instruction counts (x2: plain step 5, step with the FIR 13, warm-up step 4):
+//      first : causal [0, mid) + R warm-up + anticausal [need_lo, mid);   second: R warm-up + causal and anticausal [mid, n)
+//   4: quarters of the part somebody reads, [need_lo, n); the first one also carries [0, need_lo)
+template <int MODE, int R, int NSEG> __device__ __forceinline__ void walk_cuts(int n, int need_lo, int seg, int &lo, int &hi)
+{
+    if (NSEG == 2) {
+        constexpr int WC = MODE == 1 ? 13 : 5, WA = MODE == 2 ? 13 : 5, WW = MODE == 1 ? 13 : 4;
+        int mid = (((WW - 4) * R + (WC + WA) * n + WA * need_lo) / (2 * (WC + WA)) + 4) & ~7;
+        mid = min(max(mid, (R + 7) & ~7), (n - R) & ~7);
+        lo = seg == 0 ? 0 : mid, hi = seg == 0 ? mid : n;
+    } else {
+        const int span = n - need_lo;
+        lo = seg == 0 ? 0 : (need_lo + span * seg / NSEG) & ~7;
+        hi = seg == NSEG - 1 ? n : (need_lo + span * (seg + 1) / NSEG) & ~7;
+    }
+}
+
+// The same pass over `nlines` lines with NSEG threads per line (a block of WALK_NT threads, barriers inside): WALK_NT / NSEG lines
+// a pass, thread (line, seg) owns outputs [lo_seg, hi_seg) (walk_cuts), seg is wave-uniform.  A segment but the first starts its
+// causal recursion R samples early and a segment but the last its anticausal recursion R samples late, both from values pre-loaded
+// into registers before a neighbour may overwrite them -- the same |z|^R start-up error the tile edges already have.  Divides the
+// serial chain, which is what bounds this phase: n/2 + R steps on two of a block's four waves, n/4 + R on all four (lane = line).
+// Too short or too many lines for NSEG (walk_splits): NSEG / 2, down to walk_line and one barrier.
+template <typename T, int S, int MODE, int R, int NSEG>
+__device__ __forceinline__ void walk_pass(T *__restrict__ base, int line_pitch, int nlines, int n_in, bool edge,
+                                          const T *__restrict__ w, int tid, int need_lo = 0, int bc = 0)
+{
+    static_assert(NSEG == 1 || NSEG == 2 || NSEG == 4, "one, two or four threads per line");
+    constexpr int O = MODE == 1 ? 3 : 0, LINES = WALK_NT / NSEG;
     const int n = MODE == 1 ? n_in - 3 : n_in;
-    const T w0 = MODE ? w[0] : (T)0, w1 = MODE ? w[1] : (T)0, w2 = MODE ? w[2] : (T)0, w3 = MODE ? w[3] : (T)0;
-    const int lineid = tid & 127, seg = tid >> 7;
-    const bool active = lineid < nlines;
+    const int lineid = tid & (LINES - 1), seg = __builtin_amdgcn_readfirstlane(tid / LINES);
+    const bool active = lineid < nlines, first = seg == 0, last = NSEG == 2 ? !first : seg == NSEG - 1;
     T *line = base + (active ? lineid : 0) * line_pitch;
-    // the cut needs R <= mid <= n - R with mid a multiple of 8 (and 8 outputs before it for MODE 1's register tail)
-    if (((R + 7) & ~7) > ((n - R) & ~7)) {  // too short to split (block-uniform): one thread per line
-        if (active && seg == 0)
+    if constexpr (NSEG == 1) {
+        if (active)
             walk_line<T, S, MODE>(line, n_in, edge, w, need_lo, bc);
         __syncthreads();
-        return;
-    }
-    // Outputs below need_lo (block-uniform) are read by nobody: the first half's anticausal recursion stops there.
-    // The cut balances the two halves' instruction counts (x2: plain step 5, step with the FIR 13, warm-up step 4):
-    //   first : causal [0, mid) + R warm-up + anticausal [need_lo, mid);   second: R warm-up + causal and anticausal [mid, n)
-    constexpr int WC = MODE == 1 ? 13 : 5, WA = MODE == 2 ? 13 : 5, WW = MODE == 1 ? 13 : 4;
-    int mid = (((WW - 4) * R + (WC + WA) * n + WA * need_lo) / (2 * (WC + WA)) + 4) & ~7;
-    mid = min(max(mid, (R + 7) & ~7), (n - R) & ~7);
-    WalkState<T> st;
-    st.g0 = st.g1 = st.g2 = 0;
-    T pre[R + 3];
-    // ---- A: inputs the other half is about to overwrite ----
-    if (seg == 1) {
+    } else if (!walk_splits<R, NSEG>(nlines, n, need_lo)) {
+        walk_pass<T, S, MODE, R, NSEG / 2>(base, line_pitch, nlines, n_in, edge, w, tid, need_lo, bc);
+    } else {
+        const T z = pole<T>(), kq = (T)-6 * z;
+        const T w0 = MODE ? w[0] : (T)0, w1 = MODE ? w[1] : (T)0, w2 = MODE ? w[2] : (T)0, w3 = MODE ? w[3] : (T)0;
+        int lo, hi;
+        walk_cuts<MODE, R, NSEG>(n, need_lo, seg, lo, hi);
+        // the pre-loads of two threads per line run on the clamped line pointer, those of four under `active`
+        const bool loads = NSEG == 2 || active;
+        WalkState<T> st;
+        st.g0 = st.g1 = st.g2 = 0;
+        // pre: the R (+ 3) samples of a warm-up; post: MODE 1's three look-ahead inputs.  With two threads per line no thread holds
+        // both, and post takes pre's registers (3 VGPRs less in k_saa_shift and k_bwd_mosaic than with an array of its own)
+        T pre[R + 3], post4[3], *post = NSEG == 2 ? pre : post4;
+        // ---- A: inputs a neighbouring segment is about to overwrite ----
+        if (loads && !first) {
 #pragma unroll
-        for (int j = 0; j < R + O; j++)
-            pre[j] = line[(mid - R + j) * S];
-    } else if (MODE == 1) {
+            for (int j = 0; j < R + O; j++)
+                pre[j] = line[(lo - R + j) * S];
+        }
+        if (MODE == 1 && loads && !last) {
 #pragma unroll
-        for (int j = 0; j < 3; j++)
-            pre[j] = line[(mid + j) * S];
-    }
-    __syncthreads();
-    // ---- B: causal ----
-    if (active) {
-        if (seg == 0) {
-            causal_begin<T, S, MODE>(line, n, edge, st, w0, w1, w2, w3, bc);
-            causal_run<T, S, MODE>(line, 0, mid - 8, st, w0, w1, w2, w3);
-            // last 8 outputs: for MODE 1 the three newest FIR inputs come from registers
-            T x[8];
-#pragma unroll
-            for (int u = 0; u < 8; u++)
-                x[u] = (MODE == 1 && u >= 5) ? pre[u - 5] : line[(mid - 8 + u + O) * S];
-#pragma unroll
-            for (int u = 0; u < 8; u++) {
-                T v = x[u];
-                if (MODE == 1) {
-                    v = w0 * st.g0 + w1 * st.g1 + w2 * st.g2 + w3 * x[u];
-                    st.g0 = st.g1, st.g1 = st.g2, st.g2 = x[u];
-                }
-                st.prev = v + z * st.prev;
-                x[u] = kq * st.prev;
-            }
-#pragma unroll
-            for (int u = 0; u < 8; u++)
-                line[(mid - 8 + u) * S] = x[u];
-        } else {
-            // warm-up over the R pre-loaded samples [mid-R, mid), steady-state start
-            if (MODE == 1) {
+            for (int j = 0; j < 3; j++)
+                post[j] = line[(hi + j) * S];
+        }
+        __syncthreads();
+        // ---- B: causal ----
+        if (active) {
+            if (first) {
+                causal_begin<T, S, MODE>(line, n, edge, st, w0, w1, w2, w3, bc);
+            } else if (MODE == 1) {  // warm-up over the R pre-loaded samples [lo-R, lo), steady-state start
                 st.g0 = pre[0], st.g1 = pre[1], st.g2 = pre[2];
                 st.prev = (w0 * pre[0] + w1 * pre[1] + w2 * pre[2] + w3 * pre[3]) / ((T)1 - z);
 #pragma unroll
@@ -826,147 +839,57 @@ __device__ __forceinline__ void walk_pass_2seg(T *__restrict__ base, int line_pi
                 for (int j = 0; j < R; j++)
                     st.prev = pre[j] + z * st.prev;
             }
-            causal_run<T, S, MODE>(line, mid, n, st, w0, w1, w2, w3);
-        }
-    }
-    __syncthreads();
-    // ---- C: the first half pre-loads c+[mid, mid+R) before the second half overwrites it ----
-    if (seg == 0) {
+            if (MODE == 1 && !last) {
+                causal_run<T, S, MODE>(line, lo, hi - 8, st, w0, w1, w2, w3);
+                T x[8];  // last 8 outputs: the three newest FIR inputs come from registers
 #pragma unroll
-        for (int j = 0; j < R; j++)
-            pre[j] = line[(mid + j) * S];
-    }
-    __syncthreads();
-    // ---- D: anticausal ----
-    if (active) {
-        if (seg == 1) {
-            st.next = anticausal_end<T, S, MODE>(line, n, st.prev, bc);
-            st.a1 = st.next, st.a2 = 0, st.a3 = 0;
-            if (MODE != 2)
-                line[(n - 1) * S] = st.next;
-            anticausal_run<T, S, MODE>(line, n - 2, mid, st, w0, w1, w2, w3);
-        } else {
-            st.next = pre[R - 1] / ((T)1 - z);  // pre holds q = -z c+:  c+ z / (z - 1) = q / (1 - z)
-            st.a1 = st.next, st.a2 = 0, st.a3 = 0;
+                for (int u = 0; u < 8; u++)
+                    x[u] = u >= 5 ? post[u - 5] : line[(hi - 8 + u + O) * S];
 #pragma unroll
-            for (int j = R - 2; j >= 0; j--) {
-                st.next = z * st.next + pre[j];
-                st.a3 = st.a2, st.a2 = st.a1, st.a1 = st.next;
+                for (int u = 0; u < 8; u++) {
+                    const T v = w0 * st.g0 + w1 * st.g1 + w2 * st.g2 + w3 * x[u];
+                    st.g0 = st.g1, st.g1 = st.g2, st.g2 = x[u];
+                    st.prev = v + z * st.prev;
+                    x[u] = kq * st.prev;
+                }
+#pragma unroll
+                for (int u = 0; u < 8; u++)
+                    line[(hi - 8 + u) * S] = x[u];
+            } else {
+                causal_run<T, S, MODE>(line, lo, hi, st, w0, w1, w2, w3);
             }
-            anticausal_run<T, S, MODE>(line, mid - 1, need_lo, st, w0, w1, w2, w3);
         }
-    }
-    __syncthreads();
-}
-
-// The same pass when there are at most 64 lines: FOUR threads per line, one WAVE per quarter (lane = line), so all four
-// waves of the block walk instead of two and the serial chain is n/4 + R steps instead of n/2 + R.  Quarter s owns outputs
-// [lo_s, hi_s); it starts its causal recursion R samples early and its anticausal recursion R samples late from values
-// pre-loaded into registers before a neighbour may overwrite them, as in walk_pass_2seg.  Falls back to walk_pass_2seg
-// for more lines or short lines (block-uniform).
-template <typename T, int S, int MODE, int R>
-__device__ __forceinline__ void walk_pass_4seg(T *__restrict__ base, int line_pitch, int nlines, int n_in, bool edge,
-                                               const T *__restrict__ w, int tid, int need_lo = 0)
-{
-    constexpr int O = MODE == 1 ? 3 : 0;
-    const int n = MODE == 1 ? n_in - 3 : n_in;
-    // the cuts need lo_1 >= R, hi_2 + R <= n and quarters of at least 8 outputs: all hold for n - need_lo >= 4 (R + 8)
-    if (nlines > 64 || n - need_lo < 4 * (R + 8)) {
-        walk_pass_2seg<T, S, MODE, R>(base, line_pitch, nlines, n_in, edge, w, tid, need_lo);
-        return;
-    }
-    const T z = pole<T>(), zfin = z / (z - (T)1), kq = (T)-6 * z;
-    const T w0 = MODE ? w[0] : (T)0, w1 = MODE ? w[1] : (T)0, w2 = MODE ? w[2] : (T)0, w3 = MODE ? w[3] : (T)0;
-    const int seg = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
-    const bool active = lane < nlines, first = seg == 0, last = seg == 3;
-    T *line = base + (active ? lane : 0) * line_pitch;
-    // quarters of the part somebody reads, [need_lo, n), cut at multiples of 8; the first one also carries [0, need_lo)
-    const int span = n - need_lo;
-    const int lo = first ? 0 : (need_lo + span * seg / 4) & ~7;
-    const int hi = last ? n : (need_lo + span * (seg + 1) / 4) & ~7;
-    WalkState<T> st;
-    st.g0 = st.g1 = st.g2 = 0;
-    T pre[R + 3], post[3];
-    // ---- A: inputs a neighbouring quarter is about to overwrite ----
-    if (active && !first) {
-#pragma unroll
-        for (int j = 0; j < R + O; j++)
-            pre[j] = line[(lo - R + j) * S];
-    }
-    if (MODE == 1 && active && !last) {
-#pragma unroll
-        for (int j = 0; j < 3; j++)
-            post[j] = line[(hi + j) * S];
-    }
-    __syncthreads();
-    // ---- B: causal ----
-    if (active) {
-        if (first) {
-            causal_begin<T, S, MODE>(line, n, edge, st, w0, w1, w2, w3);
-        } else if (MODE == 1) {  // warm-up over the R pre-loaded samples [lo-R, lo), steady-state start
-            st.g0 = pre[0], st.g1 = pre[1], st.g2 = pre[2];
-            st.prev = (w0 * pre[0] + w1 * pre[1] + w2 * pre[2] + w3 * pre[3]) / ((T)1 - z);
-#pragma unroll
-            for (int j = 0; j < R; j++) {
-                const T v = w0 * st.g0 + w1 * st.g1 + w2 * st.g2 + w3 * pre[j + 3];
-                st.g0 = st.g1, st.g1 = st.g2, st.g2 = pre[j + 3];
-                st.prev = v + z * st.prev;
-            }
-        } else {
-            st.prev = pre[0] / ((T)1 - z);
+        __syncthreads();
+        // ---- C: q[hi, hi+R) (= -z c+) before the next segment's anticausal pass overwrites it ----
+        if (loads && !last) {
 #pragma unroll
             for (int j = 0; j < R; j++)
-                st.prev = pre[j] + z * st.prev;
+                pre[j] = line[(hi + j) * S];
         }
-        if (MODE == 1 && !last) {
-            causal_run<T, S, MODE>(line, lo, hi - 8, st, w0, w1, w2, w3);
-            T x[8];  // last 8 outputs: the three newest FIR inputs come from registers
+        __syncthreads();
+        // ---- D: anticausal ----
+        if (active) {
+            if (last) {
+                st.next = anticausal_end<T, S, MODE>(line, n, st.prev, bc);
+                st.a1 = st.next, st.a2 = 0, st.a3 = 0;
+                if (MODE != 2)
+                    line[(n - 1) * S] = st.next;
+                anticausal_run<T, S, MODE>(line, n - 2, lo, st, w0, w1, w2, w3);
+            } else {
+                st.next = pre[R - 1] / ((T)1 - z);  // pre holds q = -z c+:  c+ z / (z - 1) = q / (1 - z)
+                st.a1 = st.next, st.a2 = 0, st.a3 = 0;
 #pragma unroll
-            for (int u = 0; u < 8; u++)
-                x[u] = u >= 5 ? post[u - 5] : line[(hi - 8 + u + O) * S];
-#pragma unroll
-            for (int u = 0; u < 8; u++) {
-                const T v = w0 * st.g0 + w1 * st.g1 + w2 * st.g2 + w3 * x[u];
-                st.g0 = st.g1, st.g1 = st.g2, st.g2 = x[u];
-                st.prev = v + z * st.prev;
-                x[u] = kq * st.prev;
+                for (int j = R - 2; j >= 0; j--) {
+                    st.next = z * st.next + pre[j];
+                    st.a3 = st.a2, st.a2 = st.a1, st.a1 = st.next;
+                }
+                anticausal_run<T, S, MODE>(line, hi - 1, first ? need_lo : lo, st, w0, w1, w2, w3);
             }
-#pragma unroll
-            for (int u = 0; u < 8; u++)
-                line[(hi - 8 + u) * S] = x[u];
-        } else {
-            causal_run<T, S, MODE>(line, lo, hi, st, w0, w1, w2, w3);
         }
+        __syncthreads();
     }
-    __syncthreads();
-    // ---- C: q[hi, hi+R) (= -z c+) before the next quarter's anticausal pass overwrites it ----
-    if (active && !last) {
-#pragma unroll
-        for (int j = 0; j < R; j++)
-            pre[j] = line[(hi + j) * S];
-    }
-    __syncthreads();
-    // ---- D: anticausal ----
-    if (active) {
-        if (last) {
-            st.next = st.prev * ((T)6 * zfin);
-            st.a1 = st.next, st.a2 = 0, st.a3 = 0;
-            if (MODE != 2)
-                line[(n - 1) * S] = st.next;
-            anticausal_run<T, S, MODE>(line, n - 2, lo, st, w0, w1, w2, w3);
-        } else {
-            st.next = pre[R - 1] / ((T)1 - z);
-            st.a1 = st.next, st.a2 = 0, st.a3 = 0;
-#pragma unroll
-            for (int j = R - 2; j >= 0; j--) {
-                st.next = z * st.next + pre[j];
-                st.a3 = st.a2, st.a2 = st.a1, st.a1 = st.next;
-            }
-            anticausal_run<T, S, MODE>(line, hi - 1, first ? need_lo : lo, st, w0, w1, w2, w3);
-        }
-    }
-    __syncthreads();
 }
+
 
 // in-place 2-D prefilter of an LDS region [nr x nc], row stride LD (odd: conflict-free row walks).
 // Axis 0 runs over all nc columns; axis 1 only over rows [r_lo, r_hi) (the rows a consumer reads).
@@ -974,9 +897,9 @@ template <typename T, int NT, int LD, int RW = TileCfg<T>::R>
 __device__ __forceinline__ void tile_iir2d(T *reg, int nr, int nc, bool top_edge, bool left_edge, int tid, int r_lo,
                                            int r_hi, int bc_y = 0, int bc_x = 0)
 {
-    static_assert(NT == 256, "walk_pass_2seg assumes a 256-thread block");
-    walk_pass_2seg<T, LD, 0, RW>(reg, 1, nc, nr, top_edge, nullptr, tid, 0, bc_y);
-    walk_pass_2seg<T, 1, 0, RW>(reg + r_lo * LD, LD, r_hi - r_lo, nc, left_edge, nullptr, tid, 0, bc_x);
+    static_assert(NT == WALK_NT, "walk_pass assumes a block of WALK_NT threads");
+    walk_pass<T, LD, 0, RW, 2>(reg, 1, nc, nr, top_edge, nullptr, tid, 0, bc_y);
+    walk_pass<T, 1, 0, RW, 2>(reg + r_lo * LD, LD, r_hi - r_lo, nc, left_edge, nullptr, tid, 0, bc_x);
 }
 
 // spline_filter(order 3) of whole planes [B, Hc, Wc] (Hc, Wc >= 64), out of place: one block per 64 x 64 tile, the tile
@@ -1001,8 +924,8 @@ __global__ void __launch_bounds__(256)
     load_region<T, FR, FR, 13, S>(reg, LD, src + (size_t)pa * Wc + qa, Wc, nr, nc, wave, lane);
     __syncthreads();
     const bool mirror = mode == 0;  // MODE_MIRROR (srx_prims.hpp)
-    const int bc_y = mirror ? ((pa == 0 ? SRX_BC_MIRROR_LO : 0) | (pb == Hc ? SRX_BC_MIRROR_HI : 0)) : 0;
-    const int bc_x = mirror ? ((qa == 0 ? SRX_BC_MIRROR_LO : 0) | (qb == Wc ? SRX_BC_MIRROR_HI : 0)) : 0;
+    const int bc_y = mirror ? ((pa == 0 ? BC_MIRROR_LO : 0) | (pb == Hc ? BC_MIRROR_HI : 0)) : 0;
+    const int bc_x = mirror ? ((qa == 0 ? BC_MIRROR_LO : 0) | (qb == Wc ? BC_MIRROR_HI : 0)) : 0;
     const int r_lo = r0 - pa, r_hi = min(r0 + TSP, Hc) - pa;
     tile_iir2d<T, 256, LD, WU>(reg, nr, nc, pa == 0, qa == 0, tid, r_lo, r_hi, bc_y, bc_x);
     T *dst = dst_ + (size_t)b * Hc * Wc;

@@ -350,9 +350,9 @@ __global__ void __launch_bounds__(256)
             // tile of the near band also reads the first rows / columns (pa = 0 / qa = 0 there)
             const int r_lo = max(0, p0 - ma.Dy - pa), r_hi = min(nr - 3, p0 - ma.Dy + TS - pa);
             const int r_lo_w = p0 < ma.PBy ? 0 : r_lo, c_lo_w = q0 < ma.PBx ? 0 : max(0, q0 - ma.Dx - qa);
-            fused::walk_pass_2seg<T, LD, 2, R>(reg, 1, nc, nr, pa == 0, ma.wfy, tid, r_lo_w);
+            fused::walk_pass<T, LD, 2, R, 2>(reg, 1, nc, nr, pa == 0, ma.wfy, tid, r_lo_w);
             SRX_STAMP(0, 2);
-            fused::walk_pass_4seg<T, 1, 2, R>(reg + r_lo_w * LD, LD, max(r_hi - r_lo_w, 0), nc, qa == 0, ma.wfx, tid, c_lo_w);
+            fused::walk_pass<T, 1, 2, R, 4>(reg + r_lo_w * LD, LD, max(r_hi - r_lo_w, 0), nc, qa == 0, ma.wfx, tid, c_lo_w);
         }
         __syncthreads();
         SRX_STAMP(0, 3);
@@ -684,7 +684,7 @@ __global__ void __launch_bounds__(256)
         __syncthreads();
         SRX_STAMP(1, 1);
         const int r_lo = r0 + 9 - pa, ncw = nc + 3;
-        fused::walk_pass_2seg<T, LD, 1, RW>(reg, 1, ncw, nr + 3, pa == 0, ma.wby, tid, r_lo);
+        fused::walk_pass<T, LD, 1, RW, 2>(reg, 1, ncw, nr + 3, pa == 0, ma.wby, tid, r_lo);
         SRX_STAMP(1, 2);
         T *wrow = reg + r_lo * LD;  // window row 0 = image row r0 - 3
         // B' sees zeros outside the image: of the window rows only the three just above row 0 / below row H-1 are read
@@ -721,7 +721,7 @@ __global__ void __launch_bounds__(256)
             }
             __syncthreads();
         }
-        fused::walk_pass_4seg<T, 1, 1, RW>(wrow, LD, TS, ncw, qa == 0, ma.wbx, tid, c0 + 9 - qa);
+        fused::walk_pass<T, 1, 1, RW, 4>(wrow, LD, TS, ncw, qa == 0, ma.wbx, tid, c0 + 9 - qa);
         SRX_STAMP(1, 3);
         T *win = wrow + (c0 + 9 - qa);  // window column 0 = image column c0 - 3
         if (c0 == 0 || c0 + TS + 3 > W) {
@@ -764,9 +764,9 @@ __global__ void __launch_bounds__(256)
             SRX_STAMP(1, 1);
             constexpr int RW = TileCfg<T>::R;
             const int r_lo = r0 + 9 - pa, r_hi = min(r0 + TS + 15, Hp) - pa;
-            fused::walk_pass_2seg<T, LD, 1, RW>(reg, 1, nc + 3, nr + 3, pa == 0, ma.wby, tid, r_lo);
+            fused::walk_pass<T, LD, 1, RW, 2>(reg, 1, nc + 3, nr + 3, pa == 0, ma.wby, tid, r_lo);
             SRX_STAMP(1, 2);
-            fused::walk_pass_2seg<T, 1, 1, RW>(reg + r_lo * LD, LD, max(r_hi - r_lo, 0), nc + 3, qa == 0, ma.wbx, tid, c0 + 9 - qa);
+            fused::walk_pass<T, 1, 1, RW, 2>(reg + r_lo * LD, LD, max(r_hi - r_lo, 0), nc + 3, qa == 0, ma.wbx, tid, c0 + 9 - qa);
             SRX_STAMP(1, 3);
         }
         fused::zero_outside_image<T, TS, LD>(reg + (r0 + 9 - pa) * LD + (c0 + 9 - qa), r0, c0, H, W, tid);
@@ -801,6 +801,21 @@ __global__ void __launch_bounds__(256)
 // the tile like in k_bwd_mosaic.  zoom(order=3) semantics (corner-aligned, mirrored taps) come from the same
 // device-built tap tables as srx_zoom_cubic.
 // ---------------------------------------------------------------------------------------
+// one whole line of n >= 2 samples, element stride S, in place: SciPy's exact boundary sums at both ends
+template <typename T, int S> __device__ __forceinline__ void whole_line(T *line, int n, int mode)
+{
+    fused::WalkState<T> st;
+    const T z = pole<T>();
+    // causal_run keeps p = c+ / 6 as its state and stores q = -z c+ (srx_fused.hpp, WalkState)
+    const T c0 = causal_init<T>([&](int q) { return (T)6 * line[q * S]; }, n, mode);
+    st.prev = c0 / (T)6;
+    line[0] = -z * c0;
+    fused::causal_run<T, S, 0>(line, 1, n, st, (T)0, (T)0, (T)0, (T)0);
+    st.next = anticausal_init<T>((T)6 * st.prev, line[(n - 2) * S] / -z, mode);
+    line[(n - 1) * S] = st.next;
+    fused::anticausal_run<T, S, 0>(line, n - 2, 0, st, (T)0, (T)0, (T)0, (T)0);
+}
+
 // spline_filter(order 3, mode) of frames that fit a wave: h, w <= 64.  One wave per frame, the frame in LDS (row
 // stride 65: conflict-free both ways), lane = column for axis 0, lane = row for axis 1; whole lines, so SciPy's exact
 // boundary sums at both ends and no warm-up.  Replaces copy + k_prefilter_axis0 + k_prefilter_axis1 (out of place,
@@ -828,30 +843,11 @@ __global__ void __launch_bounds__(256)
                 reg[(r0 + u) * LD + lane] = (T)v[u];
     }
     __syncthreads();
-    fused::WalkState<T> st;
-    const T z = pole<T>();
-    if (lane < Wc && Hc > 1) {
-        T *line = reg + lane;
-        // causal_run keeps p = c+ / 6 as its state and stores q = -z c+ (srx_fused.hpp, WalkState)
-        const T c0 = causal_init<T>([&](int q) { return (T)6 * line[q * LD]; }, Hc, mode);
-        st.prev = c0 / (T)6;
-        line[0] = -z * c0;
-        fused::causal_run<T, LD, 0>(line, 1, Hc, st, (T)0, (T)0, (T)0, (T)0);
-        st.next = anticausal_init<T>((T)6 * st.prev, line[(Hc - 2) * LD] / -z, mode);
-        line[(Hc - 1) * LD] = st.next;
-        fused::anticausal_run<T, LD, 0>(line, Hc - 2, 0, st, (T)0, (T)0, (T)0, (T)0);
-    }
+    if (lane < Wc && Hc > 1)
+        whole_line<T, LD>(reg + lane, Hc, mode);
     __syncthreads();
-    if (lane < Hc && Wc > 1) {
-        T *line = reg + lane * LD;
-        const T c0 = causal_init<T>([&](int q) { return (T)6 * line[q]; }, Wc, mode);
-        st.prev = c0 / (T)6;
-        line[0] = -z * c0;
-        fused::causal_run<T, 1, 0>(line, 1, Wc, st, (T)0, (T)0, (T)0, (T)0);
-        st.next = anticausal_init<T>((T)6 * st.prev, line[Wc - 2] / -z, mode);
-        line[Wc - 1] = st.next;
-        fused::anticausal_run<T, 1, 0>(line, Wc - 2, 0, st, (T)0, (T)0, (T)0, (T)0);
-    }
+    if (lane < Hc && Wc > 1)
+        whole_line<T, 1>(reg + lane * LD, Wc, mode);
     __syncthreads();
     for (int r = 0; r < Hc; r++)
         if (lane < Wc)
@@ -1170,8 +1166,8 @@ __global__ void __launch_bounds__(256, sizeof(T) == 4 && F == 4 ? 4 : 1)  // flo
             reg[rr * LD + cb + t] = acc[t];
     __syncthreads();
     const int r_lo = r0 + SRX_NPAD - pa, r_hi = min(r_lo + TS, nr);
-    fused::walk_pass_2seg<T, LD, 1, R>(reg, 1, ncw, nrw, pa == 0, ma.wfy, tid, r_lo);
-    fused::walk_pass_4seg<T, 1, 1, R>(reg + r_lo * LD, LD, max(r_hi - r_lo, 0), ncw, qa == 0, ma.wfx, tid, c0 + SRX_NPAD - qa);
+    fused::walk_pass<T, LD, 1, R, 2>(reg, 1, ncw, nrw, pa == 0, ma.wfy, tid, r_lo);
+    fused::walk_pass<T, 1, 1, R, 4>(reg + r_lo * LD, LD, max(r_hi - r_lo, 0), ncw, qa == 0, ma.wfx, tid, c0 + SRX_NPAD - qa);
     SRX_STAMP(2, 6);
     for (int idx = tid; idx < TS * TS; idx += 256) {
         const int r = r0 + idx / TS, c = c0 + idx % TS;
@@ -1201,8 +1197,8 @@ __global__ void __launch_bounds__(256)
     fused::load_region<T, SR, SR>(reg, LD, Wpl + ((size_t)b * (Hp + 3) + pa) * (Wp + 3) + qa, (size_t)(Wp + 3), nrw, ncw, wave, lane);
     __syncthreads();
     const int r_lo = r0 + SRX_NPAD - pa, r_hi = min(r_lo + TS, nr);
-    fused::walk_pass_2seg<T, LD, 1, R>(reg, 1, ncw, nrw, pa == 0, ma.wfy, tid, r_lo);
-    fused::walk_pass_4seg<T, 1, 1, R>(reg + r_lo * LD, LD, max(r_hi - r_lo, 0), ncw, qa == 0, ma.wfx, tid, c0 + SRX_NPAD - qa);
+    fused::walk_pass<T, LD, 1, R, 2>(reg, 1, ncw, nrw, pa == 0, ma.wfy, tid, r_lo);
+    fused::walk_pass<T, 1, 1, R, 4>(reg + r_lo * LD, LD, max(r_hi - r_lo, 0), ncw, qa == 0, ma.wfx, tid, c0 + SRX_NPAD - qa);
     for (int idx = tid; idx < TS * TS; idx += 256) {
         const int r = r0 + idx / TS, c = c0 + idx % TS;
         if (r < H && c < W)

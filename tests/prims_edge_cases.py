@@ -11,7 +11,7 @@ csrc/srx_fused.hpp: prefilter2d_fast):
       without at_end.  axis 1 walks 64-column tiles with one warm-up and one tail tile; a last tile one column wide takes carry_prev
       from the tile before it.
   tile kernel k_prefilter_tile: float32 with both sides >= 64.  64 x 64 tiles with a 20-sample halo clipped at the array ends;
-      walk_pass_2seg splits a line of n samples between two threads only when ((R+7)&~7) <= ((n-R)&~7), R = 20: from n = 44 on.  The
+      walk_pass<.., 2> splits a line of n samples between two threads only when ((R+7)&~7) <= ((n-R)&~7), R = 20: from n = 44 on.  The
       last tile's region is n = (len mod 64) + 20 long (84 when len is a multiple of 64).
 
 A zoom prefilters lines of the image's own length (MODE_MIRROR); a shift prefilters the image padded by 12 on every side
@@ -52,12 +52,12 @@ LENGTHS = (
     # zoom: 40 = Warmup<double>::n; 42: te == 10
     39, 40, 41, 42,
     # zoom: 57 has float's te == WU without at_end (n >= 53); 63, 64, 65 are Horizon<double>::n, the 64-tile edge and the hand-over
-    # to the tile kernel; shift: n = 87, 88 -- the tile kernel's last tile region is 43, 44 long: the 2seg threshold
+    # to the tile kernel; shift: n = 87, 88 -- the tile kernel's last tile region is 43, 44 long: the two-thread threshold
     57, 63, 64, 65,
     # zoom in float64: 71 -> te == 39 < WU with at_end, 72 -> te == WU with at_end, 73 -> te == WU without (and te == 9 on chunk 1);
     # shift: n = 95, 96, 97 -- three whole chunks, and a fourth of one sample behind a tail of te == 1
     71, 72, 73,
-    # zoom: 87, 88 -- the 2seg threshold of the tile kernel's last tile (region 23 + 20, 24 + 20); 96, 97 as 32, 33 with warmed-up chunks in
+    # zoom: 87, 88 -- the two-thread threshold of the tile kernel's last tile (region 23 + 20, 24 + 20); 96, 97 as 32, 33 with warmed-up chunks in
     # front; 107, 108 end 11 / 12 samples into a chunk and 43 / 44 into a tile (shift: n = 131, 132: a third tile 3 / 4 columns wide)
     87, 88, 96, 97, 107, 108,
     # a last tile one column wide behind two, three and four whole ones (129, 193, 257); 149 = 4 * 32 + 21: float's te == WU with the line

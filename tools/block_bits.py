@@ -11,6 +11,10 @@ once per build and compare the listings:
 run with the flag off and with it on.  A run prints its path (asserted), the SHA-256 of its outputs and the launches per kernel id
 (srx_profile_get), so a flag that stops arriving where it is read changes the listing.  Compare the listings of two builds as above
 (--flags --plan: the routes, no GPU).
+
+--walk prints a third list: one case per user of the segmented LDS spline walk (fused::walk_pass, csrc/srx_fused.hpp) -- the check of a
+change to the walk that must not change a bit.  A case prints its path (asserted; the primitives have none), the SHA-256 of its outputs and
+the launches per kernel id, which name the kernels that walked (--walk --plan: the routes, no GPU).
 """
 import hashlib
 import os
@@ -65,6 +69,53 @@ FLAGS_HEADER = """# one case per reader of a SRX_FLAG_DIAG_* switch below the en
 # kernel NAMES of a kernel trace of this run tell its two runs apart (k_patch_build<0, unsigned char, true> against <..., false>)
 # (SRX_FLAG_DIAG_V1's MSE trace is printed to 10 digits, not hashed: that iteration sums it with atomics, and two runs of one build differ
 # in its last bits)"""
+
+
+# (name, call, path, precision, B, f, LR h, LR w, shifts, PSF, flags).  zoom / shift: one [h, w] image, f = the zoom factor / unused.
+HALF2, HALF4 = synth.phase_shifts(2), synth.phase_shifts(4)  # x2 / x4: every HR shift has the fraction one half
+WALK_CASES = [("zoom_cubic 70x130 (k_prefilter_tile, mirror ends)", "zoom", None, "f32", 1, 2, 70, 130, None, None, 0),
+              ("shift_cubic 70x130 (k_prefilter_tile, reflect ends)", "shift", None, "f32", 1, 1, 70, 130, None, None, 0)]
+WALK_CASES += [(f"shift_and_add x{f} {prec} {fn} (k_saa_tile{'' if fl else ', k_saa_shift'})", "saa", "mosaic", prec, 2, f, 64, 64, sh, None, fl)
+               for f, sh in ((2, HALF2), (4, HALF4)) for prec in ("f32", "f64") for fn, fl in (("two-pass", 0), ("one-pass", L.FLAG_DIAG_SAA_ONE_PASS))]
+WALK_CASES += [("ibp per frame f64 (k_fwd_tile, k_bwd_tile)", "ibp", "fused", "f64", 2, 2, 40, 50, synth.MEASURED_4, "core5", L.FLAG_PER_FRAME),
+               ("ibp per frame f32 x3 (k_fwd_tile, k_bwd_tile)", "ibp", "fused", "f32", 2, 3, 40, 50, synth.MEASURED_4, "core5", L.FLAG_PER_FRAME)]
+WALK_CASES += [(f"ibp tiles {prec} {pn} (k_fwd_mosaic, k_bwd_mosaic {'separable' if pn == 'gauss' else '7 x 7'})", "ibp", "mosaic", prec, 2, 4, 40, 50, HALF4, pn,
+                L.FLAG_TILES) for prec in ("f32", "f64") for pn in ("gauss", "core5")]
+WALK_ITERS = 2
+
+
+def walk_cases(plan_only):
+    if not plan_only:
+        import torch
+        from sr_mi355x import api as S
+    lib, bad = _lib.load(), 0
+    for i, (name, call, want, prec, B, f, h, w, sh, pn, fl) in enumerate(WALK_CASES):
+        if plan_only:
+            if want is None:
+                print(f"{name}: prefilter2d_fast takes float32 planes of at least 64 x 64 to k_prefilter_tile")
+                continue
+            got = planned(prec, sh, PSFS[pn or "gauss"](), h, w, f, fl, call)
+            print(f"{name} flags={fl:#x}: {got}" + ("" if got == want else f"  (WANTED {want})"))
+            bad += got != want
+            continue
+        rng = np.random.default_rng(3000 + i)
+        lib.srx_profile_enable(1)
+        if call in ("zoom", "shift"):
+            x = np.rint(rng.uniform(0, 255, (1, h, w)))
+            outs = (S.zoom_batched(x, f, precision=prec) if call == "zoom" else S.shift_batched(x, (0.37, -0.61), precision=prec),)
+        else:
+            lr = np.rint(rng.uniform(0, 255, (B, len(sh), h, w)))
+            hr0 = rng.uniform(0, 255, (B, h * f, w * f))
+            outs = (S.shift_and_add_batched(lr, sh, f, precision=prec, flags=fl),) if call == "saa" else \
+                S.ibp_batched(lr, sh, PSFS[pn](), hr0, f, WALK_ITERS, 0.5, precision=prec, flags=fl)
+        torch.cuda.synchronize()
+        counts = launches(lib)
+        lib.srx_profile_enable(0)
+        if want is not None:
+            assert S.last_path() == want, (name, S.last_path())
+        digest = [hashlib.sha256(np.ascontiguousarray(t.cpu().numpy()).tobytes()).hexdigest() for t in outs]
+        print(f"{name} flags={fl:#x}: path={want} out={' '.join(digest)} launches={' '.join(f'{k}:{v}' for k, v in sorted(counts.items()))}", flush=True)
+    return 1 if bad else 0
 
 
 def planned(prec, sh, psf, h, w, f, flags=0, call="ibp"):
@@ -131,6 +182,8 @@ def main(argv):
     plan_only = "--plan" in argv
     if "--flags" in argv:
         return flag_cases(plan_only)
+    if "--walk" in argv:
+        return walk_cases(plan_only)
     if not plan_only:
         import torch
         from sr_mi355x import api as S

@@ -12,7 +12,8 @@ front of its body -- comments and directives dropped, local labels renumbered) i
   reordered   the same number of instructions and the same multiset of opcodes, in another order;
   CHANGED     anything else,
 and it compares the resource figures of the kernel descriptor (VGPRs, SGPRs, scratch, LDS).  Exit status 1 when a kernel is CHANGED,
-its figures differ, or a symbol exists on one side only.  -v lists every kernel that is not identical.
+its figures differ, or a symbol exists on one side only.  -v lists every kernel that is not identical; where the listings carry the
+code-object metadata, a listed kernel's line ends in its counts there (VGPRs, AGPRs, SGPRs, scratch and LDS bytes), old -> new.
 """
 import collections
 import re
@@ -48,6 +49,21 @@ def kernels(text):
     return {n: (out.get(n, []), figs.get(n, {})) for n in names}
 
 
+METADATA = (("VGPRs", "vgpr_count"), ("AGPRs", "agpr_count"), ("SGPRs", "sgpr_count"), ("scratch", "private_segment_fixed_size"),
+            ("LDS", "group_segment_fixed_size"))
+
+
+def metadata(text):
+    """{symbol: {key: value}} of the listing's .amdgpu_metadata section (empty without one)"""
+    at = text.find(".amdgpu_metadata")
+    out = {}
+    for blk in re.split(r"\n  - ", text[at:])[1:] if at >= 0 else ():
+        name = re.search(r"^\s+\.name:\s+(\S+)", blk, re.M)
+        if name and ".vgpr_count:" in blk:
+            out[name.group(1)] = {k: int(m.group(1)) for _, k in METADATA for m in [re.search(rf"\.{k}:\s+(\d+)", blk)] if m}
+    return out
+
+
 def verdict(a, b):
     if a == b:
         return "identical"
@@ -73,7 +89,9 @@ def main(argv):
     if len(paths) != 2:
         print(__doc__)
         return 2
-    old, new = (kernels(open(p).read()) for p in paths)
+    texts = [open(p).read() for p in paths]
+    old, new = (kernels(t) for t in texts)
+    mold, mnew = (metadata(t) for t in texts)
     only = sorted(set(old) ^ set(new))
     both = [n for n in old if n in new]
     pretty = demangle(both + only)
@@ -86,6 +104,9 @@ def main(argv):
         bad = bad or v == "CHANGED" or fa != fb
         if v != "identical" or fa != fb:
             lines.append(f"  {v:9s} {pretty[n]}: {len(ia)} -> {len(ib)} instructions, {figs}")
+            if n in mold and n in mnew:
+                lines[-1] += "; " + " ".join(f"{t} {mold[n].get(k)}->{mnew[n].get(k)}" + ("(+)" if mnew[n].get(k, 0) > mold[n].get(k, 0) else "")
+                                             for t, k in METADATA)
     print(f"{len(old)} kernels in {paths[0]}, {len(new)} in {paths[1]}: " + ", ".join(f"{tally[k]} {k}" for k in ("identical", "renamed", "reordered", "CHANGED")))
     for n in only:
         print(f"  only in {paths[0] if n in old else paths[1]}: {pretty[n]}")
