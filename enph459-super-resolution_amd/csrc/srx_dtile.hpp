@@ -17,7 +17,7 @@
 //     units when ONE frame is all there is (3072 x 4096: 336 windows of 16 waves = 1.31 rounds of 256 CUs at 55 us per round, or 512 of
 //     12 waves = 2.00 rounds at 37 us).  plan() picks by modelled time of one frame.
 //   * Near band, count masks, byte mosaic: k_ibp_patch's, per window (only windows on the top / left image edge hold near-band
-//     pixels; the tables are built per such window).  The near band's code is srx_patch.hpp's too (patch::near_count, near_put_y, near_px,
+//     pixels; the tables are built per such window, by patch::block_setup as the patch's own).  The near band's code is srx_patch.hpp's too (patch::near_count, near_put_y, near_px,
 //     near_get_g_left; whole rows of G come back eight columns at a time here), the exchanges around the chains srx_block.hpp's.
 #pragma once
 #include "srx_patch.hpp"
@@ -80,12 +80,7 @@ struct DTabs {
     const float *k2;        // srx_patch.hpp's 7 x 7 weight tables (a PSF that is not rank 1)
 };
 
-// ---- host-side plan ----------------------------------------------------------------------------------------------------
-struct AxisTiles {
-    int n;
-    int o[64], a[65];  // origins; ownership boundaries (global): window t owns [a[t], a[t + 1])
-};
-
+// ---- host-side plan (AxisTiles is declared in srx_patch.hpp, whose set-up kernels take the plan) -----------------------------------
 // windows of length RL over [0, L): the first starts at 0, the last ends at L, each owns a span whose HL-neighbourhood it contains
 static inline bool plan_axis_tiles(int L, int RL, int align, AxisTiles &at)
 {
@@ -198,104 +193,8 @@ __global__ void __launch_bounds__(256) k_dtile_copy_out(const float *__restrict_
     d[0] = v.x, d[W] = v.y, d[2 * (size_t)W] = v.z, d[3 * (size_t)W] = v.w;
 }
 
-// Transposed far-field operands of the whole frame (k_patch_prep's layouts with the plane's own height):
-//   Mt[b][gx / 4][gy][gx % 4], Ct likewise (plane index B), Mt8[b][gx / 16][gy][(gx / 4) % 4] bytes gx % 4; m8[b] cleared when a value
-//   of item b is not an integer in [0, 255].  Near-band pixels (gy < nby or gx < nbx) are zero here: the kernel takes them from lists.
-// grid (ceil(W/32), ceil(H/32), B + 1), block (32, 8).
-__global__ void __launch_bounds__(256)
-    k_dtile_prep(const float *__restrict__ Mg, const float *__restrict__ Cg, int B, int H, int W, int nby, int nbx, float *__restrict__ Mt,
-                 float *__restrict__ Ct, unsigned *__restrict__ Mt8, int *__restrict__ m8)
-{
-    __shared__ float t[32][33];
-    const int Hg = H + 27, Wg = W + 27;
-    const int b = blockIdx.z, x0 = blockIdx.x * 32, y0 = blockIdx.y * 32;
-    const float *src = b < B ? Mg + (size_t)b * Hg * Wg : Cg;
-    float *dst = b < B ? Mt + (size_t)b * H * W : Ct;
-    bool ok = true;
-    for (int r = threadIdx.y; r < 32; r += 8) {
-        const int gy = y0 + r, gx = x0 + (int)threadIdx.x;
-        float v = (gy < H && gx < W) ? src[(size_t)(gy + 13) * Wg + gx + 13] : 0.f;
-        if (b < B && (gy < nby || gx < nbx))
-            v = 0.f;
-        ok = ok && v == rintf(v) && v >= 0.f && v <= 255.f;
-        t[r][threadIdx.x] = v;
-    }
-    __syncthreads();
-    const int g = threadIdx.y, row = y0 + (int)threadIdx.x, wr = x0 / 4 + g;  // column quad wr of row `row`
-    if (row < H && 4 * wr < W) {
-        reinterpret_cast<float4 *>(dst)[(size_t)wr * H + row] =
-            make_float4(t[threadIdx.x][4 * g], t[threadIdx.x][4 * g + 1], t[threadIdx.x][4 * g + 2], t[threadIdx.x][4 * g + 3]);
-        if (b < B) {
-            const unsigned w = (unsigned)t[threadIdx.x][4 * g] | (unsigned)t[threadIdx.x][4 * g + 1] << 8 |
-                               (unsigned)t[threadIdx.x][4 * g + 2] << 16 | (unsigned)t[threadIdx.x][4 * g + 3] << 24;
-            Mt8[(size_t)b * (W / 4) * H + ((size_t)(wr >> 2) * H + row) * 4 + (wr & 3)] = w;
-        }
-    }
-    const bool bad = __syncthreads_or(b < B && !ok);
-    if (bad && threadIdx.x == 0 && threadIdx.y == 0)
-        atomicAnd(&m8[b], 0);
-}
-
-// the axis parameters a window sees: the image's where it lies on that image edge, none elsewhere
-__device__ __forceinline__ void local_axes(const TileD &td, const DArgs &da, int &exy, int &nby, int &exx, int &nbx)
-{
-    exy = (td.flags & 1) ? da.y.ex : 0, nby = (td.flags & 1) ? da.y.nb : 0;
-    exx = (td.flags & 2) ? da.x.ex : 0, nbx = (td.flags & 2) ? da.x.nb : 0;
-}
-// (near-band pixel t of a window: patch::near_coords / near_count with the window's shape -- window-local natural coordinates, G strip offset)
-
-// per near-band window: the lists of k_build_near as strip offsets (k_patch_near_tab), the counted-sample count zeroed for pixels
-// whose (clamped) position another window owns.  grid (NN_PAD / 256, ntabs)
-__global__ void __launch_bounds__(256)
-    k_dtile_near_tab(const int *__restrict__ ncu, const int *__restrict__ nyx, int NS, int PBy, int PBx, DArgs da, int RX,
-                     const TileD *__restrict__ tiles, int ntiles, int *__restrict__ nn_out, uint2 *__restrict__ nrec, uint2 *__restrict__ nent, int ntabs)
-{
-    const int t = blockIdx.x * 256 + threadIdx.x, tab = blockIdx.y;
-    const TileD td = tiles[tab < da.tiles_x ? tab : (tab - da.tiles_x + 1) * da.tiles_x];  // top windows first, then the left ones (k_dtile_setup)
-    int exy, nby, exx, nbx;
-    local_axes(td, da, exy, nby, exx, nbx);
-    const int nn = patch::near_count(RY, RX, exy, exx, nby, nbx);
-    if (t == 0)
-        nn_out[tab] = nn;
-    if (t >= nn)
-        return;
-    int ngy, ngx, dst;
-    patch::near_coords(t, RX, exy, exx, nby, nbx, ngy, ngx, dst);
-    const int gy = td.oy + ngy, gx = td.ox + ngx;  // image (natural) coordinates
-    const int ni = mosaic::near_index(gy + 13, gx + 13, da.W + 27, PBy, PBx), pk = ncu[ni], cnt = pk & 255;
-    int cu = pk >> 8;
-    const int cy = max(ngy, 0), cx = max(ngx, 0);  // where its counted samples sit: the window that owns that pixel counts them
-    if (cy < td.y0 || cy >= td.y1 || cx < td.x0 || cx >= td.x1)
-        cu = 0;
-    const int own = patch::strip_off(ngy, ngx, exy, exx, nby);
-    nrec[(size_t)tab * NN_PAD + t] = make_uint2((unsigned)cnt | (unsigned)cu << 8 | (unsigned)dst << 16, (unsigned)own);
-    for (int g = 0; g < NS / 4; g++) {
-        unsigned o[4];
-        for (int e = 0; e < 4; e++) {
-            const int c = nyx[(size_t)ni * NS + 4 * g + e];
-            o[e] = 4 * g + e < cnt ? (unsigned)patch::strip_off((c & 0xffff) - da.y.E - td.oy, (c >> 16) - da.x.E - td.ox, exy, exx, nby) : (unsigned)own;
-        }
-        nent[((size_t)g * ntabs + tab) * NN_PAD + t] = make_uint2(o[0] | o[1] << 16, o[2] | o[3] << 16);
-    }
-}
-
-// (M, Mu) of the near-band pixels of every item.  grid (NN_PAD / 256, ntabs, B)
-__global__ void __launch_bounds__(256)
-    k_dtile_near_m(const float *__restrict__ Mg, const float *__restrict__ Mu, int NB, int PBy, int PBx, DArgs da, int RX,
-                   const TileD *__restrict__ tiles, int ntiles, float2 *__restrict__ Mn, int ntabs)
-{
-    const int t = blockIdx.x * 256 + threadIdx.x, tab = blockIdx.y, b = blockIdx.z;
-    const TileD td = tiles[tab < da.tiles_x ? tab : (tab - da.tiles_x + 1) * da.tiles_x];  // top windows first, then the left ones (k_dtile_setup)
-    int exy, nby, exx, nbx;
-    local_axes(td, da, exy, nby, exx, nbx);
-    if (t >= patch::near_count(RY, RX, exy, exx, nby, nbx))
-        return;
-    int ngy, ngx, dst;
-    patch::near_coords(t, RX, exy, exx, nby, nbx, ngy, ngx, dst);
-    const int gy = td.oy + ngy, gx = td.ox + ngx, Wg = da.W + 27, Hg = da.H + 27;
-    const int ni = mosaic::near_index(gy + 13, gx + 13, Wg, PBy, PBx);
-    Mn[((size_t)b * ntabs + tab) * NN_PAD + t] = make_float2(Mg[((size_t)b * Hg + gy + 13) * Wg + gx + 13], Mu[(size_t)b * NB + ni]);
-}
+// (the operand planes Mt / Ct / Mt8 / m8 of the whole frame and the near-band tables of the windows on the top / left image edge are
+// srx_patch.hpp's: patch::block_setup with this plan)
 
 // MSE trace of the LAST iteration from the windows' partial sums, fixed order (the same order as the in-kernel sum of the earlier
 // iterations: lane-strided, wave tree, waves in turn).  grid B, block NTHR of the iteration kernel
@@ -462,7 +361,7 @@ __device__ __forceinline__ void dtile_body(float *lds, const float *__restrict__
 #pragma unroll
             for (int i = 0; i < NPT; i++) {
                 const int t = tid + i * NTHR;
-                if (t < nn)  // (its counted-sample count is zero where another window owns the pixel: k_dtile_near_tab)
+                if (t < nn)  // (its counted-sample count is zero where another window owns the pixel: patch::k_near_tab)
                     patch::near_px(nr[i], ne[i], nm[i].x, nm[i].y, Ystrip, Gstrip, [&](int g) { return ld_u2(rsNe, ((g * tb.ntabs) * NN_PAD + tab0 + t) * 8); }, sq);
             }
             __syncthreads();
@@ -826,14 +725,8 @@ static int iterate(const mosaic::Common<float> &c, const float *hr_init, float *
     SRX_CHECK_LAUNCH();
     SRX_TRY(upload_record(st, aw, awp));
     // ---- operand planes, near-band tables, state
-    if (fill_bytes(m8, 0xff, (size_t)B * sizeof(int), st) != hipSuccess)
-        return SRX_E_HIP;
-    hipLaunchKernelGGL(k_dtile_prep, dim3(cdiv(W, 32), cdiv(H, 32), B + 1), dim3(32, 8), 0, st, c.Mg, c.Cg, B, H, W, da.y.nb, da.x.nb, Mt, Ct, Mt8, m8);
-    SRX_CHECK_LAUNCH();
-    hipLaunchKernelGGL(k_dtile_near_tab, dim3(NN_PAD / 256, ntabs), dim3(256), 0, st, c.ncu, c.nyx, NS, py.PB, px.PB, da, RX, tiles, ntiles, nnt, nrec, nent, ntabs);
-    SRX_CHECK_LAUNCH();
-    hipLaunchKernelGGL(k_dtile_near_m, dim3(NN_PAD / 256, ntabs, B), dim3(256), 0, st, c.Mg, c.Mu, c.NB, py.PB, px.PB, da, RX, tiles, ntiles, Mn, ntabs);
-    SRX_CHECK_LAUNCH();
+    // (every table is launched at the lists' capacity: the windows differ in their pixel counts, which the table kernel writes to nnt)
+    SRX_TRY((patch::block_setup<float, float2>(c, pl.ty, pl.tx, RY, RX, da.y, da.x, NN_PAD / 256, Mt, Ct, Mt8, m8, nnt, nrec, nent, Mn, st)));
     hipLaunchKernelGGL(k_dtile_copy_in, dim3(cdiv(W, 256), H / 4, B), dim3(256), 0, st, hr_init, H, W, s0);
     SRX_CHECK_LAUNCH();
     DTabs tb{Mt, Mt8, m8, Ct, aw, tiles, rowm, colm, nnt, nrec, nent, Mn, ntabs, k2};

@@ -1255,7 +1255,7 @@ static inline size_t ws_common(const IbpShape &s, int B)
 }
 
 // own_build: the implementation reads the LR frames itself and wants no M / C / Mu planes (a batch of patches on a full phase grid,
-// srx_patch.hpp's k_patch_build -- the M plane of 1024 patches is 328 MB written here and read back once by k_patch_prep).
+// srx_patch.hpp's k_patch_build -- the M plane of 1024 patches is 328 MB written here and read back once by k_block_prep).
 // Of `call` it reads the spec, the frames, the batch size, the step and the stream.
 template <typename T, typename S = T>
 static int common_prep(Common<T> &c, bool own_build, const IbpCall<T, S> &call, Arena &ar, int tr_lo, int tr_hi)

@@ -28,14 +28,24 @@
 // ld4 -- live in srx_block.hpp (namespace blk), templated on the element type: every wave-block kernel family calls them there, and the
 // float64 strips of srx_stile.hpp instantiate the same source in double.  This file is the patch kernel, its tables, its eligibility,
 // its carve and its driver -- and the near band of stage B for every kernel that runs it (near_count, near_coords, near_put_y, near_px,
-// near_get_g: k_ibp_patch here, the windows of srx_dtile.hpp, k_ibp_sh of srx_stile.hpp in double).
+// near_get_g: k_ibp_patch here, the windows of srx_dtile.hpp, k_ibp_sh of srx_stile.hpp in double), with what those three set up once per
+// call: the operand planes (k_block_prep<T>), the near-band lists (k_near_tab) and pairs (k_near_m<T, P>), queued by block_setup().
 #pragma once
 #include "srx_block.hpp"
 #include "srx_mosaic.hpp"
 
 namespace srx {
+namespace dtile {
+// The regions of a call along one axis: a frame is cut into overlapping windows, which srx_dtile.hpp plans and names; the set-up kernels
+// below take the plan of either axis by value, as k_dtile_setup does.
+struct AxisTiles {
+    int n;
+    int o[64], a[65];  // origins; ownership boundaries (global): window t owns [a[t], a[t + 1])
+};
+}  // namespace dtile
 namespace patch {
 using namespace blk;
+using dtile::AxisTiles;
 
 // What k_ibp_patch's memory operations cost, from timing ablations that computed wrong results (C2, 161 us per iteration): without
 // the hr park store 150, without the hr re-read 152, without both 144, without the M loads as well 139, without the near band and the
@@ -64,7 +74,7 @@ constexpr int NN_PAD = 2048;  // near-band pixels of a patch (<= 2 per thread)
 
 struct PatchArgs {
     AxisC y, x;
-    int nn, ntop;               // near-band pixels: all / those of the top rows (the enumeration of k_patch_near_tab)
+    int nn, ntop;               // near-band pixels: all / those of the top rows (the enumeration of k_near_tab)
     int ngrp;                   // groups of 4 list entries per near-band pixel
     int c01;                    // the far-field count map is C[gy, gx] = ry[gy] rx[gx], a 0/1 product (full phase grids)
     unsigned long long ry[4], rx[4];
@@ -139,7 +149,7 @@ template <typename T> __device__ __forceinline__ T near_sum4(const T *Ys, uint2 
     return (c > 0 ? Ys[e.x & 0xffff] : (T)0) + (c > 1 ? Ys[e.x >> 16] : (T)0) + (c > 2 ? Ys[e.y & 0xffff] : (T)0) + (c > 3 ? Ys[e.y >> 16] : (T)0);
 }
 // one near-band pixel: G = M - the sum of the listed Y samples, into the G strips; the counted samples' share of the MSE trace onto sq.
-// nr, ne: its records of k_patch_near_tab (ne: the first group of four entries); next(g): group g >= 1 -- more than four frames on a
+// nr, ne: its records of k_near_tab (ne: the first group of four entries); next(g): group g >= 1 -- more than four frames on a
 // pixel: the corner, or frames sharing a phase.  Ys / Gs: the strips (behind the barrier that follows near_put_y).
 template <typename T, typename NEXT> __device__ __forceinline__ void near_px(uint2 nr, uint2 ne, T M, T Mu, const T *Ys, T *Gs, NEXT next, T &sq)
 {
@@ -210,38 +220,52 @@ static inline bool eligible(const IbpSpec &s, bool rank1_only = false)
     return near_count(PN, PN, exy, exx, nby, nbx) <= NN_PAD;
 }
 
-// ---- once per call: transposed far-field operands ---------------------------------------------------------------------
-// Mt[b][gx / 4][gy][gx % 4] = M[b][gy + 13][gx + 13] (and Ct from C, plane index B): in row layout a lane is a row, and one 16-byte
-// load brings four of its columns (64 consecutive gy x 16 bytes per wave-instruction).  grid (8, 8, B + 1), block (32, 8).
-// Also Mt8: the same values as bytes, four columns per word, and m8[b] (preset non-zero by the host) cleared when a value of
-// patch b is not an integer in [0, 255] (uint8 sensor frames with at most one sample per HR pixel: one quarter of the bytes).
+// ---- once per call: the operand planes and the near-band tables, for every kernel that runs stage B ------------------------------------
+// The iteration kernels read one layout per table, so each table is built in one place: k_ibp_patch, the windows of k_ibp_dtile and the
+// strips k_ibp_sh (in T) all call block_setup() below.
+//
+// Transposed far-field operands of an H x W plane (the patch and the strips: PN x PN; a frame of windows: its own shape):
+//   Mt[b][gx / 4][gy][gx % 4] = M[b][gy + 13][gx + 13] (and Ct from C, plane index B): in row layout a lane is a row, and one 16-byte
+//   load brings four of its float columns (64 consecutive gy x 16 bytes per wave-instruction);
+//   Mt8[b][gx / 16][gy][(gx / 4) % 4]: the same values as bytes, four columns per word, four words interleaved the same way;
+//   m8[b] (preset non-zero by the host) cleared when a value of item b is not an integer in [0, 255] (uint8 sensor frames with at most one
+//   sample per HR pixel: one quarter of the bytes).
+// Near-band pixels (gy < nby or gx < nbx) are zero here: the kernels take them from the near-band lists (several frames: sums beyond a byte).
+// grid (ceil(W / 32), ceil(H / 32), B + 1), block (32, 8); W a multiple of 4.
+template <typename T>
 __global__ void __launch_bounds__(256)
-    k_patch_prep(const float *__restrict__ Mg, const float *__restrict__ Cg, int B, int Hg, int Wg, int nby, int nbx, float *__restrict__ Mt,
-                 float *__restrict__ Ct, unsigned *__restrict__ Mt8, int *__restrict__ m8)
+    k_block_prep(const T *__restrict__ Mg, const T *__restrict__ Cg, int B, int H, int W, int nby, int nbx, T *__restrict__ Mt, T *__restrict__ Ct,
+                 unsigned *__restrict__ Mt8, int *__restrict__ m8)
 {
-    __shared__ float t[32][33];
+    __shared__ T t[32][33];
+    const int Hg = H + 27, Wg = W + 27;
     const int b = blockIdx.z, x0 = blockIdx.x * 32, y0 = blockIdx.y * 32;
-    const float *src = b < B ? Mg + (size_t)b * Hg * Wg : Cg;
-    float *dst = b < B ? Mt + (size_t)b * PN * PN : Ct;
+    const T *src = b < B ? Mg + (size_t)b * Hg * Wg : Cg;
+    T *dst = b < B ? Mt + (size_t)b * H * W : Ct;
     bool ok = true;
     for (int r = threadIdx.y; r < 32; r += 8) {
-        float v = src[(size_t)(y0 + r + 13) * Wg + x0 + threadIdx.x + 13];
-        if (b < B && (y0 + r < nby || x0 + (int)threadIdx.x < nbx))
-            v = 0.f;  // near band: the kernel takes these pixels from the near-band lists (several frames: sums beyond a byte)
-        ok = ok && v == rintf(v) && v >= 0.f && v <= 255.f;
+        const int gy = y0 + r, gx = x0 + (int)threadIdx.x;
+        T v = (gy < H && gx < W) ? src[(size_t)(gy + 13) * Wg + gx + 13] : (T)0;  // (the ragged last tiles of a frame)
+        if (b < B && (gy < nby || gx < nbx))
+            v = 0;
+        ok = ok && v == rint(v) && v >= (T)0 && v <= (T)255;
         t[r][threadIdx.x] = v;
     }
     __syncthreads();
-    // transposed, FOUR COLUMNS INTERLEAVED: [column quad][row][4] -- a lane of k_ibp_patch (row layout: lane = row) reads four of
-    // its columns with one 16-byte load
-    const int g = threadIdx.y;  // 8 groups of 4 columns
-    reinterpret_cast<float4 *>(dst)[(size_t)(x0 / 4 + g) * PN + y0 + threadIdx.x] =
-        make_float4(t[threadIdx.x][4 * g], t[threadIdx.x][4 * g + 1], t[threadIdx.x][4 * g + 2], t[threadIdx.x][4 * g + 3]);
-    if (b < B) {
-        const unsigned w = (unsigned)t[threadIdx.x][4 * g] | (unsigned)t[threadIdx.x][4 * g + 1] << 8 |
-                           (unsigned)t[threadIdx.x][4 * g + 2] << 16 | (unsigned)t[threadIdx.x][4 * g + 3] << 24;
-        const int wr = x0 / 4 + g;  // word row = column quad; four word rows interleaved the same way: [wr / 4][row][4]
-        Mt8[(size_t)b * (PN / 4) * PN + ((size_t)(wr >> 2) * PN + y0 + threadIdx.x) * 4 + (wr & 3)] = w;
+    const int g = threadIdx.y, row = y0 + (int)threadIdx.x, wr = x0 / 4 + g;  // 8 groups of 4 columns: column quad wr of row `row`
+    if (row < H && 4 * wr < W) {
+        const T *q = &t[threadIdx.x][4 * g];
+        T *d = dst + ((size_t)wr * H + row) * 4;
+        if constexpr (sizeof(T) == 4) {
+            *reinterpret_cast<float4 *>(d) = make_float4(q[0], q[1], q[2], q[3]);
+        } else {
+#pragma unroll
+            for (int c = 0; c < 4; c++)
+                d[c] = q[c];
+        }
+        if (b < B)
+            Mt8[(size_t)b * (W / 4) * H + ((size_t)(wr >> 2) * H + row) * 4 + (wr & 3)] =
+                (unsigned)q[0] | (unsigned)q[1] << 8 | (unsigned)q[2] << 16 | (unsigned)q[3] << 24;
     }
     // one atomic per block, not one per pixel: a batch of float-valued patches used to spend 25 ms here (65 536 atomics per patch on
     // one address) -- twice the time of the 80 iterations that followed
@@ -250,46 +274,119 @@ __global__ void __launch_bounds__(256)
         atomicAnd(&m8[b], 0);
 }
 
-// the per-pixel lists of k_build_near, re-expressed for the kernel: strip offsets instead of padded coordinates, grouped so
-// that the threads of a wave read consecutive words.  One thread per near-band pixel.
-__global__ void __launch_bounds__(256)
-    k_patch_near_tab(const int *__restrict__ ncu, const int *__restrict__ nyx, int NS, int PBy, int PBx, int exy, int exx, int nby,
-                     int nbx, int Ey, int Ex, int nn, uint2 *__restrict__ nrec, uint2 *__restrict__ nent)
+// the patch and the strips: the plan (AxisTiles, above) with one window per axis, which owns all of itself
+static inline AxisTiles one_region(int L)
 {
-    const int t = blockIdx.x * 256 + threadIdx.x;
+    AxisTiles at = {};
+    at.n = 1, at.a[1] = L;
+    return at;
+}
+// Near-band table `tab` of such a plan: the windows on the top image edge first, then those below the first on the left edge
+// (ty.n + tx.n - 1 tables).  A window sees the image's axis parameters where it lies on that image edge, none elsewhere.
+struct NearWin {
+    int oy, ox;              // window origin (image coordinates)
+    int y0, y1, x0, x1;      // owned range, window-local
+    int exy, exx, nby, nbx;
+};
+__device__ __forceinline__ NearWin near_window(const AxisTiles &ty, const AxisTiles &tx, int tab, const AxisC &ay, const AxisC &ax)
+{
+    const int y = tab < tx.n ? 0 : tab - tx.n + 1, x = tab < tx.n ? tab : 0;
+    NearWin w;
+    w.oy = ty.o[y], w.ox = tx.o[x];
+    w.y0 = ty.a[y] - w.oy, w.y1 = ty.a[y + 1] - w.oy, w.x0 = tx.a[x] - w.ox, w.x1 = tx.a[x + 1] - w.ox;
+    w.exy = y == 0 ? ay.ex : 0, w.nby = y == 0 ? ay.nb : 0;
+    w.exx = x == 0 ? ax.ex : 0, w.nbx = x == 0 ? ax.nb : 0;
+    return w;
+}
+
+// the per-pixel lists of k_build_near, re-expressed for the kernels: strip offsets instead of padded coordinates, grouped so that the
+// threads of a wave read consecutive words; the counted-sample count zeroed for pixels whose (clamped) position another window owns.
+// nrec[tab][NN_PAD], nent[group][tab][NN_PAD]; nn_out[tab] (if asked for): the table's pixels.  RY x RX: the windows' shape; W: the image's
+// width.  One thread per near-band pixel, grid (blocks of 256 pixels, tables)
+__global__ void __launch_bounds__(256)
+    k_near_tab(const int *__restrict__ ncu, const int *__restrict__ nyx, int NS, int PBy, int PBx, AxisTiles ty, AxisTiles tx, int RY, int RX, int W, AxisC ay,
+               AxisC ax, int *__restrict__ nn_out, uint2 *__restrict__ nrec, uint2 *__restrict__ nent)
+{
+    const int t = blockIdx.x * 256 + threadIdx.x, tab = blockIdx.y, ntabs = gridDim.y;
+    const NearWin w = near_window(ty, tx, tab, ay, ax);
+    const int nn = near_count(RY, RX, w.exy, w.exx, w.nby, w.nbx);
+    if (nn_out && t == 0)
+        nn_out[tab] = nn;
     if (t >= nn)
         return;
     int ngy, ngx, dst;
-    near_coords(t, PN, exy, exx, nby, nbx, ngy, ngx, dst);
-    const int ni = mosaic::near_index(ngy + 13, ngx + 13, PN + 27, PBy, PBx), pk = ncu[ni], cnt = pk & 255, cu = pk >> 8;
-    const int own = strip_off(ngy, ngx, exy, exx, nby);
-    nrec[t] = make_uint2((unsigned)cnt | (unsigned)cu << 8 | (unsigned)dst << 16, (unsigned)own);
+    near_coords(t, RX, w.exy, w.exx, w.nby, w.nbx, ngy, ngx, dst);
+    const int gy = w.oy + ngy, gx = w.ox + ngx;  // image (natural) coordinates
+    const int ni = mosaic::near_index(gy + 13, gx + 13, W + 27, PBy, PBx), pk = ncu[ni], cnt = pk & 255;
+    int cu = pk >> 8;
+    const int cy = max(ngy, 0), cx = max(ngx, 0);  // where its counted samples sit: the window that owns that pixel counts them
+    if (cy < w.y0 || cy >= w.y1 || cx < w.x0 || cx >= w.x1)
+        cu = 0;
+    const int own = strip_off(ngy, ngx, w.exy, w.exx, w.nby);
+    nrec[(size_t)tab * NN_PAD + t] = make_uint2((unsigned)cnt | (unsigned)cu << 8 | (unsigned)dst << 16, (unsigned)own);
     for (int g = 0; g < NS / 4; g++) {
         unsigned o[4];
         for (int e = 0; e < 4; e++) {
             const int c = nyx[(size_t)ni * NS + 4 * g + e];  // slots past cnt hold an in-range coordinate (k_build_near)
-            o[e] = 4 * g + e < cnt ? (unsigned)strip_off((c & 0xffff) - Ey, (c >> 16) - Ex, exy, exx, nby) : (unsigned)own;
+            o[e] = 4 * g + e < cnt ? (unsigned)strip_off((c & 0xffff) - ay.E - w.oy, (c >> 16) - ax.E - w.ox, w.exy, w.exx, w.nby) : (unsigned)own;
         }
-        nent[(size_t)g * NN_PAD + t] = make_uint2(o[0] | o[1] << 16, o[2] | o[3] << 16);
+        nent[((size_t)g * ntabs + tab) * NN_PAD + t] = make_uint2(o[0] | o[1] << 16, o[2] | o[3] << 16);
     }
 }
 
-// (M, Mu) of the near-band pixels of every patch.  grid (ceil(nn / 256), B)
+// (M, Mu) of the near-band pixels of every item: Mn[b][tab][NN_PAD].  P: the pair of T the iteration kernel reads Mn as (float2;
+// stile::T2<T>).  grid (blocks of 256 pixels, tables, B)
+template <typename T, typename P>
 __global__ void __launch_bounds__(256)
-    k_patch_near_m(const float *__restrict__ Mg, const float *__restrict__ Mu, int NB, int PBy, int PBx, int exy, int exx, int nby, int nbx,
-                   int nn, float2 *__restrict__ Mn)
+    k_near_m(const T *__restrict__ Mg, const T *__restrict__ Mu, int NB, int PBy, int PBx, AxisTiles ty, AxisTiles tx, int RY, int RX, int H, int W, AxisC ay,
+             AxisC ax, P *__restrict__ Mn)
 {
-    const int t = blockIdx.x * 256 + threadIdx.x, b = blockIdx.y;
-    if (t >= nn)
+    static_assert(sizeof(P) == 2 * sizeof(T), "a pair of samples");
+    const int t = blockIdx.x * 256 + threadIdx.x, tab = blockIdx.y, ntabs = gridDim.y, b = blockIdx.z;
+    const NearWin w = near_window(ty, tx, tab, ay, ax);
+    if (t >= near_count(RY, RX, w.exy, w.exx, w.nby, w.nbx))
         return;
     int ngy, ngx, dst;
-    near_coords(t, PN, exy, exx, nby, nbx, ngy, ngx, dst);
-    const int Wg = PN + 27, ni = mosaic::near_index(ngy + 13, ngx + 13, Wg, PBy, PBx);
-    Mn[(size_t)b * NN_PAD + t] = make_float2(Mg[((size_t)b * Wg + ngy + 13) * Wg + ngx + 13], Mu[(size_t)b * NB + ni]);
+    near_coords(t, RX, w.exy, w.exx, w.nby, w.nbx, ngy, ngx, dst);
+    const int gy = w.oy + ngy, gx = w.ox + ngx, Wg = W + 27, Hg = H + 27;
+    const int ni = mosaic::near_index(gy + 13, gx + 13, Wg, PBy, PBx);
+    P v;
+    v.x = Mg[((size_t)b * Hg + gy + 13) * Wg + gx + 13], v.y = Mu[(size_t)b * NB + ni];
+    Mn[((size_t)b * ntabs + tab) * NN_PAD + t] = v;
+}
+
+// The host side.  c: srx_mosaic.hpp's common_prep()'s tables (M, C, Mu, the near lists); ty, tx, RY, RX: the plan and the windows' shape;
+// ay, ax: the image's axis parameters (fill_axis); blocks: blocks of 256 near-band pixels a table is launched with, 0 when the call has no
+// near band.  near_tab() alone serves a call that builds the rest of its tables itself (patch::iterate on a full phase grid).
+template <typename T>
+static int near_tab(const mosaic::Common<T> &c, const AxisTiles &ty, const AxisTiles &tx, int RY, int RX, const AxisC &ay, const AxisC &ax, int blocks,
+                    int *nn_out, uint2 *nrec, uint2 *nent, hipStream_t st)
+{
+    hipLaunchKernelGGL(k_near_tab, dim3(blocks, ty.n + tx.n - 1), dim3(256), 0, st, c.ncu, c.nyx, c.NS, c.py.PB, c.px.PB, ty, tx, RY, RX, c.W, ay, ax, nn_out, nrec,
+                       nent);
+    SRX_CHECK_LAUNCH();
+    return SRX_OK;
+}
+// the m8 preset, the operand planes, the near-band descriptor lists and the near-band (M, Mu) pairs of a call
+template <typename T, typename P>
+static int block_setup(const mosaic::Common<T> &c, const AxisTiles &ty, const AxisTiles &tx, int RY, int RX, const AxisC &ay, const AxisC &ax, int blocks, T *Mt,
+                       T *Ct, unsigned *Mt8, int *m8, int *nn_out, uint2 *nrec, uint2 *nent, P *Mn, hipStream_t st)
+{
+    if (fill_bytes(m8, 0xff, (size_t)c.B * sizeof(int), st) != hipSuccess)
+        return SRX_E_HIP;
+    hipLaunchKernelGGL(k_block_prep<T>, dim3(cdiv(c.W, 32), cdiv(c.H, 32), c.B + 1), dim3(32, 8), 0, st, c.Mg, c.Cg, c.B, c.H, c.W, ay.nb, ax.nb, Mt, Ct, Mt8, m8);
+    SRX_CHECK_LAUNCH();
+    if (blocks > 0) {
+        SRX_TRY(near_tab(c, ty, tx, RY, RX, ay, ax, blocks, nn_out, nrec, nent, st));
+        hipLaunchKernelGGL((k_near_m<T, P>), dim3(blocks, ty.n + tx.n - 1, c.B), dim3(256), 0, st, c.Mg, c.Mu, c.NB, c.py.PB, c.px.PB, ty, tx, RY, RX, c.H, c.W, ay,
+                           ax, Mn);
+        SRX_CHECK_LAUNCH();
+    }
+    return SRX_OK;
 }
 
 // ---- the same tables straight from the LR frames, for full phase grids (c01: every far-field HR pixel holds at most one sample) ------
-// k_mosaic_build + k_patch_prep write and re-read an M plane of the whole batch (1024 patches: 328 MB out, 328 MB in, on top of the 268 MB
+// k_mosaic_build + k_block_prep write and re-read an M plane of the whole batch (1024 patches: 328 MB out, 328 MB in, on top of the 268 MB
 // of LR frames, with a gather that fetches 64 useful bytes per load instruction): 0.57 ms of a 12.6 ms C2 step.  On a full phase grid
 // row gy of M is the INTERLEAVE of one LR row of the f frames of its row class -- M[gy][gx] = lr[K[cy(gy)][cx(gx)]][iy(gy)][jx(gx)],
 // depth-to-space -- so the operand planes follow from the LR frames in one pass: a lane takes a column QUAD (for x4 the four frames of
@@ -1000,10 +1097,13 @@ static int iterate(const mosaic::Common<float> &c, const float *hr_init, float *
         return SRX_E_UNSUPPORTED;
     const int gform = gstep_form(py, px, N, f, pa.ry, pa.rx);
     pa.c01 = gform > 0 ? 1 : 0;
-    if (fill_bytes(m8, 0xff, (size_t)B * sizeof(int), st) != hipSuccess)
-        return SRX_E_HIP;
-    const bool own = c.own_build;  // (common_prep built no M / C / Mu)
-    if (own) {
+    const AxisTiles one = one_region(PN);
+    const int nblk = cdiv(pa.nn, 256);
+    if (!c.own_build) {
+        SRX_TRY((block_setup<float, float2>(c, one, one, PN, PN, pa.y, pa.x, nblk, Mt, Ct, Mt8, m8, nullptr, nrec, nent, Mn, st)));
+    } else {  // common_prep built no M / C / Mu: the same tables straight from the frames
+        if (fill_bytes(m8, 0xff, (size_t)B * sizeof(int), st) != hipSuccess)
+            return SRX_E_HIP;
         BuildMaps bm;
         int cy[SRX_MAX_FRAMES], cx[SRX_MAX_FRAMES], ny, nx;
         axis_map(py, N, f, bm.y, cy, ny);
@@ -1024,31 +1124,23 @@ static int iterate(const mosaic::Common<float> &c, const float *hr_init, float *
             SRX_LAUNCH(KID_PATCH_BUILD, k_patch_build<0>, dim3(PN / 16, B), dim3(256), 0, st, (const float *)c.lr, N, c.h, c.w, maps, m8, Mt, Mt8);
             SRX_LAUNCH(KID_PATCH_FLAGS, k_patch_build<1>, dim3(PN / 16, B), dim3(256), 0, st, (const float *)c.lr, N, c.h, c.w, maps, m8, Mt, Mt8);
         }
-    } else {
-        hipLaunchKernelGGL(k_patch_prep, dim3(PN / 32, PN / 32, B + 1), dim3(32, 8), 0, st, c.Mg, c.Cg, B, Hg, Wg, pa.y.nb, pa.x.nb, Mt, Ct, Mt8, m8);
-        SRX_CHECK_LAUNCH();
-    }
-    if (pa.nn > 0) {
-        hipLaunchKernelGGL(k_patch_near_tab, dim3(cdiv(pa.nn, 256)), dim3(256), 0, st, c.ncu, c.nyx, NS, py.PB, px.PB, pa.y.ex, pa.x.ex, pa.y.nb,
-                           pa.x.nb, pa.y.E, pa.x.E, pa.nn, nrec, nent);
-        SRX_CHECK_LAUNCH();
-        if (own && c.lr_u8)
-            hipLaunchKernelGGL(k_patch_near_build<uint8_t>, dim3(cdiv(pa.nn, 256), B), dim3(256), 0, st, (const uint8_t *)c.lr, N, c.h, c.w, c.tabY, c.tabX, Hg, Wg,
-                               py.D, px.D, pa.y.ex, pa.x.ex, pa.y.nb, pa.x.nb, pa.nn, Mn, c.Vtot);
-        else if (own)
-            hipLaunchKernelGGL(k_patch_near_build<float>, dim3(cdiv(pa.nn, 256), B), dim3(256), 0, st, (const float *)c.lr, N, c.h, c.w, c.tabY, c.tabX, Hg, Wg,
-                               py.D, px.D, pa.y.ex, pa.x.ex, pa.y.nb, pa.x.nb, pa.nn, Mn, c.Vtot);
-        else
-            hipLaunchKernelGGL(k_patch_near_m, dim3(cdiv(pa.nn, 256), B), dim3(256), 0, st, c.Mg, c.Mu, c.NB, py.PB, px.PB, pa.y.ex, pa.x.ex, pa.y.nb,
-                               pa.x.nb, pa.nn, Mn);
-        SRX_CHECK_LAUNCH();
+        if (pa.nn > 0) {
+            SRX_TRY(near_tab(c, one, one, PN, PN, pa.y, pa.x, nblk, nullptr, nrec, nent, st));
+            if (c.lr_u8)
+                hipLaunchKernelGGL(k_patch_near_build<uint8_t>, dim3(nblk, B), dim3(256), 0, st, (const uint8_t *)c.lr, N, c.h, c.w, c.tabY, c.tabX, Hg, Wg, py.D, px.D,
+                                   pa.y.ex, pa.x.ex, pa.y.nb, pa.x.nb, pa.nn, Mn, c.Vtot);
+            else
+                hipLaunchKernelGGL(k_patch_near_build<float>, dim3(nblk, B), dim3(256), 0, st, (const float *)c.lr, N, c.h, c.w, c.tabY, c.tabX, Hg, Wg, py.D, px.D,
+                                   pa.y.ex, pa.x.ex, pa.y.nb, pa.x.nb, pa.nn, Mn, c.Vtot);
+            SRX_CHECK_LAUNCH();
+        }
     }
     SRX_TRY(upload_record(st, aw, awp));
     const int psf = fused::psf_form(c.kc, c.kt);
     if (psf != 0)
         SRX_TRY(upload_k2(c.kc, c.kt, k2, st));
     PatchTabs tb{Mt, Mt8, m8, Ct, aw, nrec, nent, Mn, k2};
-    // both mosaic forms over the whole batch: every patch is iterated by exactly one of the two launches (k_patch_prep's m8 flag)
+    // both mosaic forms over the whole batch: every patch is iterated by exactly one of the two launches (the m8 flag)
 #define SRX_PATCH_PAIR(C01_, PSF_)                                                                                                              \
     do {                                                                                                                                        \
         SRX_LAUNCH(KID_IBP_PATCH, (k_ibp_patch<C01_, true, PSF_>), dim3(B), dim3(1024), 0, st, hr_init, hr, tb, pa, c.Vtot, c.scale, errors, n_iter);  \

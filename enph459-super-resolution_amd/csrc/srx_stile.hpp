@@ -21,7 +21,7 @@
 // both kernels run at the memory's pace (sv 2.15 GB in ~340 us, sh 1.14 GB in ~290), VALU time is a fifth of it.
 // The closed forms of SciPy's 12-sample pad and the carry fix-ups between blocks (z^(i+1) * carry over the first FIX samples; FIX = 28 in
 // float64: |z|^29 = 3e-17) are srx_block.hpp's, the source k_ibp_patch instantiates in float; the near band is srx_patch.hpp's, tables and
-// kernel code (patch::near_put_y, near_px, near_get_g in double).  Row -1 of Y / G (frames with n_k > 0) rides as plane row 0:
+// kernel code (patch::near_put_y, near_px, near_get_g in double; the tables and the operand planes from patch::block_setup in T).  Row -1 of Y / G (frames with n_k > 0) rides as plane row 0:
 // the planes between the kernels hold row q = gy + ex (the last grid row is empty then, srx_patch.hpp's axis_ok).
 #pragma once
 #include "srx_patch.hpp"
@@ -62,55 +62,7 @@ static inline bool eligible(const IbpSpec &s)
     return patch::eligible(s4, true);  // rank-1 PSFs only (rank 1 is decided on the float64 weights there too)
 }
 
-// ---- once per call: the patch path's operand planes in T ------------------------------------------------------------------------------
-// Mt[b][gx / 4][gy][gx % 4] = M[b][gy + 13][gx + 13] (near band zeroed), Ct likewise from C (plane index B); Mt8 the same as bytes, m8[b]
-// cleared when a far-field value of patch b is not an integer in [0, 255].  grid (8, 8, B + 1), block (32, 8)
-template <typename T>
-__global__ void __launch_bounds__(256)
-    k_stile_prep(const T *__restrict__ Mg, const T *__restrict__ Cg, int B, int Hg, int Wg, int nby, int nbx, T *__restrict__ Mt, T *__restrict__ Ct,
-                 unsigned *__restrict__ Mt8, int *__restrict__ m8)
-{
-    __shared__ T t[32][33];
-    const int b = blockIdx.z, x0 = blockIdx.x * 32, y0 = blockIdx.y * 32;
-    const T *src = b < B ? Mg + (size_t)b * Hg * Wg : Cg;
-    T *dst = b < B ? Mt + (size_t)b * PN * PN : Ct;
-    bool ok = true;
-    for (int r = threadIdx.y; r < 32; r += 8) {
-        T v = src[(size_t)(y0 + r + 13) * Wg + x0 + threadIdx.x + 13];
-        if (b < B && (y0 + r < nby || x0 + (int)threadIdx.x < nbx))
-            v = 0;
-        ok = ok && v == rint(v) && v >= (T)0 && v <= (T)255;
-        t[r][threadIdx.x] = v;
-    }
-    __syncthreads();
-    const int g = threadIdx.y;  // 8 groups of 4 columns; thread x = row of the tile
-    T *d = dst + ((size_t)(x0 / 4 + g) * PN + y0 + threadIdx.x) * 4;
-#pragma unroll
-    for (int c = 0; c < 4; c++)
-        d[c] = t[threadIdx.x][4 * g + c];
-    if (b < B) {
-        const unsigned w = (unsigned)t[threadIdx.x][4 * g] | (unsigned)t[threadIdx.x][4 * g + 1] << 8 | (unsigned)t[threadIdx.x][4 * g + 2] << 16 |
-                           (unsigned)t[threadIdx.x][4 * g + 3] << 24;
-        const int wr = x0 / 4 + g;
-        Mt8[(size_t)b * (PN / 4) * PN + ((size_t)(wr >> 2) * PN + y0 + threadIdx.x) * 4 + (wr & 3)] = w;
-    }
-    const bool bad = __syncthreads_or(b < B && !ok);
-    if (bad && threadIdx.x == 0 && threadIdx.y == 0)
-        atomicAnd(&m8[b], 0);
-}
-template <typename T>
-__global__ void __launch_bounds__(256)
-    k_stile_near_m(const T *__restrict__ Mg, const T *__restrict__ Mu, int NB, int PBy, int PBx, int exy, int exx, int nby, int nbx, int nn,
-                   T2<T> *__restrict__ Mn)
-{
-    const int t = blockIdx.x * 256 + threadIdx.x, b = blockIdx.y;
-    if (t >= nn)
-        return;
-    int ngy, ngx, dst;
-    patch::near_coords(t, PN, exy, exx, nby, nbx, ngy, ngx, dst);
-    const int Wg = PN + 27, ni = mosaic::near_index(ngy + 13, ngx + 13, Wg, PBy, PBx);
-    Mn[(size_t)b * NN_PAD + t] = T2<T>{Mg[((size_t)b * Wg + ngy + 13) * Wg + ngx + 13], Mu[(size_t)b * NB + ni]};
-}
+// (once per call: the patch path's operand planes and near-band tables in T -- patch::block_setup<T, T2<T>>)
 
 template <typename T> struct STabs {
     const T *Mt;           // [B][64 column quads][256 gy][4]
@@ -206,7 +158,7 @@ __global__ void __launch_bounds__(256, 2)
 // =====================================================================================================================================
 // k_ibp_sh: grid (4 row strips, B), block 256.  Lane = plane row q = 64 strip + lane (natural row gy = q - exy), wave u = columns 64 u ...
 // =====================================================================================================================================
-// The LR mosaic as bytes when every far-field sample of the patch is an integer in [0, 255] (k_stile_prep's flag), else as T: two instantiations of
+// The LR mosaic as bytes when every far-field sample of the patch is an integer in [0, 255] (k_block_prep's flag), else as T: two instantiations of
 // the body behind ONE workgroup-uniform branch at the very top of the kernel (k_ibp_dtile's arrangement: two whole bodies share no live range).
 // As a run-time choice inside one body -- even per group of eight columns, feeding the same arithmetic -- the allocator spilled 92 registers where
 // either form alone spills 1; as a pair of launches (k_ibp_patch's arrangement) the empty twin cost 4.8 us per chunk and iteration, 5 % of the loop.
@@ -409,7 +361,7 @@ static int iterate(const mosaic::Common<T> &c, const T *hr_init, T *hr, int n_it
     const int B = c.B, N = c.N, f = c.f, NS = c.NS;
     const mosaic::AxisPlan &py = c.py, &px = c.px;
     const double scale = c.scale;
-    const int Hg = PN + 27, Wg = PN + 27, ngrp = NS / 4;
+    const int ngrp = NS / 4;
     const auto [Mt, P, Mt8, m8, Ct, nrec, nent, Mn, epart] = carve<T>(ar, patch::Dims{(size_t)B, (size_t)ngrp});
     if (!ar.ok)
         return SRX_E_WORKSPACE;
@@ -423,18 +375,8 @@ static int iterate(const mosaic::Common<T> &c, const T *hr_init, T *hr, int n_it
     if (pa.nn > NN_PAD)
         return SRX_E_UNSUPPORTED;
     pa.c01 = patch::c01_masks(py, px, N, f, pa.ry, pa.rx) ? 1 : 0;
-    if (fill_bytes(m8, 0xff, (size_t)B * sizeof(int), st) != hipSuccess)
-        return SRX_E_HIP;
-    hipLaunchKernelGGL(k_stile_prep<T>, dim3(PN / 32, PN / 32, B + 1), dim3(32, 8), 0, st, c.Mg, c.Cg, B, Hg, Wg, pa.y.nb, pa.x.nb, Mt, Ct, Mt8, m8);
-    SRX_CHECK_LAUNCH();
-    if (pa.nn > 0) {
-        hipLaunchKernelGGL(patch::k_patch_near_tab, dim3(cdiv(pa.nn, 256)), dim3(256), 0, st, c.ncu, c.nyx, NS, py.PB, px.PB, pa.y.ex, pa.x.ex, pa.y.nb, pa.x.nb,
-                           pa.y.E, pa.x.E, pa.nn, nrec, nent);
-        SRX_CHECK_LAUNCH();
-        hipLaunchKernelGGL(k_stile_near_m<T>, dim3(cdiv(pa.nn, 256), B), dim3(256), 0, st, c.Mg, c.Mu, c.NB, py.PB, px.PB, pa.y.ex, pa.x.ex, pa.y.nb, pa.x.nb, pa.nn,
-                           Mn);
-        SRX_CHECK_LAUNCH();
-    }
+    const patch::AxisTiles one = patch::one_region(PN);
+    SRX_TRY((patch::block_setup<T, T2<T>>(c, one, one, PN, PN, pa.y, pa.x, cdiv(pa.nn, 256), Mt, Ct, Mt8, m8, nullptr, nrec, nent, Mn, st)));
     const T sn = (T)(c.step / (double)N);
     const int want = errors ? 1 : 0;
     // The batch in chunks of 128 patches, every launch of a chunk before the next chunk's first: 512 workgroups = one round of the 256

@@ -304,6 +304,12 @@ IBP_CASES = [
     _ibp_case("5x1", "composed", "f64", 2, [(0.25, 0.0), (-0.25, 0.0)], (5, 1), psf="asym"),
     _ibp_case("2x9_N1", "composed", "f32", 3, [(0.1, 0.2)], (2, 9), psf="asym5", B=3),   # 6 x 27 HR
 ]
+# Shapes beside "one case per path", held to the same contract.  A list of its own: tools/ws_sweep.py prints a block of
+# tests/golden/workspace_bytes.txt per entry of IBP_CASES, and that file stays as the parent of the carve functions printed it.
+IBP_MORE_CASES = [
+    # dtile: 272 x 208 HR -- two windows on each axis (three near-band tables), ragged last 32 x 32 tiles of the operand planes on both axes
+    _from(P.DTILE_CFGS, "x4_ph16_2x2win", "dtile", "f32", B=2),
+]
 
 
 def _ibp_id(c):
@@ -311,7 +317,7 @@ def _ibp_id(c):
     return f"srx_ibp_{c['prec']}-{c['path']}-{c['name']}{fl}"
 
 
-@pytest.mark.parametrize("c", IBP_CASES, ids=ids(_ibp_id(c) for c in IBP_CASES))
+@pytest.mark.parametrize("c", IBP_CASES + IBP_MORE_CASES, ids=ids(_ibp_id(c) for c in IBP_CASES + IBP_MORE_CASES))
 def test_ibp(c):
     prec, f, (h, w), B, n_iter, flags = c["prec"], c["f"], c["hw"], c["B"], c["n_iter"], c["flags"]
     dt, eb, L = DT[prec], EB[prec], lib()

@@ -827,7 +827,7 @@ def test_strip_kernels_f64_chunks_and_traceless_calls():
 
 def test_patch_tables_from_the_lr_frames_equal_the_plane_route():
     """Round 4: on a full phase grid the patch path builds its operand planes straight from the LR frames (k_patch_build -- the byte plane of every patch, then the
-    float plane of those with a sample that is not an 8-bit integer --, k_patch_near_build) instead of through the batch's M / C / Mu planes (k_mosaic_build, k_patch_prep, k_patch_near_m: kept, on request,
+    float plane of those with a sample that is not an 8-bit integer --, k_patch_near_build) instead of through the batch's M / C / Mu planes (k_mosaic_build, k_block_prep, k_near_m: kept, on request,
     as the cross-check).  Same tables, so the same bits: integer frames (byte mosaic), non-integer frames (float mosaic), a mixed batch,
     a 3 x 4 sub-grid, x2."""
     S.set_precision("f32")
@@ -854,6 +854,7 @@ DTILE_CFGS = {
     "x4_ph16_wide": (4, _PH4, (80, 100), "wide", True),                   # 2 x 2 windows of 4 x 4 waves
     "x4_ph16_float": (4, _PH4, (80, 100), "wide", False),                 # fractional samples: the float mosaic
     "x4_ph16_3x3win": (4, _PH4, (160, 176), 0, True),                     # interior windows (no image edge on any side)
+    "x4_ph16_2x2win": (4, _PH4, (68, 52), 0, True),                       # HR 272 x 208: 2 x 2 windows (three near-band tables), no side a multiple of 32
     "x2_ph4": (2, synth.phase_shifts(2), (150, 232), 0, True),            # n in {-1, 0}: nothing above / left of the image
     "x2_ph4_w240": (2, synth.phase_shifts(2), (128, 120), 0, True),       # HR 256 x 240: ONE 4 x 3-wave window; the arena sized by the shape-only bound
     "x4_n01": (4, [s for s in _PH4 if s[0] > 0 and s[1] > 0], (80, 100), 0, True),       # n in {0, 1}: samples above the image, no near band inside

@@ -50,6 +50,8 @@ CASES += [(f"dtile {pn} frac", "dtile", "f32", 1, 4, 64, 48, GRID16, pn, "frac")
 CASES += [("patch grid16x2", "patch", "f32", 3, 4, 64, 64, GRID16 * 2, "gauss", "u8"), ("patch grid16x2 core5", "patch", "f32", 2, 4, 64, 64, GRID16 * 2, "core5", "u8"),
           ("stile grid16x2", "stile", "f64", 3, 4, 64, 64, GRID16 * 2, "gauss", "u8"), ("dtile grid16x2", "dtile", "f32", 1, 4, 64, 48, GRID16 * 2, "gauss", "u8"),
           ("dtile grid12", "dtile", "f32", 1, 4, 64, 48, GRID12, "gauss", "u8"), ("dtile grid12 frac core5", "dtile", "f32", 1, 4, 64, 48, GRID12, "core5", "frac")]
+# HR 272 x 208: two windows on each axis -- three near-band tables -- and no side a multiple of 32: the ragged last tiles of the operand-plane kernel
+CASES += [("dtile 2x2 u8", "dtile", "f32", 2, 4, 68, 52, GRID16, "gauss", "u8"), ("dtile 2x2 grid12 frac", "dtile", "f32", 2, 4, 68, 52, GRID12, "core5", "frac")]
 
 
 # (reader of the flag, call, path, precision, B, f, LR h, LR w, shifts, flags off, flag): the smallest shapes that reach each reader
