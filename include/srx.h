@@ -96,7 +96,10 @@ typedef enum {
 #define SRX_FLAG_DIAG_WIDE_WINDOWS 0x1000u     /* delta != 0 frames: 256-column windows whatever the plan's cost model says */
 #define SRX_FLAG_DIAG_COLUMN_TILES 0x2000u    /* delta = 0 frames in float32: the transpose-free kernel (float64's default) instead of k_ibp_ztile */
 #define SRX_FLAG_DIAG_TWO_LAUNCH 0x4000u     /* common-fraction frames: the two-launch window kernels (srx_atile.hpp) also where k_ibp_dtile would run */
-#define SRX_FLAG_DIAG_V1 0x800u                /* per-frame fused path with stand-alone prefilter passes (8 launches / iteration) */
+#define SRX_FLAG_DIAG_V1 0x800u                /* per-frame fused path with stand-alone prefilter passes: 8 queued operations / iteration -- 8 kernel
+                                                * launches where the two prefilters are a row and a column kernel each (float64; float32 planes below
+                                                * 64 x 64 or under SRX_FLAG_DIAG_NO_PREFILTER_TILE), 6 kernel launches and 2 device-to-device copies
+                                                * where each is the tile kernel and the copy back from its scratch plane (float32 otherwise) */
 #define SRX_FLAG_DIAG_SAA_ONE_PASS 0x8000u   /* shift_and_add on a common fraction: the one-kernel form (accumulation over the frames with the
                                               * fractional shift's halo) instead of accumulate + shift (k_saa_tile<ACC> + k_saa_shift); same bits */
 #define SRX_FLAG_DIAG_U8_BYTE_LOADS 0x10000u /* srx_ibp_u8lr_f32, "patch" on a full phase grid: k_patch_build reads the frames one byte per lane also
