@@ -80,23 +80,55 @@ def _stream():
     return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
-def _to_dev(x, prec):
-    """-> (contiguous CUDA tensor of the compute dtype, was_numpy)"""
-    dt = _TORCH_DT[prec]
-    if isinstance(x, torch.Tensor):
-        return x.to(device=_device(), dtype=dt).contiguous(), False
-    a = np.ascontiguousarray(np.asarray(x))
-    if a.dtype != np.uint8:
-        a = a.astype(np.float64, copy=False)
-    return torch.from_numpy(a).to(device=_device()).to(dt).contiguous(), True
+def _to_dev(x, prec=None, *, allowed=None, as_is=(np.uint8,), what="input", error=TypeError):
+    """The one path from caller data to the device: tensor or array -> (contiguous CUDA tensor, was_numpy).
+    prec: 'f32' / 'f64' or a torch dtype, what the data is cast to ON THE DEVICE; None keeps the dtype, which must then be one of
+    `allowed` (None: any) or `error` is raised naming `what`.  as_is: the dtypes of host arrays that are uploaded as they are and cast
+    on the device; any other host array is widened to float64 on the host first.  None: every array is handed to torch as it is, like a
+    tensor (a cast to `prec` then comes before the upload).  The dtype is checked before the device is touched."""
+    dt = _TORCH_DT.get(prec, prec)
+    was_numpy = not isinstance(x, torch.Tensor)
+    if was_numpy:
+        a = np.ascontiguousarray(np.asarray(x))
+        if as_is is not None and a.dtype not in as_is:
+            a = a.astype(np.float64, copy=False)
+        x = torch.from_numpy(a)
+    if dt is None and allowed is not None and x.dtype not in allowed:
+        raise error(f"{what} must be one of {[str(d) for d in allowed]}, not {x.dtype}")
+    if was_numpy and as_is is not None:
+        x = x.to(device=_device())
+    return x.to(device=_device(), dtype=dt).contiguous(), was_numpy
 
 
-def _stack_dev(lst, prec):
-    if isinstance(lst, torch.Tensor):
-        return _to_dev(lst, prec)
+_BYTES = {"allowed": (torch.uint8,), "as_is": None}  # _to_dev's policy for the camera's samples: uint8 only, uploaded as bytes, never cast
+
+
+def _stack_dev(lst, prec=None, **policy):
+    """_to_dev of a stack of frames: a tensor or an array as it is, a sequence of tensors stacked on the device, any other sequence as
+    one host array (np.stack: a ValueError for frames of different shapes and for no frames, an empty array included)"""
+    if isinstance(lst, torch.Tensor) or isinstance(lst, np.ndarray) and len(lst):
+        return _to_dev(lst, prec, **policy)
     if len(lst) and isinstance(lst[0], torch.Tensor):
-        return torch.stack([t.to(device=_device(), dtype=_TORCH_DT[prec]) for t in lst]).contiguous(), False
-    return _to_dev(np.stack([np.asarray(a) for a in lst]), prec)
+        return _to_dev(torch.stack([t.to(device=_device(), dtype=_TORCH_DT.get(prec, prec)) for t in lst]), prec, **policy)[0], False
+    return _to_dev(np.stack([np.asarray(a) for a in lst]), prec, **policy)
+
+
+def _is_u8(x):
+    """x, or every frame of the sequence x, is a uint8 tensor or array (a plain list of numbers is not): what goes to the library as bytes"""
+    def u8(a):
+        return isinstance(a, (torch.Tensor, np.ndarray)) and a.dtype == (torch.uint8 if isinstance(a, torch.Tensor) else np.uint8)
+    return u8(x) if isinstance(x, (torch.Tensor, np.ndarray)) else len(x) > 0 and all(u8(f) for f in x)
+
+
+def _batch(x, ndim):
+    """x [...] of rank ndim - 1 or ndim -> (x with the optional leading batch axis, whether it had to be added); _unbatch takes it off again"""
+    single = x.dim() == ndim - 1
+    return (x[None] if single else x), single
+
+
+def _unbatch(out, single, was_numpy=False):
+    out = out[0] if single else out
+    return out.cpu().numpy() if was_numpy else out
 
 
 def _out(t, was_numpy):
@@ -212,37 +244,48 @@ def back_project_batched(error_lr, kernel, shift_yx, factor, hr_shape, precision
     return out
 
 
-def shift_and_add_batched(lr, shifts_yx, factor=2, precision=None, flags=FLAG_AUTO):
-    """lr [B, N, h, w] -> [B, h*f, w*f].  shifts_yx [N, 2], or [B, N, 2] for one table per item (srx_saa_items_*)."""
-    prec = precision or get_precision()
-    B, N, h, w = _shape4(lr, "lr")
+def _saa_batched(lr, u8, shifts_yx, factor, precision, flags):
+    """the body of shift_and_add_batched and, with u8 (the frames are and stay bytes), of shift_and_add_u8_batched"""
+    prec, what = precision or get_precision(), "lr_u8" if u8 else "lr"
+    B, N, h, w = _shape4(lr, what)
     sh, shp, per_item = _shift_tables(shifts_yx, B, N)
-    x, _ = _to_dev(lr, prec)
+    x = _to_dev(lr, what=what, **_BYTES)[0] if u8 else _to_dev(lr, prec)[0]
+    if u8 and per_item:  # no uint8 items entry point: the frames are converted on the device ((T)uint8 is exact: the same bits)
+        return _saa_batched(u8_to_float(x, prec), False, sh, factor, prec, flags)
     f = int(factor)
-    out = torch.empty((B, h * f, w * f), dtype=x.dtype, device=x.device)
-    name = "srx_saa_items" if per_item else "srx_saa"
+    out = torch.empty((B, h * f, w * f), dtype=_TORCH_DT[prec], device=x.device)
+    name = "srx_saa_u8lr" if u8 else "srx_saa_items" if per_item else "srx_saa"
     wt, wp, wn = _ws(getattr(_lib.load(), name + "_workspace_bytes")(_ELEM[prec], B, N, h, w, f))
     _lib.check(_fn(name, prec)(_p(x), B, N, h, w, shp, f, _p(out), wp, wn, _stream(), flags), name)
     return out
 
 
-def ibp_batched(lr, shifts_yx, kernel, hr_init, factor=2, n_iter=80, step=0.5, precision=None, flags=FLAG_AUTO,
-                want_errors=True, out=None, exact_workspace=True):
-    """lr [B, N, h, w], hr_init [B, H, W] -> (hr [B, H, W], errors float64 [B, n_iter] or None).
-    `exact_workspace=False` sizes the arena by the shape-only bound (srx_ibp_workspace_bytes), as a caller without the shift table
-    at hand would.  shifts_yx [N, 2], or [B, N, 2] for one table per item (srx_ibp_items_*: item b gets the bits of a B = 1 call
-    on shifts_yx[b])."""
-    prec = precision or get_precision()
-    B, N, h, w = _shape4(lr, "lr")
+def shift_and_add_batched(lr, shifts_yx, factor=2, precision=None, flags=FLAG_AUTO):
+    """lr [B, N, h, w] -> [B, h*f, w*f].  shifts_yx [N, 2], or [B, N, 2] for one table per item (srx_saa_items_*)."""
+    return _saa_batched(lr, False, shifts_yx, factor, precision, flags)
+
+
+def shift_and_add_u8_batched(lr_u8, shifts_yx, factor=2, precision=None, flags=FLAG_AUTO):
+    """shift_and_add_batched on the camera's own samples: lr_u8 uint8 [B, N, h, w] -> [B, h*f, w*f] of the compute precision; the same
+    bits as shift_and_add_batched on the converted frames (srx_saa_u8lr_*)."""
+    return _saa_batched(lr_u8, True, shifts_yx, factor, precision, flags)
+
+
+def _ibp_batched(lr, u8, shifts_yx, kernel, hr_init, factor, n_iter, step, precision, flags, want_errors, out, exact_workspace):
+    """the body of ibp_batched and, with u8 (the frames are and stay bytes), of ibp_u8_batched"""
+    prec, what = precision or get_precision(), "lr_u8" if u8 else "lr"
+    B, N, h, w = _shape4(lr, what)
     sh, shp, per_item = _shift_tables(shifts_yx, B, N)
-    x, _ = _to_dev(lr, prec)
+    x = _to_dev(lr, what=what, **_BYTES)[0] if u8 else _to_dev(lr, prec)[0]
+    if u8 and per_item:  # as in _saa_batched
+        return _ibp_batched(u8_to_float(x, prec), False, sh, kernel, hr_init, factor, n_iter, step, prec, flags, want_errors, out, exact_workspace)
     h0, _ = _to_dev(hr_init, prec)
     Bh, H, W = h0.shape
     if Bh != B:
-        raise ValueError("lr and hr_init disagree on the batch size")
+        raise ValueError(f"{what} and hr_init disagree on the batch size")
     f = int(factor)
     k, kp = _host_f64(kernel)
-    name = "srx_ibp_items" if per_item else "srx_ibp"
+    name = "srx_ibp_u8lr" if u8 else "srx_ibp_items" if per_item else "srx_ibp"
     if out is not None:  # the library writes B*H*W elements of the call's precision straight through this pointer
         if (not isinstance(out, torch.Tensor) or not out.is_cuda or out.dtype != _TORCH_DT[prec] or tuple(out.shape) != (B, H, W)
                 or not out.is_contiguous()):
@@ -258,67 +301,20 @@ def ibp_batched(lr, shifts_yx, kernel, hr_init, factor=2, n_iter=80, step=0.5, p
     return hr, errors
 
 
-def _u8_dev(x, what, ndim):
-    """uint8 tensor / array -> contiguous uint8 CUDA tensor, uploaded as bytes; any other dtype is a TypeError (no silent cast)"""
-    if isinstance(x, torch.Tensor):
-        if x.dtype != torch.uint8:
-            raise TypeError(f"{what} must be uint8, not {x.dtype}")
-        t = x
-    else:
-        a = np.asarray(x)
-        if a.dtype != np.uint8:
-            raise TypeError(f"{what} must be uint8, not {a.dtype}")
-        t = torch.from_numpy(np.ascontiguousarray(a))
-    if t.dim() != ndim:
-        raise ValueError(f"{what} must have {ndim} dimensions")
-    return t.to(device=_device()).contiguous()
-
-
-def shift_and_add_u8_batched(lr_u8, shifts_yx, factor=2, precision=None, flags=FLAG_AUTO):
-    """shift_and_add_batched on the camera's own samples: lr_u8 uint8 [B, N, h, w] -> [B, h*f, w*f] of the compute precision; the same
-    bits as shift_and_add_batched on the converted frames (srx_saa_u8lr_*)."""
-    prec = precision or get_precision()
-    B, N, h, w = _shape4(lr_u8, "lr_u8")
-    sh, shp, per_item = _shift_tables(shifts_yx, B, N)
-    x = _u8_dev(lr_u8, "lr_u8", 4)
-    if per_item:  # no uint8 items entry point: the frames are converted on the device ((T)uint8 is exact: the same bits)
-        return shift_and_add_batched(u8_to_float(x, prec), sh, factor, prec, flags)
-    f = int(factor)
-    out = torch.empty((B, h * f, w * f), dtype=_TORCH_DT[prec], device=x.device)
-    wt, wp, wn = _ws(_lib.load().srx_saa_u8lr_workspace_bytes(_ELEM[prec], B, N, h, w, f))
-    _lib.check(_fn("srx_saa_u8lr", prec)(_p(x), B, N, h, w, shp, f, _p(out), wp, wn, _stream(), flags), "srx_saa_u8lr")
-    return out
+def ibp_batched(lr, shifts_yx, kernel, hr_init, factor=2, n_iter=80, step=0.5, precision=None, flags=FLAG_AUTO,
+                want_errors=True, out=None, exact_workspace=True):
+    """lr [B, N, h, w], hr_init [B, H, W] -> (hr [B, H, W], errors float64 [B, n_iter] or None).
+    `exact_workspace=False` sizes the arena by the shape-only bound (srx_ibp_workspace_bytes), as a caller without the shift table
+    at hand would.  shifts_yx [N, 2], or [B, N, 2] for one table per item (srx_ibp_items_*: item b gets the bits of a B = 1 call
+    on shifts_yx[b])."""
+    return _ibp_batched(lr, False, shifts_yx, kernel, hr_init, factor, n_iter, step, precision, flags, want_errors, out, exact_workspace)
 
 
 def ibp_u8_batched(lr_u8, shifts_yx, kernel, hr_init, factor=2, n_iter=80, step=0.5, precision=None, flags=FLAG_AUTO,
                    want_errors=True, out=None, exact_workspace=True):
     """ibp_batched on the camera's own samples: lr_u8 uint8 [B, N, h, w], hr_init [B, H, W] -> (hr, errors); the same bits as
     ibp_batched on the converted frames (srx_ibp_u8lr_*)."""
-    prec = precision or get_precision()
-    B, N, h, w = _shape4(lr_u8, "lr_u8")
-    sh, shp, per_item = _shift_tables(shifts_yx, B, N)
-    x = _u8_dev(lr_u8, "lr_u8", 4)
-    if per_item:  # as in shift_and_add_u8_batched
-        return ibp_batched(u8_to_float(x, prec), sh, kernel, hr_init, factor, n_iter, step, prec, flags, want_errors, out, exact_workspace)
-    h0, _ = _to_dev(hr_init, prec)
-    Bh, H, W = h0.shape
-    if Bh != B:
-        raise ValueError("lr_u8 and hr_init disagree on the batch size")
-    f = int(factor)
-    k, kp = _host_f64(kernel)
-    if out is not None:
-        if (not isinstance(out, torch.Tensor) or not out.is_cuda or out.dtype != _TORCH_DT[prec] or tuple(out.shape) != (B, H, W)
-                or not out.is_contiguous()):
-            raise ValueError(f"out must be a contiguous CUDA tensor of dtype {_TORCH_DT[prec]} and shape {(B, H, W)}")
-    hr = torch.empty_like(h0) if out is None else out
-    errors = torch.empty((B, int(n_iter)), dtype=torch.float64, device=x.device) if want_errors else None
-    lib = _lib.load()
-    wt, wp, wn = _ws(lib.srx_ibp_u8lr_workspace_bytes_for(_ELEM[prec], B, N, h, w, H, W, f, shp, kp, k.shape[0], k.shape[1], flags)
-                     if exact_workspace else lib.srx_ibp_u8lr_workspace_bytes(_ELEM[prec], B, N, h, w, H, W, f, flags))
-    _lib.check(_fn("srx_ibp_u8lr", prec)(_p(x), B, N, h, w, shp, kp, k.shape[0], k.shape[1], _p(h0), H, W, f, int(n_iter),
-                                         float(step), _p(hr), _p(errors) if want_errors else None, wp, wn, _stream(), flags),
-               "srx_ibp_u8lr")
-    return hr, errors
+    return _ibp_batched(lr_u8, True, shifts_yx, kernel, hr_init, factor, n_iter, step, precision, flags, want_errors, out, exact_workspace)
 
 
 class IbpPlan:
@@ -449,18 +445,14 @@ def extract_red(img):
 
 def decimate_u8(img_u8, f, py=0, px=0):
     """img[..., py::f, px::f] on bytes: uint8 [H, W] or [B, H, W] -> uint8 (srx_decimate_u8); numpy in -> numpy out."""
-    was_np = not isinstance(img_u8, torch.Tensor)
-    if (img_u8.dim() if not was_np else np.ndim(img_u8)) not in (2, 3):
+    if np.ndim(img_u8) not in (2, 3):
         raise ValueError("img_u8 must be [H, W] or [B, H, W]")
-    single = (img_u8.dim() if not was_np else np.ndim(img_u8)) == 2
-    x = _u8_dev(img_u8, "img_u8", 2 if single else 3)
-    if single:
-        x = x[None]
+    x, was_np = _to_dev(img_u8, what="img_u8", **_BYTES)
+    x, single = _batch(x, 3)
     B, H, W = x.shape
     out = torch.empty((B, -(-(H - py) // f), -(-(W - px) // f)), dtype=torch.uint8, device=x.device)
     _lib.check(_lib.load().srx_decimate_u8(_p(x), B, H, W, int(f), int(py), int(px), _p(out), _stream()), "srx_decimate_u8")
-    out = out[0] if single else out
-    return out.cpu().numpy() if was_np else out
+    return _unbatch(out, single, was_np)
 
 
 def extract_red_u8(img_u8):
@@ -505,7 +497,7 @@ def mean_u8(stack_u8, f=1, py=0, px=0, precision=None):
     np.mean(lr_frames, 0) (run_sr.py:274); the same bits as mean_frames_batched on decimate on u8_to_float, without the float frames."""
     prec = precision or get_precision()
     B, R, H, W = _shape4(stack_u8, "stack_u8")
-    x = _u8_dev(stack_u8, "stack_u8", 4)
+    x, _ = _to_dev(stack_u8, what="stack_u8", **_BYTES)
     f, py, px = int(f), int(py), int(px)
     if f <= 0 or not (0 <= py < H and 0 <= px < W):
         raise ValueError("mean_u8 needs f > 0, 0 <= py < H and 0 <= px < W")
@@ -539,14 +531,8 @@ def png_deflate(images):
 
 def _png_input(images):
     """-> (device tensor [B, H, W], the entry points' suffix): uint8 stays bytes, anything else becomes the working precision"""
-    is_u8 = (images.dtype == torch.uint8) if isinstance(images, torch.Tensor) else (np.asarray(images).dtype == np.uint8)
-    if is_u8:
-        x = images if isinstance(images, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(images))
-        x, kind = x.to(device=_device()).contiguous(), "u8"
-    else:
-        x, kind = _to_dev(images, get_precision())[0], get_precision()
-    if x.dim() == 2:
-        x = x[None]
+    kind = "u8" if _is_u8(images) else get_precision()
+    x, _ = _batch(_to_dev(images, None if kind == "u8" else kind)[0], 3)
     if x.dim() != 3:
         raise ValueError("images must have the shape [B, H, W] or [H, W]")
     return x, kind
@@ -579,12 +565,9 @@ def crc32(data, lengths=None, seed=0):
     """zlib.crc32 of device buffers (srx_crc32): `data` a [B, n] or [n] uint8 tensor / array, item b its row's first min(lengths[b], n) bytes
     (lengths: int64 [B] tensor / array, read on the device; None: whole rows), `seed` as in zlib.crc32(item, seed).
     -> int64 device tensor [B], values in [0, 2^32); nothing is synchronised."""
-    x = data if isinstance(data, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(data))
-    if x.dtype != torch.uint8 or x.dim() not in (1, 2):
-        raise ValueError("data must be a uint8 tensor or array of the shape [B, n] or [n]")
-    x = x.to(device=_device()).contiguous()
-    if x.dim() == 1:
-        x = x[None]
+    if np.ndim(data) not in (1, 2):
+        raise ValueError("data must have the shape [B, n] or [n]")
+    x, _ = _batch(_to_dev(data, what="data", error=ValueError, **_BYTES)[0], 2)
     B, n = (int(v) for v in x.shape)
     seed = int(seed)
     if B <= 0 or not 0 <= seed < (1 << 32):
@@ -606,8 +589,7 @@ def crc32(data, lengths=None, seed=0):
 def u8_to_float(img_u8, precision=None):
     """uint8 frame -> float on the device (load_gray's cast, run_sr.py:73-75)."""
     prec = precision or get_precision()
-    t = img_u8 if isinstance(img_u8, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(img_u8))
-    t = t.to(device=_device(), dtype=torch.uint8).contiguous()
+    t, _ = _to_dev(img_u8, torch.uint8, as_is=None)  # (any other dtype is cast without a word)
     out = torch.empty(t.shape, dtype=_TORCH_DT[prec], device=t.device)
     _lib.check(_fn("srx_u8_to", prec)(_p(t), t.numel(), _p(out), _stream()), "srx_u8_to")
     return out
@@ -624,16 +606,11 @@ def make_gaussian_psf(size=7, sigma=1.0):
 def interleave4(frames_u8):
     """The vendor live view's 4-frame pixel interleave (XPR_Software.py:388-410): uint8 [4, h, w] (or [B, 4, h, w])
     -> uint8 [2h, 2w]; frame k lands on the HR lattice phase its half-pixel shift corresponds to."""
-    t = frames_u8 if isinstance(frames_u8, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(frames_u8))
-    was_np = not isinstance(frames_u8, torch.Tensor)
-    t = t.to(device=_device(), dtype=torch.uint8).contiguous()
-    single = t.dim() == 3
-    if single:
-        t = t[None]
+    t, was_np = _to_dev(frames_u8, torch.uint8, as_is=None)  # (as u8_to_float)
+    t, single = _batch(t, 4)
     B, four, h, w = t.shape
     if four != 4:
         raise ValueError("interleave4 needs exactly 4 frames")
     out = torch.empty((B, 2 * h, 2 * w), dtype=torch.uint8, device=t.device)
     _lib.check(_lib.load().srx_interleave4_u8(_p(t), B, h, w, _p(out), _stream()), "srx_interleave4_u8")
-    out = out[0] if single else out
-    return out.cpu().numpy() if was_np else out
+    return _unbatch(out, single, was_np)

@@ -22,18 +22,11 @@ from . import _lib, api, metrics
 _c = ctypes
 
 
-def _dev64(x):
-    """-> contiguous float64 CUDA tensor (uint8 / float inputs alike: the notebook works on the PNGs' values as float64)"""
-    if isinstance(x, torch.Tensor):
-        return x.to(device=api._device(), dtype=torch.float64).contiguous()
-    return torch.from_numpy(np.ascontiguousarray(np.asarray(x, dtype=np.float64))).to(api._device())
-
-
-def _dev(x):
-    """-> (contiguous float32 / float64 CUDA tensor, 'f32' | 'f64'): tensors keep their precision, everything else becomes float64"""
-    if isinstance(x, torch.Tensor) and x.dtype == torch.float32:
-        return x.to(device=api._device()).contiguous(), "f32"
-    return _dev64(x), "f64"
+def _image(x, prec=None):
+    """-> (contiguous CUDA tensor, 'f32' | 'f64'): float32 tensors are computed in float32, everything else (uint8 / float alike: the
+    notebook works on the PNGs' values as float64) in float64, unless `prec` says which; host arrays go up as float64 (api._to_dev)"""
+    prec = prec or ("f32" if isinstance(x, torch.Tensor) and x.dtype == torch.float32 else "f64")
+    return api._to_dev(x, prec, as_is=())[0], prec
 
 
 def _ws(B, H, W, nbin):
@@ -48,12 +41,7 @@ def pair_moments(ref, test, border=0):
 
 def pair_moments_device(ref, test, border=0):
     """pair_moments without the copy back: the [B, 7] float64 device tensor, nothing synchronised"""
-    r, prec = _dev(ref)
-    t = test.to(device=r.device, dtype=r.dtype).contiguous() if isinstance(test, torch.Tensor) else _dev64(test).to(r.dtype)
-    if r.dim() == 2:
-        r, t = r[None], t[None]
-    if r.shape != t.shape:
-        raise ValueError("ref and test differ in shape")
+    r, t, prec, _ = _pair(ref, test)
     B, H, W = r.shape
     out = torch.empty((B, 7), dtype=torch.float64, device=r.device)
     wt, wp, wn = _ws(B, H, W, 1)
@@ -93,11 +81,11 @@ def _np_dtype(x):
 
 def _pair(ref, test):
     """-> (ref, test) as [B, H, W] device tensors of one precision, the precision, whether the input was one image"""
-    r, prec = _dev(ref)
-    t = test.to(device=r.device, dtype=r.dtype).contiguous() if isinstance(test, torch.Tensor) else _dev64(test).to(r.dtype)
-    one = r.dim() == 2
+    r, prec = _image(ref)
+    t, _ = _image(test, prec)
+    r, one = api._batch(r, 3)
     if one:
-        r, t = r[None], t[None]
+        t = t[None]
     if r.shape != t.shape or r.dim() != 3:
         raise ValueError("ref and test must be [H, W] or [B, H, W] of the same shape")
     return r, t, prec, one
@@ -113,7 +101,7 @@ def _ssim(r, t, prec, one, dtype, affine, *, win_size=None, data_range=None, gau
     taps = np.ascontiguousarray(taps, dtype=np.float64)
     mssim = torch.empty(B, dtype=torch.float64, device=r.device)
     smap = torch.empty((B, h, w), dtype=r.dtype, device=r.device) if full else None
-    aff = None if affine is None else torch.from_numpy(np.ascontiguousarray(affine, dtype=np.float64)).to(r.device)
+    aff = None if affine is None else _image(affine, "f64")[0]
     wt, wp, wn = _ws(B, H, W, 1)
     _lib.check(api._fn("srx_ssim", prec)(api._p(r), api._p(t), B, H, W, int(border), rad, taps.ctypes.data_as(_lib._HD),
                                          int(bool(use_sample_covariance)), dr, float(K1), float(K2), None if aff is None else api._p(aff),
@@ -161,18 +149,13 @@ def ecc(ref, test, border=0):
 
 def local_contrast(profile, window=20):
     """metrics.local_contrast of a device profile [n] (or [B, n]); float64 numpy out."""
-    p = _dev64(profile)
-    one = p.dim() == 1
-    p = p[None] if one else p
-    out = torch.empty_like(p)
-    _lib.check(_lib.load().srx_local_contrast_f64(api._p(p), p.shape[0], p.shape[1], int(window), api._p(out), api._stream()), "srx_local_contrast")
-    res = out.cpu().numpy()
-    return res[0] if one else res
+    p, one = api._batch(_image(profile, "f64")[0], 2)
+    return api._unbatch(local_contrast_device(p, window), one, True)
 
 
 def radial_average(data_2d, center=None, max_radius=None):
     """metrics.radial_average on a device image: (radii, ring means)."""
-    d, prec = _dev(data_2d)
+    d, prec = _image(data_2d)
     h, w = d.shape
     cy, cx = (0.5 * h, 0.5 * w) if center is None else center
     if max_radius is None:
@@ -190,7 +173,7 @@ def radial_average(data_2d, center=None, max_radius=None):
 
 def subpixel_centre(psf):
     """metrics.subpixel_centre on a device PSF image: (row, col) first moments where it exceeds a tenth of its peak."""
-    p, prec = _dev(psf)
+    p, prec = _image(psf)
     out = torch.empty(4, dtype=torch.float64, device=p.device)
     _lib.check(api._fn("srx_spot_moments", prec)(api._p(p), p.shape[0], p.shape[1], api._p(out), api._stream()), "srx_spot_moments")
     _, mass, sy, sx = out.cpu().numpy()
@@ -209,7 +192,7 @@ def compute_mtf(psf, pixel_pitch_um=None):
 
 def edge_magnitude(roi, sigma=1.5):
     """Sobel magnitude of the Gaussian-smoothed ROI (scipy.ndimage 'reflect' boundaries), device float64 tensor."""
-    r = _dev64(roi)
+    r, _ = _image(roi, "f64")
     h, w = r.shape
     mag = torch.empty_like(r)
     wt, wp, wn = _ws(1, h, w, 1)
@@ -222,7 +205,7 @@ def slanted_edge_esf(roi, side="left", verbose=False):
     normal and the 1/4-px binning run in libsrx; the percentile and the two line fits over the edge pixels run on the host from the
     magnitude image (one small device-to-host copy).  Returns (esf_x, esf_y, angle_deg)."""
     lib = _lib.load()
-    r = _dev64(roi)
+    r, _ = _image(roi, "f64")
     h, w = r.shape
     mag = edge_magnitude(r).cpu().numpy()
     rs, cs = np.where(mag > np.percentile(mag, 85))
@@ -336,7 +319,7 @@ def edge_sfr(images, side="left", sigma=1.5):
 
 def local_contrast_device(profile, window=16):
     """local_contrast without the copy back: profile [B, n] on the device -> float64 device tensor [B, n]"""
-    p = _dev64(profile)
+    p, _ = _image(profile, "f64")
     out = torch.empty_like(p)
     _lib.check(_lib.load().srx_local_contrast_f64(api._p(p), p.shape[0], p.shape[1], int(window), api._p(out), api._stream()), "srx_local_contrast")
     return out

@@ -61,22 +61,14 @@ _GATHER = {torch.uint8: "srx_patches_gather_u8", torch.float32: "srx_patches_gat
 _BLEND = {torch.float32: "srx_patches_blend_f32", torch.float64: "srx_patches_blend_f64"}
 
 
-def _dev(x, what, table):
-    if not isinstance(x, torch.Tensor):
-        a = np.ascontiguousarray(np.asarray(x))
-        x = torch.from_numpy(a if a.dtype in (np.uint8, np.float32, np.float64) else a.astype(np.float64))
-    if x.dtype not in table:
-        raise TypeError(f"{what} must be one of {[str(k) for k in table]}, not {x.dtype}")
-    return x.to(device=api._device()).contiguous()
+_AS_IS = (np.uint8, np.float32, np.float64)  # host arrays of these element types are kept; any other becomes float64 (api._to_dev)
 
 
 def gather(frames, grid):
     """frames [N, h, w] or [B, N, h, w] (uint8, float32 or float64; the element type is kept) -> device tensor [B P, N, patch_lr,
     patch_lr], the layout of the batched per-item calls: item b P + iy gx + ix is the patch at (grid.oy_lr[iy], grid.ox_lr[ix]) of
     batch item b (srx_patches_gather_*: one launch, a pure index map)."""
-    x = _dev(frames, "frames", _GATHER)
-    if x.dim() == 3:
-        x = x[None]
+    x, _ = api._batch(api._to_dev(frames, allowed=_GATHER, as_is=_AS_IS, what="frames")[0], 4)
     if x.dim() != 4 or tuple(x.shape[2:]) != (grid.h, grid.w):
         raise ValueError(f"frames must be [N, {grid.h}, {grid.w}] or [B, N, {grid.h}, {grid.w}], not {tuple(x.shape)}")
     B, N = int(x.shape[0]), int(x.shape[1])
@@ -90,7 +82,7 @@ def gather(frames, grid):
 def blend(hr_patches, grid):
     """HR patches [B P, L_hr, L_hr] (float32 or float64) -> device tensor [B, H, W]: every sample the weighted mean of the patches
     over it, weights as include/srx.h states them (srx_patches_blend_*: one launch)."""
-    x = _dev(hr_patches, "hr_patches", _BLEND)
+    x, _ = api._to_dev(hr_patches, allowed=_BLEND, as_is=_AS_IS, what="hr_patches")
     if x.dim() != 3 or tuple(x.shape[1:]) != (grid.L_hr, grid.L_hr) or x.shape[0] % grid.P or x.shape[0] == 0:
         raise ValueError(f"hr_patches must be [B * {grid.P}, {grid.L_hr}, {grid.L_hr}], not {tuple(x.shape)}")
     B = int(x.shape[0]) // grid.P

@@ -20,7 +20,7 @@ def _check(frames, halfwidth):
     if hw != halfwidth or not 1 <= hw <= MAX_HALFWIDTH:
         raise ValueError(f"halfwidth {halfwidth} outside [1, {MAX_HALFWIDTH}]")
     if isinstance(frames, (torch.Tensor, np.ndarray)):
-        shape, dtypes = tuple(frames.shape), {frames.dtype}
+        shape = tuple(frames.shape)
         if len(shape) != 3:
             raise ValueError(f"frames must be [N, H, W], got shape {shape}")
     else:
@@ -33,28 +33,18 @@ def _check(frames, halfwidth):
         (hw_shape,) = shapes
         if len(hw_shape) != 2:
             raise ValueError(f"every frame must be [H, W], got shape {hw_shape}")
-        shape, dtypes = (len(frames),) + hw_shape, {f.dtype if hasattr(f, "dtype") else np.asarray(f).dtype for f in frames}
+        shape = (len(frames),) + hw_shape
     N, H, W = shape
     if N < 1 or H < 1 or W < 1:
         raise ValueError(f"frames is empty: shape {shape}")
     if N > 65535:
         raise ValueError(f"at most 65535 frames, got {N}")
-    return N, H, W, all(d in (np.dtype(np.uint8), torch.uint8) for d in dtypes)
+    return N, H, W, api._is_u8(frames)
 
 
 def workspace_bytes(elem_bytes, N, H, W, halfwidth=session.PSF_HALFWIDTH):
     """srx_psf_estimate_workspace_bytes (no GPU needed)"""
     return int(_lib.load().srx_psf_estimate_workspace_bytes(int(elem_bytes), int(N), int(H), int(W), int(halfwidth)))
-
-
-def _stack_u8(frames):
-    if isinstance(frames, torch.Tensor):
-        return frames.to(api._device()).contiguous()
-    if isinstance(frames, np.ndarray):
-        return torch.from_numpy(np.ascontiguousarray(frames)).to(api._device())
-    if isinstance(frames[0], torch.Tensor):
-        return torch.stack([f.to(api._device()) for f in frames]).contiguous()
-    return torch.from_numpy(np.stack([np.asarray(f) for f in frames])).to(api._device())
 
 
 def estimate_psf(frames, halfwidth=session.PSF_HALFWIDTH, full=False, precision=None):
@@ -66,7 +56,7 @@ def estimate_psf(frames, halfwidth=session.PSF_HALFWIDTH, full=False, precision=
     if not isinstance(frames, (torch.Tensor, np.ndarray)):
         frames = list(frames)
     if is_u8:
-        x, fn, eb = _stack_u8(frames), _lib.load().srx_psf_estimate_u8, 1
+        x, fn, eb = api._stack_dev(frames)[0], _lib.load().srx_psf_estimate_u8, 1
     else:
         prec = precision or api.get_precision()
         x, _ = api._stack_dev(frames, prec)

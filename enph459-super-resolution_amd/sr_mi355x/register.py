@@ -53,25 +53,6 @@ def _check(shape, ref, init, anchor, search, border, n_iter, tol):
     return B, N, H, W, batched, init, anchor
 
 
-def _is_u8(frames):
-    """every frame is uint8 (a numpy array, a torch tensor, or a list of either): the stack goes to srx_register_u8_* as bytes"""
-    def u8(a):
-        return a.dtype == torch.uint8 if isinstance(a, torch.Tensor) else isinstance(a, np.ndarray) and a.dtype == np.uint8
-    return u8(frames) if isinstance(frames, (torch.Tensor, np.ndarray)) else all(u8(f) for f in frames)
-
-
-def _stack_u8(frames):
-    """uint8 frames -> one contiguous uint8 CUDA tensor; host arrays are uploaded as bytes"""
-    if isinstance(frames, np.ndarray):
-        frames = torch.from_numpy(np.ascontiguousarray(frames))
-    elif not isinstance(frames, torch.Tensor):
-        if isinstance(frames[0], torch.Tensor):
-            frames = torch.stack([f.to(api._device()) for f in frames])
-        else:
-            frames = torch.from_numpy(np.stack(frames))
-    return frames.to(api._device()).contiguous()
-
-
 def workspace_bytes(elem_bytes, B, N, H, W, search):
     """srx_register_workspace_bytes (no GPU needed)"""
     return int(_lib.load().srx_register_workspace_bytes(int(elem_bytes), int(B), int(N), int(H), int(W), int(search)))
@@ -89,9 +70,8 @@ def estimate_shifts(frames, ref=0, init=None, anchor=None, search=2, border=8, n
     converted to the compute precision give, with no float copy of them anywhere."""
     B, N, H, W, batched, init, anchor = _check(_shape(frames), ref, init, anchor, search, border, n_iter, tol)
     prec = precision or api.get_precision()
-    name = "srx_register_u8" if _is_u8(frames) else "srx_register"
-    x = _stack_u8(frames) if name == "srx_register_u8" else api._stack_dev(frames, prec)[0]
-    x = x.reshape(B, N, H, W)
+    name = "srx_register_u8" if api._is_u8(frames) else "srx_register"  # (uint8 frames go up and stay as they are)
+    x = api._stack_dev(frames, None if name == "srx_register_u8" else prec)[0].reshape(B, N, H, W)
     dev = x.device
     shifts = torch.empty((B, N, 2), dtype=torch.float64, device=dev)
     score = torch.empty((B, N), dtype=torch.float64, device=dev)

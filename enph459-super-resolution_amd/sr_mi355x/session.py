@@ -85,9 +85,8 @@ def _to_dev_frames(decoded, keep_u8):
     """The decoded files of one frame set on the device: float64 (load_gray's cast), or -- keep_u8, and every file 8-bit greyscale -- the
     bytes as they are (a quarter of the upload of float32 frames, an eighth of these; shift_and_add and ibp take them through
     srx_saa_u8lr / srx_ibp_u8lr, registration through srx_register_u8).  A colour file (load_gray's channel mean is not an integer) keeps the whole set in float64."""
-    if keep_u8 and all(a.dtype == np.uint8 for a in decoded):
-        import torch
-        return [torch.from_numpy(np.ascontiguousarray(a)).to(api._device()) for a in decoded]
+    if keep_u8 and api._is_u8(decoded):
+        return [api._to_dev(a)[0] for a in decoded]
     return [_to_dev_f(a) for a in decoded]
 
 
@@ -155,13 +154,10 @@ def load_rgb_cal_combo(combo_dir, keep_u8=False):
     decoded = _decode_many(paths)
     starts = np.concatenate([[0], np.cumsum(counts)])
     corners = [decoded[starts[k]:starts[k + 1]] for k in range(len(counts))]
-    if keep_u8 and all(a.dtype == np.uint8 for a in decoded):
+    if keep_u8 and api._is_u8(decoded):
         def reps_dev(groups):  # [len(groups), R, H, W] on the device, every file uploaded as its own bytes
-            dev = torch.empty((len(groups), len(groups[0])) + groups[0][0].shape, dtype=torch.uint8, device=api._device())
-            for k, files in enumerate(groups):
-                for r, a in enumerate(files):
-                    dev[k, r].copy_(torch.from_numpy(np.ascontiguousarray(a)))
-            return dev
+            files = _to_dev_frames([a for group in groups for a in group], True)
+            return torch.stack(files).reshape((len(groups), len(groups[0])) + files[0].shape)
 
         if len(set(counts)) == 1:  # one B = 4 call
             return list(api.mean_u8(reps_dev(corners), f=2, precision=LOADER_PRECISION)), shifts
@@ -185,7 +181,7 @@ def load_corner_reps(session_dir, red, keep_u8=False):
         if not os.path.exists(path):
             raise FileNotFoundError(f"Missing {path}")
     decoded = _decode_many(paths)
-    keep_u8 = keep_u8 and all(a.dtype == np.uint8 for a in decoded)  # (one colour file: the whole session in float64, as without the switch)
+    keep_u8 = keep_u8 and api._is_u8(decoded)  # (one colour file: the whole session in float64, as without the switch)
     all_reps = []
     for k in range(len(rep_indices)):
         frames = []
@@ -770,7 +766,6 @@ def load_measured_psf(psf_dir):
 def load_measured_psf_device(psf_dir):
     """load_measured_psf with everything behind the PNG decode on the device: the same discovery, the files decoded side by side
     (_decode_many), the uint8 frames uploaded as they are and handed to psf_device.estimate_psf (srx_psf_estimate_u8)."""
-    import torch
     from . import psf_device
     paths = []
     for sweep in sorted(os.listdir(psf_dir)):
@@ -780,9 +775,7 @@ def load_measured_psf_device(psf_dir):
     if not paths:
         raise FileNotFoundError(f"No pos4_(0,0).png found under {psf_dir}")
     imgs = _decode_many(paths)
-    if all(a.dtype == np.uint8 for a in imgs):
-        frames = torch.from_numpy(np.stack(imgs)).to(api._device())
-    else:  # colour files: load_gray's channel mean, float64
-        with _loader_precision():
-            return psf_device.estimate_psf([a.astype(np.float64) for a in imgs])
-    return psf_device.estimate_psf(frames)
+    if api._is_u8(imgs):
+        return psf_device.estimate_psf(imgs)
+    with _loader_precision():  # colour files: load_gray's channel mean, float64
+        return psf_device.estimate_psf([a.astype(np.float64) for a in imgs])

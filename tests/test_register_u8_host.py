@@ -4,7 +4,7 @@ import numpy as np
 import pytest
 import torch
 
-from sr_mi355x import _lib, session
+from sr_mi355x import _lib, api, session
 from sr_mi355x import register as G
 
 
@@ -45,9 +45,9 @@ def test_argument_errors_are_the_float_input_s(shape, kw):
 
 def test_uint8_detection():
     u, f = np.zeros((2, 3, 3), np.uint8), np.zeros((2, 3, 3))
-    assert G._is_u8(u) and G._is_u8(torch.from_numpy(u)) and G._is_u8(list(u)) and G._is_u8([torch.from_numpy(a) for a in u])
-    assert not G._is_u8(f) and not G._is_u8(torch.from_numpy(f)) and not G._is_u8(list(f)) and not G._is_u8([u[0], f[1]])
-    assert not G._is_u8(u.astype(np.int8)) and not G._is_u8(u.tolist())
+    assert api._is_u8(u) and api._is_u8(torch.from_numpy(u)) and api._is_u8(list(u)) and api._is_u8([torch.from_numpy(a) for a in u])
+    assert not api._is_u8(f) and not api._is_u8(torch.from_numpy(f)) and not api._is_u8(list(f)) and not api._is_u8([u[0], f[1]])
+    assert not api._is_u8(u.astype(np.int8)) and not api._is_u8(u.tolist())
 
 
 def test_register_shifts_hands_bytes_on_as_bytes(monkeypatch):
