@@ -17,6 +17,7 @@
 #include "srx_mean.hpp"
 #include "srx_png.hpp"
 #include "srx_crc.hpp"
+#include "srx_bayer.hpp"
 #include "srx_patches.hpp"
 
 using namespace srx;
@@ -990,6 +991,42 @@ int srx_png_file_f32(const float *img, int B, int H, int W, void *files, void *l
 int srx_png_file_f64(const double *img, int B, int H, int W, void *files, void *lengths, void *ws, size_t wsb, srx_stream_t s)
 {
     return crc::png_file(img, B, H, W, files, lengths, ws, wsb, hs(s));
+}
+
+// ---- include/srx_bayer.h ----
+int srx_bayer_split_u8(const uint8_t *raw, int B, int H, int W, void *planes, srx_stream_t s) { return bayer::split(raw, B, H, W, planes, hs(s)); }
+int srx_bayer_split_f32(const float *raw, int B, int H, int W, void *planes, srx_stream_t s) { return bayer::split(raw, B, H, W, planes, hs(s)); }
+int srx_bayer_split_f64(const double *raw, int B, int H, int W, void *planes, srx_stream_t s) { return bayer::split(raw, B, H, W, planes, hs(s)); }
+
+int srx_bayer_mean_u8(const uint8_t *raw, int B, int R, int H, int W, int out_elem_bytes, void *planes, srx_stream_t s)
+{
+    return bayer::mean_u8(raw, B, R, H, W, out_elem_bytes, planes, hs(s));
+}
+
+int srx_bayer_merge_f32(const float *planes, int B, int Hp, int Wp, int d, const double *gains, void *rgb, srx_stream_t s)
+{
+    return bayer::merge<float, false>(planes, B, Hp, Wp, d, gains, rgb, hs(s));
+}
+int srx_bayer_merge_f64(const double *planes, int B, int Hp, int Wp, int d, const double *gains, void *rgb, srx_stream_t s)
+{
+    return bayer::merge<double, false>(planes, B, Hp, Wp, d, gains, rgb, hs(s));
+}
+int srx_bayer_merge_rgb8_f32(const float *planes, int B, int Hp, int Wp, int d, const double *gains, void *rgb8, srx_stream_t s)
+{
+    return bayer::merge<float, true>(planes, B, Hp, Wp, d, gains, rgb8, hs(s));
+}
+int srx_bayer_merge_rgb8_f64(const double *planes, int B, int Hp, int Wp, int d, const double *gains, void *rgb8, srx_stream_t s)
+{
+    return bayer::merge<double, true>(planes, B, Hp, Wp, d, gains, rgb8, hs(s));
+}
+
+size_t srx_png_file_rgb8_bound(int H, int W) { return bayer::png_bound(H, W); }
+
+size_t srx_png_file_rgb8_scratch_bytes(int B, int H, int W) { return bayer::png_scratch_bytes(B, H, W); }
+
+int srx_png_file_rgb8(const uint8_t *img, int B, int H, int W, void *files, void *lengths, void *ws, size_t wsb, srx_stream_t s)
+{
+    return bayer::png_file(img, B, H, W, files, lengths, ws, wsb, hs(s));
 }
 
 int srx_interleave4_u8(const uint8_t *frames, int B, int h, int w, uint8_t *out, srx_stream_t s)

@@ -134,12 +134,13 @@ SRX_CRC_HD inline uint32_t crc_bytes(const uint8_t *d, int n, uint32_t seed)
     return v ^ 0xffffffffu;
 }
 
-// The first 33 bytes of an 8-bit greyscale PNG of W x H: signature, IHDR (length, tag, 13 bytes, CRC).  Behind them: the IDAT's length
+// The first 33 bytes of an 8-bit PNG of W x H pixels, greyscale (colour type 0) or truecolour (2: srx_png_file_rgb8): signature, IHDR
+// (length, tag, 13 bytes, CRC).  Behind them: the IDAT's length
 // (big endian), "IDAT", the stream, the CRC of "IDAT" + stream, and file_iend.
 struct FileHead {
     uint8_t b[36];  // 33 used
 };
-SRX_CRC_HD inline FileHead file_head(uint32_t W, uint32_t H)
+SRX_CRC_HD inline FileHead file_head(uint32_t W, uint32_t H, uint8_t colour_type = 0)
 {
     FileHead h{};
     const uint8_t sig[8] = {0x89, 'P', 'N', 'G', '\r', '\n', 0x1a, '\n'};
@@ -152,8 +153,9 @@ SRX_CRC_HD inline FileHead file_head(uint32_t W, uint32_t H)
         c[8 + i] = (uint8_t)(W >> (24 - 8 * i));
         c[12 + i] = (uint8_t)(H >> (24 - 8 * i));
     }
-    c[16] = 8;  // bit depth; colour type 0 (grey), compression 0, filter 0, interlace 0
-    c[17] = c[18] = c[19] = c[20] = 0;
+    c[16] = 8;  // bit depth; the colour type; compression 0, filter 0, interlace 0
+    c[17] = colour_type;
+    c[18] = c[19] = c[20] = 0;
     const uint32_t v = crc_bytes(c + 4, 17, 0);
     for (int i = 0; i < 4; i++)
         c[21 + i] = (uint8_t)(v >> (24 - 8 * i));
@@ -427,7 +429,10 @@ static inline size_t file_scratch_bytes(int B, int H, int W)
     return measured([&](Arena &m) { carve_file(m, (size_t)B, (size_t)H * ((size_t)W + 1)); });
 }
 
-template <typename T> static int png_file(const T *img, int B, int H, int W, void *files_, void *lengths_, void *ws, size_t wsb, hipStream_t st)
+// W is the scanline's width in samples; head_w / colour_type: what the IHDR says where that differs (RGB: W = 3 head_w bytes of colour type 2)
+template <typename T>
+static int png_file(const T *img, int B, int H, int W, void *files_, void *lengths_, void *ws, size_t wsb, hipStream_t st, int head_w = 0,
+                    uint8_t colour_type = 0)
 {
     uint8_t *files = (uint8_t *)files_, *lengths = (uint8_t *)lengths_;
     if (!img || !files || !lengths || B <= 0 || H <= 0 || W <= 0)
@@ -444,8 +449,8 @@ template <typename T> static int png_file(const T *img, int B, int H, int W, voi
         return SRX_E_WORKSPACE;
     SRX_TRY(png::launch(img, B, H, W, p.png, files + FILE_HEAD, slot, (uint8_t *)p.stream_len, st));
     // the IDAT's CRC covers its tag and the stream: the stream under the seed crc32("IDAT") (the tag is not in the file yet)
-    return launch<true>(files + FILE_HEAD, B, slot, bound, p.stream_len, idat_seed(), nullptr, p.seg, files, slot, file_head((uint32_t)W, (uint32_t)H),
-                        lengths, st);
+    return launch<true>(files + FILE_HEAD, B, slot, bound, p.stream_len, idat_seed(), nullptr, p.seg, files, slot,
+                        file_head((uint32_t)(head_w ? head_w : W), (uint32_t)H, colour_type), lengths, st);
 }
 
 }  // namespace crc

@@ -72,6 +72,48 @@ template <int F, int N> __device__ __forceinline__ void add_frames(const uint8_t
     }
 }
 
+// the sums over the R frames of the 16 / F wanted bytes of one aligned vector: s[k] is byte F k (+ 1 where sh = 8) of vp, frames HW apart
+template <int F> __device__ __forceinline__ void packed_sums(const uint8_t *__restrict__ vp, unsigned HW, int R, unsigned sh, unsigned (&s)[16 / F])
+{
+    constexpr int NO = 16 / F;
+#pragma unroll
+    for (int k = 0; k < NO; k++)
+        s[k] = 0;
+    for (int r0 = 0; r0 < R; r0 += PACKED_MAX_R) {
+        const int r1 = min(r0 + PACKED_MAX_R, R);
+        unsigned pk[NO / 2];  // two 16-bit sums each
+#pragma unroll
+        for (int q = 0; q < NO / 2; q++)
+            pk[q] = 0;
+        int r = r0;
+        for (; r + BATCH <= r1; r += BATCH)
+            add_frames<F, BATCH>(vp + (unsigned)r * HW, HW, sh, pk);
+        switch (r1 - r) {  // the rest, < BATCH frames: each count its own unpredicated run of loads (wave-uniform)
+        case 1: add_frames<F, 1>(vp + (unsigned)r * HW, HW, sh, pk); break;
+        case 2: add_frames<F, 2>(vp + (unsigned)r * HW, HW, sh, pk); break;
+        case 3: add_frames<F, 3>(vp + (unsigned)r * HW, HW, sh, pk); break;
+        case 4: add_frames<F, 4>(vp + (unsigned)r * HW, HW, sh, pk); break;
+        case 5: add_frames<F, 5>(vp + (unsigned)r * HW, HW, sh, pk); break;
+        case 6: add_frames<F, 6>(vp + (unsigned)r * HW, HW, sh, pk); break;
+        case 7: add_frames<F, 7>(vp + (unsigned)r * HW, HW, sh, pk); break;
+        default: break;
+        }
+        // field -> output: F = 1, dword d: pk[2d] = bytes 0, 2 and pk[2d + 1] = bytes 1, 3; F = 2: pk[d] = outputs 2d, 2d + 1
+#pragma unroll
+        for (int d = 0; d < 4; d++) {
+            if (F == 1) {
+                s[4 * d] += pk[2 * d] & 0xffffu;
+                s[4 * d + 1] += pk[2 * d + 1] & 0xffffu;
+                s[4 * d + 2] += pk[2 * d] >> 16;
+                s[4 * d + 3] += pk[2 * d + 1] >> 16;
+            } else {
+                s[2 * d] += pk[d] & 0xffffu;
+                s[2 * d + 1] += pk[d] >> 16;
+            }
+        }
+    }
+}
+
 template <typename T, int F>
 __global__ void __launch_bounds__(256) k_mean_u8_vec(const uint8_t *__restrict__ in, int R, int H, int W, int py, int px, int h, int w,
                                                      T *__restrict__ out)
@@ -99,42 +141,7 @@ __global__ void __launch_bounds__(256) k_mean_u8_vec(const uint8_t *__restrict__
         for (unsigned v = lane; v < nvec; v += lanes) {
             const uint8_t *vp = p + a0 + 16u * v;  // 16-byte aligned by construction, in every frame (HW % 16 == 0)
             unsigned s[NO];
-#pragma unroll
-            for (int k = 0; k < NO; k++)
-                s[k] = 0;
-            for (int r0 = 0; r0 < R; r0 += PACKED_MAX_R) {
-                const int r1 = min(r0 + PACKED_MAX_R, R);
-                unsigned pk[NO / 2];  // two 16-bit sums each
-#pragma unroll
-                for (int q = 0; q < NO / 2; q++)
-                    pk[q] = 0;
-                int r = r0;
-                for (; r + BATCH <= r1; r += BATCH)
-                    add_frames<F, BATCH>(vp + (unsigned)r * HW, HW, sh, pk);
-                switch (r1 - r) {  // the rest, < BATCH frames: each count its own unpredicated run of loads (wave-uniform)
-                case 1: add_frames<F, 1>(vp + (unsigned)r * HW, HW, sh, pk); break;
-                case 2: add_frames<F, 2>(vp + (unsigned)r * HW, HW, sh, pk); break;
-                case 3: add_frames<F, 3>(vp + (unsigned)r * HW, HW, sh, pk); break;
-                case 4: add_frames<F, 4>(vp + (unsigned)r * HW, HW, sh, pk); break;
-                case 5: add_frames<F, 5>(vp + (unsigned)r * HW, HW, sh, pk); break;
-                case 6: add_frames<F, 6>(vp + (unsigned)r * HW, HW, sh, pk); break;
-                case 7: add_frames<F, 7>(vp + (unsigned)r * HW, HW, sh, pk); break;
-                default: break;
-                }
-                // field -> output: F = 1, dword d: pk[2d] = bytes 0, 2 and pk[2d + 1] = bytes 1, 3; F = 2: pk[d] = outputs 2d, 2d + 1
-#pragma unroll
-                for (int d = 0; d < 4; d++) {
-                    if (F == 1) {
-                        s[4 * d] += pk[2 * d] & 0xffffu;
-                        s[4 * d + 1] += pk[2 * d + 1] & 0xffffu;
-                        s[4 * d + 2] += pk[2 * d] >> 16;
-                        s[4 * d + 3] += pk[2 * d + 1] >> 16;
-                    } else {
-                        s[2 * d] += pk[d] & 0xffffu;
-                        s[2 * d + 1] += pk[d] >> 16;
-                    }
-                }
-            }
+            packed_sums<F>(vp, HW, R, sh, s);
             T *dst = orow + head + (size_t)v * NO;
             const T den = (T)R;
             if (((uintptr_t)dst & 15u) == 0) {  // the lane's own check: 16-byte stores only here

@@ -1,4 +1,4 @@
-"""ctypes binding of libsrx.so (include/srx.h).  No torch types cross this boundary:
+"""ctypes binding of libsrx.so (include/srx.h, include/srx_bayer.h).  No torch types cross this boundary:
 device pointers go through as integers, small parameter arrays as host float64 buffers.
 
 The product path has no CPU fallback: if libsrx.so is missing, load() raises.
@@ -110,13 +110,34 @@ _PLAIN = {
     "srx_patches_gather_u8": (_I, [_P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P]),
 }
 
+# the same for include/srx_bayer.h, a table of its own: symbols() stays the census of srx.h ({T} expands to f32 and f64 here too)
+_BAYER = {
+    "srx_bayer_split_u8": (_I, [_P, _I, _I, _I, _P, _P]),
+    "srx_bayer_split_{T}": (_I, [_P, _I, _I, _I, _P, _P]),
+    "srx_bayer_mean_u8": (_I, [_P, _I, _I, _I, _I, _I, _P, _P]),
+    "srx_bayer_merge_{T}": (_I, [_P, _I, _I, _I, _I, _HD, _P, _P]),
+    "srx_bayer_merge_rgb8_{T}": (_I, [_P, _I, _I, _I, _I, _HD, _P, _P]),
+    "srx_png_file_rgb8_bound": (_Z, [_I, _I]),
+    "srx_png_file_rgb8_scratch_bytes": (_Z, [_I, _I, _I]),
+    "srx_png_file_rgb8": (_I, [_P, _I, _I, _I, _P, _P, _P, _Z, _P]),
+}
+
+
+def _expand(table):
+    """(name, restype, argtypes) of every symbol of a table, {T} expanded"""
+    for pat, (res, args) in table.items():
+        for name in ([pat.format(T="f32"), pat.format(T="f64")] if "{T}" in pat else [pat]):
+            yield name, res, args
+
 
 def symbols():
     """Every symbol name include/srx.h declares."""
-    names = list(_PLAIN)
-    for pat in _TYPED:
-        names += [pat.format(T="f32"), pat.format(T="f64")]
-    return names
+    return [name for table in (_PLAIN, _TYPED) for name, _, _ in _expand(table)]
+
+
+def bayer_symbols():
+    """Every symbol name include/srx_bayer.h declares."""
+    return [name for name, _, _ in _expand(_BAYER)]
 
 
 def build(force=False):
@@ -140,12 +161,9 @@ def load():
     # holds two HIP runtimes and every launch on a torch pointer fails with hipErrorInvalidValue.
     import torch  # noqa: F401
     lib = ctypes.CDLL(SO_PATH)
-    for name, (res, args) in _PLAIN.items():
-        fn = getattr(lib, name)
-        fn.restype, fn.argtypes = res, args
-    for pat, (res, args) in _TYPED.items():
-        for t in ("f32", "f64"):
-            fn = getattr(lib, pat.format(T=t))
+    for table in (_PLAIN, _TYPED, _BAYER):
+        for name, res, args in _expand(table):
+            fn = getattr(lib, name)
             fn.restype, fn.argtypes = res, args
     _lib = lib
     return lib

@@ -614,3 +614,83 @@ def interleave4(frames_u8):
     out = torch.empty((B, 2 * h, 2 * w), dtype=torch.uint8, device=t.device)
     _lib.check(_lib.load().srx_interleave4_u8(_p(t), B, h, w, _p(out), _stream()), "srx_interleave4_u8")
     return _unbatch(out, single, was_np)
+
+
+# ------------------------------------------------------------------------------------------
+# colour from raw RGGB frames (include/srx_bayer.h): plane p = 0..3 is R, G1, G2, B = raw[p >> 1::2, p & 1::2]
+# ------------------------------------------------------------------------------------------
+_RAW = (torch.uint8, torch.float32, torch.float64)
+_SUFFIX = {torch.uint8: "u8", torch.float32: "f32", torch.float64: "f64"}
+
+
+def bayer_split(raw):
+    """The four Bayer planes of raw frames in one pass (srx_bayer_split_*): [H, W] or [B, H, W], uint8 / float32 / float64 ->
+    [4, H/2, W/2] or [B, 4, H/2, W/2] of the same dtype; plane p has the bits of decimate(raw, 2, p >> 1, p & 1).  H and W must be even.
+    numpy in -> numpy out."""
+    if np.ndim(raw) not in (2, 3):
+        raise ValueError("raw must be [H, W] or [B, H, W]")
+    x, was_np = _to_dev(raw, what="raw", allowed=_RAW, as_is=None)
+    x, single = _batch(x, 3)
+    B, H, W = (int(v) for v in x.shape)
+    if H % 2 or W % 2:
+        raise ValueError(f"bayer_split needs an even H and W (the four planes would differ in size), not {H} x {W}")
+    out = torch.empty((B, 4, H // 2, W // 2), dtype=x.dtype, device=x.device)
+    name = "srx_bayer_split_" + _SUFFIX[x.dtype]
+    _lib.check(getattr(_lib.load(), name)(_p(x), B, H, W, _p(out), _stream()), name)
+    return _unbatch(out, single, was_np)
+
+
+def bayer_mean_u8(stack_u8, precision=None):
+    """The mean over R raw uint8 frames, all four Bayer planes from one read of the stack (srx_bayer_mean_u8): uint8 [B, R, H, W] ->
+    device tensor [B, 4, H/2, W/2] of the compute precision; plane p has the bits of mean_u8(stack_u8, 2, p >> 1, p & 1)."""
+    prec = precision or get_precision()
+    B, R, H, W = _shape4(stack_u8, "stack_u8")
+    if H % 2 or W % 2:
+        raise ValueError(f"bayer_mean_u8 needs an even H and W (the four planes would differ in size), not {H} x {W}")
+    x, _ = _to_dev(stack_u8, what="stack_u8", **_BYTES)
+    out = torch.empty((B, 4, H // 2, W // 2), dtype=_TORCH_DT[prec], device=x.device)
+    _lib.check(_lib.load().srx_bayer_mean_u8(_p(x), B, R, H, W, _ELEM[prec], _p(out), _stream()), "srx_bayer_mean_u8")
+    return out
+
+
+def bayer_merge(planes, factor, gains=None, rgb8=False):
+    """Four reconstructed Bayer planes laid over each other as one RGB image (srx_bayer_merge_*): [4, Hp, Wp] or [B, 4, Hp, Wp] ->
+    planar [B, 3, Hp, Wp] of the working precision, or with rgb8 the quantised interleaved bytes [B, Hp, Wp, 3].  `factor` is the
+    reconstruction's: G1, G2 and B sit one raw pixel = factor / 2 HR samples to the right of / below R, and are read there (clamped at the
+    edge); G is the mean of G1 and G2.  factor=0 stacks the planes as they are.  An odd factor would need a half-sample shift of three
+    planes and is refused.  gains: three factors (R, G, B), each channel multiplied once; None: none.  numpy in -> numpy out."""
+    factor = int(factor)
+    if factor < 0 or factor % 2:
+        raise ValueError(f"bayer_merge needs an even factor (or 0 to stack the planes): at factor {factor} the planes are offset by "
+                         f"{factor / 2} HR samples, and a half-sample shift is an interpolation this call does not make")
+    prec = get_precision()
+    x, was_np = _to_dev(planes, prec)
+    x, single = _batch(x, 4)
+    if x.dim() != 4 or x.shape[1] != 4:
+        raise ValueError("planes must be [4, Hp, Wp] or [B, 4, Hp, Wp]")
+    B, _, Hp, Wp = (int(v) for v in x.shape)
+    g = None if gains is None else _host_f64(gains, (3,))
+    out = (torch.empty((B, Hp, Wp, 3), dtype=torch.uint8, device=x.device) if rgb8
+           else torch.empty((B, 3, Hp, Wp), dtype=x.dtype, device=x.device))
+    name = ("srx_bayer_merge_rgb8" if rgb8 else "srx_bayer_merge")
+    _lib.check(_fn(name, prec)(_p(x), B, Hp, Wp, factor // 2, None if g is None else g[1], _p(out), _stream()), name)
+    out = out[0] if single else out
+    return (out.cpu().numpy() if rgb8 else _out(out, True)) if was_np else out
+
+
+def png_file_rgb8(images):
+    """The 8-bit truecolour PNG files of RGB byte images (srx_png_file_rgb8), complete on the device: uint8 [B, H, W, 3] or [H, W, 3] ->
+    (files uint8 [B, srx_png_file_rgb8_bound(H, W)], lengths int64 [B]) on the device, nothing synchronised, as png_file.  The IDAT is
+    png_deflate's stream of the images viewed as [B, H, 3 W]."""
+    if np.ndim(images) not in (3, 4):
+        raise ValueError("images must have the shape [B, H, W, 3] or [H, W, 3]")
+    x, _ = _batch(_to_dev(images, what="images", **_BYTES)[0], 4)
+    B, H, W, C = (int(v) for v in x.shape)
+    if C != 3:
+        raise ValueError("images must have three interleaved channels")
+    lib = _lib.load()
+    files = torch.empty((B, lib.srx_png_file_rgb8_bound(H, W)), dtype=torch.uint8, device=x.device)
+    lengths = torch.empty((B,), dtype=torch.int64, device=x.device)
+    ws, wsp, wsn = _ws(lib.srx_png_file_rgb8_scratch_bytes(B, H, W))
+    _lib.check(lib.srx_png_file_rgb8(_p(x), B, H, W, _p(files), _p(lengths), wsp, wsn, _stream()), "srx_png_file_rgb8")
+    return files, lengths

@@ -53,9 +53,18 @@ def main(argv=None):
                     help="cal_target kinds: reconstruct in overlapping 256 x 256 HR patches that are blended back (sr_mi355x/patchwise.py).  "
                          "local: every patch under the shifts registered on it, the shift field written as shift_field.json next to the "
                          "PNGs; global: every patch under the session's one table (the baseline of local)")
+    ap.add_argument("--colour", action="store_true",
+                    help="the two rgb_* kinds: reconstruct all four Bayer planes (one batch under the one table; with --register the shifts "
+                         "measured on the red planes) and write native_2x_rgb.png, SAA_rgb.png, SAA_IBP_rgb.png and "
+                         "convergence_planes.json beside the files of the plain run, which do not change.  Goes with --u8-frames, "
+                         "--register and --png-on-device; not with --patchwise or --row-bands")
     args = ap.parse_args(argv)
     if args.metrics_on_device and not args.metrics:
         ap.error("--metrics-on-device needs --metrics")
+    if args.colour and args.kind not in ("rgb_cal_target", "rgb_barcodes"):
+        ap.error("--colour is for the two rgb_* kinds (raw RGGB frames)")
+    if args.colour and (args.patchwise or args.row_bands):
+        ap.error("--colour goes with neither --patchwise nor --row-bands")
     if args.patchwise and args.row_bands:
         ap.error("--patchwise and --row-bands exclude each other")
     if args.patchwise and args.kind not in ("mono_cal_target", "rgb_cal_target"):
@@ -90,7 +99,7 @@ def main(argv=None):
         metrics_cb = session.queue_metrics_device if args.metrics_on_device else session.write_metrics_device
     session.process_sessions(sessions, psf, args.output_dir, args.kind, rank=rank, world=world, on_images=metrics_cb,
                              row_bands=args.row_bands and world > 1, register=args.register,
-                             keep_u8=args.u8_frames, device_png=args.png_on_device, patchwise=args.patchwise)
+                             keep_u8=args.u8_frames, device_png=args.png_on_device, patchwise=args.patchwise, colour=args.colour)
     if dist is not None:
         dist.barrier()
     if rank == 0:

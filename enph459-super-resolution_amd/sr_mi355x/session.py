@@ -20,6 +20,10 @@ register=True (run_sr --register) measures the shifts from the loaded frames (sr
 table above as init and anchor: one item per rep for the barcode kinds, the rep-averaged red planes for rgb_cal_target) and
 reconstructs with them (uint8 frames, keep_u8, are measured as bytes); frames whose estimate has a nonzero status keep their table shift.  registration.json records the table,
 the estimates, the shifts used, the scores and the status codes.  Without it, nothing differs.
+
+colour=True (run_sr --colour; the two rgb_* kinds) reconstructs all four Bayer planes of the raw frames as one batch under the one table
+(reconstruct_colour) and writes native_2x_rgb.png, SAA_rgb.png, SAA_IBP_rgb.png and convergence_planes.json beside the files above, which
+keep their bytes: the reference's grey images of the red plane stay the default.
 """
 import json
 import os
@@ -125,8 +129,10 @@ def load_mono_cal_session(session_dir, keep_u8=False):
     return frames, shifts
 
 
-def load_rgb_cal_combo(combo_dir, keep_u8=False):
+def load_rgb_cal_combo(combo_dir, keep_u8=False, planes="red"):
     """rgb_cal_target/run_sr.py:78-113: red plane of every rep, mean over reps, shifts = metadata px / 2.
+    planes="all": every corner's frame is the [4, h, w] stack of its four Bayer planes (R, G1, G2, B; api.bayer_split / bayer_mean_u8: the
+    raw frames are read once); plane 0 is the red frame of the default, bit for bit.
     keep_u8, and every file 8-bit greyscale: the reps go up as bytes and mean_u8(f=2) forms each corner's frame from them -- the four
     corners in one call when they have the same number of reps -- which is the same float64 frame, bit for bit.  A colour file (load_gray's
     channel mean is not an integer) keeps the whole combo on the float64 path, as in load_corner_reps."""
@@ -154,24 +160,32 @@ def load_rgb_cal_combo(combo_dir, keep_u8=False):
     decoded = _decode_many(paths)
     starts = np.concatenate([[0], np.cumsum(counts)])
     corners = [decoded[starts[k]:starts[k + 1]] for k in range(len(counts))]
+    if planes not in ("red", "all"):
+        raise ValueError("planes must be 'red' or 'all'")
     if keep_u8 and api._is_u8(decoded):
+        def mean_u8(x):  # [B, R, H, W] bytes -> the B frames
+            return api.bayer_mean_u8(x, precision=LOADER_PRECISION) if planes == "all" else api.mean_u8(x, f=2, precision=LOADER_PRECISION)
+
         def reps_dev(groups):  # [len(groups), R, H, W] on the device, every file uploaded as its own bytes
             files = _to_dev_frames([a for group in groups for a in group], True)
             return torch.stack(files).reshape((len(groups), len(groups[0])) + files[0].shape)
 
         if len(set(counts)) == 1:  # one B = 4 call
-            return list(api.mean_u8(reps_dev(corners), f=2, precision=LOADER_PRECISION)), shifts
-        return [api.mean_u8(reps_dev([c]), f=2, precision=LOADER_PRECISION)[0] for c in corners], shifts
+            return list(mean_u8(reps_dev(corners))), shifts
+        return [mean_u8(reps_dev([c]))[0] for c in corners], shifts
+    cut = api.bayer_split if planes == "all" else api.extract_red
     frames = []
     with _loader_precision():
         for c in corners:
-            frames.append(api.mean_frames([api.extract_red(_to_dev_f(a)) for a in c]))
+            frames.append(api.mean_frames([cut(_to_dev_f(a)) for a in c]))
     return frames, shifts
 
 
 def load_corner_reps(session_dir, red, keep_u8=False):
     """mono_barcodes/run_sr.py:89-130 / rgb_barcodes/run_sr.py:102-143 -> (list over reps of 4 frames, shifts).
-    keep_u8: the frames stay uint8 (_to_dev_frames); the red plane is then cut out of the bytes (extract_red_u8)."""
+    keep_u8: the frames stay uint8 (_to_dev_frames); the red plane is then cut out of the bytes (extract_red_u8).
+    red="all": every frame is the [4, h, w] stack of its four Bayer planes (api.bayer_split, on the bytes under keep_u8); plane 0 is the
+    red frame of red=True."""
     rep_indices = sorted({int(m.group(1)) for m in (re.match(r"corner\d+_rep(\d+)\.png", n) for n in os.listdir(session_dir))
                           if m})
     if not rep_indices:
@@ -187,10 +201,10 @@ def load_corner_reps(session_dir, red, keep_u8=False):
         frames = []
         for img in _to_dev_frames(decoded[4 * k:4 * k + 4], keep_u8):
             if keep_u8:
-                frames.append(api.extract_red_u8(img) if red else img)
+                frames.append(api.bayer_split(img) if red == "all" else api.extract_red_u8(img) if red else img)
                 continue
             with _loader_precision():
-                frames.append(api.extract_red(img) if red else img)
+                frames.append(api.bayer_split(img) if red == "all" else api.extract_red(img) if red else img)
         all_reps.append(frames)
     return all_reps, list(CORNER_SHIFTS)
 
@@ -293,6 +307,38 @@ def reconstruct_batch(frame_sets, shifts, psf_kernel, n_iter, factor=UPSAMPLE_FA
             for i in range(B)]
 
 
+HR_NAMES = ("native_2x", "SAA", "SAA_IBP")
+
+
+def reconstruct_colour_batch(rep_frames, shifts, psf_kernel, n_iter, factor=UPSAMPLE_FACTOR, step=IBP_STEP_SIZE, gains=None):
+    """The colour reconstruction of B frame sets (the reps of an rgb_barcodes session): every set is N frames of [4, h, w] Bayer planes
+    (load_corner_reps(red="all")), and the B x 4 planes go through reconstruct_batch as ONE batch -- one library call per stage, uint8 stacks
+    through the u8lr calls -- under the one table, or under one table per set (shifts [B, N, 2]: every set's four planes share its table;
+    all four planes have the same pitch).  Item 4 b of the batch is the red reconstruction of set b, what reconstruct gives for its red
+    frames.  native_2x, SAA and SAA_IBP are then laid over each other (api.bayer_merge at `factor`, rgb8).
+    -> per set (the RGB byte images {name: uint8 [H, W, 3]}, the four per-plane image dicts, the four MSE traces)."""
+    import torch
+    B = len(rep_frames)
+    sets = [[fr[p] for fr in frames] for frames in rep_frames for p in range(4)]
+    table = np.asarray(shifts, dtype=np.float64)
+    if table.ndim == 3:
+        table = np.repeat(table, 4, axis=0)
+    results = reconstruct_batch(sets, table, psf_kernel, n_iter, factor, step)
+    out = []
+    for b in range(B):
+        mine = results[4 * b:4 * b + 4]
+        stacks = torch.stack([torch.stack([images[name] for images, _ in mine]) for name in HR_NAMES])  # [3 names, 4 planes, H, W]
+        rgb = api.bayer_merge(stacks, factor, gains, rgb8=True)
+        out.append(({name: rgb[k] for k, name in enumerate(HR_NAMES)}, [images for images, _ in mine], [trace for _, trace in mine]))
+    return out
+
+
+def reconstruct_colour(plane_frames, shifts, psf_kernel, n_iter, factor=UPSAMPLE_FACTOR, step=IBP_STEP_SIZE, gains=None):
+    """reconstruct_colour_batch for one frame set: the N frames of [4, h, w] as a batch of four items under the one table.
+    -> (RGB byte images, the four per-plane image dicts, the four MSE traces); item 0 is the red reconstruction."""
+    return reconstruct_colour_batch([plane_frames], shifts, psf_kernel, n_iter, factor, step, gains)[0]
+
+
 class Prefetcher:
     """Host work of items k + 1 .. k + depth (PNG decode, uint8 -> device) overlapped with the device work of item k: worker threads run
     `load(item)` for the next items while the caller consumes the current one.  PIL releases the GIL while it inflates a PNG,
@@ -360,25 +406,41 @@ def write_png_u8(path, arr):
     1536 x 2048 plane -- the files-to-files rate of a session is exactly this work.  Here: the Up filter on the whole image as one
     numpy subtraction and one zlib pass with run-length matching only (Z_RLE: on Up-filtered reconstructions within 8 % of PIL's file
     size at level 1, in 0.4x its time -- measured on the reference's committed 3072 x 4096 SAA.png: 118 against 298 ms)."""
-    import zlib
     a = np.ascontiguousarray(arr)
     if a.ndim != 2 or a.dtype != np.uint8:
         from PIL import Image
         Image.fromarray(a).save(path, compress_level=PNG_COMPRESS_LEVEL)
         return
     h, w = a.shape
+    with open(path, "wb") as fp:
+        fp.write(png_container(w, h, _up_filtered_stream(a)))
+
+
+def _up_filtered_stream(a):
+    """the zlib stream of the Up-filtered scanlines of a 2-D uint8 array (write_png_u8's and write_png_rgb8's IDAT data)"""
+    import zlib
+    h, w = a.shape
     raw = np.empty((h, w + 1), np.uint8)
     raw[:, 0] = 2          # filter type of every scanline: Up
     raw[0, 1:] = a[0]      # (the row above the first is zero)
     np.subtract(a[1:], a[:-1], out=raw[1:, 1:])  # modulo 256
     c = zlib.compressobj(PNG_COMPRESS_LEVEL, zlib.DEFLATED, 15, 9, zlib.Z_RLE)
-    z = c.compress(raw) + c.flush()
+    return c.compress(raw) + c.flush()
+
+
+def write_png_rgb8(path, arr):
+    """An 8-bit truecolour PNG of a uint8 [H, W, 3] array, write_png_u8's way: under the Up filter the scanlines are those of the grey
+    image [H, 3 W], in the container api.png_file_rgb8 builds on the device (colour type 2)."""
+    a = np.ascontiguousarray(arr)
+    if a.ndim != 3 or a.shape[2] != 3 or a.dtype != np.uint8:
+        raise ValueError("write_png_rgb8 needs a uint8 [H, W, 3] array")
+    h, w = a.shape[:2]
     with open(path, "wb") as fp:
-        fp.write(png_container(w, h, z))
+        fp.write(png_container(w, h, _up_filtered_stream(a.reshape(h, 3 * w)), colour_type=2))
 
 
-def png_container(w, h, zstream):
-    """The bytes of an 8-bit greyscale PNG file around the zlib stream of its scanlines: signature, IHDR, one IDAT, IEND.  The stream is
+def png_container(w, h, zstream, colour_type=0):
+    """The bytes of an 8-bit greyscale (or, colour_type=2, truecolour) PNG file around the zlib stream of its scanlines: signature, IHDR, one IDAT, IEND.  The stream is
     write_png_u8's own or the device's (api.png_deflate); the chunks' CRC-32 is host work either way (zlib.crc32 releases the GIL and
     takes a few ms on the few MB of a 3072 x 4096 plane)."""
     import struct
@@ -387,7 +449,7 @@ def png_container(w, h, zstream):
     def chunk(tag, data):
         return struct.pack(">I", len(data)) + tag + data + struct.pack(">I", zlib.crc32(data, zlib.crc32(tag)) & 0xffffffff)
 
-    return b"\x89PNG\r\n\x1a\n" + chunk(b"IHDR", struct.pack(">IIBBBBB", w, h, 8, 0, 0, 0, 0)) + chunk(b"IDAT", bytes(zstream)) + chunk(b"IEND", b"")
+    return b"\x89PNG\r\n\x1a\n" + chunk(b"IHDR", struct.pack(">IIBBBBB", w, h, 8, colour_type, 0, 0, 0)) + chunk(b"IDAT", bytes(zstream)) + chunk(b"IEND", b"")
 
 
 def _writer_pool():
@@ -406,14 +468,16 @@ def flush_writes():
         f.result()
 
 
-def _save_outputs(out_dir, images, errors, lr_name, extra=None, device_png=False):
+def _save_outputs(out_dir, images, errors, lr_name, extra=None, device_png=False, rgb=None):
     """Quantise on the device (clip + truncate, run_sr.py:303), queue the copies of the uint8 planes into pinned host buffers and hand
     the PNG encoding to worker threads, which wait for the copies' event -- the calling thread waits for nothing and goes on to queue the
     next item's device work.  `errors`: the MSE trace, a list or a device tensor (downloaded with the planes).  done.flag is written by
     the last job of the directory, after every file of it exists.
     device_png: the device compresses as well (same pixels in the files, other bytes) and, with DEVICE_PNG_FILES, builds the container and
     its CRC-32 around the stream (api.png_file): a job writes its slot's bytes as they are.  With DEVICE_PNG_FILES off the device makes the
-    streams only (api.png_deflate) and the jobs wrap them (png_container: the CRC-32 on the host) -- the same files byte for byte."""
+    streams only (api.png_deflate) and the jobs wrap them (png_container: the CRC-32 on the host) -- the same files byte for byte.
+    rgb: {name: uint8 [H, W, 3]} (reconstruct_colour) -> {name}_rgb.png beside the grey files: whole files from api.png_file_rgb8 under
+    device_png, write_png_rgb8 otherwise."""
     import torch
     os.makedirs(out_dir, exist_ok=True)
 
@@ -424,7 +488,7 @@ def _save_outputs(out_dir, images, errors, lr_name, extra=None, device_png=False
         h.copy_(t, non_blocking=True)
         return h
 
-    hr_names = ("native_2x", "SAA", "SAA_IBP")
+    hr_names = HR_NAMES
     if device_png:
         # the three HR planes as one [3, H, W] call on the float tensors (quantised as they are read), LR_mean as a second one in the
         # loader's precision; what goes to the host is the slots and their lengths, and a job slices and writes
@@ -435,12 +499,18 @@ def _save_outputs(out_dir, images, errors, lr_name, extra=None, device_png=False
         with _loader_precision():
             lr_streams, lr_lengths = encode(images["LR_mean"])
         hr_host, hr_len, lr_host, lr_len = to_host(streams), to_host(lengths), to_host(lr_streams), to_host(lr_lengths)
-        planes = {f"{name}.png": (hr_host, hr_len, k, tuple(hr.shape[1:])) for k, name in enumerate(hr_names)}
-        planes[lr_name] = (lr_host, lr_len, 0, tuple(images["LR_mean"].shape))
+        planes = {f"{name}.png": (hr_host, hr_len, k, tuple(hr.shape[1:]), files) for k, name in enumerate(hr_names)}
+        planes[lr_name] = (lr_host, lr_len, 0, tuple(images["LR_mean"].shape), files)
+        if rgb:
+            rgb_files, rgb_lengths = api.png_file_rgb8(torch.stack([rgb[name] for name in hr_names]))
+            rgb_host, rgb_len = to_host(rgb_files), to_host(rgb_lengths)
+            planes.update({f"{name}_rgb.png": (rgb_host, rgb_len, k, tuple(rgb[name].shape[:2]), True) for k, name in enumerate(hr_names)})
     else:
         planes = {f"{name}.png": to_host(api.quantize_u8(images[name])) for name in hr_names}
         with _loader_precision():
             planes[lr_name] = to_host(api.quantize_u8(images["LR_mean"]))
+        if rgb:
+            planes.update({f"{name}_rgb.png": to_host(rgb[name]) for name in hr_names})
     err_host = to_host(errors) if isinstance(errors, torch.Tensor) else None
     ready = None
     if torch.cuda.is_available():
@@ -466,12 +536,14 @@ def _save_outputs(out_dir, images, errors, lr_name, extra=None, device_png=False
         if ready is not None:
             ready.synchronize()
         if device_png:
-            slots, lens, k, (h, w) = host
+            slots, lens, k, (h, w), whole = host
             with open(os.path.join(out_dir, fname), "wb") as fp:
-                if files:
+                if whole:
                     fp.write(memoryview(slots[k, :int(lens[k])].numpy()))
                 else:
                     fp.write(png_container(w, h, slots[k, :int(lens[k])].numpy().tobytes()))
+        elif host.dim() == 3:
+            write_png_rgb8(os.path.join(out_dir, fname), host.numpy())
         else:
             write_png_u8(os.path.join(out_dir, fname), host.numpy())
         with lock:
@@ -485,7 +557,8 @@ def _save_outputs(out_dir, images, errors, lr_name, extra=None, device_png=False
 
 
 def process_session(session_dir, psf_kernel, output_base, kind=None, n_iter=None, verbose=True, batch_reps=True, loaded=None, flush=True,
-                    row_bands=False, on_images=None, register=False, keep_u8=False, device_png=False, patchwise=None, patch_opts=None):
+                    row_bands=False, on_images=None, register=False, keep_u8=False, device_png=False, patchwise=None, patch_opts=None,
+                    colour=False):
     """Counterpart of process_session / process_combo.  Returns the list of output directories written
     (empty if everything was already done).  batch_reps: the reps of a barcode session that are still to do go through the
     library in one B = reps call (reconstruct_batch) instead of one call per rep (with register, every rep under its own table); `loaded`: frames already decoded by a
@@ -495,10 +568,15 @@ def process_session(session_dir, psf_kernel, output_base, kind=None, n_iter=None
     keep_u8 (run_sr --u8-frames): the frames this call loads itself stay uint8 on the device; the files written are the same.
     device_png (run_sr --png-on-device): the PNGs' streams are compressed on the device (_save_outputs): the same pixels in every file.
     patchwise (run_sr --patchwise; the two cal_target kinds): "global" or "local", reconstruct's argument, with patch_opts the keywords
-    of patchwise.PatchGrid; "local" writes shift_field.json (the grid, the patch centres, estimated / used / score / status) beside the PNGs."""
+    of patchwise.PatchGrid; "local" writes shift_field.json (the grid, the patch centres, estimated / used / score / status) beside the PNGs.
+    colour (run_sr --colour; the two rgb_* kinds, not with patchwise or row_bands): all four Bayer planes are reconstructed as one batch
+    under the one table (reconstruct_colour; with register the shifts are measured on the red planes, as without it), every file of the
+    plain run is written byte for byte, and beside them native_2x_rgb.png, SAA_rgb.png, SAA_IBP_rgb.png and convergence_planes.json (the
+    four planes' MSE traces).  `loaded` must then come from load_session(..., colour=True)."""
     kind = kind or detect_kind(session_dir)
     if kind not in IBP_ITERATIONS:
         raise ValueError("kind must be one of " + ", ".join(IBP_ITERATIONS))
+    _check_colour(colour, kind, patchwise, row_bands)
     if patchwise is not None and (kind not in ("mono_cal_target", "rgb_cal_target") or row_bands):
         raise ValueError("patchwise is for the one-image-per-session kinds, and not together with row_bands")
     n_iter = IBP_ITERATIONS[kind] if n_iter is None else n_iter
@@ -514,18 +592,24 @@ def process_session(session_dir, psf_kernel, output_base, kind=None, n_iter=None
             frames, shifts = loaded or load_mono_cal_session(session_dir, keep_u8=keep_u8)
             lr_name, extra = "LR_mean.png", None
         else:
-            frames, shifts = loaded or load_rgb_cal_combo(session_dir, keep_u8=keep_u8)
+            frames, shifts = loaded or load_rgb_cal_combo(session_dir, keep_u8=keep_u8, planes="all" if colour else "red")
             lr_name = "LR_red_mean.png"
             extra = {"shifts.json": {"shifts_lr_yx": [list(s) for s in shifts], "corner_labels": CORNER_ORDER}}
         if register:
-            shifts, reg = register_shifts([frames], shifts)[0]
+            shifts, reg = register_shifts([[f[0] for f in frames] if colour else frames], shifts)[0]
             extra = dict(extra or {}, **{"registration.json": reg})
-        images, errors = reconstruct(frames, shifts, psf_kernel, n_iter, row_bands=row_bands, patchwise=patchwise, patch_opts=patch_opts)
+        rgb = None
+        if colour:
+            rgb, plane_images, traces = reconstruct_colour(frames, shifts, psf_kernel, n_iter)
+            images, errors = plane_images[0], traces[0]
+            extra = dict(extra, **{"convergence_planes.json": {"ibp_mse": traces}})
+        else:
+            images, errors = reconstruct(frames, shifts, psf_kernel, n_iter, row_bands=row_bands, patchwise=patchwise, patch_opts=patch_opts)
         if "shift_field" in images:
             extra = dict(extra or {}, **{"shift_field.json": images.pop("shift_field")})
         if images["SAA_IBP"] is None:  # row-band mode, not rank 0: the assembled image lives on rank 0
             return written
-        _save_outputs(out_dir, images, errors, lr_name, extra, device_png=device_png)
+        _save_outputs(out_dir, images, errors, lr_name, extra, device_png=device_png, rgb=rgb)
         if on_images:  # (the device tensors the PNGs were quantised from: metrics without reading the files back)
             on_images(out_dir, images)
         if flush:
@@ -534,7 +618,7 @@ def process_session(session_dir, psf_kernel, output_base, kind=None, n_iter=None
         written.append(out_dir)
         return written
     red = kind == "rgb_barcodes"
-    all_reps, shifts = loaded or load_corner_reps(session_dir, red, keep_u8=keep_u8)
+    all_reps, shifts = loaded or load_corner_reps(session_dir, "all" if colour else red, keep_u8=keep_u8)
     todo = []
     for rep_idx, frames in enumerate(all_reps):
         out_dir = os.path.join(output_base, name, f"rep{rep_idx}")
@@ -544,8 +628,20 @@ def process_session(session_dir, psf_kernel, output_base, kind=None, n_iter=None
         todo.append((out_dir, frames))
     if not todo:
         return written
-    extras = [None] * len(todo)
-    if register:  # one registration item per rep (one batched call); each rep then reconstructs with its own shifts
+    extras, rgbs = [None] * len(todo), [None] * len(todo)
+    if colour:  # the reps x 4 planes as one batch; registration, as below, on the red planes
+        tables, extras = shifts, [{} for _ in todo]
+        if register:
+            regs = register_shifts([[f[0] for f in fr] for _, fr in todo], shifts)
+            tables, extras = [used for used, _ in regs], [{"registration.json": reg} for _, reg in regs]
+        if batch_reps:
+            colour_results = reconstruct_colour_batch([fr for _, fr in todo], tables, psf_kernel, n_iter)
+        else:
+            colour_results = [reconstruct_colour(fr, tables[k] if register else tables, psf_kernel, n_iter) for k, (_, fr) in enumerate(todo)]
+        results, rgbs = [(planes[0], traces[0]) for _, planes, traces in colour_results], [rgb for rgb, _, _ in colour_results]
+        for extra, (_, _, traces) in zip(extras, colour_results):
+            extra["convergence_planes.json"] = {"ibp_mse": traces}
+    elif register:  # one registration item per rep (one batched call); each rep then reconstructs with its own shifts
         regs = register_shifts([fr for _, fr in todo], shifts)
         if batch_reps:  # ... in one library call per stage, each with its own table
             results = reconstruct_batch([fr for _, fr in todo], [used for used, _ in regs], psf_kernel, n_iter, lazy_errors=True)
@@ -556,8 +652,8 @@ def process_session(session_dir, psf_kernel, output_base, kind=None, n_iter=None
         results = reconstruct_batch([fr for _, fr in todo], shifts, psf_kernel, n_iter, lazy_errors=True)
     else:
         results = [reconstruct(fr, shifts, psf_kernel, n_iter) for _, fr in todo]
-    for (out_dir, _), (images, errors), extra in zip(todo, results, extras):
-        _save_outputs(out_dir, images, errors, "LR_red_mean.png" if red else "LR_mean.png", extra, device_png=device_png)
+    for (out_dir, _), (images, errors), extra, rgb in zip(todo, results, extras, rgbs):
+        _save_outputs(out_dir, images, errors, "LR_red_mean.png" if red else "LR_mean.png", extra, device_png=device_png, rgb=rgb)
         say(f"    Output: {out_dir}")
         written.append(out_dir)
     if flush:
@@ -565,19 +661,26 @@ def process_session(session_dir, psf_kernel, output_base, kind=None, n_iter=None
     return written
 
 
-def load_session(session_dir, kind, keep_u8=False):
+def _check_colour(colour, kind, patchwise, row_bands):
+    if colour and kind not in ("rgb_cal_target", "rgb_barcodes"):
+        raise ValueError("colour is for the two rgb_* kinds (raw RGGB frames)")
+    if colour and (patchwise is not None or row_bands):
+        raise ValueError("colour goes with neither patchwise nor row_bands")
+
+
+def load_session(session_dir, kind, keep_u8=False, colour=False):
     """The host + upload half of process_session (what a Prefetcher runs ahead): decoded frames on the device.  keep_u8: as uint8 where
     the kind's frames are the camera's samples (rgb_cal_target averages its reps: float64 frames either way, formed from the bytes by
-    mean_u8 with keep_u8)."""
+    mean_u8 with keep_u8).  colour (the two rgb_* kinds): every frame is the [4, h, w] stack of its Bayer planes."""
     if kind == "mono_cal_target":
         return load_mono_cal_session(session_dir, keep_u8=keep_u8)
     if kind == "rgb_cal_target":
-        return load_rgb_cal_combo(session_dir, keep_u8=keep_u8)
-    return load_corner_reps(session_dir, kind == "rgb_barcodes", keep_u8=keep_u8)
+        return load_rgb_cal_combo(session_dir, keep_u8=keep_u8, planes="all" if colour else "red")
+    return load_corner_reps(session_dir, "all" if colour and kind == "rgb_barcodes" else kind == "rgb_barcodes", keep_u8=keep_u8)
 
 
 def process_sessions(sessions, psf_kernel, output_base, kind, n_iter=None, verbose=True, rank=0, world=1, on_written=None, row_bands=False,
-                     on_images=None, register=False, keep_u8=False, device_png=False, patchwise=None, patch_opts=None):
+                     on_images=None, register=False, keep_u8=False, device_png=False, patchwise=None, patch_opts=None, colour=False):
     """The reference's outer loop (mono_cal_target/run_sr.py:358-360, mono_barcodes/run_sr.py:301) over the sessions this
     rank owns (session i -> rank i mod world, parallel.map_sharded: independent items, no data-path collective), with the PNG
     decode and upload of session k + 1 overlapped with the device work of session k.  -> output directories written: by every
@@ -590,6 +693,7 @@ def process_sessions(sessions, psf_kernel, output_base, kind, n_iter=None, verbo
         raise ValueError("row_bands is for the one-image-per-session kinds (the barcode kinds batch their reps instead)")
     if patchwise is not None and (kind not in ("mono_cal_target", "rgb_cal_target") or row_bands):
         raise ValueError("patchwise is for the one-image-per-session kinds, and not together with row_bands")
+    _check_colour(colour, kind, patchwise, row_bands)
     owned = list(range(len(sessions))) if row_bands else parallel.shard_indices(len(sessions), rank, world)
     say = print if verbose else (lambda *a, **k: None)
 
@@ -597,7 +701,7 @@ def process_sessions(sessions, psf_kernel, output_base, kind, n_iter=None, verbo
         name = os.path.basename(os.path.normpath(sessions[i]))
         if kind in ("mono_cal_target", "rgb_cal_target") and os.path.exists(os.path.join(output_base, name, "done.flag")):
             return None  # process_session will skip it: do not decode
-        return load_session(sessions[i], kind, keep_u8=keep_u8)
+        return load_session(sessions[i], kind, keep_u8=keep_u8, colour=colour)
 
     feed = iter(Prefetcher(owned, load))
     count = [0]
@@ -609,7 +713,7 @@ def process_sessions(sessions, psf_kernel, output_base, kind, n_iter=None, verbo
         say(f"\n[rank {rank}: {count[0]}/{len(owned)}] {os.path.basename(sessions[i])}")
         out = process_session(sessions[i], psf_kernel, output_base, kind=kind, n_iter=n_iter, verbose=verbose, loaded=loaded,
                               flush=on_written is not None, row_bands=row_bands, on_images=on_images, register=register, device_png=device_png,
-                              patchwise=patchwise, patch_opts=patch_opts)
+                              patchwise=patchwise, patch_opts=patch_opts, colour=colour)
         if on_written:
             for d in out:
                 on_written(d)
