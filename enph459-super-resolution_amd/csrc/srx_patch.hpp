@@ -50,7 +50,8 @@ using dtile::AxisTiles;
 // What k_ibp_patch's memory operations cost, from timing ablations that computed wrong results (C2, 161 us per iteration): without
 // the hr park store 150, without the hr re-read 152, without both 144, without the M loads as well 139, without the near band and the
 // MSE sums too 138: the memory operations are 14 % of the iteration; requesting the parked state or the near-band descriptors a chain
-// earlier changes nothing.
+// earlier changes nothing.  What did: not parking the quarter of the state whose reload had no cover (resident_rows() below; 137.6 -> 127.1 us
+// on one box).
 constexpr int PN = 256;        // patch edge (HR pixels)
 constexpr int YW = 260;        // row pitch of the near-band strips
 constexpr int OFF_YT = 16 * RW, OFF_YL = OFF_YT + 4 * YW, OFF_GT = OFF_YL + 4 * YW, OFF_GL = OFF_GT + 3 * YW,
@@ -565,12 +566,42 @@ __global__ void __launch_bounds__(256)
 // =========================================================================================================================
 // All n_iter IBP iterations of one patch.  grid B, block 1024 (16 waves = 4 x 4 blocks of 64 x 64).
 // Between iterations the HR state stays in registers (column layout); per iteration the kernel stores it (hr_out doubles as
-// the parking place of the pre-update state, re-read for the update -- the register file holds the state OR the working
-// plane, not both), reads the LR mosaic (bytes when the patch's samples are uint8) and the near-band descriptors.
+// the parking place of the pre-update state, re-read for the update -- at its peak, the last blur of stage C, the register file
+// holds the working plane and two landing batches and nothing else; through the other stages it also holds the first
+// resident_rows() rows of the pre-update state, which are then not parked), reads the LR mosaic (bytes when the patch's
+// samples are uint8) and the near-band descriptors.
 // =========================================================================================================================
 struct AxisWPair {  // PatchTabs::aw as the host fills it
     AxisW y, x;
 };
+
+// Rows of every wave's block whose pre-update state stays in registers through the iteration instead of being parked (0 or 16: quarter 0
+// of stage C's blur).  16 where the instantiation takes them without a spilled register: the pair of kernels the
+// flagship's grid launches (rank-1 PSF; the byte mosaic under all-ones masks, the float mosaic of a full phase grid).  The byte-mosaic form with
+// a mask test and the count-plane forms gain 2 - 11 spilled registers with 16 rows, every rank-1 form 19 - 30 with 32, and the 7 x 7 forms spill as they are: they park everything, and are
+// the code they were.
+constexpr int resident_rows(bool c01, bool m8, int form) { return c01 && (m8 ? form == 1 : form == 0) ? 16 : 0; }
+
+// With resident rows the file has no register left for a value that merely waits: the thread index and the lane index of wave_sum's
+// shuffles, which the compiler carries through the whole iteration loop (and then spills, one scratch read per stage), are formed
+// where they are used instead -- the lane index by v_mbcnt, two instructions the compiler may not hoist.
+__device__ __forceinline__ int lane_here()
+{
+    int l;
+    asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(l));
+    return l;
+}
+// wave_sum of srx_common.h -- the same tree in the same order, bit for bit -- on the caller's lane index
+__device__ __forceinline__ double wave_sum_at(double v, int lane)
+{
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const int idx = (lane + o >= 64 ? lane : lane + o) << 2;
+        const int lo = __builtin_amdgcn_ds_bpermute(idx, __double2loint(v)), hi = __builtin_amdgcn_ds_bpermute(idx, __double2hiint(v));
+        v += __hiloint2double(hi, lo);
+    }
+    return v;
+}
 
 // FORM: 0 rank 1 (7 + 7 taps per blur), 3 full 7 x 7, 2 a 7 x 7 whose outer ring is zero; 1 (with C01 and M8) rank 1 on a grid whose count
 // masks the host found all ones wherever the G step's result is used (gstep_form): the byte-mosaic G loop runs without the mask test.  A
@@ -612,8 +643,12 @@ __global__ void __launch_bounds__(1024)
     const unsigned long long rmask = C01 ? pa.ry[s] : 0ull, cmask = C01 ? pa.rx[u] : 0ull;
 
     // The state (this wave's 64 x 64 block of hr, column layout) stays in registers from one iteration's update to the next
-    // iteration's blur; every iteration also parks it in hr_out, where the update re-reads it 16 rows at a time (the register
-    // file holds the state OR the working plane, not both).
+    // iteration's blur.  Beside the working plane the file holds KRES of its 64 rows through the stages in between (xs, below: rows
+    // 0 .. KRES - 1, the quarter of stage C's blur whose reload had no cover); every iteration parks the other rows in hr_out, where
+    // the update re-reads them 16 rows at a time.
+    constexpr int KRES = resident_rows(C01, M8, FORM);
+    constexpr int PB0 = KRES / 16;  // the first parked batch of 16 rows
+    static_assert(KRES == 0 || KRES == 16, "the reload schedule of stage C");
     float a[64];
     {
         const int l4 = (tid0 & 63) * 4;
@@ -628,12 +663,13 @@ __global__ void __launch_bounds__(1024)
     const int park0 = wave * 16384;  // byte offset of this wave's 64 x 64 block in the parking layout
     for (int it = 0; it < n_iter; it++) {
         float r[64];
+        float xs[KRES > 0 ? KRES : 1];  // the pre-update state of rows 0 .. KRES - 1, from stage A to the first quarter(s) of stage C's blur
         // Everything derived from the lane index (LDS and global addresses, predicates) and from the block offsets is re-derived
         // PER STAGE from opaque copies.  Left to itself the compiler computes all of it once -- at the top of the loop, or above it
         // -- and carries ~55 registers of addresses across stages whose working plane needs the file: they were spilled, one
         // scratch round trip per use (the spill traffic was as large as the kernel's real traffic).
 #define SRX_STAGE_LOCALS()                                 \
-    int tid = tid0;                                        \
+    int tid = KRES > 0 ? wave * 64 + lane_here() : tid0;   \
     asm volatile("" : "+v"(tid));                          \
     const int lane = tid & 63, l4 = lane * 4;              \
     int cbl = cb0, tbl = tb0, m8l = (4 * u * PN + 64 * s) * 16; \
@@ -649,7 +685,10 @@ __global__ void __launch_bounds__(1024)
             int pk = park0;
             asm volatile("" : "+s"(pk));
 #pragma unroll
-            for (int q = 0; q < 16; q++)
+            for (int i = 0; i < KRES; i++)
+                xs[i] = a[i];
+#pragma unroll
+            for (int q = KRES / 4; q < 16; q++)  // (the resident rows' slots of the parking layout are never written or read)
                 st4(rs_out, l4 * 4, pk + q * 1024, a[4 * q], a[4 * q + 1], a[4 * q + 2], a[4 * q + 3]);
         }
         if (PSF == 0) {
@@ -711,10 +750,11 @@ __global__ void __launch_bounds__(1024)
         // ---- near-band strips of Y
         near_put_y(r, yexx, wrapped || (s == 0 && lane <= nby), u == 0, gy + exy, u, exx, nbx, Yt, Yl);
         __syncthreads();
-        // the LR mosaic of the G step: in flight during the near-band phase
+        // the LR mosaic of the G step: in flight during the near-band phase -- with resident rows (the phase then holds the plane, the
+        // descriptors and xs) requested behind the near-band pixels instead, in flight across the phase's closing barrier
         const __amdgpu_buffer_rsrc_t rsM8 = fused::plane_rsrc(tb.Mt8 + (size_t)b * (PN / 4) * PN, (size_t)(PN / 4) * PN);
         unsigned m8w[16];
-        if (m8) {
+        if (m8 && KRES == 0) {
 #pragma unroll
             for (int q = 0; q < 4; q++) {
                 const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(rsM8, l4 * 4, m8l + q * PN * 16, 0);
@@ -734,6 +774,14 @@ __global__ void __launch_bounds__(1024)
                 px(nr0, ne0, nm0, tid);
             if (n1)
                 px(nr1, ne1, nm1, tid + 1024);
+        }
+        if (m8 && KRES > 0) {
+            __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+            for (int q = 0; q < 4; q++) {
+                const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(rsM8, l4 * 4, m8l + q * PN * 16, 0);
+                m8w[4 * q] = v.x, m8w[4 * q + 1] = v.y, m8w[4 * q + 2] = v.z, m8w[4 * q + 3] = v.w;
+            }
         }
         __syncthreads();
         __builtin_amdgcn_sched_barrier(0);
@@ -813,7 +861,7 @@ __global__ void __launch_bounds__(1024)
         // ---- MSE trace of this iteration (before the update): per-wave sums now, added up in a fixed order by thread 0 behind the
         // next barrier (no barrier of its own)
         if (errors) {
-            const double ws = wave_sum((double)sq);
+            const double ws = KRES > 0 ? wave_sum_at((double)sq, lane) : wave_sum((double)sq);
             if (lane == 0)
                 part[wave] = ws;
         }
@@ -861,7 +909,9 @@ __global__ void __launch_bounds__(1024)
             const float gtop = exy ? rowbuf[64 * u + lane] : r[0];
             const GNbr<float> nbr = gnbr_get(s == 0, s == 3, Rup, Rdn, SLOT0, lane, gtop);
             auto mid = [&](int q) {
-                          // the parked state in 16-row batches, two in flight: batch q is consumed by quarter q of the blur
+                          // the parked state in 16-row batches, at most two in flight: batch q is consumed by quarter q of the blur, the parked
+                          // batches PB0 .. 3 land in hv and hw alternately.  With resident rows no batch is consumed in the quarter whose hook
+                          // requests it (quarter 0 takes xs): every request has a quarter of the blur as cover
                           auto load16 = [&](float(&ld)[16], int bq) {
                               int pk = park0;
                               asm volatile("" : "+s"(pk));
@@ -869,18 +919,26 @@ __global__ void __launch_bounds__(1024)
                               for (int q = 0; q < 4; q++)
                                   ld4(rs_out, l4 * 4, pk + (4 * bq + q) * 1024, ld[4 * q], ld[4 * q + 1], ld[4 * q + 2], ld[4 * q + 3]);
                           };
-                          if (q == 0) {
+                          if (q == 0)
                               SRX_PSTAMP(13);
-                              load16(hv, 0), load16(hw, 1);
+                          if (KRES == 0) {
+                              if (q == 0)
+                                  load16(hv, 0), load16(hw, 1);
+                              if (q == 1)
+                                  load16(hv, 2);
+                              else if (q == 2)
+                                  load16(hw, 3);
+                          } else {
+                              if (q == 0)
+                                  load16(hv, 1), load16(hw, 2);
+                              else if (q == 2)
+                                  load16(hv, 3);
                           }
-                          if (q == 1)
-                              load16(hv, 2);
-                          else if (q == 2)
-                              load16(hw, 3);
                       };
             auto post = [&](int i, float corr) {
                           // the update, fused into the blur's epilogue: hr <- clip(hr + step * corr / N, 0, 255), one v_med3_f32
-                          return __builtin_amdgcn_fmed3f(fmaf(corr, sn, ((i >> 4) & 1) ? hw[i & 15] : hv[i & 15]), 0.f, 255.f);
+                          const float old = i < KRES ? xs[i < KRES ? i : 0] : (((i >> 4) - PB0) & 1) ? hw[i & 15] : hv[i & 15];
+                          return __builtin_amdgcn_fmed3f(fmaf(corr, sn, old), 0.f, 255.f);
                       };
             if (PSF == 0) {
                 bwd_chain(r, a, s == 0, s == 3, Rown, Rup, Rdn, SLOT1 + 384, SLOT1, lane, sload8(awy + 16), sload8(awy + 8), nbr.gm1, nbr.gp1, nbr.gp2, gtop, mid, post);
@@ -900,7 +958,7 @@ __global__ void __launch_bounds__(1024)
         // the result goes out in image layout, over the parking layout: not before every wave has re-read its last parked rows
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
-        const int l4 = (tid0 & 63) * 4;
+        const int l4 = (KRES > 0 ? lane_here() : tid0 & 63) * 4;
 #pragma unroll
         for (int i = 0; i < 64; i++)
             fused::buf_store<float>(a[i], rs_out, l4 + (i & 3) * PN * 4, cb0 + (i >> 2) * PN * 16);
