@@ -938,6 +938,9 @@ struct FrameOffsets {
 static_assert(SRX_MAX_FRAMES <= 32, "FrameOffsets::last is one word");
 
 constexpr int SAA_ACC_TS = 96;  // edge of a W-plane tile of the two-pass form (k_saa_tile<T, F, true>)
+// frames staged per step of k_saa_tile<T, 4, true, G>: two in float32, whose four patch slots fit under the region staging (no LDS, four blocks per
+// compute unit still; G = 4 needs 48 KB and three blocks and measured slower); float64 keeps the per-frame form
+template <typename T> constexpr int SAA_STAGE_G = sizeof(T) == 4 ? 2 : 1;
 template <typename T, int F, bool ACC = false> struct SaaCfg {
     static constexpr int R = TileCfg<T>::R, TS = TileCfg<T>::T_HR, SR = ACC ? SAA_ACC_TS : TS + 2 * R + 3;  // region edge (<= 128)
     static constexpr int PD = (SR + 12) / F + 6;                                          // LR patch edge bound
@@ -960,21 +963,28 @@ template <typename T, int F, bool ACC = false> struct SaaCfg {
 // filtered: the accumulated sum goes to `out` (the plane) and k_saa_shift runs the fractional shift on regions of it.  The fused form
 // accumulates (TS + 2 R + 3)^2 samples per TS^2 outputs over all N frames: 2.07x the work in float32 (TS = 64, R = 11), 6.4x in float64
 // (TS = 32, R = 23); the halo now costs one more read of W instead (C2: 1.08 -> ... ms in float32, 7.2 -> ... in float64).
-template <typename T, int F, bool ACC = false>
-__global__ void __launch_bounds__(256, sizeof(T) == 4 && F == 4 ? 4 : 1)  // float32 at x4: four blocks per compute unit (128 registers, 6 spilled; x2 would spill 68)
+// G ("the staged row pass"): the frames of a group are staged G at a time into LDS slots of their own and their row
+// passes run back to back, one barrier per G frames; the slots are doubled, so the next chunk is staged while this one is read.  G = 1 is
+// the per-frame form above.
+template <typename T, int F, bool ACC = false, int G = 1>
+__global__ void __launch_bounds__(256, sizeof(T) == 4 && F == 4 ? 4 : 1)  // float32 at x4: four blocks per compute unit (128 registers, 6 spilled, G = 2: 4; x2 would spill 68)
     k_saa_tile(const T *__restrict__ coef, int N, int h, int w, const AxisTap<T> *__restrict__ zy,
                const AxisTap<T> *__restrict__ zx, FrameOffsets fo, MosaicArgs<T> ma, int H, int W, T inv_n_div,
                T *__restrict__ out)
 {
     using C = SaaCfg<T, F, ACC>;
-    constexpr int R = C::R, TS = C::TS, SR = C::SR, LD = SR, PD = C::PD, NT = C::NT, PPT = C::PPT, RS = C::RS;
+    // LD, the pitch of the region staging: in the staged form one word more than the 96 of the ACC tile.  In the store of the sums below a lane is
+    // a region ROW, and at a pitch of 96 = 3 x 32 words the 32 lanes of a half-wave fall on one bank: 39 % of the kernel's LDS cycles were those
+    // conflicts (SQ_LDS_BANK_CONFLICT).  (The per-frame instantiations keep 96 and the conflicts: DESIGN.md section 8.4.)
+    constexpr int R = C::R, TS = C::TS, SR = C::SR, LD = ACC && G > 1 ? SR + 1 : SR, PD = C::PD, NT = C::NT, PPT = C::PPT, RS = C::RS;
     constexpr int ROWS0 = (PD * PD + 3) & ~3;  // the row-pass image starts on a 16-byte boundary (for T = float)
     static_assert(SR <= 128, "two 64-lane chunks per axis");
-    // LDS: during the frame loop [patch PD*PD | rows PD*SR]; afterwards the SR*SR region
-    constexpr int FRAME_WORDS = ROWS0 + PD * RS;
-    constexpr int WORDS = FRAME_WORDS + NT > SR * SR ? FRAME_WORDS + NT : SR * SR;  // discarded lanes read up to NT words past a row
+    // LDS: during the frame loop [patch PD*PD (G > 1: two sets of G patch slots) | rows PD*SR]; afterwards the SR*SR region
+    constexpr int NSLOT = G > 1 ? 2 * G : 1;
+    constexpr int FRAME_WORDS = NSLOT * ROWS0 + PD * RS;
+    constexpr int WORDS = FRAME_WORDS + NT > SR * LD ? FRAME_WORDS + NT : SR * LD;  // discarded lanes read up to NT words past a row
     __shared__ __attribute__((aligned(16))) T lds[WORDS];
-    T *patch = lds, *rows = lds + ROWS0, *reg = lds;
+    T *patch = lds, *rows = lds + NSLOT * ROWS0, *reg = lds;
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), chunk = wave & 1, half = wave >> 1;
     const int Hp = H + 2 * SRX_NPAD, Wp = W + 2 * SRX_NPAD;
@@ -1035,16 +1045,19 @@ __global__ void __launch_bounds__(256, sizeof(T) == 4 && F == 4 ? 4 : 1)  // flo
         }
     };
     SRX_STAMP(2, 0);
-    geometry(0);
-    fetch(0);
-    fetch_ty(0);
-    stash();
-    __syncthreads();
-    SRX_STAMP(2, 1);
+    if constexpr (G == 1) {
+        geometry(0);
+        fetch(0);
+        fetch_ty(0);
+        stash();
+        __syncthreads();
+        SRX_STAMP(2, 1);
+    }
     // The column pass of a frame is Ay(oy) . rows: it depends on the frame through oy alone (tY, jy0, npy), so the frames of a group -- equal
     // oy, neighbours in fo's order -- add up their row-pass images in registers and ONE column pass runs on the sum (a 4 x 4 phase grid: 4
-    // column passes for 16 frames).  A group of one is a frame of the per-frame form, operation for operation.  Every frame keeps its two
-    // barriers: with the patch double-buffered in LDS a frame inside a group needs one, and the kernel measured the same.
+    // column passes for 16 frames).  A group of one is a frame of the per-frame form, operation for operation.  In the per-frame form (G = 1)
+    // every frame keeps its two barriers: with the patch double-buffered in LDS a frame inside a group needs one, and the kernel measured the
+    // same.  What did measure is below: G > 1, a barrier per G frames.
     int cjy0, cjx0, cnpy;
     auto begin_frame = [&](int k) {
         tX = tXn;
@@ -1069,26 +1082,97 @@ __global__ void __launch_bounds__(256, sizeof(T) == 4 && F == 4 ? 4 : 1)  // flo
                 asm volatile("" : "+v"(v[t - 3]), "+v"(v[t - 2]), "+v"(v[t - 1]), "+v"(v[t])::"memory");
         }
     };
+    // G > 1, the staged row pass.  The frames of a group are read in chunks of up to G (a chunk ends with its group), chunk after chunk from
+    // the two sets of G slots in turn.  Staging runs ahead of reading by one chunk: position nf is the next frame to stage, into slot nsl of
+    // set nset; every row pass, and every column pass, has one frame of the next chunk in flight (loaded before it, stored after it), and
+    // what a short chunk leaves unstaged of a longer successor is staged at the turn.  One barrier per chunk: behind it every wave is done
+    // with the set that the chunk after the next is staged into.  Everything here is uniform over the block.
+    [[maybe_unused]] int nf = 0, nsl = 0, nset = 0, cur = 1, sl = 0;
+    [[maybe_unused]] bool nfull = false;  // the next chunk is staged in full
+    [[maybe_unused]] auto stage_fetch = [&]() {  // as fetch(nf), without the x taps
+        geometry(nf);
+        const T *src = coef + ((size_t)b * N + fo.frame[nf]) * h * w;
+#pragma unroll
+        for (int i = 0; i < PPT; i++) {
+            const int idx = tid + 256 * i, py = idx / PD, px = idx - py * PD;
+            pre[i] = src[(size_t)min(jy0 + py, h - 1) * w + min(jx0 + px, w - 1)];
+        }
+    };
+    [[maybe_unused]] auto stage_stash = [&]() {
+        T *slot = lds + (nset * G + nsl) * ROWS0;
+#pragma unroll
+        for (int i = 0; i < PPT; i++) {
+            const int idx = tid + 256 * i, py = idx / PD, px = idx - py * PD;
+            if (py < npy && px < npx)
+                slot[py * PD + px] = pre[i];
+        }
+        if ((fo.last >> nf & 1) || nsl == G - 1)
+            nfull = true, nsl = 0, nset ^= 1;
+        else
+            nsl++;
+        nf++;
+    };
+    [[maybe_unused]] auto chunk_turn = [&]() {  // the chunk that was read is done with: the next one is staged in full and becomes the one read
+        while (!nfull && nf < N) {
+            stage_fetch();
+            stage_stash();
+        }
+        __syncthreads();
+        nfull = false, cur ^= 1, sl = 0;
+    };
+    [[maybe_unused]] auto fetch_tx = [&](int k) { tXn = zx[min(max(qa + cc + fo.ox[k] - SRX_NPAD, 0), W - 1)]; };
+    [[maybe_unused]] auto staged_frame = [&](int k, T(&v)[(PD + 1) / 2], auto first) {  // the row pass of the frame at position k, slot sl of set cur
+        tX = tXn;
+        cjx0 = geo[k][1];
+        patch = lds + (cur * G + sl) * ROWS0;
+        if (k + 1 < N)
+            fetch_tx(k + 1);  // in flight under this frame
+        const bool pf = !nfull && nf < N;
+        if (pf)
+            stage_fetch();
+        row_pass(v, first);
+        if (pf)
+            stage_stash();
+    };
+    if constexpr (G > 1) {
+        fetch_tx(0);
+        fetch_ty(0);
+        chunk_turn();  // the first chunk
+        SRX_STAMP(2, 1);
+    }
     for (int k = 0; k < N; k++) {  // one trip per group
         [[maybe_unused]] const bool g0 = k == 0;  // the first group (stamps)
         // all reads of the patch first: rows and patch share the LDS array, so hipcc would otherwise order each
         // row's store before the next row's loads (one LDS round trip per row)
         T v[(PD + 1) / 2];
-        begin_frame(k);
-        row_pass(v, std::true_type());
-        while (!(fo.last >> k & 1) && k + 1 < N) {  // wave-uniform: the group's other frames add to v
-            __syncthreads();  // every wave is done with the patch
-            if (k == 0) {
-                SRX_STAMP(2, 2);
-                SRX_STAMP(2, 3);
+        if constexpr (G > 1) {
+            cjy0 = geo[k][0], cnpy = geo[k][2];
+            staged_frame(k, v, std::true_type());
+            while (!(fo.last >> k & 1) && k + 1 < N) {  // wave-uniform: the group's other frames add to v, no barrier inside a chunk
+                if (sl == G - 1)
+                    chunk_turn();
+                else
+                    sl++;
+                k++;
+                staged_frame(k, v, std::false_type());
             }
-            stash();
-            __syncthreads();
-            if (k == 0)
-                SRX_STAMP(2, 4);
-            k++;
+        } else {
             begin_frame(k);
-            row_pass(v, std::false_type());
+            row_pass(v, std::true_type());
+            while (!(fo.last >> k & 1) && k + 1 < N) {  // wave-uniform: the group's other frames add to v
+                __syncthreads();  // every wave is done with the patch
+                if (k == 0) {
+                    SRX_STAMP(2, 2);
+                    SRX_STAMP(2, 3);
+                }
+                stash();
+                __syncthreads();
+                if (k == 0)
+                    SRX_STAMP(2, 4);
+                k++;
+                begin_frame(k);
+                row_pass(v, std::false_type());
+            }
         }
 #pragma unroll
         for (int t = 0; t < (PD + 1) / 2; t++) {
@@ -1097,11 +1181,17 @@ __global__ void __launch_bounds__(256, sizeof(T) == 4 && F == 4 ? 4 : 1)  // flo
                 rows[py * RS + cc] = v[t];
         }
         __syncthreads();
-        if (k == 0)
+        if (G > 1 ? g0 : k == 0)  // (G > 1: the row passes of the whole first group, stamps 1 -> 2)
             SRX_STAMP(2, 2);
         if constexpr (ACC)
             if (g0)
                 SRX_STAMP(2, 6);
+        [[maybe_unused]] bool pf = false;  // G > 1: a frame of the next chunk in flight under the column pass
+        if constexpr (G > 1) {
+            pf = !nfull && nf < N;
+            if (pf)
+                stage_fetch();
+        }
         // column pass of the group, accumulated over the groups: up(y(rr), x) = sum_i zy[y].w[i] * rows[idx[i]][x]
         {
             // four columns per LDS read: rows of pitch 4k from a column 4j, so every quad is 16-byte aligned.  ds_read_b128 moves 256 B
@@ -1130,18 +1220,28 @@ __global__ void __launch_bounds__(256, sizeof(T) == 4 && F == 4 ? 4 : 1)  // flo
                                  "+v"(acc[t - 2]), "+v"(acc[t - 1]), "+v"(acc[t])::"memory");
             }
         }
-        if (k == 0)
+        if (G > 1 ? g0 : k == 0)
             SRX_STAMP(2, 3);
         if constexpr (ACC)
             if (g0)
                 SRX_STAMP(2, 7);
-        if (k + 1 < N) {
-            fetch_ty(k + 1);
-            stash();  // the row pass of this frame is done with the patch
+        if constexpr (G > 1) {
+            if (k + 1 < N)
+                fetch_ty(k + 1);
+            if (pf)
+                stage_stash();
+            chunk_turn();  // a group's end is a chunk's end; its barrier is the one behind the column pass
+            if (g0)
+                SRX_STAMP(2, 4);
+        } else {
+            if (k + 1 < N) {
+                fetch_ty(k + 1);
+                stash();  // the row pass of this frame is done with the patch
+            }
+            __syncthreads();
+            if (k == 0)
+                SRX_STAMP(2, 4);
         }
-        __syncthreads();
-        if (k == 0)
-            SRX_STAMP(2, 4);
     }
     SRX_STAMP(2, 5);
     if constexpr (ACC) {
@@ -1492,7 +1592,7 @@ template <typename T, typename S = T> static int saa(const SaaCall<T, S> &c)
         // through memory instead of (TS + 2 R + 3)^2 / TS^2 times the zoom work)
         const dim3 agrid(cdiv(Ww, SAA_ACC_TS), cdiv(Hw, SAA_ACC_TS), B);
         if (f == 4)
-            SRX_LAUNCH(KID_SAA_TILE, (k_saa_tile<T, 4, true>), agrid, dim3(256), 0, st, coef, N, h, w, zy, zx, fo, ma, H, W, (T)N, Wpl);
+            SRX_LAUNCH(KID_SAA_TILE, (k_saa_tile<T, 4, true, SAA_STAGE_G<T>>), agrid, dim3(256), 0, st, coef, N, h, w, zy, zx, fo, ma, H, W, (T)N, Wpl);
         else if (f == 3)
             SRX_LAUNCH(KID_SAA_TILE, (k_saa_tile<T, 3, true>), agrid, dim3(256), 0, st, coef, N, h, w, zy, zx, fo, ma, H, W, (T)N, Wpl);
         else

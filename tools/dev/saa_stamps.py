@@ -17,6 +17,9 @@ t = buf[2].astype(np.int64)
 nb = 9 * B
 # stamps 2 -> 3 hold a column pass only where frame 0 closes its group (a group of one); the first group's column pass is between stamps 6 and 7
 names = ["geometry + frame 0 fetch + stash", "frame 0 row pass (+ barrier)", "frame 0 column pass (if it ends a group)", "frame 0 stash next (+ barrier)", "frames 1..N-1"]
+if os.environ.get("STAMPS_STAGED"):  # the staged form (k_saa_tile<float, 4, true, G > 1>): the stamps are per chunk and group, not per frame
+    names = ["geometry + first chunk staged", "first group: row passes of its chunks (+ barrier)", "first group: column pass", "first group: turn (rest of the next chunk, barrier)",
+             "groups 1.."]
 ok = (t[0, :nb] > 0) & (t[5, :nb] > t[0, :nb])
 tot = (t[5, :nb] - t[0, :nb])[ok]
 print(f"blocks {ok.sum()}, median cycles/block {np.median(tot):.0f} (p10 {np.percentile(tot, 10):.0f}, p90 {np.percentile(tot, 90):.0f})")

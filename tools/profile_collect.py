@@ -12,6 +12,7 @@ import subprocess
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+XCDS, CUS, SIMDS = 8, 256, 1024  # MI355X: what the chip-wide SQ / GRBM counter sums are divided by
 WL = {"c2": "c2:B=1024:f32", "c3_mono": "c3_mono:B=1:f32", "c3_mono_measured": "c3_mono_measured:B=1:f32", "c3_f4": "c3_f4:B=1:f32",
       "c3_rgb": "c3_rgb:B=1:f32", "c3_rgb_measured": "c3_rgb_measured:B=1:f32", "c3_mono_f64": "c3_mono:B=1:f64", "c2_f64": "c2:B=1024:f64", "c2_measured": "c2_measured:B=1024:f32", "c3_f4_measured": "c3_f4_measured:B=1:f32", "c3_rgb_f64": "c3_rgb:B=1:f64"}
 
@@ -58,19 +59,23 @@ def main():
             f.write(f"# rocprofv3 --kernel-trace --pmc <8 counters> (two passes), workload {wtag}, mean per launch; tools/profile_round.sh\n")
             f.write("# VALU busy = SQ_INSTS_VALU / 1024 SIMDs x 2 cycles / (GRBM_GUI_ACTIVE / 8 XCDs)   (issue cost: profiles/README.md, microbenchmark)\n")
             for k in sorted(c):
-                if not k.startswith(("k_ibp", "k_ztile_trace", "k_fwd_", "k_bwd_", "k_blur_pad")):
+                if not k.startswith(("k_ibp", "k_ztile_trace", "k_fwd_", "k_bwd_", "k_blur_pad", "k_saa_")):
                     continue
                 d = c[k]
                 f.write(f"{k}\n")
                 for n in sorted(d):
                     f.write(f"    {n:28s} {d[n]:18.1f}\n")
                 if "SQ_INSTS_VALU" in d and d.get("GRBM_GUI_ACTIVE"):
-                    cyc = d["GRBM_GUI_ACTIVE"] / 8
-                    valu[k.split("<")[0]] = {"valu_busy": round(d["SQ_INSTS_VALU"] / 1024 * 2 / cyc, 4),
+                    cyc = d["GRBM_GUI_ACTIVE"] / XCDS
+                    valu[k.split("<")[0]] = {"valu_busy": round(d["SQ_INSTS_VALU"] / SIMDS * 2 / cyc, 4),
                                              "wave_cycles_waiting": round(d["SQ_WAIT_ANY"] / d["SQ_WAVE_CYCLES"], 4),
                                              "method": "SQ_INSTS_VALU / 1024 SIMDs x 2 cycles / (GRBM_GUI_ACTIVE / 8 XCDs); SQ_WAIT_ANY / SQ_WAVE_CYCLES"}
-                    f.write(f"    -> VALU busy {d['SQ_INSTS_VALU'] / 1024 * 2 / cyc:.3f}, wave-cycles waiting {d['SQ_WAIT_ANY'] / d['SQ_WAVE_CYCLES']:.3f}, "
+                    f.write(f"    -> VALU busy {d['SQ_INSTS_VALU'] / SIMDS * 2 / cyc:.3f}, wave-cycles waiting {d['SQ_WAIT_ANY'] / d['SQ_WAVE_CYCLES']:.3f}, "
                             f"GPU cycles per launch {cyc:.0f}\n")
+                    if d.get("SQ_LDS_IDX_ACTIVE"):  # the LDS array's cycles, summed over the compute units
+                        f.write(f"    -> LDS busy {d['SQ_LDS_IDX_ACTIVE'] / CUS / cyc:.3f} of the launch's cycles (SQ_LDS_IDX_ACTIVE / {CUS} CUs / GPU cycles), "
+                                f"bank conflicts {d.get('SQ_LDS_BANK_CONFLICT', 0) / d['SQ_LDS_IDX_ACTIVE']:.3f} of the LDS cycles, "
+                                f"LDS cycles per LDS instruction {d['SQ_LDS_IDX_ACTIVE'] / max(d.get('SQ_INSTS_LDS', 0), 1):.2f}\n")
         # the VALU view of the same kernels goes beside their traffic (bench.py's roofline.valu)
         doc = json.load(open(f"{dst}/traffic.json"))
         for k, v in valu.items():
